@@ -15,7 +15,21 @@ tutorial model (``moose_amd/models/predictors/tutorial.py``: 200 x 10 rows, fixe
 Z_2^128, secure sigmoid) through ``predictors.from_onnx``: p50 latency of whole
 evaluations (share -> predict -> reveal) on rank 0's GPU, eager and hipGraph replay, and
 with >= 3 GPUs also one party per GPU (SPMD over RCCL).  Measured after the timed matmul
-steps, outside their timed region.
+steps, outside their timed region, and only with ``--full``.
+
+A plain run (``bench.py --gpus N --steps K --warmup W``) does what the headline needs and
+no more: set up, preflight, W warmup steps, K timed steps, the JSON line.  ``--full`` adds
+everything else the benchmark measures or checks after the headline: the output check
+against float64 torch, the link probe, the LR inference, BASELINE configs 2/3/5 and the
+zero-slot-aware steps.
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller as
+``DIR/<name>.npy`` (float64): ``output_0`` (one rank; ``output_0.rank<r>`` per output owner
+with several) and, on the rank that collected every session's output, ``output_0.gathered``.
+An array over its share of the size budget (48 MiB in all) is written as a fixed, seeded
+sample of its rows, the same rows in every run with the same arguments; the inputs are
+seeded too, so two builds can be compared output for output (TruncPr rounds
+probabilistically with fresh keys: outputs of two runs differ by about 2^-23).
 
 Layouts (``--layout``; default ``auto`` = stacked on 1 and 2 GPUs, cyclic on N >= 3: with
 two GPUs the three parties of a session cannot sit on three different GPUs, so the cyclic
@@ -40,16 +54,16 @@ client, as the reference's benchmark collects them) over RCCL inside the timed r
 overlapped with the next step (``--gather all`` all-gathers them to every rank instead).
 Inputs are synthetic (uniform [-4, 4)), device-resident; tracing/conversion happens once
 before the timed region (the reference's client-side compile).  Every step creates a fresh
-session (fresh PRF keys).  After the timed steps the last step's outputs are checked
-against float64 torch on every rank (``--no-check`` skips it).
+session (fresh PRF keys).  With ``--full`` the last step's outputs are checked against
+float64 torch on every rank after the timed steps (``--no-check`` skips it).
 
 Failing loudly (``moose_amd/utils/benchwatch.py``): the whole run has one wall-clock
 deadline (``--deadline``, default 540 s, under the driver's 600 s).  Every phase (init +
-rendezvous, preflight, warmup, timed, then the optional extras) runs under a watchdog budget
-clipped to it; an extra is skipped (and listed) when too little time is left; ``phase_s``
-in the line records what each phase took.  Before the warmup every rank does one grouped
-round trip with each of its peers on every communicator it will use and verifies who
-answered.
+rendezvous, preflight, warmup, timed, then with ``--full`` the extras) runs under a watchdog
+budget clipped to it; an extra is skipped (and listed) when too little time is left;
+``phase_s`` in the line records what each phase took.  Before the warmup every rank does
+one grouped round trip with each of its peers on every communicator it will use and
+verifies who answered.
 
 Launch: ``python bench.py --gpus N`` starts torch.distributed.run on 127.0.0.1 itself.
 Under a launcher (WORLD_SIZE set) each rank process is a supervisor that never touches the
@@ -110,14 +124,22 @@ def _parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--size", type=int, default=4096)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else the benchmark measures "
+                         "or checks (output check, link probe, LR inference, BASELINE "
+                         "configs 2/3/5, zero-slot-aware steps); a plain run stops at the "
+                         "headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float64; a "
+                         "fixed seeded row sample of an array over the size budget)")
     ap.add_argument("--link-probe-mib", type=int, default=256,
-                    help="after the headline (cyclic, N > 1): point-to-point GB/s of the "
+                    help="--full, after the headline (cyclic, N > 1): point-to-point GB/s of the "
                          "layout's exchange pattern with this many MiB per message (0: off)")
     ap.add_argument("--spmd-configs", action=argparse.BooleanOptionalAction, default=True,
-                    help="with >= 3 GPUs also time BASELINE configs 2 (tutorials/"
+                    help="--full, with >= 3 GPUs: also time BASELINE configs 2 (tutorials/"
                          "dotprod.moose) and 3 (RingDot, one party per GPU) on ranks 0-2")
     ap.add_argument("--zero-slot-steps", type=int, default=10,
-                    help="one GPU, stacked: also time this many steps with the opt-in "
+                    help="--full, one GPU, stacked: also time this many steps with the opt-in "
                          "zero-slot-aware product (reported apart from the headline)")
     ap.add_argument("--ring", type=int, default=128, choices=[64, 128])
     ap.add_argument("--gather", default="root", choices=["root", "all", "none"],
@@ -129,10 +151,11 @@ def _parse():
                     help="HIP streams (and RCCL communicators) consecutive steps alternate "
                          "between (default: 2 for cyclic at N > 1, else 1)")
     ap.add_argument("--check", dest="check", action="store_true", default=True,
-                    help="verify the last step's outputs against float64 torch (default)")
+                    help="--full: verify the last step's outputs against float64 torch "
+                         "(default)")
     ap.add_argument("--no-check", dest="check", action="store_false")
     ap.add_argument("--lr-runs", type=int, default=30,
-                    help="LR-inference evaluations per mode (0 = skip)")
+                    help="--full: LR-inference evaluations per mode (0 = skip)")
     ap.add_argument("--backend", default="auto", choices=["auto", "nccl", "gloo"],
                     help="process-group backend (auto: RCCL on GPUs, gloo on the CPU and "
                          "with MOOSEX_SHARED_GPU=1)")
@@ -246,6 +269,30 @@ def _inputs(n, session, which, device):
 
     g = torch.Generator(device="cpu").manual_seed(1234 + 2 * session + (which == "y"))
     return (torch.rand(n, n, generator=g, dtype=torch.float64) * 8 - 4).to(device)
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # all dumped arrays of a run together (float64)
+
+
+def _dump_outputs(directory, arrays, n_arrays):
+    """``--dump-outputs``: write this rank's ``{name: 2-d tensor}`` as ``<name>.npy``
+    (float64).  ``n_arrays`` = arrays written by all ranks together; each gets an equal share
+    of the budget, and one over its share is written as a sample of its rows (ascending row
+    numbers drawn with a fixed seed, so every run with the same arguments samples the same
+    rows)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, n_arrays)
+    for name, t in arrays.items():
+        rows = max(1, share // (8 * t.shape[1]))
+        if rows < t.shape[0]:
+            g = torch.Generator(device="cpu").manual_seed(4321)
+            idx = torch.randperm(t.shape[0], generator=g)[:rows].sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(directory, name + ".npy"),
+                t.detach().to(device="cpu", dtype=torch.float64).numpy())
 
 
 def _device_info(device):
@@ -1102,10 +1149,20 @@ def _main(args, prog_out):
             "device_in_use": round((total - free) / 2**30, 2),
             "device_total": round(total / 2**30, 1)}
     line["revision"] = _revision()
+    if args.dump_outputs:
+        # what the last timed step handed to its caller: this rank's revealed output and,
+        # on the collecting rank, every session's (the buffer the last step filled)
+        dump = {}
+        if z is not None:
+            dump["output_0" if world == 1 else f"output_0.rank{rank}"] = z
+        if gather_bufs is not None and rank == root:
+            dump["output_0.gathered"] = gather_bufs[(n_steps[0] - 1) % len(gather_bufs)]
+        _dump_outputs(args.dump_outputs, dump,
+                      (len(owners) if world > 1 else 1) + (gather_mode != "none"))
     prog.headline_done(line)
 
     exit_code = 0
-    if args.check and fits("check"):
+    if args.full and args.check and fits("check"):
         prog.phase("check")
         check = None
         if out_owner:
@@ -1138,7 +1195,8 @@ def _main(args, prog_out):
     # the optional extras after the headline: each runs only when its expected need is
     # left before the deadline (all ranks agree), under a budget clipped to the deadline;
     # a hang in one fires the watchdog, which reports the measured line with the error
-    if layout == "cyclic" and world > 1 and args.link_probe_mib > 0 and fits("link_probe"):
+    if (args.full and layout == "cyclic" and world > 1 and args.link_probe_mib > 0
+            and fits("link_probe")):
         prog.phase("link_probe")
         off = list(offsets.values())
         dists = sorted({(b - a) % world for a in off for b in off} - {0})
@@ -1147,7 +1205,7 @@ def _main(args, prog_out):
         if rank == 0:
             line["link_probe"] = probe
 
-    if args.lr_runs > 0 and fits("lr"):
+    if args.full and args.lr_runs > 0 and fits("lr"):
         prog.phase("lr")
         lr = {"model": "ml-inference-with-onnx tutorial LogisticRegression (200x10, "
                        "fixed(24,40), Z_2^128, from_onnx)"}
@@ -1190,7 +1248,7 @@ def _main(args, prog_out):
                 line["lr_inference_rounds"] = best["rounds"]
             line["lr_inference"] = lr
 
-    if world >= 3 and args.spmd_configs and fits("spmd_configs"):
+    if args.full and world >= 3 and args.spmd_configs and fits("spmd_configs"):
         prog.phase("spmd_configs")
         rec = _spmd_configs(args, world, rank, device, prog)
         recs = [None] * world
@@ -1204,7 +1262,7 @@ def _main(args, prog_out):
                 line["config5_dp2_replicas"] = merged.pop("config5_dp2_replicas")
             line["spmd_three_gpus"] = merged
 
-    if (world == 1 and layout == "stacked" and args.zero_slot_steps > 0
+    if (args.full and world == 1 and layout == "stacked" and args.zero_slot_steps > 0
             and fits("zero_slot")):
         # secondary figure, NOT the headline: the same steps with the zero-slot-aware RSS
         # product (protocols/replicated.py _zero_slot_cross, opt-in MOOSEX_ZERO_SLOTS=1):

@@ -63,13 +63,15 @@ if has driver; then
     "driver command kernel stats" > gpurun_out/driver_prof_summary.md 2>&1 || true
 fi
 if has bench; then
-  run bench128 600 python bench.py --steps 10 --warmup 3 && summary gpurun_out/bench128.log
-  run bench64 600 python bench.py --steps 10 --warmup 3 --ring 64 && summary gpurun_out/bench64.log
+  # --full: the steps below read the check / LR / link-probe records of the line;
+  # */<name>.log is the log run() just wrote into the output directory
+  run bench128 600 python bench.py --full --steps 10 --warmup 3 && summary */bench128.log
+  run bench64 600 python bench.py --full --steps 10 --warmup 3 --ring 64 && summary */bench64.log
 fi
 if has cyclic; then
   for s in 1 2; do
-    run cyc_s$s 300 python bench.py --layout cyclic --steps 10 --warmup 3 --step-streams $s \
-      --lr-runs 0 && summary gpurun_out/cyc_s$s.log
+    run cyc_s$s 300 python bench.py --full --layout cyclic --steps 10 --warmup 3 \
+      --step-streams $s --lr-runs 0 && summary */cyc_s$s.log
   done
 fi
 if has cycprof; then
@@ -80,15 +82,15 @@ if has cycprof; then
 fi
 if has shared; then
   for N in ${NS:-3 8}; do
-    run shared$N 600 env MOOSEX_SHARED_GPU=1 python bench.py --gpus $N --steps ${SSTEPS:-5} \
-      --warmup 2 --size ${SIZE:-4096} --lr-runs 5 && summary gpurun_out/shared$N.log
+    run shared$N 600 env MOOSEX_SHARED_GPU=1 python bench.py --gpus $N --full \
+      --steps ${SSTEPS:-5} --warmup 2 --size ${SIZE:-4096} --lr-runs 5 && summary */shared$N.log
   done
 fi
 if has ladder; then
   # the fallback ladder on a real GPU: attempt 0 (cyclic, 2 streams) hangs in its warmup on
   # rank 1, the supervisors kill it on every rank and attempt 1 (1 stream) measures
   run ladder3 400 env MOOSEX_SHARED_GPU=1 MOOSEX_BENCH_STALL=1:warmup python bench.py --gpus 3 \
-    --steps 3 --warmup 1 --size 1024 --lr-runs 3 --deadline 300 && summary gpurun_out/ladder3.log
+    --full --steps 3 --warmup 1 --size 1024 --lr-runs 3 --deadline 300 && summary */ladder3.log
 fi
 if has ab; then
   # A/B of env configurations on the driver command (ABCFG="NAME=VAR=v,VAR2=w ...")

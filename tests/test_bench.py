@@ -41,9 +41,86 @@ def test_bench_json_line(n, layout):
     assert {"model", "global_batch", "seq_len", "parallelism"} <= set(d["config"])
 
 
+EXTRAS = {"check", "zero_slot_aware", "lr_inference", "lr_inference_p50_ms", "link_probe",
+          "spmd_three_gpus", "config5_dp2_replicas"}
+
+
+def _run_one(tmp, name, *extra):
+    """One process, no launcher: bench.py --gpus 1 at a small size on the CPU, outputs
+    dumped."""
+    import numpy as np
+
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--size", "48", "--lr-runs", "0", "--zero-slot-steps", "1",
+           "--dump-outputs", str(tmp / name), *extra]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["HIP_VISIBLE_DEVICES"] = ""  # a CPU test: the same run with or without a GPU present
+    out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300, env=env)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    assert sorted(os.listdir(tmp / name)) == ["output_0.npy"]
+    return json.loads(lines[0]), np.load(tmp / name / "output_0.npy")
+
+
+@pytest.fixture(scope="module")
+def plain_and_full(tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("bench_dump")
+    return _run_one(tmp, "plain"), _run_one(tmp, "full", "--full")
+
+
+def test_plain_run_stops_at_the_headline(plain_and_full):
+    """Without --full the line has the driver's fields and none of the post-headline
+    extras; --steps is the number of timed steps and ms_per_step one step's time."""
+    (d, _), (f, _) = plain_and_full
+    assert FIELDS <= set(d) and not EXTRAS & set(d)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(48 * 48 / d["ms_per_step"] * 1e3)
+    assert {"check", "zero_slot_aware"} <= set(f) and f["check"]["ok"]
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert d[k] == f[k]
+
+
+def test_dump_outputs_are_the_last_steps_outputs(plain_and_full):
+    """--dump-outputs: float64 arrays of the last timed step; the inputs are seeded, so two
+    runs agree to TruncPr's probabilistic rounding (each output is off by at most one unit
+    of 2^-23, two runs by at most two) and with the float64 product of the same inputs
+    (fixed(14,23) encoding: |x|, |y| < 4 rounded to 2^-23, K = 48 terms)."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    (_, a), (_, b) = plain_and_full
+    assert a.dtype == b.dtype == np.float64 and a.shape == b.shape == (48, 48)
+    assert np.abs(a - b).max() <= 2.0 ** -22
+    cpu = torch.device("cpu")
+    ref = (bench._inputs(48, 0, "x", cpu) @ bench._inputs(48, 0, "y", cpu)).numpy()
+    assert np.abs(a - ref).max() <= 48 * 8 * 2.0 ** -23 + 2.0 ** -22
+
+
+def test_dump_outputs_samples_rows_over_the_budget(tmp_path, monkeypatch):
+    """An array over its share of the budget is written as the same seeded ascending row
+    sample every time."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 10 * 16 * 8)
+    t = torch.arange(64 * 16, dtype=torch.float64).reshape(64, 16)
+    for d in ("a", "b"):
+        bench._dump_outputs(str(tmp_path / d), {"output_0": t, "small": t[:4]}, 2)
+    a, b = (np.load(tmp_path / d / "output_0.npy") for d in ("a", "b"))
+    assert a.shape == (10, 16) and np.array_equal(a, b)
+    rows = (a[:, 0] / 16).astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, t.numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), t[:4].numpy())
+
+
 def _run_self(n, *extra):
     """No launcher: bench.py --gpus N spawns its N ranks itself."""
-    cmd = [sys.executable, "bench.py", "--gpus", str(n), "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, "bench.py", "--gpus", str(n), "--full", "--steps", "2", "--warmup", "1",
            "--size", "48", "--lr-runs", "0", *extra]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300, env=env)
@@ -82,7 +159,7 @@ def test_bench_self_launch(n, layout, sessions):
 def test_bench_lr_inference_in_line():
     """The second half of the headline metric: LR-inference p50 in the same JSON line
     (one GPU eager/graphs, and with >= 3 ranks one party per rank)."""
-    cmd = [sys.executable, "bench.py", "--gpus", "3", "--steps", "1", "--warmup", "1",
+    cmd = [sys.executable, "bench.py", "--gpus", "3", "--full", "--steps", "1", "--warmup", "1",
            "--size", "32", "--lr-runs", "2"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
@@ -102,7 +179,7 @@ def test_bench_lr_inference_in_line():
 
 
 def _run_env(n, env_extra, *extra, timeout=300):
-    cmd = [sys.executable, "bench.py", "--gpus", str(n), "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, "bench.py", "--gpus", str(n), "--full", "--steps", "2", "--warmup", "1",
            "--size", "32", "--lr-runs", "0", *extra]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(env_extra)
@@ -200,7 +277,7 @@ def test_bench_rank_exception_ends_the_run_promptly(phase, rank, headline):
     its failure record instead of waiting out their phase budget).  After the headline was
     measured (an optional extra failed) the line keeps the measurement and notes the error;
     before it, the next rung of the ladder measures instead."""
-    cmd = [sys.executable, "bench.py", "--gpus", "3", "--steps", "1", "--warmup", "1",
+    cmd = [sys.executable, "bench.py", "--gpus", "3", "--full", "--steps", "1", "--warmup", "1",
            "--size", "32", "--lr-runs", "2", "--deadline", "200"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["MOOSEX_BENCH_FAIL"] = f"{rank}:{phase}"
@@ -248,7 +325,7 @@ def test_bench_rccl_multi_gpu(n):
     six GPUs).  Gated on the device count, as SURVEY section 4 asks."""
     if _gpus() < n:
         pytest.skip(f"needs {n} GPUs")
-    cmd = [sys.executable, "bench.py", "--gpus", str(n), "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, "bench.py", "--gpus", str(n), "--full", "--steps", "2", "--warmup", "1",
            "--size", "1024", "--lr-runs", "3", "--deadline", "400"]
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MOOSEX_SHARED_GPU")}

@@ -1,6 +1,7 @@
 """Textual format: parse/print round trips (reference textual/parsing.rs tests and
 computation.rs:1974-2009)."""
 import glob
+import os
 
 import numpy as np
 import pytest
@@ -13,9 +14,26 @@ from moose_amd.ir.textual import ParseError
 from moose_amd.ir.textual import parse_computation
 
 REF_FILES = sorted(glob.glob("/root/reference/**/*.moose", recursive=True))
+# the repository's own computations: the round-trip test has cases without a reference checkout
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OWN_FILES = sorted(glob.glob(os.path.join(REPO, "examples", "*.moose")))
 
 
-@pytest.mark.parametrize("path", REF_FILES, ids=lambda p: p.split("/reference/")[-1])
+def _dotprod_source():
+    """The fixed(24,40) 1x3 . 3x1 dot product between player0/1/2 that the benchmark times
+    as BASELINE config 2 (kept in bench.py, so the tests need no file outside the tree)."""
+    import bench
+
+    return bench.DOTPROD_MOOSE
+
+
+def _file_id(path):
+    if path in OWN_FILES:
+        return os.path.relpath(path, REPO)
+    return path.split("/reference/")[-1]
+
+
+@pytest.mark.parametrize("path", REF_FILES + OWN_FILES, ids=_file_id)
 def test_reference_files_roundtrip(path):
     src = open(path).read()
     comp = parse_computation(src)
@@ -27,7 +45,7 @@ def test_reference_files_roundtrip(path):
 
 
 def test_dotprod_structure():
-    comp = parse_computation(open("/root/reference/tutorials/dotprod.moose").read())
+    comp = parse_computation(_dotprod_source())
     kinds = [op.kind for op in comp]
     assert kinds == ["Constant", "Cast", "Constant", "Cast", "Dot", "Cast", "Output"]
     dot = comp.operations[4]
@@ -82,7 +100,11 @@ def test_parse_errors_are_reported():
 
 
 def test_msgpack_roundtrip(tmp_path):
-    comp = parse_computation(open("/root/reference/tutorials/dotprod-networked.moose").read())
+    from moose_amd.compiler import passes
+
+    # the dot product lowered to host operations with its Send/Receive pairs
+    comp = passes.compile(parse_computation(_dotprod_source()))
+    assert {"Send", "Receive"} <= {op.kind for op in comp}
     data = comp.to_msgpack()
     back = Computation.from_msgpack(data)
     assert back.to_textual() == comp.to_textual()
