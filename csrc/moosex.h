@@ -285,6 +285,15 @@ int mx_trunc_pr3_kmo(int dev, int words, const void* s0, void* out0, void* out1,
 int mx_share3_k(int dev, int kind, int words, const void* x, void* out0, void* out1, int64_t n,
                 int j, const uint32_t* slot_next, const uint32_t* slot_all, uint64_t n1,
                 uint64_t na, void* stream);
+// ring_extend3: exact widening of a replicated sharing over Z_2^64 to Z_2^128, valid for
+// -2^62 <= x < 2^62 (rss_fused.h).  s0: [3, n] u64 slots; out0 / out1: [3, n] u128 slot
+// vectors (out1 == out0 + n: the 4-slot ring).  nonces: r0, r1, R0, M0, z0, z2 (dealer keys
+// k0, k2), every stream drawn at 128-bit width.
+int mx_ring_extend3_k(int dev, const void* s0, void* out0, void* out1, int64_t n,
+                      const uint32_t* slot_k0, const uint32_t* slot_k2, const uint64_t* nonces,
+                      void* stream);
+// largest n that the device entry point runs with the latency form of the kernel
+int64_t mx_ring_extend3_lat_max(void);
 
 // Per-party protocol rounds for layouts with the parties of a session on different GPUs
 // (rss_party.hip): ncomp stacked components [ncomp, n], component c in role roles[c]

@@ -104,6 +104,25 @@ __device__ inline void prf_chunk(const uint32_t* key, uint64_t nonce, uint64_t c
   mx::prf_chunk(key, nonce, c, lo, hi);
 }
 
+// prf_chunk with the block's part picked by selects over constant indices, so the sixteen
+// block words stay in registers (indexing them by the part puts them in scratch)
+__device__ inline void prf_chunk_reg(const uint32_t* key, uint64_t nonce, uint64_t c, uint64_t* lo,
+                                     uint64_t* hi) {
+  uint32_t w[16];
+  mx::chacha_block(key, nonce, mx::ks_block_of(c), w);
+  const int part = mx::ks_part_of(c);
+  uint32_t a = w[0], b = w[1], d = w[2], e = w[3];
+#pragma unroll
+  for (int p = 1; p < 4; ++p) {
+    a = part == p ? w[4 * p] : a;
+    b = part == p ? w[4 * p + 1] : b;
+    d = part == p ? w[4 * p + 2] : d;
+    e = part == p ? w[4 * p + 3] : e;
+  }
+  *lo = (uint64_t)a | ((uint64_t)b << 32);
+  *hi = (uint64_t)d | ((uint64_t)e << 32);
+}
+
 inline int grid_for(int64_t n, int block = 256) {
   int64_t blocks = (n + block - 1) / block;
   if (blocks < 1) blocks = 1;

@@ -46,6 +46,52 @@ MX_HD inline T trunc_pr_z1(T x0, T x1, T x2, T r0, T r1, T rt0, T rm0, T z0, T z
   return (y0 - z0) + (y1 - z2);
 }
 
+// ---------------------------------------------------------------------------------------
+// Ring extension Z_2^64 -> Z_2^128 of a replicated sharing (dealer P2), exact for
+// -2^62 <= x < 2^62: TruncPr's overflow trick without the truncation.  With x' = x + 2^62 in
+// [0, 2^63) and c = x' + r (mod 2^64) opened, the integer sum x' + r wraps exactly when
+// r_msb = 1 and c_msb = 0, so x' = c - R + 2^64 r_msb (1 - c_msb) over Z_2^128 (R = r
+// zero-extended).  The dealer shares R and r_msb additively between P0 and P1; the share of
+// r_msb only matters modulo 2^64 (it is shifted left by 64) and travels as a u64.
+// ---------------------------------------------------------------------------------------
+using u128_t = unsigned __int128;
+
+// launches of at most this many elements take the latency form of the device kernel
+constexpr int64_t kRingExtendLatMax = 8192;
+
+// dealer P2: r = r0 + r1 -> (R1, M1) for P1
+MX_HD inline void ring_extend_dealer(uint64_t r0, uint64_t r1, u128_t R0, uint64_t M0, u128_t* R1,
+                                     uint64_t* M1) {
+  const uint64_t r = r0 + r1;
+  *R1 = (u128_t)r - R0;
+  *M1 = (r >> 63) - M0;
+}
+
+// P0's masked opening share: x0 + x1 + 2^62 + r0 (P1's is x2 + r1)
+MX_HD inline uint64_t ring_extend_mask0(uint64_t x0, uint64_t x1, uint64_t r0) {
+  return x0 + x1 + ((uint64_t)1 << 62) + r0;
+}
+
+// P0's (first) / P1's additive share of the widened value from the opened c
+MX_HD inline u128_t ring_extend_y(uint64_t c, u128_t R, uint64_t M, bool first) {
+  const uint64_t nc = 1 - (c >> 63);
+  const u128_t y = ((u128_t)(uint64_t)(nc * M) << 64) - R;
+  return first ? y + (u128_t)c - ((u128_t)1 << 62) : y;
+}
+
+// inputs: slots x0, x1, x2 and the six PRF values (dealer key k0: r0, R0, M0, z0; dealer key
+// k2: r1, z2).  Returns the new slot z1 (z0, z2 are the PRF values).
+MX_HD inline u128_t ring_extend_z1(uint64_t x0, uint64_t x1, uint64_t x2, uint64_t r0, uint64_t r1,
+                                   u128_t R0, uint64_t M0, u128_t z0, u128_t z2) {
+  u128_t R1;
+  uint64_t M1;
+  ring_extend_dealer(r0, r1, R0, M0, &R1, &M1);
+  const uint64_t c = ring_extend_mask0(x0, x1, r0) + (x2 + r1);
+  const u128_t y0 = ring_extend_y(c, R0, M0, true);
+  const u128_t y1 = ring_extend_y(c, R1, M1, false);
+  return (y0 - z0) + (y1 - z2);
+}
+
 }  // namespace mxf
 
 // ---------------------------------------------------------------------------------------

@@ -5,6 +5,7 @@
 // parties -- six keystream chunks (prf_core.h) and ~40 integer ops per element, one read of
 // the three input slots, one write of the two output share vectors.
 // share3: input sharing by a member party (two keystream chunks per element).
+// ring_extend3: exact widening of a Z_2^64 sharing to Z_2^128 (six keystream chunks).
 #include <hip/hip_runtime.h>
 
 #include "prf_dev.h"
@@ -107,6 +108,89 @@ __global__ void __launch_bounds__(256) k_trunc_pr3_lat(const T* __restrict__ s0,
         }
         out1[2 * os + i] = z0;
       }
+    }
+    __syncthreads();
+  }
+}
+
+// Ring extension Z_2^64 -> Z_2^128 (rss_fused.h: ring_extend_z1) for all three parties: one
+// read of the three u64 input slots, six keystream chunks, one write of the two u128 output
+// share vectors.  All six streams are drawn at 128-bit lane width (one chunk per element);
+// r0, r1 and M0 use the low 64 bits of their lane, so element i of every stream is the
+// 128-bit PRF draw of the composed protocol, truncated where it is narrower.
+__global__ void __launch_bounds__(256) k_ring_extend3(const u64* __restrict__ s0, u128* __restrict__ out0,
+                                                      u128* __restrict__ out1, int64_t n, int64_t os,
+                                                      mxd::KeySrc keys, uint64_t n_r0, uint64_t n_r1,
+                                                      uint64_t n_R, uint64_t n_M, uint64_t n_z0,
+                                                      uint64_t n_z2) {
+  __shared__ uint32_t rks[2][mxd::kKeyWords];
+  mxd::stage_keys(rks, keys, 2);
+  // streams r0, r1, R0, M0, z0, z2 (dealer keys k0 / k2)
+  const uint32_t* const key[6] = {rks[0], rks[1], rks[0], rks[0], rks[0], rks[1]};
+  const uint64_t nonce[6] = {n_r0, n_r1, n_R, n_M, n_z0, n_z2};
+  mxd::walk_chunks<6>(n, key, nonce, [&](int64_t i, const uint64_t (&lo)[6], const uint64_t (&hi)[6]) {
+    const u128 z0 = mxd::pick<u128>(lo[4], hi[4], 0);
+    const u128 z2 = mxd::pick<u128>(lo[5], hi[5], 0);
+    const u128 z1 = mxf::ring_extend_z1(s0[i], s0[n + i], s0[2 * n + i], lo[0], lo[1],
+                                        mxd::pick<u128>(lo[2], hi[2], 0), lo[3], z0, z2);
+    out0[i] = z0;
+    out0[os + i] = z1;
+    out0[2 * os + i] = z2;
+    if (out1 != out0 + os) {  // else out1 = out0 + os: a 4-slot ring, slots 1, 2 shared
+      out1[i] = z1;
+      out1[os + i] = z2;
+    }
+    out1[2 * os + i] = z0;
+  });
+}
+
+// Latency variant (small n), as k_trunc_pr3_lat: the six keystream chunks of each of the
+// block's EPB elements are computed one per thread into LDS; then EPB threads finish them.
+// The chunk comes from prf_chunk_reg: with prf_chunk the compiler reports 80 bytes of scratch
+// per lane and 48 VGPRs for this kernel (as for k_trunc_pr3_lat), with the select form no
+// scratch and 44 VGPRs.
+__global__ void __launch_bounds__(256) k_ring_extend3_lat(const u64* __restrict__ s0, u128* __restrict__ out0,
+                                                          u128* __restrict__ out1, int64_t n, int64_t os,
+                                                          mxd::KeySrc keys, uint64_t n_r0, uint64_t n_r1,
+                                                          uint64_t n_R, uint64_t n_M, uint64_t n_z0,
+                                                          uint64_t n_z2) {
+  constexpr int EPB = 256 / 6;
+  __shared__ uint32_t rks[2][mxd::kKeyWords];
+  __shared__ uint64_t kl[6][EPB], kh[6][EPB];
+  mxd::stage_keys(rks, keys, 2);
+  const int tid = threadIdx.x, s = tid / EPB, lb = tid % EPB;
+  // stream s: (key, nonce) of r0, r1, R0, M0, z0, z2 -- as in k_ring_extend3
+  const int key_of = (s == 1 || s == 5) ? 1 : 0;
+  const uint64_t nonce_of = s == 0 ? n_r0 : s == 1 ? n_r1 : s == 2 ? n_R : s == 3 ? n_M
+                            : s == 4 ? n_z0 : n_z2;
+  for (int64_t b0 = (int64_t)blockIdx.x * EPB; b0 < n; b0 += (int64_t)gridDim.x * EPB) {
+    // the finishing threads' operands first: their loads overlap the keystream work
+    const bool fin = tid < EPB && b0 + tid < n;
+    u64 xv[3];
+#pragma unroll
+    for (int p = 0; p < 3; ++p) xv[p] = fin ? s0[p * n + b0 + tid] : 0;
+    if (s < 6 && b0 + lb < n) {
+      uint64_t lo, hi;
+      mxd::prf_chunk_reg(rks[key_of], nonce_of, (uint64_t)(b0 + lb), &lo, &hi);
+      kl[s][lb] = lo;
+      kh[s][lb] = hi;
+    }
+    __syncthreads();
+    if (fin) {
+      const int64_t i = b0 + tid;
+      const u128 z0 = mxd::pick<u128>(kl[4][tid], kh[4][tid], 0);
+      const u128 z2 = mxd::pick<u128>(kl[5][tid], kh[5][tid], 0);
+      const u128 z1 = mxf::ring_extend_z1(xv[0], xv[1], xv[2], kl[0][tid], kl[1][tid],
+                                          mxd::pick<u128>(kl[2][tid], kh[2][tid], 0), kl[3][tid],
+                                          z0, z2);
+      out0[i] = z0;
+      out0[os + i] = z1;
+      out0[2 * os + i] = z2;
+      if (out1 != out0 + os) {
+        out1[i] = z1;
+        out1[os + i] = z2;
+      }
+      out1[2 * os + i] = z0;
     }
     __syncthreads();
   }
@@ -258,6 +342,24 @@ int launch_trunc_pr3(int words, const void* s0, void* out0, void* out1, int64_t 
   return e == hipSuccess ? 0 : -100 - (int)e;
 }
 
+// s0: [3, n] u64 slots; out0 / out1: party p's u128 slot at out + p * os
+int launch_ring_extend3(const void* s0, void* out0, void* out1, int64_t n, int64_t os,
+                        const mxd::KeySrc& keys, const uint64_t* nn, void* stream) {
+  if (n == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (n <= mxf::kRingExtendLatMax) {  // latency-bound: one PRF chunk per thread
+    hipLaunchKernelGGL(k_ring_extend3_lat, dim3((unsigned)((n + 41) / 42)), dim3(256), 0, st,
+                       (const u64*)s0, (u128*)out0, (u128*)out1, n, os, keys, nn[0], nn[1], nn[2],
+                       nn[3], nn[4], nn[5]);
+  } else {
+    hipLaunchKernelGGL(k_ring_extend3, dim3(mxd::grid_for_chunks(n)), dim3(256), 0, st,
+                       (const u64*)s0, (u128*)out0, (u128*)out1, n, os, keys, nn[0], nn[1], nn[2],
+                       nn[3], nn[4], nn[5]);
+  }
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : -100 - (int)e;
+}
+
 int launch_share3(int kind, int words, const void* x, void* out0, void* out1, int64_t n, int j,
                   const mxd::KeySrc& keys, uint64_t n1, uint64_t na, void* stream) {
   if (n == 0) return 0;
@@ -342,6 +444,13 @@ int mxh_trunc_pr3_kmo(int words, const void* s0, void* out0, void* out1, int64_t
   const uint32_t* ptrs[2] = {slot_k0, slot_k2};
   return launch_trunc_pr3(words, s0, out0, out1, n, ostride, m, mxd::keysrc_slots(ptrs, 2), nn,
                           stream, cm);
+}
+
+int mxh_ring_extend3_k(const void* s0, void* out0, void* out1, int64_t n,
+                       const uint32_t* slot_k0, const uint32_t* slot_k2, const uint64_t* nn,
+                       void* stream) {
+  const uint32_t* ptrs[2] = {slot_k0, slot_k2};
+  return launch_ring_extend3(s0, out0, out1, n, n, mxd::keysrc_slots(ptrs, 2), nn, stream);
 }
 
 int mxh_share3(int kind, int words, const void* x, void* out0, void* out1, int64_t n, int j,

@@ -34,7 +34,43 @@ extern "C" int mxh_share3_k(int kind, int words, const void* x, void* out0, void
                             int64_t n, int j, const uint32_t* slot_next,
                             const uint32_t* slot_all, uint64_t n1, uint64_t na, void* stream);
 
+extern "C" int mxh_ring_extend3_k(const void* s0, void* out0, void* out1, int64_t n,
+                                  const uint32_t* slot_k0, const uint32_t* slot_k2,
+                                  const uint64_t* nonces, void* stream);
+
 namespace {
+
+// all six streams at 128-bit width (element i = the composed protocol's 128-bit draw);
+// r0, r1, M0 use the low 64 bits
+int ring_extend3_host(const uint64_t* s0, unsigned __int128* out0, unsigned __int128* out1,
+                      int64_t n, const uint8_t* k0, const uint8_t* k2, const uint64_t* nn) {
+  using u128 = unsigned __int128;
+  mx_cpu_parallel_for(n, 1 << 12, [&](int64_t s, int64_t e) {
+    const int64_t CH = 512;
+    std::vector<u128> r0(CH), r1(CH), R0(CH), M0(CH), z0(CH), z2(CH);
+    for (int64_t c = s; c < e; c += CH) {
+      int64_t len = std::min(CH, e - c);
+      mx_cpu_prf_range(k0, nn[0], 2, c, len, r0.data());
+      mx_cpu_prf_range(k2, nn[1], 2, c, len, r1.data());
+      mx_cpu_prf_range(k0, nn[2], 2, c, len, R0.data());
+      mx_cpu_prf_range(k0, nn[3], 2, c, len, M0.data());
+      mx_cpu_prf_range(k0, nn[4], 2, c, len, z0.data());
+      mx_cpu_prf_range(k2, nn[5], 2, c, len, z2.data());
+      for (int64_t t = 0; t < len; ++t) {
+        int64_t i = c + t;
+        u128 z1 = mxf::ring_extend_z1(s0[i], s0[n + i], s0[2 * n + i], (uint64_t)r0[t],
+                                      (uint64_t)r1[t], R0[t], (uint64_t)M0[t], z0[t], z2[t]);
+        out0[i] = z0[t];
+        out0[n + i] = z1;
+        out0[2 * n + i] = z2[t];
+        out1[i] = z1;
+        out1[n + i] = z2[t];
+        out1[2 * n + i] = z0[t];
+      }
+    }
+  });
+  return 0;
+}
 
 template <class T>
 int trunc3_host(const T* s0, T* out0, T* out1, int64_t n, int m, const uint8_t* k0,
@@ -189,6 +225,17 @@ int mx_trunc_pr3_kmo(int dev, int words, const void* s0, void* out0, void* out1,
   }
   return -2;
 }
+
+int mx_ring_extend3_k(int dev, const void* s0, void* out0, void* out1, int64_t n,
+                      const uint32_t* slot_k0, const uint32_t* slot_k2, const uint64_t* nonces,
+                      void* stream) {
+  if (dev) return mxh_ring_extend3_k(s0, out0, out1, n, slot_k0, slot_k2, nonces, stream);
+  return ring_extend3_host((const uint64_t*)s0, (unsigned __int128*)out0,
+                           (unsigned __int128*)out1, n, (const uint8_t*)slot_k0,
+                           (const uint8_t*)slot_k2, nonces);
+}
+
+int64_t mx_ring_extend3_lat_max(void) { return mxf::kRingExtendLatMax; }
 
 int mx_share3_k(int dev, int kind, int words, const void* x, void* out0, void* out1, int64_t n,
                 int j, const uint32_t* slot_next, const uint32_t* slot_all, uint64_t n1,

@@ -93,8 +93,10 @@ _NP_CONST = {
 
 def map_dtype(d: edt.DType, fixedpoint_ring=128) -> T.TensorDType:
     if d.is_fixedpoint:
-        kind = "Fixed64" if fixedpoint_ring == 64 else "Fixed128"
-        return T.TensorDType(kind, d.integral_precision, d.fractional_precision)
+        ring = d.ring or fixedpoint_ring  # a pinned ring wins, and stays pinned in the IR
+        kind = "Fixed64" if ring == 64 else "Fixed128"
+        return T.TensorDType(kind, d.integral_precision, d.fractional_precision,
+                             pinned=d.ring is not None)
     m = {
         "float32": T.FLOAT32,
         "float64": T.FLOAT64,

@@ -63,9 +63,26 @@ def typing_pass(comp: Computation, **_) -> Computation:
                         args[i].name == "Tensor" and args[i].inner is not None
                         and args[i].inner.kind == "Unknown"):
                     args[i] = src.sig.ret
+        _check_one_ring(op, args)
         out.append(Operation(op.name, op.kind, list(op.inputs), op.placement,
                              Signature(tuple(args), op.sig.ret, op.sig.variadic), dict(op.attrs)))
     return Computation(out)
+
+
+def _check_one_ring(op, args):
+    """The fixed-point operands of one replicated operation share a ring: shares over
+    Z_2^64 and Z_2^128 do not combine, the narrow operand has to be widened first."""
+    from moose_amd.ir.computation import ReplicatedPlacement
+
+    if not isinstance(op.placement, ReplicatedPlacement):
+        return
+    fixed = [a.inner for a in args if a.name == "Tensor" and a.inner is not None
+             and a.inner.is_fixed]
+    if len({d.kind for d in fixed}) > 1:
+        raise CompilationError(
+            f"{op.name}: {op.kind} on a replicated placement mixes operands over Z_2^64 and "
+            f"Z_2^128 ({', '.join(d.to_textual() for d in fixed)}); Cast the Fixed64 operand "
+            "to a Fixed128 dtype first (the widening is exact)")
 
 
 def deprecated_shape(comp: Computation, **_) -> Computation:

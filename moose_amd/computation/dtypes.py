@@ -9,7 +9,7 @@ import numpy as np
 
 
 class DType:
-    __slots__ = ("_name", "_short", "_np", "_flags", "_prec")
+    __slots__ = ("_name", "_short", "_np", "_flags", "_prec", "_ring")
 
     _FLAG_NAMES = (
         "is_native",
@@ -20,7 +20,8 @@ class DType:
         "is_boolean",
     )
 
-    def __init__(self, name, short, numpy_dtype, flags, precision=(None, None)):
+    def __init__(self, name, short, numpy_dtype, flags, precision=(None, None), ring=None):
+        self._ring = ring
         self._name = name
         self._short = short
         self._np = numpy_dtype
@@ -47,6 +48,12 @@ class DType:
         return self._prec[1]
 
     @property
+    def ring(self):
+        """Ring width (64 or 128) a fixed-point dtype is pinned to; None: the run-wide
+        ``fixedpoint_ring`` decides."""
+        return self._ring
+
+    @property
     def name(self):
         return self._name
 
@@ -55,19 +62,20 @@ class DType:
         return self._np
 
     def __str__(self):
-        return self._name
+        return self._name if self._ring is None else f"{self._name}@ring{self._ring}"
 
     def __repr__(self):
-        return self._short
+        return self._short if self._ring is None else f"{self._short}@ring{self._ring}"
 
     def __eq__(self, other):
-        return isinstance(other, DType) and (self._name, self._short) == (
+        return isinstance(other, DType) and (self._name, self._short, self._ring) == (
             other._name,
             other._short,
+            other._ring,
         )
 
     def __hash__(self):
-        return hash((self._name, self._short))
+        return hash((self._name, self._short, self._ring))
 
 
 _N, _FX, _I, _F, _S, _B = (
@@ -89,13 +97,17 @@ bool_ = DType("bool_", "bool", np.bool_, {_N, _B})
 ring64 = DType("ring64", "ring64", None, {_I})
 
 
-def fixed(integ, frac):
-    """Fixed-point dtype with ``integ`` integral and ``frac`` fractional bits."""
+def fixed(integ, frac, ring=None):
+    """Fixed-point dtype with ``integ`` integral and ``frac`` fractional bits.  ``ring``
+    (64 or 128) pins the ring its values are shared over, whatever the run-wide
+    ``fixedpoint_ring``; None leaves the choice to that setting."""
     for p in (integ, frac):
         if not isinstance(p, int):
             raise TypeError("Fixed-point dtype expects integers for its bounds.")
+    if ring not in (None, 64, 128):
+        raise ValueError("Fixed-point dtype expects ring=64, ring=128 or None.")
     return DType(
-        f"fixed{integ}_{frac}", f"q{integ}.{frac}", None, {_FX, _S}, (integ, frac)
+        f"fixed{integ}_{frac}", f"q{integ}.{frac}", None, {_FX, _S}, (integ, frac), ring
     )
 
 

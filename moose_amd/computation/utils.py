@@ -68,12 +68,15 @@ def _encode(val):
         }
     if isinstance(val, dtypes.DType):
         if FIXED_DTYPE_REGEX.match(val.name):
-            return {
+            d = {
                 "__type__": "DType",
                 "name": "fixed",
                 "integral_precision": val.integral_precision,
                 "fractional_precision": val.fractional_precision,
             }
+            if val.ring is not None:  # a pinned ring only: unpinned bytes stay as they were
+                d["ring"] = val.ring
+            return d
         return {"__type__": "DType", "name": val.name}
     if isinstance(val, np.ndarray):
         return {
@@ -112,7 +115,8 @@ def _decode(obj):
     if tname == "DType":
         name = obj["name"]
         if name == "fixed":
-            return dtypes.fixed(obj["integral_precision"], obj["fractional_precision"])
+            return dtypes.fixed(obj["integral_precision"], obj["fractional_precision"],
+                                obj.get("ring"))
         m = FIXED_DTYPE_REGEX.match(name)
         if m is not None:
             return dtypes.fixed(int(m.group(1)), int(m.group(2)))

@@ -392,7 +392,12 @@ class Computation:
 
     def digest(self) -> str:
         """Stable content hash (used as the compiled-plan cache key)."""
-        return hashlib.blake2b(self.to_textual().encode(), digest_size=16).hexdigest()
+        text = self.to_textual()
+        pins = [op.name for op in self.operations if op.sig is not None and any(
+            getattr(t.dtype, "pinned", False) for t in tuple(op.sig.args) + (op.sig.ret,))]
+        if pins:  # pinned rings are not in the textual form
+            text += "\n# pinned: " + " ".join(pins)
+        return hashlib.blake2b(text.encode(), digest_size=16).hexdigest()
 
 
 # ---------------------------------------------------------------------------

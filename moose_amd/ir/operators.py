@@ -118,7 +118,7 @@ EXTENSION_OPERATORS = {
     # host primitives of lowered graphs that the reference expresses with other ops
     "Sar": [("amount", "int")],                      # arithmetic right shift
     "AddConst": [("value", "const")],                # x + public ring constant
-    "RingCast": [],                                  # Z_2^128 -> Z_2^64 (width = ret type)
+    "RingCast": [],                                  # ring width change (width = ret type)
     "FromBool": [],
     "ToBool": [],
     "RingToInt": [],

@@ -20,13 +20,15 @@ _FORMAT = "moosex-ir-1"
 
 def _enc_ty(t: Ty):
     if isinstance(t.inner, TensorDType):
-        return [t.name, t.inner.kind, t.inner.integral_precision, t.inner.fractional_precision]
+        d = t.inner
+        enc = [t.name, d.kind, d.integral_precision, d.fractional_precision]
+        return enc + [True] if d.pinned else enc  # a pinned ring only: other bytes unchanged
     return [t.name, t.inner]
 
 
 def _dec_ty(x):
-    if len(x) == 4:
-        return Ty(x[0], TensorDType(x[1], x[2], x[3]))
+    if len(x) >= 4:
+        return Ty(x[0], TensorDType(x[1], x[2], x[3], pinned=len(x) > 4 and bool(x[4])))
     return Ty(x[0], x[1])
 
 

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import re
 from dataclasses import dataclass
+from dataclasses import field
 from typing import Optional
 from typing import Union
 
@@ -20,6 +21,10 @@ class TensorDType:
     kind: str  # Fixed64 | Fixed128 | Float32 | Float64 | Bool | Uint64 | Unknown
     integral_precision: int = 0
     fractional_precision: int = 0
+    # the ring is the author's choice (eDSL ``fixed(i, f, ring=)``): a run-wide
+    # ``fixedpoint_ring`` does not move it.  Not part of the type's identity or of its
+    # textual form; the compact msgpack form carries it.
+    pinned: bool = field(default=False, compare=False)
 
     @property
     def is_fixed(self):

@@ -182,6 +182,8 @@ _SIGS = {
         c_int,
         [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_u64, c_u64, c_vp],
     ),
+    "mx_ring_extend3_k": (c_int, [c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "mx_ring_extend3_lat_max": (c_i64, []),
     "mx_trunc_party_r0": (
         c_int,
         [c_int, c_int, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

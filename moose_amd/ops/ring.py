@@ -1262,6 +1262,28 @@ def prf_expand_k(slot_ptr: int, nkeys: int, nonce: int, shape, bits, device) -> 
     return out
 
 
+def ring_extend3_k(s0: RT, slot_k0: int, slot_k2: int, nonces, out=None):
+    """Exact widening Z_2^64 -> Z_2^128 of a stacked replicated sharing (slots ``s0``,
+    [3, ...]), all three parties in one kernel (csrc/rss_fused.h: ring_extend_z1; valid for
+    -2^62 <= x < 2^62).  ``slot_k0`` / ``slot_k2``: addresses of the dealer key slots;
+    ``nonces``: r0, r1, R0, M0, z0, z2.  Returns the two share vectors (a ``ring4`` pair
+    unless ``out`` = (out0, out1) is given)."""
+    if s0.bits != 64 or not s0.shape or s0.shape[0] != 3:
+        raise TypeError("ring_extend3_k: expects stacked [3, ...] Z_2^64 slots")
+    d = s0.data.contiguous()
+    n = d.numel() // 3
+    out0, out1 = out if out is not None else ring4(s0.shape, 128, d.device)
+    nn = (ctypes.c_uint64 * 6)(*[int(v) & MASK64 for v in nonces])
+    nat.check(
+        nat.lib().mx_ring_extend3_k(
+            nat.dev_of(d), nat.ptr(d), nat.ptr(out0.data), nat.ptr(out1.data), n,
+            ctypes.c_void_p(slot_k0), ctypes.c_void_p(slot_k2), nn, nat.stream_of(d),
+        ),
+        "ring_extend3",
+    )
+    return out0, out1
+
+
 def prg_bytes(key: bytes, nonce: int, nbytes: int, device="cpu", ctr0=0) -> torch.Tensor:
     out = torch.empty(nbytes, dtype=torch.uint8, device=device)
     kb = nat.key_buffer([key])

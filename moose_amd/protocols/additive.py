@@ -199,3 +199,57 @@ def trunc_pr(sess, rep_plc, x: AdtTensor, m: int, nonces, shapes=None) -> AdtTen
             y = sess.h("AddConst", host, y, value=-(1 << (k - 1 - m)), bits=bits)
         outs.append(y)
     return AdtTensor(x.plc, bits, outs[0], outs[1])
+
+
+def ring_extend(sess, rep_plc, x: AdtTensor, nonces, shapes=None) -> AdtTensor:
+    """Additive sharing over Z_2^64 -> the same value over Z_2^128 (sign extended), exact
+    for -2^62 <= x < 2^62, with dealer P2: TruncPr's overflow trick without the truncation.
+
+    With x' = x + 2^62 in [0, 2^63) and c = x' + r (mod 2^64) opened, the integer sum x' + r
+    wraps exactly when r_msb = 1 and c_msb = 0, so over Z_2^128
+    x' = c - R + 2^64 r_msb (1 - c_msb) with R = r zero-extended -- linear in the dealer's
+    additive shares of R and r_msb.  r = r0 + r1 (r0 = PRF(k_0) [P0, P2], r1 = PRF(k_2)
+    [P1, P2]) needs no message; the dealer sends P1 its shares R1 and M1 (P0 re-derives
+    R0, M0 from k_0); M1 only matters modulo 2^64 (it is shifted left by 64) and travels as
+    a 64-bit tensor.  Every stream is drawn at 128-bit width and narrowed where it is
+    shorter, as the fused kernel draws it (csrc/rss_fused.h: ring_extend_z1)."""
+    p0, p1, p2 = rep_plc.owners
+    if x.bits != 64:
+        raise ValueError("ring_extend widens a sharing over Z_2^64")
+    nr0, nr1, nR, nM = nonces
+    if shapes is None:
+        sh0 = sess.h("Shape", p0, x.s0)
+        sh1 = sess.h("Shape", p1, x.s1)
+        sh2 = sess.move(sh0, p2)
+    else:
+        sh0, sh1, sh2 = shapes
+
+    def low(host, key_id, sh, nonce):  # the low 64 bits of a 128-bit draw
+        return sess.h("RingCast", host, sess.h_prf(rep_plc, host, key_id, sh, 128, nonce),
+                      bits=64)
+
+    r = sess.h("Add", p2, low(p2, 0, sh2, nr0), low(p2, 2, sh2, nr1))
+    R = sess.h("RingCast", p2, r, bits=128)  # zero extension
+    r_msb = sess.h("Shr", p2, r, amount=63)
+    R1 = sess.move(sess.h("Sub", p2, R, sess.h_prf(rep_plc, p2, 0, sh2, 128, nR)), p1)
+    M1 = sess.move(sess.h("Sub", p2, r_msb, low(p2, 0, sh2, nM)), p1)
+    r0 = low(p0, 0, sh0, nr0)
+    R0 = sess.h_prf(rep_plc, p0, 0, sh0, 128, nR)
+    M0 = low(p0, 0, sh0, nM)
+    r1 = low(p1, 2, sh1, nr1)
+    mk0 = sess.h("Add", p0, sess.h("AddConst", p0, x.s0, value=1 << 62, bits=64), r0)
+    mk1 = sess.h("Add", p1, x.s1, r1)
+    c_at0 = sess.h("Add", p0, mk0, sess.move(mk1, p0))
+    c_at1 = sess.h("Add", p1, mk1, sess.move(mk0, p1))
+    outs = []
+    for host, c, Rs, Ms, first in ((p0, c_at0, R0, M0, True), (p1, c_at1, R1, M1, False)):
+        # (1 - c_msb) * M: this party's share of the wrap bit r_msb AND NOT c_msb
+        nc = sess.h("AddConst", host, sess.h("Neg", host, sess.h("Shr", host, c, amount=63)),
+                    value=1, bits=64)
+        wrap = sess.h("RingCast", host, sess.h("Mul", host, nc, Ms), bits=128)
+        y = sess.h("Sub", host, sess.h("Shl", host, wrap, amount=64), Rs)
+        if first:
+            y = sess.h("Add", host, y, sess.h("RingCast", host, c, bits=128))
+            y = sess.h("AddConst", host, y, value=-(1 << 62), bits=128)
+        outs.append(y)
+    return AdtTensor(x.plc, 128, outs[0], outs[1])

@@ -228,11 +228,8 @@ def cast(sess, x: RepFixed, target) -> RepFixed:
     df = target.fractional_precision - x.frac
     if df < 0:
         t = rep.trunc_pr(sess, t, -df)
-    if bits != t.bits:
-        if bits < t.bits:
-            t = rep.ring_cast(sess, t, bits)
-        else:
-            raise NotImplementedError("replicated ring extension 64 -> 128")
+    if bits != t.bits:  # narrowing is share-wise; widening is rep.ring_extend (exact)
+        t = rep.ring_cast(sess, t, bits)
     if df > 0:
         t = rep.shl(sess, t, df)
     return RepFixed(t, target.fractional_precision, target.integral_precision)

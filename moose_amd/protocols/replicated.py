@@ -1248,7 +1248,44 @@ def relu(sess, x: RepTensor) -> RepTensor:
     return sub(sess, x, mul(sess, s, x))
 
 
+def ring_extend(sess, x: RepTensor, bits: int = 128) -> RepTensor:
+    """Z_2^64 -> Z_2^128, exact (the result reveals to the sign extension of x, bit for
+    bit) for -2^62 <= x < 2^62 -- the input bound of trunc_pr, and its dealer pattern:
+      * r = r0 + r1 with r0 = PRF(k_0) [P0,P2] and r1 = PRF(k_2) [P1,P2]: no message;
+      * the dealer's shares of R = r over Z_2^128 and of r_msb for P1 are its only
+        messages (input independent);
+      * round 1: P0 and P1 open c = x + 2^62 + r (mod 2^64); the sum wrapped exactly when
+        r_msb = 1 and c_msb = 0, so x + 2^62 = c - R + 2^64 r_msb (1 - c_msb);
+      * round 2: additive -> replicated exchange.
+
+    A fused stacked session runs one kernel for all three parties; every other session
+    (per-party threads, SPMD, cyclic, symbolic) composes the protocol from host primitives
+    with the same nonces, hence the same shares."""
+    if x.bits == bits:
+        return x
+    if x.bits != 64 or bits != 128 or x.kind != "arith":
+        raise NotImplementedError(f"ring extension of a Z_2^{x.bits} {x.kind} sharing to "
+                                  f"Z_2^{bits}")
+    with span("rep.ring_extend"):
+        plc = x.plc
+        nr0, nr1, nR, nM = (sess.nonce(plc) for _ in range(4))
+        n0, n2 = sess.nonce(plc), sess.nonce(plc)
+        if getattr(sess, "fused", False):
+            s0, s1 = sess.fused_ring_extend(x, (nr0, nr1, nR, nM, n0, n2))
+            return RepTensor(plc, bits, "arith", s0, s1)
+        from moose_amd.protocols import additive
+
+        # every party takes the shape from its own share: no metadata messages
+        sh = [sess.h("Shape", plc.owners[i], sess.take(x.s0, i)) for i in range(3)]
+        a = additive.from_rep(sess, x)  # P0: x0 + x1, P1: x2 (local)
+        y = additive.ring_extend(sess, plc, a, (nr0, nr1, nR, nM), shapes=sh)
+        return additive.to_rep(sess, plc, y, nonces=(n0, n2), shapes=sh)
+
+
 def ring_cast(sess, x: RepTensor, bits: int) -> RepTensor:
-    """Z_2^128 -> Z_2^64 (share-wise truncation; valid for values that fit)."""
+    """Ring width change: Z_2^128 -> Z_2^64 share-wise (valid for values that fit);
+    Z_2^64 -> Z_2^128 by the ring extension protocol (``ring_extend``)."""
+    if x.bits == 64 and bits == 128:
+        return ring_extend(sess, x, bits)
     return RepTensor(x.plc, bits, x.kind, sess.p("RingCast", x.plc, x.s0, bits=bits),
                      sess.p("RingCast", x.plc, x.s1, bits=bits))

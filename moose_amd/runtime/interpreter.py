@@ -648,7 +648,7 @@ class Interpreter:
     # dtype helpers
     # ------------------------------------------------------------------------
     def _dtype(self, d: T.TensorDType) -> T.TensorDType:
-        if d is not None and d.kind == "Fixed128" and self.fixed_ring == 64:
+        if d is not None and d.kind == "Fixed128" and self.fixed_ring == 64 and not d.pinned:
             return T.TensorDType("Fixed64", d.integral_precision, d.fractional_precision)
         return d
 
@@ -1105,7 +1105,13 @@ class Interpreter:
             if src.is_fixed:
                 v = x.v
                 df = target.fractional_precision - src.fractional_precision
-                if src.ring_bits != bits:
+                if src.ring_bits < bits:
+                    # sign extension from the zero-extending RingCast: (x + 2^63) - 2^63
+                    half = 1 << (src.ring_bits - 1)
+                    v = sess.h("AddConst", host, v, value=half, bits=src.ring_bits)
+                    v = sess.h("RingCast", host, v, bits=bits)
+                    v = sess.h("AddConst", host, v, value=-half, bits=bits)
+                elif src.ring_bits != bits:
                     v = sess.h("RingCast", host, v, bits=bits)
                 if df > 0:
                     v = sess.h("Shl", host, v, amount=df)

@@ -967,6 +967,16 @@ class StackedSession(Session):
         self._trunc_traffic(x, out0.numel() * out0.element_size() // 3)
         return PV(x.plc, R.RT(out0, x.bits)), PV(x.plc, R.RT(out1, x.bits))
 
+    def fused_ring_extend(self, x, nonces):
+        """All three parties' ring extension Z_2^64 -> Z_2^128 in one kernel (see
+        replicated.ring_extend).  ``nonces``: r0, r1, R0, M0, z0, z2."""
+        out0, out1 = R.ring_extend3_k(x.s0.v, self.key_ptr(x.plc, 0), self.key_ptr(x.plc, 2),
+                                      nonces)
+        # two messages per link, one of 64-bit and one of 128-bit elements (dealer: M1, R1;
+        # P0 <-> P1: the opening of c, then w): 12 bytes per element on average
+        self._trunc_traffic(x, 12 * (x.s0.v.numel() // 3))
+        return PV(x.plc, out0), PV(x.plc, out1)
+
     def p_wsum_trunc_add(self, plc, S, weights, m, cadd: int):
         """rep.trunc_pr(weighted sum of the powers stack ``S`` (a party vector [3, R, ...]),
         m) + the public constant ``cadd`` on party 0's share, in one launch
