@@ -310,6 +310,21 @@ int mx_trunc_party_r1(int dev, int words, int64_t n, int m, int ncomp, const int
                       const void* msg, const void* rmk, const void* rrt, const void* rrm,
                       void* w, void* out0, void* out1, const uint32_t* const* slots,
                       const uint64_t* nonces, void* stream);
+// Per-party rounds of the ring extension Z_2^64 -> Z_2^128 (rss_party.hip), same layout:
+// s0, s1, msg, rmk, msg_M / rM: [ncomp, n] u64; msg_R / rR, w, out0, out1: [ncomp, n] u128.
+// nonces: r0, r1, R0, M0, z0, z2, every stream drawn at 128-bit width (as mx_ring_extend3_k).
+// Round 0 writes the outgoing messages (P0 / P1: the masked opening share in msg; P2: R1 in
+// msg_R, M1 in msg_M) and P2's new shares; round 1 takes the other party's msg (rmk) and the
+// dealer shares (rR, rM; P1 only) and writes w (P0: y0 - z0, P1: y1 - z2) and P0's s0 /
+// P1's s1.
+int mx_ring_extend_party_r0(int dev, int64_t n, int ncomp, const int* roles, const void* s0,
+                            const void* s1, void* msg, void* msg_R, void* msg_M, void* out0,
+                            void* out1, const uint32_t* const* slots, const uint64_t* nonces,
+                            void* stream);
+int mx_ring_extend_party_r1(int dev, int64_t n, int ncomp, const int* roles, const void* msg,
+                            const void* rmk, const void* rR, const void* rM, void* w, void* out0,
+                            void* out1, const uint32_t* const* slots, const uint64_t* nonces,
+                            void* stream);
 // Share by member j, per component: rel[c] = (role - j) mod 3; key slots per component:
 // rel 0 (next, all), rel 1 (own, all), rel 2 (all, all).  The owner's out0 (its masked
 // x_j) is then sent to P_{j+2}, whose out1 it becomes.

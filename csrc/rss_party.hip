@@ -222,6 +222,149 @@ __global__ void __launch_bounds__(256) k_trunc_party_r1(int64_t n, int m, Roles 
                       ncomp);
 }
 
+// Ring extension Z_2^64 -> Z_2^128 (dealer P2; rss_fused.h: ring_extend_dealer / _mask0 / _y),
+// rounds as TruncPr's:
+//   r0: P0 msg = x0 + x1 + 2^62 + r0 (u64)        -> P1
+//       P1 msg = x2 + r1 (u64)                     -> P0
+//       P2 R1 (u128), M1 (u64)                     -> P1;  P2's new shares (z2, z0)
+//   r1: P0 c = msg + rmk, w0 = y0 - z0             -> P1;  P0's s0 = z0
+//       P1 c = msg + rmk, w1 = y1 - z2             -> P0;  P1's s1 = z2
+//   r2: z1 = w0 + w1 (elementwise, host side)
+// All six streams are drawn at 128-bit lane width, one chunk per element, as k_ring_extend3
+// and additive.ring_extend draw them (r0, r1, M0 use the low 64 bits of their lane): the
+// walk is over n chunks although the input is u64.
+__device__ __forceinline__ void d_ring_extend_party_r0(
+    int64_t n, const Roles& roles, const u64* __restrict__ s0, const u64* __restrict__ s1,
+    u64* __restrict__ msg, u128* __restrict__ msg_R, u64* __restrict__ msg_M,
+    u128* __restrict__ out0, u128* __restrict__ out1, const mxd::KeySrc& keys, uint64_t n_r0,
+    uint64_t n_r1, uint64_t n_R, uint64_t n_M, uint64_t n_z0, uint64_t n_z2, int ncomp) {
+  __shared__ uint32_t rks[mxd::kMaxKeySlots][mxd::kKeyWords];
+  mxd::stage_keys(rks, keys, 2 * ncomp);
+  MX_PARTY_WALK(n, ncomp) {
+    const int c = (int)(g / nblk);
+    const uint64_t B = (uint64_t)(g - c * nblk);
+    const int role = roles.r[c];
+    const uint32_t* own = rks[2 * c];
+    const uint32_t* nxt = rks[2 * c + 1];
+    const int64_t base = (int64_t)c * n;
+    if (role == 0) {  // k0 = own
+      uint32_t wa[16];
+      mx::chacha_block(own, n_r0, B, wa);
+#pragma unroll
+      for (int part = 0; part < 4; ++part) {
+        const int64_t i = (int64_t)mx::ks_chunk(B, part);
+        if (i >= n) break;
+        uint64_t al, ah;
+        mx::part_u64(wa, part, &al, &ah);
+        msg[base + i] = mxf::ring_extend_mask0(s0[base + i], s1[base + i], al);
+      }
+    } else if (role == 1) {  // k2 = next
+      uint32_t wa[16];
+      mx::chacha_block(nxt, n_r1, B, wa);
+#pragma unroll
+      for (int part = 0; part < 4; ++part) {
+        const int64_t i = (int64_t)mx::ks_chunk(B, part);
+        if (i >= n) break;
+        uint64_t al, ah;
+        mx::part_u64(wa, part, &al, &ah);
+        msg[base + i] = s1[base + i] + al;
+      }
+    } else if (role == 2) {  // k2 = own, k0 = next
+      // streams r0, r1, R0, M0, z0, z2
+      uint32_t w[6][16];
+      mx::chacha_block(nxt, n_r0, B, w[0]);
+      mx::chacha_block(own, n_r1, B, w[1]);
+      mx::chacha_block(nxt, n_R, B, w[2]);
+      mx::chacha_block(nxt, n_M, B, w[3]);
+      mx::chacha_block(nxt, n_z0, B, w[4]);
+      mx::chacha_block(own, n_z2, B, w[5]);
+#pragma unroll
+      for (int part = 0; part < 4; ++part) {
+        const int64_t i = (int64_t)mx::ks_chunk(B, part);
+        if (i >= n) break;
+        uint64_t lo[6], hi[6];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) mx::part_u64(w[q], part, &lo[q], &hi[q]);
+        u128 R1;
+        u64 M1;
+        mxf::ring_extend_dealer(lo[0], lo[1], mxd::pick<u128>(lo[2], hi[2], 0), lo[3], &R1, &M1);
+        msg_R[base + i] = R1;
+        msg_M[base + i] = M1;
+        out0[base + i] = mxd::pick<u128>(lo[5], hi[5], 0);
+        out1[base + i] = mxd::pick<u128>(lo[4], hi[4], 0);
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) k_ring_extend_party_r0(
+    int64_t n, Roles roles, const u64* __restrict__ s0, const u64* __restrict__ s1,
+    u64* __restrict__ msg, u128* __restrict__ msg_R, u64* __restrict__ msg_M,
+    u128* __restrict__ out0, u128* __restrict__ out1, mxd::KeySrc keys, uint64_t n_r0,
+    uint64_t n_r1, uint64_t n_R, uint64_t n_M, uint64_t n_z0, uint64_t n_z2, int ncomp) {
+  d_ring_extend_party_r0(n, roles, s0, s1, msg, msg_R, msg_M, out0, out1, keys, n_r0, n_r1, n_R,
+                         n_M, n_z0, n_z2, ncomp);
+}
+
+__device__ __forceinline__ void d_ring_extend_party_r1(
+    int64_t n, const Roles& roles, const u64* __restrict__ msg, const u64* __restrict__ rmk,
+    const u128* __restrict__ rR, const u64* __restrict__ rM, u128* __restrict__ w,
+    u128* __restrict__ out0, u128* __restrict__ out1, const mxd::KeySrc& keys, uint64_t n_R,
+    uint64_t n_M, uint64_t n_z0, uint64_t n_z2, int ncomp) {
+  __shared__ uint32_t rks[mxd::kMaxKeySlots][mxd::kKeyWords];
+  mxd::stage_keys(rks, keys, 2 * ncomp);
+  MX_PARTY_WALK(n, ncomp) {
+    const int c = (int)(g / nblk);
+    const uint64_t B = (uint64_t)(g - c * nblk);
+    const int role = roles.r[c];
+    const int64_t base = (int64_t)c * n;
+    if (role == 0) {
+      const uint32_t* k0 = rks[2 * c];
+      uint32_t wR[16], wM[16], wz[16];
+      mx::chacha_block(k0, n_R, B, wR);
+      mx::chacha_block(k0, n_M, B, wM);
+      mx::chacha_block(k0, n_z0, B, wz);
+#pragma unroll
+      for (int part = 0; part < 4; ++part) {
+        const int64_t i = (int64_t)mx::ks_chunk(B, part);
+        if (i >= n) break;
+        uint64_t Rl, Rh, ml, mh, zl, zh;
+        mx::part_u64(wR, part, &Rl, &Rh);
+        mx::part_u64(wM, part, &ml, &mh);
+        mx::part_u64(wz, part, &zl, &zh);
+        const u64 cc = msg[base + i] + rmk[base + i];
+        const u128 z0 = mxd::pick<u128>(zl, zh, 0);
+        w[base + i] = mxf::ring_extend_y(cc, mxd::pick<u128>(Rl, Rh, 0), ml, true) - z0;
+        out0[base + i] = z0;
+      }
+    } else if (role == 1) {
+      const uint32_t* k2 = rks[2 * c + 1];
+      uint32_t wz[16];
+      mx::chacha_block(k2, n_z2, B, wz);
+#pragma unroll
+      for (int part = 0; part < 4; ++part) {
+        const int64_t i = (int64_t)mx::ks_chunk(B, part);
+        if (i >= n) break;
+        uint64_t zl, zh;
+        mx::part_u64(wz, part, &zl, &zh);
+        const u64 cc = msg[base + i] + rmk[base + i];
+        const u128 z2 = mxd::pick<u128>(zl, zh, 0);
+        w[base + i] = mxf::ring_extend_y(cc, rR[base + i], rM[base + i], false) - z2;
+        out1[base + i] = z2;
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) k_ring_extend_party_r1(
+    int64_t n, Roles roles, const u64* __restrict__ msg, const u64* __restrict__ rmk,
+    const u128* __restrict__ rR, const u64* __restrict__ rM, u128* __restrict__ w,
+    u128* __restrict__ out0, u128* __restrict__ out1, mxd::KeySrc keys, uint64_t n_R,
+    uint64_t n_M, uint64_t n_z0, uint64_t n_z2, int ncomp) {
+  d_ring_extend_party_r1(n, roles, msg, rmk, rR, rM, w, out0, out1, keys, n_R, n_M, n_z0, n_z2,
+                         ncomp);
+}
+
 template <class T>
 __device__ __forceinline__ void d_share_party(int kind, int64_t n, const Roles& rel,
                                               const void* __restrict__ xv, T* __restrict__ out0,
@@ -533,6 +676,8 @@ MX_X3(k_trunc_party_r0<u64>, d_trunc_party_r0<u64>);
 MX_X3(k_trunc_party_r0<u128>, d_trunc_party_r0<u128>);
 MX_X3(k_trunc_party_r1<u64>, d_trunc_party_r1<u64>);
 MX_X3(k_trunc_party_r1<u128>, d_trunc_party_r1<u128>);
+MX_X3(k_ring_extend_party_r0, d_ring_extend_party_r0);
+MX_X3(k_ring_extend_party_r1, d_ring_extend_party_r1);
 MX_X3(k_share_party<u64>, d_share_party<u64>);
 MX_X3(k_share_party<u128>, d_share_party<u128>);
 MX_X3(k_dot_tail_r0<u64>, d_dot_tail_r0<u64>);
@@ -607,6 +752,38 @@ int mxh_trunc_party_r1(int words, int64_t n, int m, int ncomp, const int* roles,
   } else {
     return -2;
   }
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : -100 - (int)e;
+}
+
+int mxh_ring_extend_party_r0(int64_t n, int ncomp, const int* roles, const void* s0,
+                             const void* s1, void* msg, void* msg_R, void* msg_M, void* out0,
+                             void* out1, const uint32_t* const* slots, const uint64_t* nn,
+                             void* stream) {
+  if (n == 0) return 0;
+  if (ncomp < 1 || ncomp > 3) return -3;
+  const mxd::KeySrc k = mxd::keysrc_slots(slots, 2 * ncomp);
+  const Roles rr = roles_of(roles, ncomp);
+  hipLaunchKernelGGL(k_ring_extend_party_r0, dim3(mxd::grid_for_chunks(n) * ncomp), dim3(256), 0,
+                     (hipStream_t)stream, n, rr, (const u64*)s0, (const u64*)s1, (u64*)msg,
+                     (u128*)msg_R, (u64*)msg_M, (u128*)out0, (u128*)out1, k, nn[0], nn[1], nn[2],
+                     nn[3], nn[4], nn[5], ncomp);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : -100 - (int)e;
+}
+
+int mxh_ring_extend_party_r1(int64_t n, int ncomp, const int* roles, const void* msg,
+                             const void* rmk, const void* rR, const void* rM, void* w,
+                             void* out0, void* out1, const uint32_t* const* slots,
+                             const uint64_t* nn, void* stream) {
+  if (n == 0) return 0;
+  if (ncomp < 1 || ncomp > 3) return -3;
+  const mxd::KeySrc k = mxd::keysrc_slots(slots, 2 * ncomp);
+  const Roles rr = roles_of(roles, ncomp);
+  hipLaunchKernelGGL(k_ring_extend_party_r1, dim3(mxd::grid_for_chunks(n) * ncomp), dim3(256), 0,
+                     (hipStream_t)stream, n, rr, (const u64*)msg, (const u64*)rmk,
+                     (const u128*)rR, (const u64*)rM, (u128*)w, (u128*)out0, (u128*)out1, k,
+                     nn[2], nn[3], nn[4], nn[5], ncomp);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : -100 - (int)e;
 }

@@ -23,6 +23,14 @@ int mxh_trunc_party_r1(int words, int64_t n, int m, int ncomp, const int* roles,
                        const void* msg, const void* rmk, const void* rrt, const void* rrm,
                        void* w, void* out0, void* out1, const uint32_t* const* slots,
                        const uint64_t* nn, void* stream);
+int mxh_ring_extend_party_r0(int64_t n, int ncomp, const int* roles, const void* s0,
+                             const void* s1, void* msg, void* msg_R, void* msg_M, void* out0,
+                             void* out1, const uint32_t* const* slots, const uint64_t* nn,
+                             void* stream);
+int mxh_ring_extend_party_r1(int64_t n, int ncomp, const int* roles, const void* msg,
+                             const void* rmk, const void* rR, const void* rM, void* w,
+                             void* out0, void* out1, const uint32_t* const* slots,
+                             const uint64_t* nn, void* stream);
 int mxh_share_party(int kind, int words, int64_t n, int ncomp, const int* rel, const void* x,
                     void* out0, void* out1, const uint32_t* const* slots, uint64_t n1,
                     uint64_t na, void* stream);
@@ -128,6 +136,80 @@ int trunc_r1(int64_t n, int m, int ncomp, const int* roles, const T* msg, const 
           const int64_t i = base + i0 + q;
           const T y1 = mxf::trunc_y<T>(msg[i] + rmk[i], rrt[i], (T)rrm[i], m, false);
           w[i] = y1 - z[q];
+          out1[i] = z[q];
+        }
+      }
+    });
+  }
+  return 0;
+}
+
+// Ring extension Z_2^64 -> Z_2^128 (k_ring_extend_party_r0 / r1): every stream at 128-bit
+// width (element i = the composed protocol's 128-bit draw); r0, r1, M0 use the low 64 bits
+int ring_extend_r0(int64_t n, int ncomp, const int* roles, const u64* s0, const u64* s1, u64* msg,
+                   u128* msg_R, u64* msg_M, u128* out0, u128* out1,
+                   const uint32_t* const* slots, const uint64_t* nn) {
+  for (int c = 0; c < ncomp; ++c) {
+    const int role = roles[c];
+    const uint32_t* own = slots[2 * c];
+    const uint32_t* nxt = slots[2 * c + 1];
+    const int64_t base = (int64_t)c * n;
+    for_chunks<u128>(n, [&](int64_t i0, int64_t len) {
+      std::vector<u128> a(len), b(len), R(len), mm(len), z0(len), z2(len);
+      if (role == 0) {
+        prf<u128>(own, nn[0], i0, len, a.data());
+        for (int64_t q = 0; q < len; ++q) {
+          const int64_t i = base + i0 + q;
+          msg[i] = mxf::ring_extend_mask0(s0[i], s1[i], (u64)a[q]);
+        }
+      } else if (role == 1) {
+        prf<u128>(nxt, nn[1], i0, len, a.data());
+        for (int64_t q = 0; q < len; ++q) {
+          const int64_t i = base + i0 + q;
+          msg[i] = s1[i] + (u64)a[q];
+        }
+      } else if (role == 2) {
+        prf<u128>(nxt, nn[0], i0, len, a.data());
+        prf<u128>(own, nn[1], i0, len, b.data());
+        prf<u128>(nxt, nn[2], i0, len, R.data());
+        prf<u128>(nxt, nn[3], i0, len, mm.data());
+        prf<u128>(nxt, nn[4], i0, len, z0.data());
+        prf<u128>(own, nn[5], i0, len, z2.data());
+        for (int64_t q = 0; q < len; ++q) {
+          const int64_t i = base + i0 + q;
+          mxf::ring_extend_dealer((u64)a[q], (u64)b[q], R[q], (u64)mm[q], &msg_R[i], &msg_M[i]);
+          out0[i] = z2[q];
+          out1[i] = z0[q];
+        }
+      }
+    });
+  }
+  return 0;
+}
+
+int ring_extend_r1(int64_t n, int ncomp, const int* roles, const u64* msg, const u64* rmk,
+                   const u128* rR, const u64* rM, u128* w, u128* out0, u128* out1,
+                   const uint32_t* const* slots, const uint64_t* nn) {
+  for (int c = 0; c < ncomp; ++c) {
+    const int role = roles[c];
+    const int64_t base = (int64_t)c * n;
+    for_chunks<u128>(n, [&](int64_t i0, int64_t len) {
+      std::vector<u128> R(len), mm(len), z(len);
+      if (role == 0) {
+        const uint32_t* k0 = slots[2 * c];
+        prf<u128>(k0, nn[2], i0, len, R.data());
+        prf<u128>(k0, nn[3], i0, len, mm.data());
+        prf<u128>(k0, nn[4], i0, len, z.data());
+        for (int64_t q = 0; q < len; ++q) {
+          const int64_t i = base + i0 + q;
+          w[i] = mxf::ring_extend_y(msg[i] + rmk[i], R[q], (u64)mm[q], true) - z[q];
+          out0[i] = z[q];
+        }
+      } else if (role == 1) {
+        prf<u128>(slots[2 * c + 1], nn[5], i0, len, z.data());
+        for (int64_t q = 0; q < len; ++q) {
+          const int64_t i = base + i0 + q;
+          w[i] = mxf::ring_extend_y(msg[i] + rmk[i], rR[i], rM[i], false) - z[q];
           out1[i] = z[q];
         }
       }
@@ -317,6 +399,32 @@ int mx_trunc_party_r1(int dev, int words, int64_t n, int m, int ncomp, const int
                           (const u128*)rrt, (const u64*)rrm, (u128*)w, (u128*)out0,
                           (u128*)out1, slots, nn);
   return -2;
+}
+
+int mx_ring_extend_party_r0(int dev, int64_t n, int ncomp, const int* roles, const void* s0,
+                            const void* s1, void* msg, void* msg_R, void* msg_M, void* out0,
+                            void* out1, const uint32_t* const* slots, const uint64_t* nn,
+                            void* stream) {
+  if (n == 0) return 0;
+  if (ncomp < 1 || ncomp > 3) return -3;
+  if (dev)
+    return mxh_ring_extend_party_r0(n, ncomp, roles, s0, s1, msg, msg_R, msg_M, out0, out1,
+                                    slots, nn, stream);
+  return ring_extend_r0(n, ncomp, roles, (const u64*)s0, (const u64*)s1, (u64*)msg, (u128*)msg_R,
+                        (u64*)msg_M, (u128*)out0, (u128*)out1, slots, nn);
+}
+
+int mx_ring_extend_party_r1(int dev, int64_t n, int ncomp, const int* roles, const void* msg,
+                            const void* rmk, const void* rR, const void* rM, void* w, void* out0,
+                            void* out1, const uint32_t* const* slots, const uint64_t* nn,
+                            void* stream) {
+  if (n == 0) return 0;
+  if (ncomp < 1 || ncomp > 3) return -3;
+  if (dev)
+    return mxh_ring_extend_party_r1(n, ncomp, roles, msg, rmk, rR, rM, w, out0, out1, slots, nn,
+                                    stream);
+  return ring_extend_r1(n, ncomp, roles, (const u64*)msg, (const u64*)rmk, (const u128*)rR,
+                        (const u64*)rM, (u128*)w, (u128*)out0, (u128*)out1, slots, nn);
 }
 
 int mx_share_party(int dev, int kind, int words, int64_t n, int ncomp, const int* rel,

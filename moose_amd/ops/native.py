@@ -194,6 +194,14 @@ _SIGS = {
         [c_int, c_int, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
          c_vp, c_vp, c_vp],
     ),
+    "mx_ring_extend_party_r0": (
+        c_int,
+        [c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    ),
+    "mx_ring_extend_party_r1": (
+        c_int,
+        [c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    ),
     "mx_dot_tail_r0": (
         c_int,
         [c_int, c_int, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

@@ -2103,6 +2103,44 @@ def trunc_party_r1(msg, rmk, rrt, rrm, out0, out1, bits, m, roles, slots, nonces
     return w
 
 
+def ring_extend_party_r0(s0: RT, s1: RT, roles, slots, nonces, alloc=None):
+    """Round 0 of the per-party ring extension Z_2^64 -> Z_2^128 (mx_ring_extend_party_r0) on
+    stacked [ncomp, ...] shares over Z_2^64.  Returns (msg, msg_R, msg_M, out0, out1): the
+    outgoing messages (P0 / P1: msg; the dealer P2: msg_R over Z_2^128 and msg_M) and the
+    (partly filled) new shares over Z_2^128.  ``nonces``: r0, r1, R0, M0, z0, z2.  ``alloc``:
+    where the messages go."""
+    if s0.bits != 64 or s1.bits != 64:
+        raise TypeError("ring_extend_party_r0: expects shares over Z_2^64")
+    ncomp = len(roles)
+    d0 = s0.data.contiguous()
+    d1 = s1.data.contiguous()
+    n = math.prod(s0.shape) // ncomp
+    wide = tuple(d0.shape) + (2,)
+    msg = _new(alloc, d0.shape, torch.int64, d0.device)
+    msg_R = _new(alloc, wide, torch.int64, d0.device)
+    msg_M = _new(alloc, d0.shape, torch.int64, d0.device)
+    out0 = torch.empty(wide, dtype=torch.int64, device=d0.device)
+    out1 = torch.empty(wide, dtype=torch.int64, device=d0.device)
+    nat.check(nat.lib().mx_ring_extend_party_r0(
+        nat.dev_of(d0), n, ncomp, _roles_arr(roles), nat.ptr(d0), nat.ptr(d1), nat.ptr(msg),
+        nat.ptr(msg_R), nat.ptr(msg_M), nat.ptr(out0), nat.ptr(out1), _slots_arr(slots),
+        _nonces_arr(nonces), nat.stream_of(d0)), "ring_extend_party_r0")
+    return msg, msg_R, msg_M, out0, out1
+
+
+def ring_extend_party_r1(msg, rmk, rR, rM, out0, out1, roles, slots, nonces, alloc=None):
+    """Round 1 (mx_ring_extend_party_r1): returns w (over Z_2^128); writes P0's s0 / P1's s1
+    into out0 / out1."""
+    ncomp = len(roles)
+    n = msg.numel() // ncomp
+    w = _new(alloc, tuple(msg.shape) + (2,), torch.int64, msg.device)
+    nat.check(nat.lib().mx_ring_extend_party_r1(
+        nat.dev_of(msg), n, ncomp, _roles_arr(roles), nat.ptr(msg), nat.ptr(rmk), nat.ptr(rR),
+        nat.ptr(rM), nat.ptr(w), nat.ptr(out0), nat.ptr(out1), _slots_arr(slots),
+        _nonces_arr(nonces), nat.stream_of(msg)), "ring_extend_party_r1")
+    return w
+
+
 SHARE_MIRROR = 8  # MX_SHARE_MIRROR (moosex.h): the masked slot goes to P_{j+2}
 
 

@@ -427,6 +427,33 @@ class CyclicSession(StackedSession):
         self.stats.record_round(2 * nb)
         return PV(plc, R.RT(out0, bits)), PV(plc, R.RT(out1, bits))
 
+    def party_ring_extend(self, x, nonces):
+        """Ring extension Z_2^64 -> Z_2^128 as two per-party kernels + two grouped exchanges
+        (+ one add), as :meth:`party_trunc`: component p runs party p's local work of each
+        round (replicated.ring_extend, composed path)."""
+        plc = x.plc
+        roles = [0, 1, 2]
+        slots = self._pair_ptrs(plc)
+        o = [self.offset(r) for r in plc.owners]
+        p01, p10, p21 = self._peer(o[1] - o[0]), self._peer(o[0] - o[1]), self._peer(o[1] - o[2])
+        p12 = self._peer(o[2] - o[1])
+        msg, msg_R, msg_M, out0, out1 = R.ring_extend_party_r0(x.s0.v, x.s1.v, roles, slots,
+                                                               nonces)
+        # round A, by message type: msg P0->P1, msg P1->P0, R1 P2->P1, M1 P2->P1
+        rmk, rR, rM = torch.empty_like(msg), torch.empty_like(msg_R), torch.empty_like(msg_M)
+        self.comm.exchange([(msg[0], p01), (msg[1], p10), (msg_R[2], p21), (msg_M[2], p21)],
+                           [(rmk[1], p10), (rmk[0], p01), (rR[1], p12), (rM[1], p12)])
+        w = R.ring_extend_party_r1(msg, rmk, rR, rM, out0, out1, roles, slots, nonces)
+        # round B: w0 P0->P1, w1 P1->P0; then z1 = w0 + w1 at both
+        rw = torch.empty_like(w)
+        self.comm.exchange([(w[0], p01), (w[1], p10)], [(rw[1], p10), (rw[0], p01)])
+        out1[0].copy_(R.binary("add", R.RT(w[0], 128), R.RT(rw[0], 128)).data)
+        out0[1].copy_(R.binary("add", R.RT(w[1], 128), R.RT(rw[1], 128)).data)
+        nb = _nbytes(x.s0.v) // 3  # 8 bytes per element
+        self.stats.record_round(5 * nb)  # msg0, msg1, M1: 8 bytes per element, R1: 16
+        self.stats.record_round(4 * nb)  # w0, w1: 16 bytes per element
+        return PV(plc, R.RT(out0, 128)), PV(plc, R.RT(out1, 128))
+
     def party_share(self, plc, x, j, kind, n1, na):
         """Input sharing by member j: one kernel for every component's slots, then the
         owner's masked slot goes to its recipient -- x_{j+1} to P_{j+1} (its s0), or,

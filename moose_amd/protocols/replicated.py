@@ -1248,6 +1248,10 @@ def relu(sess, x: RepTensor) -> RepTensor:
     return sub(sess, x, mul(sess, s, x))
 
 
+# per-party sessions widen with the kernel pair of csrc/rss_party.hip (off: the composed path)
+PARTY_RING_EXTEND = True
+
+
 def ring_extend(sess, x: RepTensor, bits: int = 128) -> RepTensor:
     """Z_2^64 -> Z_2^128, exact (the result reveals to the sign extension of x, bit for
     bit) for -2^62 <= x < 2^62 -- the input bound of trunc_pr, and its dealer pattern:
@@ -1258,9 +1262,10 @@ def ring_extend(sess, x: RepTensor, bits: int = 128) -> RepTensor:
         r_msb = 1 and c_msb = 0, so x + 2^62 = c - R + 2^64 r_msb (1 - c_msb);
       * round 2: additive -> replicated exchange.
 
-    A fused stacked session runs one kernel for all three parties; every other session
-    (per-party threads, SPMD, cyclic, symbolic) composes the protocol from host primitives
-    with the same nonces, hence the same shares."""
+    A fused stacked session runs one kernel for all three parties; a session with
+    ``party_ring_extend`` (per-party threads, SPMD, cyclic) runs two per-party kernels and two
+    grouped message rounds (``PARTY_RING_EXTEND``); a symbolic session composes the protocol
+    from host primitives.  All three use the same nonces, hence give the same shares."""
     if x.bits == bits:
         return x
     if x.bits != 64 or bits != 128 or x.kind != "arith":
@@ -1272,6 +1277,11 @@ def ring_extend(sess, x: RepTensor, bits: int = 128) -> RepTensor:
         n0, n2 = sess.nonce(plc), sess.nonce(plc)
         if getattr(sess, "fused", False):
             s0, s1 = sess.fused_ring_extend(x, (nr0, nr1, nR, nM, n0, n2))
+            return RepTensor(plc, bits, "arith", s0, s1)
+        party = getattr(sess, "party_ring_extend", None)
+        if party is not None and PARTY_RING_EXTEND:
+            with span("rep.ring_extend_party"):
+                s0, s1 = party(x, (nr0, nr1, nR, nM, n0, n2))
             return RepTensor(plc, bits, "arith", s0, s1)
         from moose_amd.protocols import additive
 
