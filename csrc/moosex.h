@@ -64,6 +64,16 @@ int mx_ew_unary2(int dev, int op, int words, const void* a0, void* out0, const v
 // out_y = a_y^T, y = 0, 1 ([rows, cols] ring matrices -> [cols, rows])
 int mx_transpose2(int dev, int words, const void* a0, void* out0, const void* a1, void* out1,
                   int64_t rows, int64_t cols, void* stream);
+// im2col, the patch gather of a 2-D convolution: in[slots, N, C, H, W] (nhwc: [slots, N, H,
+// W, C]) of elem_bytes-wide elements (1, 8 or 16) -> out[slots, N*OH*OW, C*KH*KW], rows
+// ordered (n, oh, ow), columns (c, kh, kw) (nhwc: (kh, kw, c)); taps in the padding (pt rows
+// above, pl columns left; below / right follow from OH / OW) are zero.  Input slots are
+// in_slot_stride elements apart (a slot view of a larger buffer is read in place), output
+// slots are dense.
+int mx_im2col(int dev, int elem_bytes, const void* in, void* out, int64_t slots,
+              int64_t in_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH,
+              int64_t KW, int64_t sh, int64_t sw, int64_t pt, int64_t pl, int64_t dh,
+              int64_t dw, int64_t OH, int64_t OW, int nhwc, void* stream);
 // mx_ew_binary_slot on a0 (slot which0) and a1 (slot which1) with one public b
 int mx_ew_binary_slot2(int dev, int op, int words, const void* a0, const void* a1,
                        const void* b, int64_t nb, void* out0, void* out1, int64_t m,

@@ -322,6 +322,35 @@ void mx_cpu_parallel_for(int64_t n, int64_t grain,
     default: return -2;                               \
   }
 
+namespace {
+
+template <class T>
+void im2col_cpu(const T* in, T* out, int64_t slots, int64_t in_slot_stride, int64_t N,
+                       int64_t C, int64_t H, int64_t W, int64_t KH, int64_t KW, int64_t sh,
+                       int64_t sw, int64_t pt, int64_t pl, int64_t dh, int64_t dw, int64_t OH,
+                       int64_t OW, int nhwc) {
+  const int64_t K = C * KH * KW, rows = N * OH * OW;
+  const int64_t sN = C * H * W, sH = nhwc ? W * C : W, sW = nhwc ? C : 1, sC = nhwc ? 1 : H * W;
+  parallel_for(slots * rows, std::max<int64_t>(1, 4096 / K), [=](int64_t b, int64_t e) {
+    for (int64_t g = b; g < e; ++g) {
+      const int64_t s = g / rows, row = g - s * rows;
+      const int64_t ow = row % OW, oh = (row / OW) % OH, n = row / (OW * OH);
+      const T* src = in + s * in_slot_stride + n * sN;
+      T* dst = out + g * K;
+      for (int64_t c = 0; c < C; ++c)
+        for (int64_t kh = 0; kh < KH; ++kh)
+          for (int64_t kw = 0; kw < KW; ++kw) {
+            const int64_t iy = oh * sh + kh * dh - pt, ix = ow * sw + kw * dw - pl;
+            const int64_t col = nhwc ? (kh * KW + kw) * C + c : (c * KH + kh) * KW + kw;
+            const bool inside = iy >= 0 && iy < H && ix >= 0 && ix < W;
+            dst[col] = inside ? src[c * sC + iy * sH + ix * sW] : (T)0;
+          }
+    }
+  });
+}
+
+}  // namespace
+
 extern "C" {
 
 int mx_version(void) { return 3; }
@@ -415,6 +444,41 @@ int mx_transpose2(int dev, int words, const void* a0, void* out0, const void* a1
     }
     return 0;
   });
+}
+
+int mx_im2col(int dev, int elem_bytes, const void* in, void* out, int64_t slots,
+              int64_t in_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH,
+              int64_t KW, int64_t sh, int64_t sw, int64_t pt, int64_t pl, int64_t dh,
+              int64_t dw, int64_t OH, int64_t OW, int nhwc, void* stream) {
+  if (OH <= 0 || OW <= 0 || KH <= 0 || KW <= 0 || sh <= 0 || sw <= 0 || dh <= 0 || dw <= 0 ||
+      pt < 0 || pl < 0 || N < 0 || C < 0 || H < 0 || W < 0 || slots < 0)
+    return -3;
+  // every tap coordinate oh*sh + kh*dh - pt (and its w twin) has to fit an int: the kernels
+  // compute them in 32 bits
+  const int64_t lim = 0x7fffffff;
+  const int64_t dims[] = {N, C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW};
+  for (int64_t d : dims)
+    if (d > lim) return -3;
+  if ((OH - 1) * sh + (KH - 1) * dh > lim || (OW - 1) * sw + (KW - 1) * dw > lim) return -3;
+  if (dev)
+    return mxh_im2col(elem_bytes, in, out, slots, in_slot_stride, N, C, H, W, KH, KW, sh, sw, pt,
+                      pl, dh, dw, OH, OW, nhwc, stream);
+  if (slots * N * OH * OW * C * KH * KW == 0) return 0;
+  switch (elem_bytes) {
+    case 1:
+      im2col_cpu((const uint8_t*)in, (uint8_t*)out, slots, in_slot_stride, N, C, H, W, KH, KW,
+                 sh, sw, pt, pl, dh, dw, OH, OW, nhwc);
+      return 0;
+    case 8:
+      im2col_cpu((const u64*)in, (u64*)out, slots, in_slot_stride, N, C, H, W, KH, KW, sh, sw,
+                 pt, pl, dh, dw, OH, OW, nhwc);
+      return 0;
+    case 16:
+      im2col_cpu((const u128*)in, (u128*)out, slots, in_slot_stride, N, C, H, W, KH, KW, sh,
+                 sw, pt, pl, dh, dw, OH, OW, nhwc);
+      return 0;
+    default: return -2;
+  }
 }
 
 int mx_ew_unary2(int dev, int op, int words, const void* a0, void* out0, const void* a1,

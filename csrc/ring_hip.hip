@@ -15,6 +15,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 
 #include "prf_dev.h"
 #include "moosex.h"
@@ -1732,6 +1733,103 @@ __global__ void __launch_bounds__(256) k_prf_expand(T* __restrict__ out, int64_t
   d_prf_expand<T>(out, n, nkeys, keys, nonce);
 }
 
+// im2col: the patch gather that turns a 2-D convolution into a GEMM over shares.  Output-
+// stationary: a lane owns V adjacent output columns of one row, so stores are coalesced
+// (V = 2 for u64 with an even row length: one 16-byte store; u128 moves 16 bytes per lane as
+// is).  Block = 64 columns x 4 rows: a wave walks one output row, reading contiguous c runs
+// (NHWC) or kw runs (NCHW, dw == 1).  The column (c, kh, kw) is decomposed once per lane and
+// kept while the lane strides over rows; a row (n, oh, ow) once per visit.  A tap in the
+// padding stores zero without a load.  Slots (share slots of a stacked buffer) are
+// blockIdx.z, read at in_slot_stride and written densely.  I is the index type: 32-bit when
+// both extents are below 2^31.
+template <class I>
+struct Im2colP {
+  I in_slot_stride, sN, sH, sW, sC;  // input strides in elements (format-dependent)
+  I K, rows;
+  int C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW, nhwc;
+};
+
+template <class T, int V>
+struct alignas(sizeof(T) * V) Im2colVec {
+  T v[V];
+};
+
+template <class T, class I, int V>
+__global__ void __launch_bounds__(256) k_im2col(const T* __restrict__ in, T* __restrict__ out,
+                                                Im2colP<I> p) {
+  using U = typename std::make_unsigned<I>::type;
+  const I col0 = (I)((blockIdx.x * (I)64 + threadIdx.x) * V);
+  if (col0 >= p.K) return;
+  I coff[V];
+  int dy[V], dx[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    const U col = (U)(col0 + j);
+    U c, kh, kw;
+    if (p.nhwc) {
+      const U t = col / (U)p.C;
+      c = col - t * (U)p.C;
+      kh = t / (U)p.KW;
+      kw = t - kh * (U)p.KW;
+    } else {
+      const U kk = (U)(p.KH * p.KW);
+      c = col / kk;
+      const U r = col - c * kk;
+      kh = r / (U)p.KW;
+      kw = r - kh * (U)p.KW;
+    }
+    coff[j] = (I)c * p.sC;
+    dy[j] = (int)kh * p.dh - p.pt;
+    dx[j] = (int)kw * p.dw - p.pl;
+  }
+  const T* __restrict__ src = in + (I)blockIdx.z * p.in_slot_stride;
+  T* __restrict__ dst = out + (I)blockIdx.z * p.rows * p.K;
+  for (I row = (I)(blockIdx.y * blockDim.y + threadIdx.y); row < p.rows;
+       row += (I)(gridDim.y * blockDim.y)) {
+    const U q = (U)row / (U)p.OW;
+    const int ow = (int)((U)row - q * (U)p.OW);
+    const U n = q / (U)p.OH;
+    const int oh = (int)(q - n * (U)p.OH);
+    const I base = (I)n * p.sN;
+    const int y0 = oh * p.sh, x0 = ow * p.sw;
+    Im2colVec<T, V> o;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const int iy = y0 + dy[j], ix = x0 + dx[j];
+      T v = (T)0;
+      if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W)
+        v = src[base + coff[j] + (I)iy * p.sH + (I)ix * p.sW];
+      o.v[j] = v;
+    }
+    *reinterpret_cast<Im2colVec<T, V>*>(dst + row * p.K + col0) = o;
+  }
+}
+
+template <class T, class I, int V>
+static int im2col_launch(const void* in, void* out, int64_t slots, int64_t in_slot_stride,
+                         int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH, int64_t KW,
+                         int64_t sh, int64_t sw, int64_t pt, int64_t pl, int64_t dh, int64_t dw,
+                         int64_t OH, int64_t OW, int nhwc, void* stream) {
+  Im2colP<I> p;
+  p.in_slot_stride = (I)in_slot_stride;
+  p.sN = (I)(C * H * W);
+  p.sH = (I)(nhwc ? W * C : W);
+  p.sW = (I)(nhwc ? C : 1);
+  p.sC = (I)(nhwc ? 1 : H * W);
+  p.K = (I)(C * KH * KW);
+  p.rows = (I)(N * OH * OW);
+  p.C = (int)C, p.H = (int)H, p.W = (int)W, p.KH = (int)KH, p.KW = (int)KW;
+  p.sh = (int)sh, p.sw = (int)sw, p.pt = (int)pt, p.pl = (int)pl, p.dh = (int)dh;
+  p.dw = (int)dw, p.OH = (int)OH, p.OW = (int)OW, p.nhwc = nhwc;
+  const int64_t K = C * KH * KW, rows = N * OH * OW;
+  const int64_t gx = (K + 64 * V - 1) / (64 * V);
+  const int64_t gy = std::min<int64_t>((rows + 3) / 4, 16384);
+  hipLaunchKernelGGL((k_im2col<T, I, V>), dim3((unsigned)gx, (unsigned)gy, (unsigned)slots),
+                     dim3(64, 4), 0, S(stream), (const T*)in, (T*)out, p);
+  MX_LAUNCH_CHECK();
+  return 0;
+}
+
 // party-batched twins of the per-party sessions' local kernels (party_batch.h)
 MX_X3_GS(k_binary2<u64>, d_binary2<u64>);
 MX_X3_GS(k_binary2<u128>, d_binary2<u128>);
@@ -2003,6 +2101,37 @@ int mxh_transpose2(int words, const void* a0, void* out0, const void* a1, void* 
     MX_LAUNCH_CHECK();
     return 0;
   });
+}
+
+int mxh_im2col(int elem_bytes, const void* in, void* out, int64_t slots, int64_t in_slot_stride,
+               int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH, int64_t KW, int64_t sh,
+               int64_t sw, int64_t pt, int64_t pl, int64_t dh, int64_t dw, int64_t OH,
+               int64_t OW, int nhwc, void* stream) {
+  const int64_t K = C * KH * KW, rows = N * OH * OW;
+  if (slots <= 0 || rows <= 0 || K <= 0) return 0;
+  const int64_t dims[] = {N, C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW};
+  for (int64_t d : dims)
+    if (d < 0 || d > 0x7fffffff) return -3;
+  if (slots > 65535 || (K + 63) / 64 > 0x7fffffff || in_slot_stride < 0) return -3;
+  const int64_t in_extent = (slots - 1) * in_slot_stride + N * C * H * W;
+  // 32-bit indices below 2^31 elements, less the overshoot of a lane's last loop step
+  const int64_t lim = (1ll << 31) - (1ll << 17);
+  const bool small = in_extent < lim && slots * rows * K < lim;
+#define MX_IM2COL(T, V)                                                                       \
+  return small ? im2col_launch<T, int32_t, V>(in, out, slots, in_slot_stride, N, C, H, W, KH, \
+                                              KW, sh, sw, pt, pl, dh, dw, OH, OW, nhwc,       \
+                                              stream)                                         \
+               : im2col_launch<T, int64_t, V>(in, out, slots, in_slot_stride, N, C, H, W, KH, \
+                                              KW, sh, sw, pt, pl, dh, dw, OH, OW, nhwc, stream)
+  switch (elem_bytes) {
+    case 1: MX_IM2COL(uint8_t, 1);
+    case 8:
+      if (K % 2 == 0 && ((uintptr_t)out & 15) == 0) { MX_IM2COL(u64, 2); }
+      MX_IM2COL(u64, 1);
+    case 16: MX_IM2COL(u128, 1);
+    default: return -2;
+  }
+#undef MX_IM2COL
 }
 
 int mxh_ew_binary_slot2(int op, int words, const void* a0, const void* a1, const void* b,

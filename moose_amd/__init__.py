@@ -82,6 +82,11 @@ from moose_amd.edsl.base import sub  # noqa: F401
 from moose_amd.edsl.base import sum  # noqa: F401,A004
 from moose_amd.edsl.base import transpose  # noqa: F401
 from moose_amd.edsl.base import zeros  # noqa: F401
+from moose_amd.edsl.base import avg_pool2d  # noqa: F401
+from moose_amd.edsl.base import conv2d  # noqa: F401
+from moose_amd.edsl.base import im2col  # noqa: F401
+from moose_amd.edsl.base import max_pool2d  # noqa: F401
+from moose_amd.edsl.base import permute  # noqa: F401
 from moose_amd.edsl.tracer import trace  # noqa: F401
 from moose_amd.edsl.tracer import trace_and_compile  # noqa: F401
 from moose_amd.runtime.local import LocalMooseRuntime  # noqa: F401

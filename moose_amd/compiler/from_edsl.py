@@ -74,6 +74,14 @@ _OPS = {
     "SubOperation": ("Sub", ["lhs", "rhs"], None),
     "SumOperation": ("Sum", ["x"], lambda o: {"axis": o.axis}),
     "TransposeOperation": ("Transpose", ["x"], None),
+    "Im2ColOperation": (
+        "Im2Col",
+        ["x"],
+        lambda o: {"kernel_shape": list(o.kernel_shape), "strides": list(o.strides),
+                   "pads": list(o.pads), "dilations": list(o.dilations),
+                   "data_format": o.data_format},
+    ),
+    "PermuteOperation": ("Permute", ["x"], lambda o: {"axes": list(o.axes)}),
 }
 
 _NP_CONST = {

@@ -47,6 +47,7 @@ def typing_pass(comp: Computation, **_) -> Computation:
     """Fill Unknown argument types from the producers' return types (one hop)."""
     by_name = comp.by_name()
     out = []
+    shapes = {}  # operation name -> statically known shape (constants and what follows)
     for op in comp.operations:
         args = list(op.sig.args)
         if op.sig.variadic:
@@ -64,9 +65,72 @@ def typing_pass(comp: Computation, **_) -> Computation:
                         and args[i].inner.kind == "Unknown"):
                     args[i] = src.sig.ret
         _check_one_ring(op, args)
+        _static_shape(op, shapes)
         out.append(Operation(op.name, op.kind, list(op.inputs), op.placement,
                              Signature(tuple(args), op.sig.ret, op.sig.variadic), dict(op.attrs)))
     return Computation(out)
+
+
+_SAME_SHAPE_OPS = {"Cast", "Identity", "Relu", "Sigmoid", "Abs", "Neg", "Exp", "Sqrt", "Log",
+                   "Log2", "Softmax", "Share", "Reveal"}
+
+
+def _static_shape(op, shapes):
+    """Shape inference over what is statically known (tensor constants and the shape-class
+    operators downstream of them), recorded in ``shapes``; rejects an Im2Col whose input is
+    not rank 4 or whose output would be empty, a Permute whose axes do not match the rank
+    and a Dot whose inner dimensions differ (a convolution's channel mismatch)."""
+    import numpy as np
+
+    from moose_amd.ops import ring as R
+
+    ins = [shapes.get(i) for i in op.inputs]
+    kind, a = op.kind, op.attrs
+    shp = None
+    try:
+        if kind == "Constant":
+            v = getattr(a.get("value"), "value", None)
+            if isinstance(v, np.ndarray):
+                shp = tuple(v.shape)
+            elif isinstance(v, (tuple, list)):
+                shapes[op.name] = ("shape", tuple(int(s) for s in v))
+                return
+        elif not ins or ins[0] is None or ins[0][:1] == ("shape",):
+            return
+        elif kind in _SAME_SHAPE_OPS:
+            shp = ins[0]
+        elif kind == "Transpose":
+            shp = ins[0][::-1]
+        elif kind == "Permute":
+            axes = list(a["axes"])
+            if sorted(axes) != list(range(len(ins[0]))):
+                raise ValueError(f"axes {axes} are not a permutation of the axes of a "
+                                 f"rank-{len(ins[0])} tensor")
+            shp = tuple(ins[0][i] for i in axes)
+        elif kind == "Im2Col":
+            g = R.im2col_geometry(ins[0], a["kernel_shape"], a["strides"], a["pads"],
+                                  a["dilations"], a["data_format"])
+            shp = (g[0] * g[-2] * g[-1], g[1] * g[4] * g[5])
+        elif kind == "Reshape" and len(ins) == 2 and ins[1] is not None and ins[1][0] == "shape":
+            want, n = list(ins[1][1]), int(np.prod(ins[0]))
+            if want.count(-1) == 1:
+                rest = -int(np.prod(want))
+                want[want.index(-1)] = n // rest if rest and n % rest == 0 else -1
+            if -1 not in want:
+                if int(np.prod(want)) != n:
+                    raise ValueError(f"cannot reshape {ins[0]} to {tuple(ins[1][1])}")
+                shp = tuple(want)
+        elif kind == "Dot" and len(ins) == 2 and ins[1] is not None and ins[1][0] != "shape":
+            x, y = ins
+            if len(x) == 2 and len(y) == 2:
+                if x[1] != y[0]:
+                    raise ValueError(f"inner dimensions differ: {x} . {y} (for a convolution: "
+                                     "the input's channels and the weight's do not match)")
+                shp = (x[0], y[1])
+    except ValueError as e:
+        raise CompilationError(f"{op.name}: {kind}: {e}") from None
+    if shp is not None:
+        shapes[op.name] = tuple(shp)
 
 
 def _check_one_ring(op, args):

@@ -83,6 +83,8 @@ OPERATION_TABLE = [
     ("SubOperation", []),
     ("SumOperation", ["axis"]),
     ("TransposeOperation", []),
+    ("Im2ColOperation", ["kernel_shape", "strides", "pads", "dilations", "data_format"]),
+    ("PermuteOperation", ["axes"]),
 ]
 
 OPERATION_CLASSES = {}

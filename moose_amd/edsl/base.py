@@ -130,10 +130,13 @@ class Argument:
     dtype: Optional[dtypes.DType] = None
     vtype: Optional[ty.ValueType] = None
 
-    def __init__(self, placement, dtype=None, vtype=None):
+    def __init__(self, placement, dtype=None, vtype=None, shape=None):
         self.placement = placement
         self.dtype = dtype
         self.vtype = _maybe_lift_dtype_to_tensor_vtype(dtype, vtype)
+        # optional static shape (None for a dimension only known at run time): what the
+        # shape-dependent builders (conv2d, pooling) read when it is given
+        self.shape = None if shape is None else tuple(shape)
 
 
 @dataclass(eq=False)
@@ -149,6 +152,8 @@ class Expression:
     inputs: List["Expression"]
     vtype: Optional[ty.ValueType]
     attrs: Dict[str, Any] = field(default_factory=dict)
+    # statically known shape, where a builder could tell (None entries: run-time sizes)
+    static_shape: Optional[tuple] = None
 
     def __hash__(self):
         return id(self)
@@ -262,13 +267,23 @@ def _check_arithmetickable(expr, fn_name):
         raise TypeError(f"Value of vtype {getattr(expr, 'vtype', expr)} is not {fn_name}-able.")
 
 
+# builders whose result has the shape of their (first) operand
+_SAME_SHAPE = {"identity", "cast", "exp", "sqrt", "sigmoid", "relu", "log", "log2", "abs",
+               "softmax"}
+
+
 def _expr(kind, inputs, vtype, placement, **attrs):
+    inputs = list(inputs)
+    shape = None
+    if kind in _SAME_SHAPE and inputs and isinstance(inputs[0], Expression):
+        shape = inputs[0].static_shape
     return Expression(
         kind=kind,
         placement=_materialize_placement_arg(placement),
-        inputs=list(inputs),
+        inputs=inputs,
         vtype=vtype,
         attrs=attrs,
+        static_shape=shape,
     )
 
 
@@ -384,7 +399,9 @@ def constant(value, dtype=None, vtype=None, placement=None):
             inner = constant(value, dtype=moose_dtype, placement=placement)
             return cast(inner, target, placement)
         vtype = vtype or ty.TensorType(moose_dtype)
-        value = values.TensorConstant(value=value)
+        return Expression("constant", placement, [], vtype,
+                          {"value": values.TensorConstant(value=value)},
+                          static_shape=tuple(value.shape))
     elif isinstance(value, bool):
         value = values.TensorConstant(value=np.array(value))
         vtype = vtype or ty.TensorType(dtypes.bool_)
@@ -583,6 +600,179 @@ def strided_slice(x, slices, placement=None):
         if not isinstance(s, slice):
             raise ValueError(f"`slices` argument must a list/tuple of slices, found {type(s)}")
     return _expr("strided_slice", [x], x.vtype, placement, slices=list(slices))
+
+
+def permute(x, axes, placement=None):
+    """Reorder the axes of ``x``: result axis ``i`` is input axis ``axes[i]``."""
+    if not isinstance(axes, (tuple, list)) or not all(isinstance(a, int) for a in axes):
+        raise ValueError(f"`axes` argument must be a list/tuple of ints, found {axes!r}")
+    axes = list(axes)
+    if sorted(axes) != list(range(len(axes))):
+        raise ValueError(f"`axes` argument must be a permutation of 0..{len(axes) - 1}, "
+                         f"found {axes}")
+    shp = x.static_shape
+    if shp is not None and len(shp) != len(axes):
+        raise ValueError(f"`axes` {axes} do not match a tensor of rank {len(shp)}")
+    e = _expr("permute", [x], x.vtype, placement, axes=axes)
+    if shp is not None:
+        e.static_shape = tuple(shp[a] for a in axes)
+    return e
+
+
+def _conv_geometry(fn, shape, kernel_shape, strides, pads, dilations, data_format):
+    """Validated attributes of a 2-D window op, and (C, H, W, OH, OW) where the static
+    ``shape`` (rank 4, batch entry may be None) is known."""
+    if data_format not in ("NCHW", "NHWC"):
+        raise ValueError(f"`{fn}`: data_format must be 'NCHW' or 'NHWC', found {data_format!r}")
+    for name, v, n in (("kernel_shape", kernel_shape, 2), ("strides", strides, 2),
+                       ("pads", pads, 4), ("dilations", dilations, 2)):
+        if not isinstance(v, (tuple, list)) or len(v) != n or \
+                not all(isinstance(i, int) for i in v):
+            raise ValueError(f"`{fn}`: `{name}` must be a list/tuple of {n} ints, found {v!r}")
+    if builtins.min(kernel_shape) <= 0:
+        raise ValueError(f"`{fn}`: kernel_shape must be positive, found {tuple(kernel_shape)}")
+    if builtins.min(strides) <= 0 or builtins.min(dilations) <= 0:
+        raise ValueError(f"`{fn}`: strides and dilations must be positive, found "
+                         f"{tuple(strides)} and {tuple(dilations)}")
+    if builtins.min(pads) < 0:
+        raise ValueError(f"`{fn}`: pads must be non-negative, found {tuple(pads)}")
+    if shape is None:
+        return None
+    if len(shape) != 4:
+        raise ValueError(f"`{fn}` expects a rank-4 {data_format} tensor, found shape "
+                         f"{tuple(shape)}")
+    c, h, w = (shape[1:] if data_format == "NCHW" else (shape[3], shape[1], shape[2]))
+    if None in (c, h, w):
+        return None
+    (kh, kw), (sh, sw), (pt, pl, pb, pr), (dh, dw) = kernel_shape, strides, pads, dilations
+    oh = (h + pt + pb - dh * (kh - 1) - 1) // sh + 1
+    ow = (w + pl + pr - dw * (kw - 1) - 1) // sw + 1
+    if oh <= 0 or ow <= 0:
+        raise ValueError(f"`{fn}`: a {kh}x{kw} kernel does not fit the padded "
+                         f"{h + pt + pb}x{w + pl + pr} image (output {oh}x{ow})")
+    return c, h, w, oh, ow
+
+
+def im2col(x, kernel_shape, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1),
+           data_format="NCHW", placement=None, input_shape=None):
+    """Patch matrix ``[N*OH*OW, C*KH*KW]`` of a rank-4 tensor: rows ordered (n, oh, ow),
+    columns (c, kh, kw) for NCHW and (kh, kw, c) for NHWC; ``pads`` is (top, left, bottom,
+    right) and padded taps are zero.  ``input_shape`` is the static shape of ``x`` where the
+    expression does not carry it (optional: it only types the result)."""
+    shape = tuple(input_shape) if input_shape is not None else x.static_shape
+    g = _conv_geometry("im2col", shape, kernel_shape, strides, pads, dilations, data_format)
+    e = _expr("im2col", [x], x.vtype, placement, kernel_shape=list(kernel_shape),
+              strides=list(strides), pads=list(pads), dilations=list(dilations),
+              data_format=data_format)
+    if g is not None:
+        c, _h, _w, oh, ow = g
+        n = shape[0]
+        e.static_shape = (None if n is None or n < 0 else n * oh * ow,
+                          c * kernel_shape[0] * kernel_shape[1])
+    return e
+
+
+def _window_input(fn, x, input_shape, data_format):
+    shape = tuple(input_shape) if input_shape is not None else x.static_shape
+    if shape is None:
+        raise ValueError(
+            f"`{fn}` needs the static shape of its input (the batch size may be None): "
+            "pass `input_shape=`, or give the pm.Argument a `shape=`")
+    shape = tuple(None if s is None or s < 0 else int(s) for s in shape)
+    if len(shape) != 4:
+        raise ValueError(f"`{fn}` expects a rank-4 {data_format} tensor, found shape {shape}")
+    if None in shape[1:]:
+        raise ValueError(f"`{fn}`: only the batch size may be unknown, found shape {shape}")
+    return shape
+
+
+def _batch(n):
+    return -1 if n is None else n
+
+
+def conv2d(x, w, bias=None, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1),
+           data_format="NCHW", placement=None, input_shape=None, weight_shape=None):
+    """2-D convolution (cross-correlation, as ONNX ``Conv``) of ``x`` (rank 4, ``data_format``)
+    with ``w`` of shape ``[OC, C, KH, KW]``: ``im2col`` + one ``dot`` (+ ``bias`` of shape
+    ``[OC]``); the result has the input's ``data_format``.  The static shapes come from the
+    expressions (constants, ``pm.Argument(shape=...)``) or from ``input_shape`` /
+    ``weight_shape``; only the batch size may be unknown (None).  ``groups`` is not
+    supported."""
+    if data_format not in ("NCHW", "NHWC"):
+        raise ValueError(f"`conv2d`: data_format must be 'NCHW' or 'NHWC', found {data_format!r}")
+    ws = tuple(weight_shape) if weight_shape is not None else w.static_shape
+    if ws is None:
+        raise ValueError("`conv2d` needs the static shape of `w`: pass `weight_shape=`")
+    if len(ws) != 4 or None in ws:
+        raise ValueError(f"`conv2d` expects `w` of shape [OC, C, KH, KW], found {tuple(ws)}")
+    oc, wc, kh, kw = (int(s) for s in ws)
+    xs = _window_input("conv2d", x, input_shape, data_format)
+    c, _h, _w, oh, ow = _conv_geometry("conv2d", xs, (kh, kw), strides, pads, dilations,
+                                       data_format)
+    if c != wc:
+        raise ValueError(f"`conv2d`: input has {c} channels but `w` {tuple(ws)} expects {wc} "
+                         "(groups are not supported)")
+    k = c * kh * kw
+    cols = im2col(x, (kh, kw), strides, pads, dilations, data_format, placement, xs)
+    if data_format == "NCHW":
+        wm = transpose(reshape(w, [oc, k], placement), placement)
+    else:  # rows in the patch matrix's (kh, kw, c) order
+        wm = reshape(permute(w, (2, 3, 1, 0), placement), [k, oc], placement)
+    y = dot(cols, wm, placement)
+    if bias is not None:
+        y = add(y, bias, placement)
+    y = reshape(y, [_batch(xs[0]), oh, ow, oc], placement)
+    y.static_shape = (xs[0], oh, ow, oc)
+    if data_format == "NCHW":
+        y = permute(y, (0, 3, 1, 2), placement)
+    return y
+
+
+def _pool_taps(fn, x, kernel_shape, strides, pads, data_format, placement, input_shape):
+    """([M, KH*KW] or [M, KH*KW, C] tap matrix, tap axis, result builder) of a pooling."""
+    strides = tuple(kernel_shape) if strides is None else strides
+    xs = _window_input(fn, x, input_shape, data_format)
+    c, h, w, oh, ow = _conv_geometry(fn, xs, kernel_shape, strides, pads, (1, 1), data_format)
+    taps = kernel_shape[0] * kernel_shape[1]
+    if data_format == "NCHW":
+        # every channel is an image of its own: no permute on shares
+        per = reshape(x, [-1, 1, h, w], placement)
+        per.static_shape = (None, 1, h, w)
+        cols = im2col(per, kernel_shape, strides, pads, (1, 1), "NCHW", placement)
+        out = [_batch(xs[0]), c, oh, ow]
+        static = (xs[0], c, oh, ow)
+    else:
+        cols = im2col(x, kernel_shape, strides, pads, (1, 1), "NHWC", placement, xs)
+        cols = reshape(cols, [-1, taps, c], placement)
+        out = [_batch(xs[0]), oh, ow, c]
+        static = (xs[0], oh, ow, c)
+
+    def finish(y):
+        y = reshape(y, out, placement)
+        y.static_shape = static
+        return y
+
+    return cols, taps, finish
+
+
+def avg_pool2d(x, kernel_shape, strides=None, pads=(0, 0, 0, 0), data_format="NCHW",
+               placement=None, input_shape=None):
+    """2-D average pooling (``strides`` default to ``kernel_shape``): ``im2col`` on a
+    per-channel view, then ``mean`` over the taps.  Padded taps count as zeros (ONNX
+    ``count_include_pad=1``)."""
+    cols, _taps, finish = _pool_taps("avg_pool2d", x, kernel_shape, strides, pads, data_format,
+                                     placement, input_shape)
+    return finish(mean(cols, axis=1, placement=placement))
+
+
+def max_pool2d(x, kernel_shape, strides=None, data_format="NCHW", placement=None,
+               input_shape=None):
+    """2-D max pooling without padding: ``im2col``, one ``index_axis`` per tap, then
+    ``maximum``."""
+    cols, taps, finish = _pool_taps("max_pool2d", x, kernel_shape, strides, (0, 0, 0, 0),
+                                    data_format, placement, input_shape)
+    views = [index_axis(cols, axis=1, index=t, placement=placement) for t in range(taps)]
+    return finish(views[0] if taps == 1 else maximum(views, placement))
 
 
 def atleast_2d(x, to_column_vector=False, placement=None):

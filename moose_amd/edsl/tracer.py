@@ -55,6 +55,9 @@ _OPS = {
     "select": ("SelectOperation", ["x", "index"], "select", ["axis"]),
     "slice": ("SliceOperation", ["x"], "slice", ["begin", "end"]),
     "strided_slice": ("StridedSliceOperation", ["x"], "strided_slice", ["slices"]),
+    "im2col": ("Im2ColOperation", ["x"], "im2col",
+               ["kernel_shape", "strides", "pads", "dilations", "data_format"]),
+    "permute": ("PermuteOperation", ["x"], "permute", ["axes"]),
     "shape": ("ShapeOperation", ["x"], "shape", []),
     "mux": ("MuxOperation", ["selector", "x", "y"], "mux", []),
     "load": ("LoadOperation", ["key", "query"], "load", []),
@@ -87,7 +90,8 @@ def trace(abstract_computation):
         if not isinstance(ann, expr.Argument):
             raise TypeError(f"Parameter `{arg_name}` must be annotated with pm.Argument")
         symbolic_args.append(
-            expr.Expression("argument", ann.placement, [], ann.vtype, {"arg_name": arg_name})
+            expr.Expression("argument", ann.placement, [], ann.vtype, {"arg_name": arg_name},
+                            static_shape=getattr(ann, "shape", None))
         )
     result = abstract_computation.func(*symbolic_args)
     return AstTracer(role_map=abstract_computation.role_map).trace(result)

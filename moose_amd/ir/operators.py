@@ -127,6 +127,14 @@ EXTENSION_OPERATORS = {
     "WeightedSum": [("weights", "ints"), ("bits", "int")],
     "StridedSlice": [("slices", "ints")],
     "MulLeading": [],  # x[i, ...] * c[i]: rank-agnostic public scaling (polymorphic plans)
+    # patch gather of a 2-D convolution: rank-4 NCHW / NHWC -> [N*OH*OW, C*KH*KW], rows
+    # (n, oh, ow), columns (c, kh, kw) (NHWC: (kh, kw, c)); pads are (top, left, bottom,
+    # right) and padded taps are zero.  Share-wise on replicated values (a convolution is
+    # linear): the GEMM that follows is the ordinary fixed-point Dot
+    "Im2Col": [("kernel_shape", "ints"), ("strides", "ints"), ("pads", "ints"),
+               ("dilations", "ints"), ("data_format", "str")],
+    # general axis permutation (Transpose reverses all axes); share-wise
+    "Permute": [("axes", "ints")],
 }
 
 ALL_OPERATORS = {**OPERATORS, **EXTENSION_OPERATORS}

@@ -4,6 +4,7 @@ from moose_amd.models.predictors.base import DEFAULT_FIXED_DTYPE  # noqa: F401
 from moose_amd.models.predictors.base import DEFAULT_FLOAT_DTYPE  # noqa: F401
 from moose_amd.models.predictors.base import AesWrapper  # noqa: F401
 from moose_amd.models.predictors.base import Predictor  # noqa: F401
+from moose_amd.models.predictors.conv import ConvNetwork  # noqa: F401
 from moose_amd.models.predictors.convert import from_onnx  # noqa: F401
 from moose_amd.models.predictors.linear import LinearClassifier  # noqa: F401
 from moose_amd.models.predictors.linear import LinearRegressor  # noqa: F401

@@ -1,0 +1,257 @@
+"""Convolutional networks exported from PyTorch or Keras/tf2onnx.
+
+The reference has no convolution; this predictor is this framework's own.  A graph is a
+chain of ``Conv`` (``group = 1``), ``Relu`` / ``Sigmoid``, ``MaxPool`` / ``AveragePool``,
+``Flatten`` (or ``Reshape`` to ``[N, -1]``), ``Gemm`` / ``MatMul`` + ``Add`` and a final
+``Softmax``.  The model input is rank 4, NCHW.  Inside the MPC the activations are NHWC from
+the first convolution on, so no permutation ever runs on shares: the first ``im2col`` reads
+NCHW, the convolution weights are re-ordered to the patch matrix's (kh, kw, c) rows and the
+first dense layer's rows from the ONNX (c, h, w) flatten order to (h, w, c), all in numpy when
+the model is loaded.  Weights are mirrored fixed-point constants, as in ``DenseNetwork``.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+import moose_amd as pm
+from moose_amd.models.predictors import onnx_proto
+from moose_amd.models.predictors.base import DEFAULT_FIXED_DTYPE
+from moose_amd.models.predictors.base import Predictor
+from moose_amd.models.predictors.base import find_attribute
+from moose_amd.models.predictors.base import initializers
+from moose_amd.models.predictors.base import load_onnx
+
+
+def _ints(node, name, default):
+    a = find_attribute(node, name, enforce=False)
+    return tuple(int(v) for v in a.ints) if a is not None and list(a.ints) else tuple(default)
+
+
+def _int(node, name, default=0):
+    a = find_attribute(node, name, enforce=False)
+    return int(a.i) if a is not None else default
+
+
+def _unsupported(node, why):
+    return ValueError(f"unsupported ONNX node {node.name or node.op_type} ({node.op_type}): {why}")
+
+
+def _window_attrs(node):
+    """(kernel_shape, strides, pads) of a pooling node, rejecting what the MPC does not run."""
+    ap = find_attribute(node, "auto_pad", enforce=False)
+    if ap is not None and ap.s not in (b"", b"NOTSET"):
+        raise _unsupported(node, f"auto_pad={ap.s.decode()}")
+    if _int(node, "ceil_mode"):
+        raise _unsupported(node, "ceil_mode=1")
+    kernel = _ints(node, "kernel_shape", ())
+    if len(kernel) != 2:
+        raise _unsupported(node, f"kernel_shape {kernel} is not 2-D")
+    if any(d != 1 for d in _ints(node, "dilations", (1, 1))):
+        raise _unsupported(node, "dilations")
+    return kernel, _ints(node, "strides", (1, 1)), _ints(node, "pads", (0, 0, 0, 0))
+
+
+def hwc_rows(w, c, h, w_):
+    """Rows of a dense weight ``[c*h*w_, out]`` moved from the (c, h, w) flatten order of an
+    NCHW activation to the (h, w, c) order of its NHWC form."""
+    w = np.asarray(w)
+    return w.reshape(c, h, w_, -1).transpose(1, 2, 0, 3).reshape(c * h * w_, -1)
+
+
+def conv_layers_from_onnx(model):
+    """-> (input (C, H, W), layers): each layer a dict with ``op`` in conv / relu / sigmoid /
+    maxpool / avgpool / flatten / dense / softmax and its parameters (ONNX layouts)."""
+    dims = model.graph.input[0].type.tensor_type.shape.dim
+    if len(dims) != 4:
+        raise ValueError("a convolutional predictor expects a rank-4 [batch, C, H, W] model input")
+    chw = tuple(int(d.dim_value) for d in dims[1:])
+    if min(chw) <= 0:
+        raise ValueError(f"the model input's channel and image sizes must be static, found {chw}")
+    init = dict(initializers(model))
+    layers = []
+    for node in model.graph.node:
+        op = node.op_type
+        if op == "Constant":
+            t = find_attribute(node, "value", enforce=False)
+            if t is None:
+                raise _unsupported(node, "a Constant without a tensor value")
+            init[node.output[0]] = onnx_proto.to_array(t.t)
+        elif op == "Conv":
+            if _int(node, "group", 1) != 1:
+                raise _unsupported(node, f"group={_int(node, 'group', 1)}")
+            ap = find_attribute(node, "auto_pad", enforce=False)
+            if ap is not None and ap.s not in (b"", b"NOTSET"):
+                raise _unsupported(node, f"auto_pad={ap.s.decode()}")
+            if len(node.input) < 2 or node.input[1] not in init:
+                raise _unsupported(node, "its weight is not an initializer")
+            w = np.asarray(init[node.input[1]], dtype=np.float64)
+            if w.ndim != 4:
+                raise _unsupported(node, f"weight of shape {w.shape} is not 2-D")
+            b = init[node.input[2]] if len(node.input) > 2 else np.zeros(w.shape[0])
+            layers.append({"op": "conv", "w": w, "b": np.asarray(b, np.float64).reshape(-1),
+                           "strides": _ints(node, "strides", (1, 1)),
+                           "pads": _ints(node, "pads", (0, 0, 0, 0)),
+                           "dilations": _ints(node, "dilations", (1, 1))})
+        elif op in ("Relu", "Sigmoid"):
+            layers.append({"op": op.lower()})
+        elif op == "MaxPool":
+            kernel, strides, pads = _window_attrs(node)
+            if any(pads):
+                raise _unsupported(node, f"pads={pads}")
+            layers.append({"op": "maxpool", "kernel": kernel, "strides": strides})
+        elif op == "AveragePool":
+            kernel, strides, pads = _window_attrs(node)
+            if any(pads) and not _int(node, "count_include_pad"):
+                raise _unsupported(node, f"pads={pads} without count_include_pad=1")
+            layers.append({"op": "avgpool", "kernel": kernel, "strides": strides, "pads": pads})
+        elif op == "Flatten":
+            if _int(node, "axis", 1) != 1:
+                raise _unsupported(node, f"axis={_int(node, 'axis', 1)}")
+            layers.append({"op": "flatten"})
+        elif op == "Reshape":
+            shape = init.get(node.input[1]) if len(node.input) > 1 else None
+            shape = None if shape is None else [int(s) for s in np.asarray(shape).reshape(-1)]
+            if shape is None or len(shape) != 2 or -1 not in shape:
+                raise _unsupported(node, f"only a Reshape to [N, -1] is supported, found {shape}")
+            layers.append({"op": "flatten"})
+        elif op == "Gemm" and len(node.input) >= 2 and node.input[1] in init:
+            w = np.asarray(init[node.input[1]], dtype=np.float64)
+            if _int(node, "transB"):
+                w = w.T
+            if _int(node, "transA"):
+                raise _unsupported(node, "transA=1")
+            alpha = find_attribute(node, "alpha", enforce=False)
+            if alpha is not None:  # present: its value holds, an explicit 0 included
+                w = w * float(alpha.f)
+            b = init[node.input[2]] if len(node.input) > 2 else np.zeros(w.shape[1])
+            beta = find_attribute(node, "beta", enforce=False)
+            if beta is not None:
+                b = np.asarray(b, np.float64) * float(beta.f)
+            layers.append({"op": "dense", "w": w, "b": np.asarray(b, np.float64).reshape(-1)})
+        elif op == "MatMul" and len(node.input) == 2 and node.input[1] in init:
+            w = np.asarray(init[node.input[1]], dtype=np.float64)
+            layers.append({"op": "dense", "w": w, "b": np.zeros(w.shape[1])})
+        elif (op == "Add" and layers and layers[-1]["op"] == "dense"
+              and any(i in init for i in node.input)):
+            b = init[next(i for i in node.input if i in init)]
+            layers[-1]["b"] = layers[-1]["b"] + np.asarray(b, np.float64).reshape(-1)
+        elif op == "Softmax":
+            layers.append({"op": "softmax"})
+        else:
+            raise _unsupported(node, "not an operator of a convolutional predictor")
+    if any(l["op"] == "softmax" for l in layers[:-1]):
+        raise ValueError("unsupported ONNX graph: Softmax is only supported as the final node")
+    if not any(l["op"] == "conv" for l in layers):
+        raise ValueError("no Conv node found in the ONNX graph")
+    return chw, layers
+
+
+class ConvNetwork(Predictor):
+    """A convolutional network (see the module doc); ``input_chw`` is the model input's
+    (C, H, W), the batch size is free."""
+
+    def __init__(self, input_chw, layers):
+        super().__init__()
+        self.input_chw = tuple(int(v) for v in input_chw)
+        self.layers = [dict(l) for l in layers]
+        self._plan()
+
+    @classmethod
+    def from_onnx(cls, model):
+        return cls(*conv_layers_from_onnx(load_onnx(model)))
+
+    def _plan(self):
+        """Walk the layers once in numpy: per-layer activation shapes, the layouts (NCHW
+        until the first convolution, NHWC after it) and the re-ordered weight matrices."""
+        c, h, w = self.input_chw
+        fmt, flat = "NCHW", None
+        for l in self.layers:
+            op = l["op"]
+            if op in ("conv", "maxpool", "avgpool") and flat is not None:
+                raise ValueError(f"unsupported ONNX graph: {op} after Flatten")
+            if op == "conv":
+                oc, wc, kh, kw = l["w"].shape
+                if wc != c:
+                    raise ValueError(f"Conv weight {l['w'].shape} does not match {c} channels")
+                l.update(fmt=fmt, chw=(c, h, w), kernel=(kh, kw))
+                if fmt == "NCHW":  # columns (c, kh, kw): the ONNX weight as it is
+                    l["wm"] = l["w"].reshape(oc, -1).T
+                else:  # columns (kh, kw, c)
+                    l["wm"] = l["w"].transpose(2, 3, 1, 0).reshape(-1, oc)
+                h, w = _out_hw(h, w, (kh, kw), l["strides"], l["pads"], l["dilations"])
+                c, fmt = oc, "NHWC"
+            elif op in ("maxpool", "avgpool"):
+                l.update(fmt=fmt, chw=(c, h, w))
+                h, w = _out_hw(h, w, l["kernel"], l["strides"], l.get("pads", (0, 0, 0, 0)),
+                               (1, 1))
+            elif op == "flatten":
+                flat = (fmt, c, h, w)
+            elif op == "dense":
+                if flat is None:
+                    raise ValueError("unsupported ONNX graph: Gemm / MatMul before Flatten")
+                wm = l["w"]
+                if flat[0] is not None:
+                    f, fc, fh, fw = flat
+                    if wm.shape[0] != fc * fh * fw:
+                        raise ValueError(f"dense weight {wm.shape} does not match the flattened "
+                                         f"{(fc, fh, fw)} activation")
+                    if f == "NHWC":
+                        wm = hwc_rows(wm, fc, fh, fw)
+                    flat = (None,) + flat[1:]
+                l["wm"] = wm
+                self.n_outputs = wm.shape[1]
+            if min(h, w) <= 0:
+                raise ValueError(f"layer {op} leaves an empty {h}x{w} image")
+
+    def predict(self, x, fixedpoint_dtype=DEFAULT_FIXED_DTYPE):
+        const = lambda v: self.fixedpoint_constant(v, plc=self.mirrored,  # noqa: E731
+                                                   dtype=fixedpoint_dtype)
+        for l in self.layers:
+            op = l["op"]
+            if op == "conv":
+                c, h, w = l["chw"]
+                shape = (None, c, h, w) if l["fmt"] == "NCHW" else (None, h, w, c)
+                cols = pm.im2col(x, l["kernel"], l["strides"], l["pads"], l["dilations"],
+                                 l["fmt"], input_shape=shape)
+                y = pm.add(pm.dot(cols, const(l["wm"])), const(l["b"]))
+                oh, ow = _out_hw(h, w, l["kernel"], l["strides"], l["pads"], l["dilations"])
+                x = pm.reshape(y, [-1, oh, ow, l["w"].shape[0]])
+            elif op in ("maxpool", "avgpool"):
+                c, h, w = l["chw"]
+                shape = (None, c, h, w) if l["fmt"] == "NCHW" else (None, h, w, c)
+                if op == "maxpool":
+                    x = pm.max_pool2d(x, l["kernel"], l["strides"], l["fmt"], input_shape=shape)
+                else:
+                    x = pm.avg_pool2d(x, l["kernel"], l["strides"], l["pads"], l["fmt"],
+                                      input_shape=shape)
+            elif op == "relu":
+                x = pm.relu(x)
+            elif op == "sigmoid":
+                x = pm.sigmoid(x)
+            elif op == "flatten":
+                c, h, w = self._flat_size()
+                x = pm.reshape(x, [-1, c * h * w])
+            elif op == "dense":
+                x = pm.add(pm.dot(x, const(l["wm"])), const(l["b"]))
+            elif op == "softmax":
+                x = pm.softmax(x, axis=1, upmost_index=self.n_outputs)
+        return x
+
+    def _flat_size(self):
+        c, h, w = self.input_chw
+        for l in self.layers:
+            if l["op"] == "conv":
+                h, w = _out_hw(h, w, l["kernel"], l["strides"], l["pads"], l["dilations"])
+                c = l["w"].shape[0]
+            elif l["op"] in ("maxpool", "avgpool"):
+                h, w = _out_hw(h, w, l["kernel"], l["strides"], l.get("pads", (0, 0, 0, 0)),
+                               (1, 1))
+            elif l["op"] == "flatten":
+                break
+        return c, h, w
+
+
+def _out_hw(h, w, kernel, strides, pads, dilations):
+    (kh, kw), (sh, sw), (pt, pl, pb, pr), (dh, dw) = kernel, strides, pads, dilations
+    return ((h + pt + pb - dh * (kh - 1) - 1) // sh + 1,
+            (w + pl + pr - dw * (kw - 1) - 1) // sw + 1)

@@ -1,13 +1,15 @@
 """``from_onnx``: infer the predictor type of an ONNX model.
 
 Parity: reference ``pymoose/pymoose/predictors/onnx_convert.py:8-92``: PyTorch and
-tf2onnx exports are neural networks; otherwise the single recognised ML operator
+tf2onnx exports are neural networks (convolutional ones, which the reference does not have,
+when the graph has a ``Conv`` node); otherwise the single recognised ML operator
 (LinearRegressor / LinearClassifier / TreeEnsembleRegressor / TreeEnsembleClassifier)
 decides, and graphs with several weight matrices are sklearn MLPs (classifiers have a
 ``ZipMap`` node).
 """
 from __future__ import annotations
 
+from moose_amd.models.predictors import conv
 from moose_amd.models.predictors import linear
 from moose_amd.models.predictors import neural
 from moose_amd.models.predictors import trees
@@ -24,6 +26,8 @@ _SUPPORTED = {
 def from_onnx(model):
     model = load_onnx(model)
     if model.producer_name in ("pytorch", "tf2onnx"):
+        if any(n.op_type == "Conv" for n in model.graph.node):
+            return conv.ConvNetwork.from_onnx(model)
         return neural.NeuralNetwork.from_onnx(model)
     ops = [n.op_type for n in model.graph.node]
     found = [o for o in ops if o in _SUPPORTED]

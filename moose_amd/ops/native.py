@@ -33,6 +33,9 @@ _SIGS = {
                               c_i64, c_i64, c_vp]),
     "mx_ew_unary2": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp]),
     "mx_transpose2": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp]),
+    # (dev, elem_bytes, in, out, slots, in_slot_stride, N C H W, KH KW, sh sw, pt pl, dh dw,
+    #  OH OW, nhwc, stream)
+    "mx_im2col": (c_int, [c_int, c_int, c_vp, c_vp, c_i64, c_i64] + [c_i64] * 14 + [c_int, c_vp]),
     "mx_ew_binary_slot2": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp,
                                    c_i64, c_int, c_int, c_int, c_vp]),
     "mx_mul_trunc3_kv": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,

@@ -718,6 +718,118 @@ def strided_slice(a: RT, slices, nb=0) -> RT:
     return RT(d[tuple(idx)].contiguous(), a.bits)
 
 
+def im2col_geometry(shape, kernel_shape, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1),
+                    data_format="NCHW"):
+    """Validate the attributes of an im2col over a rank-4 ``shape`` and return
+    ``(N, C, H, W, KH, KW, sh, sw, pt, pl, pb, pr, dh, dw, OH, OW)``; ``pads`` is (top, left,
+    bottom, right), the ONNX order.  ``ValueError`` on anything malformed, and on an output
+    that would be empty (``OH <= 0`` or ``OW <= 0``)."""
+    if data_format not in ("NCHW", "NHWC"):
+        raise ValueError(f"im2col: data_format must be 'NCHW' or 'NHWC', found {data_format!r}")
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 4:
+        raise ValueError(f"im2col expects a rank-4 {data_format} tensor, found shape {shape}")
+    for name, v, n in (("kernel_shape", kernel_shape, 2), ("strides", strides, 2),
+                       ("pads", pads, 4), ("dilations", dilations, 2)):
+        if not isinstance(v, (tuple, list)) or len(v) != n or \
+                not all(isinstance(x, (int, np.integer)) for x in v):
+            raise ValueError(f"im2col: `{name}` must be {n} ints, found {v!r}")
+    KH, KW = (int(k) for k in kernel_shape)
+    sh, sw = (int(s) for s in strides)
+    pt, pl, pb, pr = (int(p) for p in pads)
+    dh, dw = (int(d) for d in dilations)
+    if min(KH, KW) <= 0 or min(sh, sw) <= 0 or min(dh, dw) <= 0:
+        raise ValueError("im2col: kernel_shape, strides and dilations must be positive, found "
+                         f"{tuple(kernel_shape)}, {tuple(strides)}, {tuple(dilations)}")
+    if min(pt, pl, pb, pr) < 0:
+        raise ValueError(f"im2col: pads must be non-negative, found {tuple(pads)}")
+    if data_format == "NCHW":
+        N, C, H, W = shape
+    else:
+        N, H, W, C = shape
+    OH = (H + pt + pb - dh * (KH - 1) - 1) // sh + 1
+    OW = (W + pl + pr - dw * (KW - 1) - 1) // sw + 1
+    if OH <= 0 or OW <= 0:
+        raise ValueError(
+            f"im2col: a {KH}x{KW} kernel (dilations {(dh, dw)}) does not fit the padded "
+            f"{H + pt + pb}x{W + pl + pr} image: output would be {OH}x{OW}")
+    return N, C, H, W, KH, KW, sh, sw, pt, pl, pb, pr, dh, dw, OH, OW
+
+
+def im2col_torch(d: torch.Tensor, geom, data_format, nb=0) -> torch.Tensor:
+    """im2col as a torch composition (zero pad, ``as_strided`` window view, ``contiguous``)
+    on a tensor of dims ``[nb batch dims, N, C, H, W, trailing...]`` (or N, H, W, C): the
+    path of plain host tensors, and the yardstick of the ring kernel."""
+    N, C, H, W, KH, KW, sh, sw, pt, pl, pb, pr, dh, dw, OH, OW = geom
+    lead, tail = tuple(d.shape[:nb]), tuple(d.shape[nb + 4:])
+    nhwc = data_format == "NHWC"
+    hax = nb + (1 if nhwc else 2)
+    if pt or pl or pb or pr:
+        shp = list(d.shape)
+        shp[hax] += pt + pb
+        shp[hax + 1] += pl + pr
+        padded = d.new_zeros(shp)
+        idx = [slice(None)] * d.dim()
+        idx[hax], idx[hax + 1] = slice(pt, pt + H), slice(pl, pl + W)
+        padded[tuple(idx)] = d
+    else:
+        padded = d.contiguous()
+    st = padded.stride()
+    sN, sH, sW = st[nb], st[hax], st[hax + 1]
+    sC = st[nb + 3] if nhwc else st[nb + 1]
+    if nhwc:
+        size = (N, OH, OW, KH, KW, C)
+        stride = (sN, sH * sh, sW * sw, sH * dh, sW * dw, sC)
+    else:
+        size = (N, OH, OW, C, KH, KW)
+        stride = (sN, sH * sh, sW * sw, sC, sH * dh, sW * dw)
+    nt = len(tail)
+    view = padded.as_strided(lead + size + tail,
+                             tuple(st[:nb]) + stride + tuple(st[len(st) - nt:] if nt else ()))
+    return view.contiguous().reshape(lead + (N * OH * OW, C * KH * KW) + tail)
+
+
+# The device default of im2col: the gather kernel, or the torch composition when False
+# (benchmarks/conv2d.py measures both; profiles/conv2d.md has the numbers)
+IM2COL_KERNEL = True
+
+
+def im2col(a: RT, kernel_shape, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1),
+           data_format="NCHW", nb=0) -> RT:
+    """Patch matrix of a rank-4 ring tensor after ``nb`` batch dims: ``[..., N*OH*OW,
+    C*KH*KW]``, rows (n, oh, ow), columns (c, kh, kw) for NCHW and (kh, kw, c) for NHWC, zero
+    in the padding.  One native launch over all batch slots (``mx_im2col``), which reads a
+    slot-strided view ([slots, ...] with dense slots) in place."""
+    geom = im2col_geometry(a.shape[nb:], kernel_shape, strides, pads, dilations, data_format)
+    N, C, H, W, KH, KW, sh, sw, pt, pl, _pb, _pr, dh, dw, OH, OW = geom
+    lead = tuple(a.shape[:nb])
+    out_shape = lead + (N * OH * OW, C * KH * KW)
+    if a.device.type == "meta":  # shape inference of the symbolic session
+        return empty(out_shape, a.bits, a.device)
+    if a.device.type == "cuda" and not IM2COL_KERNEL:
+        tail = 1 if a.bits == 128 else 0
+        assert a.data.dim() == nb + 4 + tail
+        return RT(im2col_torch(a.data, geom, data_format, nb), a.bits)
+    d = a.data
+    w = 2 if a.bits == 128 else 1  # int64 words per element (uint8 for bits)
+    slots = math.prod(lead)
+    slot = d[(0,) * nb] if nb and slots else d
+    if nb == 1 and slots and slot.is_contiguous() and d.stride(0) >= 0 and d.stride(0) % w == 0:
+        slot_stride = d.stride(0) // w
+    else:
+        d = d.contiguous()
+        slot_stride = N * C * H * W
+    out = empty(out_shape, a.bits, a.device)
+    nat.check(
+        nat.lib().mx_im2col(
+            nat.dev_of(d), {1: 1, 64: 8, 128: 16}[a.bits], nat.ptr(d), nat.ptr(out.data),
+            slots, slot_stride, N, C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW,
+            1 if data_format == "NHWC" else 0, nat.stream_of(d)),
+        "im2col",
+    )
+    return out
+
+
 def select_mask(a: RT, axis: int, mask: torch.Tensor, nb=0) -> RT:
     ax = _ax(a, axis, nb)
     keep = torch.nonzero(mask.reshape(-1).to(torch.bool)).reshape(-1).to(a.device)

@@ -194,7 +194,7 @@ kernel("Share", "rep", "host_bit")(lambda c, x: rep.share(c.sess, c.plc, x, kind
 
 # shape / linear ops are share-wise
 for _op in ("Reshape", "ExpandDims", "Squeeze", "Transpose", "Slice", "IndexAxis", "Broadcast",
-            "Concat"):
+            "Im2Col", "Permute", "Concat"):
     kernel(_op, "rep", "rep_ring", variadic=_op == "Concat")(
         lambda c, *xs, p=_op: _local(c, p, xs))
     kernel(_op, "rep", "rep_bit", variadic=_op == "Concat")(

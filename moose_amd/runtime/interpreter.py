@@ -155,6 +155,7 @@ class Interpreter:
         self.storage_tap = None
         # independent operations on separate HIP streams (runtime/lanes.py)
         self.lanes = None
+        self._const_shapes = {}  # shape constants of the running computation (run)
         dev = getattr(sess, "device", None)
         n = lanes if lanes is not None else _lanes.default_lanes()
         if n > 1 and dev is not None and dev.type == "cuda" and getattr(sess, "me", None) is None:
@@ -167,6 +168,9 @@ class Interpreter:
         self.arguments = arguments or {}
         self._at_memo = {}
         comp = comp.toposorted()
+        self._const_shapes = {  # shape constants: known on every party wherever they live
+            op.name: tuple(op.attrs["value"].value) for op in comp.operations
+            if op.kind == "Constant" and getattr(op.attrs.get("value"), "kind", "") == "HostShape"}
         # every non-host operation draws its PRF nonces from a scope of its own, numbered by
         # its place among them in the toposorted program (the same on every party and in
         # every layout; host operations -- which draw none -- do not shift the numbering)
@@ -1475,7 +1479,9 @@ class Interpreter:
         return self._shape_op(op, ins[0], "Diag")
 
     def op_Reshape(self, op, ins):
-        shape = tuple(self._plain(ins[1]))
+        shape = self._const_shapes.get(op.inputs[1])
+        if shape is None:
+            shape = tuple(self._plain(ins[1]))
         return self._shape_op(op, ins[0], "Reshape", shape=shape)
 
     def op_Broadcast(self, op, ins):
@@ -1494,6 +1500,15 @@ class Interpreter:
         slices = sl if isinstance(sl, list) else [sl]
         py = [slice(a, b, c) for (a, b, c) in slices]
         return self._shape_op(op, x, "StridedSlice", slices=py)
+
+    def op_Im2Col(self, op, ins):
+        a = op.attrs
+        return self._shape_op(op, ins[0], "Im2Col", kernel_shape=tuple(a["kernel_shape"]),
+                              strides=tuple(a["strides"]), pads=tuple(a["pads"]),
+                              dilations=tuple(a["dilations"]), data_format=a["data_format"])
+
+    def op_Permute(self, op, ins):
+        return self._shape_op(op, ins[0], "Permute", axes=tuple(op.attrs["axes"]))
 
     def op_Select(self, op, ins):
         # operands (index, x), as the reference's SelectOp (kernels/indexing.rs:60)

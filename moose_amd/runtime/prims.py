@@ -306,10 +306,26 @@ builtins_slice = slice
 
 
 @prim("Permute")
-def _permute(nb, a, perm):
+def _permute(nb, a, perm=None, axes=None):
+    perm = list(axes if perm is None else perm)  # `axes` is the IR operator's attribute
+    rank = (a.ndim if _is_rt(a) else a.dim()) - nb
+    if sorted(perm) != list(range(rank)):
+        raise ValueError(f"Permute: axes {perm} are not a permutation of the tensor's axes")
     if _is_rt(a):
         return R.transpose(a, nb, perm)
     return a.permute(list(range(nb)) + [p + nb for p in perm]).contiguous()
+
+
+@prim("Im2Col")
+def _im2col(nb, a, kernel_shape, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1),
+            data_format="NCHW"):
+    """Patch matrix [N*OH*OW, C*KH*KW] of a rank-4 tensor (R.im2col): ring tensors through
+    the native gather, plain tensors through pad + as_strided + contiguous."""
+    if _is_rt(a):
+        return R.im2col(a, kernel_shape, strides, pads, dilations, data_format, nb)
+    geom = R.im2col_geometry(tuple(a.shape[nb:]), kernel_shape, strides, pads, dilations,
+                             data_format)
+    return R.im2col_torch(a, geom, data_format, nb)
 
 
 @prim("StridedSlice")
