@@ -119,8 +119,17 @@ MX_HD inline T zs_combine(int kind, T v, T ra, T rb) {
   return (T)(v + ra - rb);
 }
 
-// double -> two's complement integer, truncating toward zero (Rust `as i128`
-// semantics, saturating at the range limits; NaN -> 0)
+// Fixed-point conversions follow Rust's numeric `as` casts, which the reference applies at
+// the ring's own width:
+//   double -> Z_2^64  is `x as i64 as u64`:   truncates toward zero, saturates at
+//                     [-2^63, 2^63 - 1], NaN -> 0;
+//   double -> Z_2^128 is `x as i128 as u128`: the same at [-2^127, 2^127 - 1];
+//   Z_2^w  -> double  is `x as iW as f64`:    the nearest double of the signed value, ties
+//                     to even, one rounding.
+// Kernels encode through f64_to_ring<T> only, so the stand-alone encode and the share
+// kernels that encode their input cannot drift apart.
+
+// double -> i128, truncating toward zero, saturating at the limits of i128; NaN -> 0
 MX_HD inline i128 f64_to_i128(double x) {
   uint64_t bits;
   memcpy(&bits, &x, 8);
@@ -143,12 +152,38 @@ MX_HD inline i128 f64_to_i128(double x) {
   return neg ? -(i128)mag : (i128)mag;
 }
 
+// double -> element of the ring T (u64 or u128), saturating at the signed range of T
+template <class T>
+MX_HD inline T f64_to_ring(double x) {
+  if constexpr (sizeof(T) == 8) {
+    if (x >= 9223372036854775808.0) return (T)0x7fffffffffffffffull;
+    if (x > -9223372036854775808.0) return (T)(int64_t)x;  // in range: the cast truncates
+    return x != x ? (T)0 : (T)1 << 63;
+  } else {
+    return (T)f64_to_i128(x);
+  }
+}
+
+// signed value of a Z_2^128 element -> nearest double (ties to even).  The magnitude is taken
+// in unsigned arithmetic (-2^127 has no signed negation) and rounded once: its top 64 bits,
+// with a sticky bit for whatever lies below them, convert in one correctly rounded step, and
+// the scaling back by a power of two is exact.
 MX_HD inline double i128_to_f64(u128 v) {
-  i128 s = (i128)v;
-  int neg = s < 0;
-  u128 m = neg ? (u128)(-s) : (u128)s;
-  uint64_t hi = (uint64_t)(m >> 64), lo = (uint64_t)m;
-  double r = (double)hi * 18446744073709551616.0 + (double)lo;
+  const bool neg = (v >> 127) != 0;
+  const u128 m = neg ? (u128)0 - v : v;
+  const uint64_t hi = (uint64_t)(m >> 64), lo = (uint64_t)m;
+  double r;
+  if (hi == 0) {
+    r = (double)lo;
+  } else {
+    const int s = 64 - __builtin_clzll(hi);  // 1..64 bits of m lie above the low limb
+    const uint64_t lost = s == 64 ? lo : lo & ((1ull << s) - 1);
+    const uint64_t top = (uint64_t)(m >> s) | (uint64_t)(lost != 0);  // bit 63 is set
+    const uint64_t pbits = (uint64_t)(1023 + s) << 52;                // 2^s as a double
+    double p;
+    memcpy(&p, &pbits, 8);
+    r = (double)top * p;
+  }
   return neg ? -r : r;
 }
 

@@ -625,14 +625,14 @@ int mx_encode(int dev, int words, const double* x, void* out, int64_t n, int fra
   if (words == 1) {
     u64* o = (u64*)out;
     parallel_for(n, 1 << 16, [&](int64_t s, int64_t e) {
-      for (int64_t i = s; i < e; ++i) o[i] = (u64)mxr::f64_to_i128(x[i] * std::ldexp(1.0, frac));
+      for (int64_t i = s; i < e; ++i) o[i] = mxr::f64_to_ring<u64>(x[i] * std::ldexp(1.0, frac));
     });
     return 0;
   }
   if (words == 2) {
     u128* o = (u128*)out;
     parallel_for(n, 1 << 16, [&](int64_t s, int64_t e) {
-      for (int64_t i = s; i < e; ++i) o[i] = (u128)mxr::f64_to_i128(x[i] * std::ldexp(1.0, frac));
+      for (int64_t i = s; i < e; ++i) o[i] = mxr::f64_to_ring<u128>(x[i] * std::ldexp(1.0, frac));
     });
     return 0;
   }

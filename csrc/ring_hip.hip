@@ -546,7 +546,7 @@ __device__ __forceinline__ void d_encode(const double* __restrict__ x, T* __rest
                                          int64_t n, double scale) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = (T)mxr::f64_to_i128(x[i] * scale);
+    out[i] = mxr::f64_to_ring<T>(x[i] * scale);
 }
 
 template <class T>

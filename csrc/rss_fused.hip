@@ -287,7 +287,7 @@ __global__ void __launch_bounds__(256) k_share3(int kind, const void* __restrict
       const int64_t i = b * P + j;
       if (i >= n) break;
       const T r = mxd::pick<T>(lo[0], hi[0], j);
-      const T xi = kind == MX_SHARE_F64 ? (T)mxr::f64_to_i128(xf[i] * scale) : x[i];
+      const T xi = kind == MX_SHARE_F64 ? mxr::f64_to_ring<T>(xf[i] * scale) : x[i];
       const T v = kind == MX_CROSS_BOOL ? (T)(xi ^ r) : (T)(xi - r);
       T slot[3];
       slot[j0] = mir ? v : r;

@@ -120,7 +120,7 @@ int share3_host(int kind, const void* xv, T* out0, T* out1, int64_t n, int j, co
       mx_cpu_prf_range(kn, n1, words, c, len, r1.data());
       for (int64_t t = 0; t < len; ++t) {
         int64_t i = c + t;
-        const T xi = kind == MX_SHARE_F64 ? (T)mxr::f64_to_i128(xf[i] * scale) : x[i];
+        const T xi = kind == MX_SHARE_F64 ? mxr::f64_to_ring<T>(xf[i] * scale) : x[i];
         const T v = kind == MX_CROSS_BOOL ? (T)(xi ^ r1[t]) : (T)(xi - r1[t]);
         T slot[3];
         slot[j] = mir ? v : r1[t];

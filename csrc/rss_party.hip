@@ -410,7 +410,7 @@ __device__ __forceinline__ void d_share_party(int kind, int64_t n, const Roles& 
         if (i >= n) break;
         const T rr = mxd::pick<T>(al, ah, j);
         if (r == 0) {  // owner: (PRF(k_j), x - PRF(k_j)); mirrored (x - PRF(k_{j+1}), PRF)
-          const T xi = kind == MX_SHARE_F64 ? (T)mxr::f64_to_i128(xf[i] * scale) : x[i];
+          const T xi = kind == MX_SHARE_F64 ? mxr::f64_to_ring<T>(xf[i] * scale) : x[i];
           const T v = kind == MX_CROSS_BOOL ? (T)(xi ^ rr) : (T)(xi - rr);
           out0[base + i] = mir ? v : rr;
           out1[base + i] = mir ? rr : v;

@@ -239,7 +239,7 @@ int share_party(int kind, int64_t n, int ncomp, const int* rel, const void* xp, 
         const int64_t i = base + i0 + q;
         if (r == 0) {
           const T xv =
-              kind == MX_SHARE_F64 ? (T)mxr::f64_to_i128(xf[i0 + q] * scale) : x[i0 + q];
+              kind == MX_SHARE_F64 ? mxr::f64_to_ring<T>(xf[i0 + q] * scale) : x[i0 + q];
           const T v = kind == MX_CROSS_BOOL ? (T)(xv ^ a[q]) : (T)(xv - a[q]);
           out0[i] = mir ? v : a[q];
           out1[i] = mir ? a[q] : v;

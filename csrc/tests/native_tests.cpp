@@ -10,10 +10,12 @@
 // (mxh_*) are never called with dev == 0 and are left unresolved at link time.
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <random>
 #include <string>
 #include <thread>
@@ -160,6 +162,77 @@ TEST(ring, fixedpoint_encode_decode_roundtrip) {
   CHECK(mx_encode(0, 2, x.data(), e.data(), n, 40, nullptr) == 0);
   CHECK(mx_decode(0, 2, e.data(), y.data(), n, 40, nullptr) == 0);
   for (int64_t i = 0; i < n; ++i) CHECK(std::abs(x[i] - y[i]) < 1e-11);
+}
+
+static uint64_t f64_pattern(double x) {
+  uint64_t b;
+  std::memcpy(&b, &x, 8);
+  return b;
+}
+
+TEST(ring, fixedpoint_decode_int_min_and_single_rounding) {
+  // Z_2^128 -> double is the nearest double of the signed value (ties to even), one rounding
+  const u128 one = 1;
+  const u128 x[] = {
+      one << 127,                                      // INT_MIN: -2^127, no signed negation
+      (one << 127) | 1,                                // -(2^127 - 1) rounds to -2^127
+      (((one << 53) + 1) << 11) | 1,                   // tie broken by a bit below the top 64
+      ((one << 53) + 1) << 11,                         // the tie itself: to even (down)
+      ((one << 53) + 3) << 11,                         // the tie that goes up
+      ((u128)0x5135c190bbd8aa00ull << 64) | 0xd520bf347a436450ull,  // hi, lo rounded apart
+      ~(u128)0,                                        // -1
+      (one << 64) - 1,                                 // 2^64 - 1 rounds to 2^64
+  };
+  const double want0[] = {
+      -0x1p127, -0x1p127, 0x1.0000000000001p64, 0x1p64, 0x1.0000000000002p64,
+      0x1.44d70642ef62bp126, -1.0, 0x1p64,
+  };
+  const int64_t n = (int64_t)(sizeof(x) / sizeof(x[0]));
+  std::vector<double> y(n);
+  for (int frac : {0, 23, 40}) {
+    CHECK(mx_decode(0, 2, x, y.data(), n, frac, nullptr) == 0);
+    for (int64_t i = 0; i < n; ++i)
+      CHECK(f64_pattern(y[i]) == f64_pattern(std::ldexp(want0[i], -frac)));
+    // the reveal's fused add + decode, on three parts of each value
+    std::vector<u128> a(n), b(n), c(n);
+    for (int64_t i = 0; i < n; ++i) {
+      a[i] = ((u128)rng() << 64) | rng();
+      b[i] = ((u128)rng() << 64) | rng();
+      c[i] = x[i] - a[i] - b[i];
+    }
+    CHECK(mx_addn_decode(0, 2, a.data(), b.data(), c.data(), nullptr, y.data(), n, frac,
+                         nullptr) == 0);
+    for (int64_t i = 0; i < n; ++i)
+      CHECK(f64_pattern(y[i]) == f64_pattern(std::ldexp(want0[i], -frac)));
+  }
+  const uint64_t x64[] = {1ull << 63, ~0ull, (1ull << 53) + 1, (1ull << 63) - 1};
+  const double want64[] = {-0x1p63, -1.0, 0x1p53, 0x1p63};
+  CHECK(mx_decode(0, 1, x64, y.data(), 4, 23, nullptr) == 0);
+  for (int i = 0; i < 4; ++i)
+    CHECK(f64_pattern(y[i]) == f64_pattern(std::ldexp(want64[i], -23)));
+}
+
+TEST(ring, fixedpoint_encode_saturates_at_the_ring_width) {
+  // double -> Z_2^w truncates toward zero, saturates at [-2^(w-1), 2^(w-1) - 1]; NaN -> 0
+  const double inf = std::numeric_limits<double>::infinity();
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  const double x[] = {0x1p40, -0x1p40, 0x1p40 - 0x1p-13, inf, -inf, nan, 1e300, -1e300,
+                      0x1p104, -0x1p104, 0x1p105, -1.5, 0x1p39};
+  const int64_t n = (int64_t)(sizeof(x) / sizeof(x[0]));
+  const uint64_t max64 = 0x7fffffffffffffffull, min64 = 1ull << 63;
+  const uint64_t want64[] = {max64, min64, max64 - 1023, max64, min64, 0, max64, min64,
+                             max64, min64, max64, (uint64_t)(-(int64_t)(3ull << 22)),
+                             1ull << 62};
+  std::vector<uint64_t> e64(n);
+  CHECK(mx_encode(0, 1, x, e64.data(), n, 23, nullptr) == 0);
+  for (int64_t i = 0; i < n; ++i) CHECK(e64[i] == want64[i]);
+  const u128 one = 1, max128 = ~(one << 127), min128 = one << 127;
+  const u128 want128[] = {one << 63, (u128)0 - (one << 63), (one << 63) - 1024, max128, min128, 0,
+                          max128, min128, max128, min128, max128,
+                          (u128)0 - (u128)(3ull << 22), one << 62};
+  std::vector<u128> e128(n);
+  CHECK(mx_encode(0, 2, x, e128.data(), n, 23, nullptr) == 0);
+  for (int64_t i = 0; i < n; ++i) CHECK(e128[i] == want128[i]);
 }
 
 // ---------------------------------------------------------------------------------

@@ -515,7 +515,8 @@ def sign_extend(a: RT, from_bits: int, bits: int) -> RT:
 
 
 # ---------------------------------------------------------------------------
-# fixed-point encode / decode (reference host/fixedpoint.rs: truncating `as i128`)
+# fixed-point encode / decode (reference host/fixedpoint.rs, host/ops.rs: truncating,
+# saturating `as i64` / `as i128` at the ring's own width; correctly rounded `as f64`)
 # ---------------------------------------------------------------------------
 def encode(x: torch.Tensor, frac: int, bits: int) -> RT:
     x = x.to(torch.float64).contiguous()

@@ -1,5 +1,8 @@
-"""Bit-exact checks of every gfx950 ring kernel against the host (CPU) kernels, which
-are in turn checked against python-int arithmetic in test_ring_cpu.py."""
+"""Bit-exact checks of every gfx950 ring kernel against the host (CPU) kernels on random
+values.  The host kernels are checked against python-int arithmetic in test_ring_cpu.py;
+test_ring_edges.py pins the leaf kernels of both the host and the device to python integers
+at the edges that random values never reach (limb boundaries, INT_MIN, shift counts past a
+limb, floats beyond the ring, more elements than one pass of the grid)."""
 import random
 
 import pytest
