@@ -131,4 +131,67 @@ MX_HD inline T trunc_y(T c, T rt, T rm, int m, bool first) {
   return shl<T>(ov, k - m) - rt + c_top - shl<T>((T)1, k - 1 - m);
 }
 
+// ---------------------------------------------------------------------------------------
+// The rounds of one element as a party in ``role`` computes them: the ONE statement of the
+// per-party protocol for the device kernels (party_rounds.h) and their host twins
+// (party_rounds_cpu.h).  PRF streams (key of the drawing party):
+//   r0, t, m, z0 under k0 (P0 own, P2 next);  r1, z2 under k2 (P1 next, P2 own)
+// ---------------------------------------------------------------------------------------
+
+// The dot tail's zero-share form of a party's local product x: P0 a = f(k0), P1 b = f(k2),
+// P2 both (f = PRF at the zero-share nonce); a stream the role does not draw is 0.
+template <class T>
+MX_HD inline T zero_masked(T x, T a, T b) {
+  return x + a - b;
+}
+
+// Round 0: what P0 / P1 / P2 send of their additive part v of the value (TruncPr: P0's
+// x0 + x1, P1's x2; dot tail: zero_masked) under the opening mask r (P0 r0, P1 r1).
+template <class T>
+MX_HD inline T trunc_open_msg(int role, T v, T r) {
+  return role == 0 ? trunc_mask0<T>(v, (T)0, r) : role == 1 ? (T)(v + r) : v;
+}
+
+// Round 0, dealer P2: the messages for P1 and its own new share (s0, s1) = (z2, z0).
+template <class T>
+struct TruncDeal {
+  T rt1;
+  uint64_t rm1;
+  T s0, s1;
+};
+template <class T>
+MX_HD inline TruncDeal<T> trunc_deal(T r0, T r1, T t, T mm, T z0, T z2, int m) {
+  TruncDeal<T> d;
+  trunc_dealer<T>(r0, r1, t, mm, m, &d.rt1, &d.rm1);
+  d.s0 = z2;
+  d.s1 = z0;
+  return d;
+}
+
+// Round 1, P0 / P1: w = y - z from the opened c; (rt, rm) are P0's own draws t, m or what
+// P1 received from the dealer; z (P0 z0, P1 z2) is the party's new share s0 / s1.
+template <class T>
+MX_HD inline T trunc_round1_w(int role, T c, T rt, T rm, T z, int m) {
+  return trunc_y<T>(c, rt, rm, m, role == 0) - z;
+}
+
+// The same two for the ring extension; every draw is a 128-bit lane, r0, r1 and M0 its low
+// 64 bits.
+struct RingExtendDeal {
+  u128_t R1;
+  uint64_t M1;
+  u128_t s0, s1;
+};
+MX_HD inline RingExtendDeal ring_extend_deal(u128_t r0, u128_t r1, u128_t R0, u128_t M0, u128_t z0,
+                                             u128_t z2) {
+  RingExtendDeal d;
+  ring_extend_dealer((uint64_t)r0, (uint64_t)r1, R0, (uint64_t)M0, &d.R1, &d.M1);
+  d.s0 = z2;
+  d.s1 = z0;
+  return d;
+}
+MX_HD inline u128_t ring_extend_round1_w(int role, uint64_t c, u128_t R, uint64_t M, u128_t z) {
+  return ring_extend_y(c, R, M, role == 0) - z;
+}
+
 }  // namespace mxf

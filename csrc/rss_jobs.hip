@@ -11,7 +11,10 @@
 // product tensor, no concatenation) and the new shares are written straight to each job's
 // output rows (no slicing, no stacking).  Element i of the concatenation of the jobs' rows
 // uses the same keystream chunk as element i of the concatenated tensor in the generic
-// path, so the shares are bitwise those of cross + concat + k_dot_tail_r0/r1/r2.
+// path, so the shares are bitwise those of cross + concat + k_dot_tail_r0/r1/r2.  The rounds
+// themselves -- the streams a role draws, the keystream walk, the round bodies -- are those
+// of party_rounds.h (one element's arithmetic: rss_fused.h); this file adds where a job's
+// elements are read (job_value) and written (job_out), and the latency forms.
 //
 // A job (row length L shared by all jobs of a call):
 //   value[r, e] = cb * (x0 y0 + x0 y1 + x1 y0)  +  ca * a[r, e]  +  ca2 * a2[r, e]
@@ -23,7 +26,9 @@
 #include <cstdlib>
 
 #include "moosex.h"
+#include "party_abi.h"
 #include "party_batch.h"
+#include "party_rounds.h"
 #include "prf_dev.h"
 #include "ring_common.h"
 #include "rss_fused.h"
@@ -131,6 +136,17 @@ __device__ __forceinline__ T* job_out(const Jobs& js, const Loc<T>& l, int which
   return (T*)(which == 0 ? J.o0 : J.o1) + l.r * js.L + l.e;
 }
 
+// the dealer's element i: rt1 / rm1 dense, its new shares at the job's output rows
+template <class T>
+__device__ __forceinline__ void deal_out(const Jobs& js, int64_t i, const mxf::TruncDeal<T>& d,
+                                         T* __restrict__ msg_rt, u64* __restrict__ msg_rm) {
+  msg_rt[i] = d.rt1;
+  msg_rm[i] = d.rm1;
+  const Loc<T> l = locate<T>(js, i);
+  *job_out<T>(js, l, 0) = d.s0;
+  *job_out<T>(js, l, 1) = d.s1;
+}
+
 // Round 0 (rss_party.hip k_dot_tail_r0 for one component of role ``role``): P0 m0, P1 m1, P2
 // z2 of the jobs' values (main != 0), and the dealer P2's rt1 / rm1 and its new shares
 // (dealer != 0; independent of the values, so it may run before they exist).
@@ -143,75 +159,24 @@ __device__ __forceinline__ void
   __shared__ uint32_t rks[mxd::kMaxKeySlots][mxd::kKeyWords];
   mxd::stage_keys(rks, keys, 2);
   fill_pending<T>(js);
-  constexpr int P = mxd::Lane<T>::kPer;
-  const int64_t nb = (n + P - 1) / P;
+  const int64_t nb = mxp::chunks_of<T>(n);
   const uint32_t* own = rks[0];
   const uint32_t* nxt = rks[1];
+  const uint64_t nn[6] = {n_r0, n_r1, n_t, n_m, n_z0, n_z2}, nr[2] = {n_r0, n_r1};
   const int64_t nblk = (int64_t)mx::ks_blocks_for((uint64_t)nb);
   for (int64_t g = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; g < nblk;
        g += (int64_t)gridDim.x * blockDim.x) {
     const uint64_t B = (uint64_t)g;
-    if (main) {
-      uint32_t wa[16], wb[16], wr[16];
-      if (role != 1) mx::chacha_block(own, n_a, B, wa);
-      if (role != 0) mx::chacha_block(nxt, n_a, B, wb);
-      if (role == 0) mx::chacha_block(own, n_r0, B, wr);
-      if (role == 1) mx::chacha_block(nxt, n_r1, B, wr);
-#pragma unroll
-      for (int part = 0; part < 4; ++part) {
-        const int64_t b = (int64_t)mx::ks_chunk(B, part);
-        if (b >= nb) break;
-        uint64_t al = 0, ah = 0, bl = 0, bh = 0, rl = 0, rh = 0;
-        if (role != 1) mx::part_u64(wa, part, &al, &ah);
-        if (role != 0) mx::part_u64(wb, part, &bl, &bh);
-        if (role != 2) mx::part_u64(wr, part, &rl, &rh);
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-          const int64_t i = b * P + j;
-          if (i >= n) break;
-          const Loc<T> l = locate<T>(js, i);
-          const T z = job_value<T>(js, l) + mxd::pick<T>(al, ah, j) - mxd::pick<T>(bl, bh, j);
-          if (role == 0)
-            msg[i] = mxf::trunc_mask0<T>(z, (T)0, mxd::pick<T>(rl, rh, j));
-          else if (role == 1)
-            msg[i] = z + mxd::pick<T>(rl, rh, j);
-          else
-            msg[i] = z;
-        }
-      }
-    }
-    if (role == 2 && dealer) {
-      uint32_t w[6][16];
-      mx::chacha_block(nxt, n_r0, B, w[0]);
-      mx::chacha_block(own, n_r1, B, w[1]);
-      mx::chacha_block(nxt, n_t, B, w[2]);
-      mx::chacha_block(nxt, n_m, B, w[3]);
-      mx::chacha_block(nxt, n_z0, B, w[4]);
-      mx::chacha_block(own, n_z2, B, w[5]);
-#pragma unroll
-      for (int part = 0; part < 4; ++part) {
-        const int64_t b = (int64_t)mx::ks_chunk(B, part);
-        if (b >= nb) break;
-        uint64_t lo[6], hi[6];
-#pragma unroll
-        for (int q = 0; q < 6; ++q) mx::part_u64(w[q], part, &lo[q], &hi[q]);
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-          const int64_t i = b * P + j;
-          if (i >= n) break;
-          T rt1;
-          u64 rm1;
-          mxf::trunc_dealer<T>(mxd::pick<T>(lo[0], hi[0], j), mxd::pick<T>(lo[1], hi[1], j),
-                               mxd::pick<T>(lo[2], hi[2], j), mxd::pick<T>(lo[3], hi[3], j), m,
-                               &rt1, &rm1);
-          msg_rt[i] = rt1;
-          msg_rm[i] = rm1;
-          const Loc<T> l = locate<T>(js, i);
-          *job_out<T>(js, l, 0) = mxd::pick<T>(lo[5], hi[5], j);
-          *job_out<T>(js, l, 1) = mxd::pick<T>(lo[4], hi[4], j);
-        }
-      }
-    }
+    if (main)
+      mxp::main_r0<T, true>(
+          role, own, nxt, n_a, nr, B, nb, n,
+          [&](int64_t i) MX_LAMBDA_INLINE { return job_value<T>(js, locate<T>(js, i)); },
+          [&](int64_t i) MX_LAMBDA_INLINE -> T& { return msg[i]; });
+    if (role == 2 && dealer)
+      mxp::dealer_r0<T>(own, nxt, nn, m, B, nb, n,
+                        [&](int64_t i, const mxf::TruncDeal<T>& d) MX_LAMBDA_INLINE {
+                          deal_out<T>(js, i, d, msg_rt, msg_rm);
+                        });
   }
 }
 
@@ -236,44 +201,26 @@ __device__ __forceinline__ void
   __shared__ uint32_t rks[mxd::kMaxKeySlots][mxd::kKeyWords];
   mxd::stage_keys(rks, keys, 2);
   if (role != 0 && role != 1) return;
-  constexpr int P = mxd::Lane<T>::kPer;
-  const int64_t nb = (n + P - 1) / P;
+  const int64_t nb = mxp::chunks_of<T>(n);
+  const uint64_t nn[4] = {n_t, n_m, n_z0, n_z2};
   const int64_t nblk = (int64_t)mx::ks_blocks_for((uint64_t)nb);
   for (int64_t g = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; g < nblk;
        g += (int64_t)gridDim.x * blockDim.x) {
-    const uint64_t B = (uint64_t)g;
-    uint32_t wt[16], wm[16], wz[16];
-    if (role == 0) {
-      mx::chacha_block(rks[0], n_t, B, wt);
-      mx::chacha_block(rks[0], n_m, B, wm);
-      mx::chacha_block(rks[0], n_z0, B, wz);
-    } else {
-      mx::chacha_block(rks[1], n_z2, B, wz);
-    }
-#pragma unroll
-    for (int part = 0; part < 4; ++part) {
-      const int64_t b = (int64_t)mx::ks_chunk(B, part);
-      if (b >= nb) break;
-      uint64_t tl = 0, th = 0, ml = 0, mh = 0, zl, zh;
-      if (role == 0) {
-        mx::part_u64(wt, part, &tl, &th);
-        mx::part_u64(wm, part, &ml, &mh);
-      }
-      mx::part_u64(wz, part, &zl, &zh);
-#pragma unroll
-      for (int j = 0; j < P; ++j) {
-        const int64_t i = b * P + j;
-        if (i >= n) break;
-        T cc = mine[i] + other[i];
-        if (z2m != nullptr) cc += z2m[i];
-        const T z = mxd::pick<T>(zl, zh, j);
-        const T y = role == 0 ? mxf::trunc_y<T>(cc, mxd::pick<T>(tl, th, j),
-                                                mxd::pick<T>(ml, mh, j), m, true)
-                              : mxf::trunc_y<T>(cc, rt[i], (T)rm[i], m, false);
-        wo[i] = y - z;
-        *job_out<T>(js, locate<T>(js, i), role == 0 ? 0 : 1) = z;
-      }
-    }
+    mxp::round1<T>(
+        role, rks[0], rks[1], nn, m, (uint64_t)g, nb, n,
+        [&](int64_t i) MX_LAMBDA_INLINE {
+          T cc = mine[i] + other[i];
+          if (z2m != nullptr) cc += z2m[i];
+          return cc;
+        },
+        [&](int64_t i, T* t, T* mm) MX_LAMBDA_INLINE {
+          *t = rt[i];
+          *mm = (T)rm[i];
+        },
+        [&](int64_t i, T w, T z) MX_LAMBDA_INLINE {
+          wo[i] = w;
+          *job_out<T>(js, locate<T>(js, i), role == 0 ? 0 : 1) = z;
+        });
   }
 }
 
@@ -317,6 +264,23 @@ struct Streams {
   uint64_t nonce[8];
 };
 
+// One keystream chunk by random access, its ChaCha block computed out of line.  This pins the
+// code the latency kernels had before the round bodies were shared: whether the compiler
+// inlines the block function is a heuristic, and when it does, the block's sixteen words
+// (indexed by the chunk's part) are promoted to a per-thread LDS array, 16 KB a block instead
+// of 80 B of scratch a lane, and these small launches get slower.  To be revisited with the
+// scratch item of docs/NEXT.md (prf_chunk_reg keeps the words in registers).
+__device__ __noinline__ void lat_block(const uint32_t* key, uint64_t nonce, uint64_t blk,
+                                       uint32_t* w) {
+  mx::chacha_block(key, nonce, blk, w);
+}
+__device__ __forceinline__ void lat_chunk(const uint32_t* key, uint64_t nonce, uint64_t c,
+                                          uint64_t* lo, uint64_t* hi) {
+  uint32_t w[16];
+  lat_block(key, nonce, mx::ks_block_of(c), w);
+  mx::part_u64(w, mx::ks_part_of(c), lo, hi);
+}
+
 template <class T>
 __device__ __forceinline__ void
     d_jobs_r0_lat(const Jobs& js, int64_t n, int m, int role, int main, int dealer,
@@ -343,7 +307,7 @@ __device__ __forceinline__ void
     }
     if (s < ss.n && b0 + lb < nb) {
       uint64_t lo, hi;
-      mxd::prf_chunk(rks[ss.key[s]], ss.nonce[s], (uint64_t)(b0 + lb), &lo, &hi);
+      lat_chunk(rks[ss.key[s]], ss.nonce[s], (uint64_t)(b0 + lb), &lo, &hi);
       kl[s][lb] = lo;
       kh[s][lb] = hi;
     }
@@ -354,29 +318,15 @@ __device__ __forceinline__ void
       for (int j = 0; j < P; ++j) {
         const int64_t i = b * P + j;
         if (i >= n) break;
-        if (main) {
-          const T k0 = mxd::pick<T>(kl[0][tid], kh[0][tid], j);
-          const T k1 = mxd::pick<T>(kl[1][tid], kh[1][tid], j);
-          if (role == 0)
-            msg[i] = mxf::trunc_mask0<T>(val[j] + k0, (T)0, k1);
-          else if (role == 1)
-            msg[i] = val[j] - k0 + k1;
-          else
-            msg[i] = val[j] + k0 - k1;
+        const auto ks = [&](int q) { return mxd::pick<T>(kl[q][tid], kh[q][tid], j); };
+        if (main) {  // P0: a, r0; P1: b, r1; P2: a, b
+          const T za = role != 1 ? ks(0) : (T)0;
+          const T zb = role == 1 ? ks(0) : role == 2 ? ks(1) : (T)0;
+          msg[i] = mxf::trunc_open_msg<T>(role, mxf::zero_masked<T>(val[j], za, zb), ks(1));
         }
-        if (role == 2 && dealer) {
-          T rt1;
-          u64 rm1;
-          mxf::trunc_dealer<T>(mxd::pick<T>(kl[2][tid], kh[2][tid], j),
-                               mxd::pick<T>(kl[3][tid], kh[3][tid], j),
-                               mxd::pick<T>(kl[4][tid], kh[4][tid], j),
-                               mxd::pick<T>(kl[5][tid], kh[5][tid], j), m, &rt1, &rm1);
-          msg_rt[i] = rt1;
-          msg_rm[i] = rm1;
-          const Loc<T> l = locate<T>(js, i);
-          *job_out<T>(js, l, 0) = mxd::pick<T>(kl[7][tid], kh[7][tid], j);
-          *job_out<T>(js, l, 1) = mxd::pick<T>(kl[6][tid], kh[6][tid], j);
-        }
+        if (role == 2 && dealer)
+          deal_out<T>(js, i, mxf::trunc_deal<T>(ks(2), ks(3), ks(4), ks(5), ks(6), ks(7), m),
+                      msg_rt, msg_rm);
       }
     }
     __syncthreads();
@@ -419,7 +369,7 @@ __device__ __forceinline__ void
     const int slot = role == 0 ? s : 2;  // P1 draws z2 only, kept in slot 2
     if (s < ss.n && b0 + lb < nb) {
       uint64_t lo, hi;
-      mxd::prf_chunk(rks[ss.key[s]], ss.nonce[s], (uint64_t)(b0 + lb), &lo, &hi);
+      lat_chunk(rks[ss.key[s]], ss.nonce[s], (uint64_t)(b0 + lb), &lo, &hi);
       kl[slot][lb] = lo;
       kh[slot][lb] = hi;
     }
@@ -431,10 +381,10 @@ __device__ __forceinline__ void
         const int64_t i = b * P + j;
         if (i >= n) break;
         const T z = mxd::pick<T>(kl[2][tid], kh[2][tid], j);
-        const T y = role == 0 ? mxf::trunc_y<T>(cc[j], mxd::pick<T>(kl[0][tid], kh[0][tid], j),
-                                                mxd::pick<T>(kl[1][tid], kh[1][tid], j), m, true)
-                              : mxf::trunc_y<T>(cc[j], r1t[j], r1m[j], m, false);
-        wo[i] = y - z;
+        wo[i] = role == 0
+                    ? mxf::trunc_round1_w<T>(0, cc[j], mxd::pick<T>(kl[0][tid], kh[0][tid], j),
+                                             mxd::pick<T>(kl[1][tid], kh[1][tid], j), z, m)
+                    : mxf::trunc_round1_w<T>(1, cc[j], r1t[j], r1m[j], z, m);
         *job_out<T>(js, locate<T>(js, i), role == 0 ? 0 : 1) = z;
       }
     }
@@ -471,6 +421,20 @@ bool lat_on() {  // MOOSEX_JOBS_LAT=0: the walking kernels at every size (A/B co
     return !(e && e[0] == '0');
   }();
   return on;
+}
+
+// whether a launch over n elements takes the latency form (-2 for other widths comes from
+// the launch itself)
+bool lat_launch(int words, int64_t n) {
+  return (words == 1 ? (n + 1) / 2 : n) <= kLatMaxChunks && lat_on();
+}
+template <class T>
+dim3 lat_grid(int64_t n) {
+  return dim3((unsigned)((mxp::chunks_of<T>(n) + kLatEpb - 1) / kLatEpb));
+}
+template <class T>
+dim3 walk_grid(int64_t n) {
+  return dim3(mxd::grid_for_chunks(mxp::chunks_of<T>(n)));
 }
 
 // host: the flat (ptrs[8 q .. 8 q + 7], dims[8 q .. 8 q + 7]) job description
@@ -537,8 +501,7 @@ int mxh_jobs_r0p(int words, int njobs, const void* const* ptrs, const int64_t* d
   if (n == 0) return 0;
   const mxd::KeySrc k = mxd::keysrc_slots(slots, 2);
   hipStream_t st = (hipStream_t)stream;
-  const int64_t nchunks = words == 1 ? (n + 1) / 2 : n;
-  if (nchunks <= kLatMaxChunks && lat_on()) {
+  if (lat_launch(words, n)) {
     Streams ss{};
     // main: P0 a (own), r0 (own); P1 b (next), r1 (next); P2 a (own), b (next)
     const int mk[3][2] = {{0, 0}, {1, 1}, {0, 1}};
@@ -556,30 +519,18 @@ int mxh_jobs_r0p(int words, int njobs, const void* const* ptrs, const int64_t* d
       }
       ss.n = 8;
     }
-    const dim3 grid((unsigned)((nchunks + kLatEpb - 1) / kLatEpb));
-    if (words == 1)
-      hipLaunchKernelGGL(k_jobs_r0_lat<u64>, grid, dim3(256), 0, st, js, n, m, role, main, dealer,
-                         (u64*)msg, (u64*)msg_rt, (u64*)msg_rm, k, ss);
-    else if (words == 2)
-      hipLaunchKernelGGL(k_jobs_r0_lat<u128>, grid, dim3(256), 0, st, js, n, m, role, main,
-                         dealer, (u128*)msg, (u128*)msg_rt, (u64*)msg_rm, k, ss);
-    else
-      return -2;
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -100 - (int)e;
+    return mxp::for_width(words, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(k_jobs_r0_lat<T>, lat_grid<T>(n), dim3(256), 0, st, js, n, m, role, main,
+                         dealer, (T*)msg, (T*)msg_rt, (u64*)msg_rm, k, ss);
+    });
   }
-  if (words == 1)
-    hipLaunchKernelGGL(k_jobs_r0<u64>, dim3(mxd::grid_for_chunks((n + 1) / 2)), dim3(256), 0, st,
-                       js, n, m, role, main, dealer, (u64*)msg, (u64*)msg_rt, (u64*)msg_rm, k,
-                       nn[0], nn[1], nn[2], nn[3], nn[4], nn[5], nn[6]);
-  else if (words == 2)
-    hipLaunchKernelGGL(k_jobs_r0<u128>, dim3(mxd::grid_for_chunks(n)), dim3(256), 0, st, js, n, m,
-                       role, main, dealer, (u128*)msg, (u128*)msg_rt, (u64*)msg_rm, k, nn[0],
-                       nn[1], nn[2], nn[3], nn[4], nn[5], nn[6]);
-  else
-    return -2;
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -100 - (int)e;
+  return mxp::for_width(words, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_jobs_r0<T>, walk_grid<T>(n), dim3(256), 0, st, js, n, m, role, main,
+                       dealer, (T*)msg, (T*)msg_rt, (u64*)msg_rm, k, nn[0], nn[1], nn[2], nn[3],
+                       nn[4], nn[5], nn[6]);
+  });
 }
 
 int mxh_jobs_r0(int words, int njobs, const void* const* ptrs, const int64_t* dims, int64_t L,
@@ -601,8 +552,7 @@ int mxh_jobs_r1(int words, int njobs, const void* const* ptrs, const int64_t* di
   const mxd::KeySrc k = mxd::keysrc_slots(slots, 2);
   hipStream_t st = (hipStream_t)stream;
   if (role != 0 && role != 1) return 0;
-  const int64_t nchunks = words == 1 ? (n + 1) / 2 : n;
-  if (nchunks <= kLatMaxChunks && lat_on()) {
+  if (lat_launch(words, n)) {
     Streams ss{};
     if (role == 0) {  // t, m, z0 under own
       ss.n = 3;
@@ -615,33 +565,19 @@ int mxh_jobs_r1(int words, int njobs, const void* const* ptrs, const int64_t* di
       ss.key[0] = 1;
       ss.nonce[0] = nn[6];
     }
-    const dim3 grid((unsigned)((nchunks + kLatEpb - 1) / kLatEpb));
-    if (words == 1)
-      hipLaunchKernelGGL(k_jobs_r1_lat<u64>, grid, dim3(256), 0, st, js, n, m, role,
-                         (const u64*)msg, (const u64*)rmk, (const u64*)rz, (const u64*)rrt,
-                         (const u64*)rrm, (u64*)w, k, ss);
-    else if (words == 2)
-      hipLaunchKernelGGL(k_jobs_r1_lat<u128>, grid, dim3(256), 0, st, js, n, m, role,
-                         (const u128*)msg, (const u128*)rmk, (const u128*)rz, (const u128*)rrt,
-                         (const u64*)rrm, (u128*)w, k, ss);
-    else
-      return -2;
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -100 - (int)e;
+    return mxp::for_width(words, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(k_jobs_r1_lat<T>, lat_grid<T>(n), dim3(256), 0, st, js, n, m, role,
+                         (const T*)msg, (const T*)rmk, (const T*)rz, (const T*)rrt,
+                         (const u64*)rrm, (T*)w, k, ss);
+    });
   }
-  if (words == 1)
-    hipLaunchKernelGGL(k_jobs_r1<u64>, dim3(mxd::grid_for_chunks((n + 1) / 2)), dim3(256), 0, st,
-                       js, n, m, role, (const u64*)msg, (const u64*)rmk, (const u64*)rz,
-                       (const u64*)rrt, (const u64*)rrm, (u64*)w, k, nn[3], nn[4], nn[5], nn[6]);
-  else if (words == 2)
-    hipLaunchKernelGGL(k_jobs_r1<u128>, dim3(mxd::grid_for_chunks(n)), dim3(256), 0, st, js, n, m,
-                       role, (const u128*)msg, (const u128*)rmk, (const u128*)rz,
-                       (const u128*)rrt, (const u64*)rrm, (u128*)w, k, nn[3], nn[4], nn[5],
-                       nn[6]);
-  else
-    return -2;
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -100 - (int)e;
+  return mxp::for_width(words, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_jobs_r1<T>, walk_grid<T>(n), dim3(256), 0, st, js, n, m, role,
+                       (const T*)msg, (const T*)rmk, (const T*)rz, (const T*)rrt, (const u64*)rrm,
+                       (T*)w, k, nn[3], nn[4], nn[5], nn[6]);
+  });
 }
 
 int mxh_jobs_r2(int words, int njobs, const void* const* ptrs, const int64_t* dims, int64_t L,
@@ -652,17 +588,11 @@ int mxh_jobs_r2(int words, int njobs, const void* const* ptrs, const int64_t* di
   if (rc) return rc;
   if (n == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  const int grid = mxd::grid_for(n);
-  if (words == 1)
-    hipLaunchKernelGGL(k_jobs_r2<u64>, dim3(grid), dim3(256), 0, st, js, n, role,
-                       (const u64*)a, (const u64*)b);
-  else if (words == 2)
-    hipLaunchKernelGGL(k_jobs_r2<u128>, dim3(grid), dim3(256), 0, st, js, n, role,
-                       (const u128*)a, (const u128*)b);
-  else
-    return -2;
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -100 - (int)e;
+  return mxp::for_width(words, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_jobs_r2<T>, dim3(mxd::grid_for(n)), dim3(256), 0, st, js, n, role,
+                       (const T*)a, (const T*)b);
+  });
 }
 
 }  // extern "C"

@@ -1,34 +1,13 @@
 // Host versions of the per-party job tail (rss_jobs.hip) and the C ABI entry points that
 // dispatch host / device.  Same PRF streams and element order as the device kernels.
-#include <algorithm>
 #include <climits>
-#include <functional>
 #include <vector>
 
 #include "moosex.h"
+#include "party_abi.h"
+#include "party_rounds_cpu.h"
 #include "ring_common.h"
 #include "rss_fused.h"
-
-void mx_cpu_prf_range(const uint8_t* key, uint64_t nonce, int words, int64_t i0, int64_t n,
-                      void* out);
-void mx_cpu_parallel_for(int64_t n, int64_t grain,
-                         const std::function<void(int64_t, int64_t)>& f);
-
-extern "C" {
-int mxh_jobs_r0(int words, int njobs, const void* const* ptrs, const int64_t* dims, int64_t L,
-                int m, int role, int main, int dealer, void* msg, void* msg_rt, void* msg_rm,
-                const uint32_t* const* slots, const uint64_t* nn, void* stream);
-int mxh_jobs_r0p(int words, int njobs, const void* const* ptrs, const int64_t* dims, int64_t L,
-                 int m, int role, int main, int dealer, void* msg, void* msg_rt, void* msg_rm,
-                 const uint32_t* const* slots, const uint64_t* nn, int npend,
-                 const void* const* pend, const int64_t* pend_len, void* stream);
-int mxh_jobs_r1(int words, int njobs, const void* const* ptrs, const int64_t* dims, int64_t L,
-                int m, int role, const void* msg, const void* rmk, const void* rz,
-                const void* rrt, const void* rrm, void* w, const uint32_t* const* slots,
-                const uint64_t* nn, void* stream);
-int mxh_jobs_r2(int words, int njobs, const void* const* ptrs, const int64_t* dims, int64_t L,
-                int role, const void* a, const void* b, void* stream);
-}
 
 namespace {
 
@@ -118,54 +97,27 @@ T* out(const std::vector<Job>& js, int64_t L, const Loc& l, int which) {
   return (T*)js[l.q].p[6 + which] + l.r * L + l.e;
 }
 
-template <class F>
-void for_chunks(int64_t n, F&& f) {
-  mx_cpu_parallel_for(n, 1 << 12, [&](int64_t s, int64_t e) {
-    const int64_t CH = 512;
-    for (int64_t c = s; c < e; c += CH) f(c, std::min(CH, e - c));
-  });
-}
-
-template <class T>
-void prf(const uint32_t* slot, uint64_t nonce, int64_t i0, int64_t len, T* o) {
-  mx_cpu_prf_range((const uint8_t*)slot, nonce, (int)(sizeof(T) / 8), i0, len, o);
-}
-
 template <class T>
 int r0(const std::vector<Job>& js, int64_t L, int64_t n, int m, int role, int main, int dealer,
        T* msg, T* msg_rt, u64* msg_rm, const uint32_t* const* slots, const uint64_t* nn,
        const Pending& pd) {
   const uint32_t* own = slots[0];
   const uint32_t* nxt = slots[1];
-  for_chunks(n, [&](int64_t i0, int64_t len) {
-    if (main) {
-      std::vector<T> a(len, (T)0), b(len, (T)0), r(len);
-      if (role != 1) prf<T>(own, nn[0], i0, len, a.data());
-      if (role != 0) prf<T>(nxt, nn[0], i0, len, b.data());
-      if (role == 0) prf<T>(own, nn[1], i0, len, r.data());
-      if (role == 1) prf<T>(nxt, nn[2], i0, len, r.data());
-      for (int64_t q = 0; q < len; ++q) {
-        const int64_t i = i0 + q;
-        const T z = value<T>(js, locate(js, L, i), pd) + a[q] - b[q];
-        msg[i] = role == 0 ? mxf::trunc_mask0<T>(z, (T)0, r[q]) : role == 1 ? (T)(z + r[q]) : z;
-      }
-    }
-    if (role == 2 && dealer) {
-      std::vector<T> v0(len), v1(len), t(len), mm(len), z0(len), z2(len);
-      prf<T>(nxt, nn[1], i0, len, v0.data());
-      prf<T>(own, nn[2], i0, len, v1.data());
-      prf<T>(nxt, nn[3], i0, len, t.data());
-      prf<T>(nxt, nn[4], i0, len, mm.data());
-      prf<T>(nxt, nn[5], i0, len, z0.data());
-      prf<T>(own, nn[6], i0, len, z2.data());
-      for (int64_t q = 0; q < len; ++q) {
-        const int64_t i = i0 + q;
-        mxf::trunc_dealer<T>(v0[q], v1[q], t[q], mm[q], m, &msg_rt[i], &msg_rm[i]);
-        const Loc l = locate(js, L, i);
-        *out<T>(js, L, l, 0) = z2[q];
-        *out<T>(js, L, l, 1) = z0[q];
-      }
-    }
+  mxc::for_chunks(n, [&](int64_t i0, int64_t len) {
+    if (main)
+      mxc::main_r0<T>(
+          true, role, own, nxt, nn[0], nn + 1, i0, len,
+          [&](int64_t i) { return value<T>(js, locate(js, L, i), pd); },
+          [&](int64_t i) -> T& { return msg[i]; });
+    if (role == 2 && dealer)
+      mxc::dealer_r0<T>(own, nxt, nn + 1, m, i0, len,
+                        [&](int64_t i, const mxf::TruncDeal<T>& d) {
+                          msg_rt[i] = d.rt1;
+                          msg_rm[i] = d.rm1;
+                          const Loc l = locate(js, L, i);
+                          *out<T>(js, L, l, 0) = d.s0;
+                          *out<T>(js, L, l, 1) = d.s1;
+                        });
   });
   // the pending sums, materialised after every read above went through ld()
   for (int k = 0; k < pd.n; ++k)
@@ -179,24 +131,18 @@ int r1(const std::vector<Job>& js, int64_t L, int64_t n, int m, int role, const 
        const T* other, const T* z2m, const T* rt, const u64* rm, T* wo,
        const uint32_t* const* slots, const uint64_t* nn) {
   if (role != 0 && role != 1) return 0;
-  for_chunks(n, [&](int64_t i0, int64_t len) {
-    std::vector<T> t(len), mm(len), z(len);
-    if (role == 0) {
-      prf<T>(slots[0], nn[3], i0, len, t.data());
-      prf<T>(slots[0], nn[4], i0, len, mm.data());
-      prf<T>(slots[0], nn[5], i0, len, z.data());
-    } else {
-      prf<T>(slots[1], nn[6], i0, len, z.data());
-    }
-    for (int64_t q = 0; q < len; ++q) {
-      const int64_t i = i0 + q;
-      T cc = mine[i] + other[i];
-      if (z2m) cc += z2m[i];
-      const T y = role == 0 ? mxf::trunc_y<T>(cc, t[q], mm[q], m, true)
-                            : mxf::trunc_y<T>(cc, rt[i], (T)rm[i], m, false);
-      wo[i] = y - z[q];
-      *out<T>(js, L, locate(js, L, i), role == 0 ? 0 : 1) = z[q];
-    }
+  mxc::for_chunks(n, [&](int64_t i0, int64_t len) {
+    mxc::round1<T>(
+        role, slots[0], slots[1], nn + 3, m, i0, len,
+        [&](int64_t i) { return (T)(mine[i] + other[i] + (z2m ? z2m[i] : (T)0)); },
+        [&](int64_t i, T* t, T* mm) {
+          *t = rt[i];
+          *mm = (T)rm[i];
+        },
+        [&](int64_t i, T w, T z) {
+          wo[i] = w;
+          *out<T>(js, L, locate(js, L, i), role == 0 ? 0 : 1) = z;
+        });
   });
   return 0;
 }

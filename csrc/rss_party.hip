@@ -5,21 +5,18 @@
 // over RCCL.  Same PRF keys / nonces / counters as the generic protocol code, so the shares
 // are bitwise equal to it (and to the single-GPU fused kernels of rss_fused.hip).
 //
-// TruncPr (dealer P2, reference additive/trunc.rs:114-170), rounds:
-//   r0: P0 mk0 = x0 + x1 + 2^(k-2) + r0          -> P1
-//       P1 mk1 = x2 + r1                          -> P0
-//       P2 rt1, rm1 (dealer shares for P1)        -> P1;  P2's new shares (z2, z0)
-//   r1: P0 c = mk0 + mk1, y0, w0 = y0 - z0        -> P1;  P0's s0 = z0
-//       P1 c = mk1 + mk0, y1, w1 = y1 - z2        -> P0;  P1's s1 = z2
-//   r2: z1 = w0 + w1 (elementwise, host side)
-// Share by member j: one kernel computing every role's two slots (the owner's masked
-// x_j is then sent to P_{j+2}).
+// The TruncPr and dot-tail rounds, the streams each role draws and the round bodies are in
+// party_rounds.h (one element's arithmetic: rss_fused.h); the kernels here say where a
+// component's elements are read and written.  Share by member j: one kernel computing every
+// role's two slots (the owner's masked x_j is then sent to P_{j+2}).
 // Key slots: component c passes (own k_p, next k_{p+1}[, k_all]) of its session.
 #include <hip/hip_runtime.h>
 
-#include "prf_dev.h"
 #include "moosex.h"
+#include "party_abi.h"
 #include "party_batch.h"
+#include "party_rounds.h"
+#include "prf_dev.h"
 #include "ring_common.h"
 #include "rss_fused.h"
 
@@ -49,8 +46,8 @@ __device__ __forceinline__ void d_trunc_party_r0(int64_t n, int m, const Roles& 
                                                  uint64_t n_z0, uint64_t n_z2, int ncomp) {
   __shared__ uint32_t rks[mxd::kMaxKeySlots][mxd::kKeyWords];
   mxd::stage_keys(rks, keys, 2 * ncomp);
-  constexpr int P = mxd::Lane<T>::kPer;
-  const int64_t nb = (n + P - 1) / P;
+  const int64_t nb = mxp::chunks_of<T>(n);
+  const uint64_t nn[6] = {n_r0, n_r1, n_t, n_m, n_z0, n_z2}, nr[2] = {n_r0, n_r1};
   MX_PARTY_WALK(nb, ncomp) {
     const int c = (int)(g / nblk);
     const uint64_t B = (uint64_t)(g - c * nblk);
@@ -58,69 +55,21 @@ __device__ __forceinline__ void d_trunc_party_r0(int64_t n, int m, const Roles& 
     const uint32_t* own = rks[2 * c];
     const uint32_t* nxt = rks[2 * c + 1];
     const int64_t base = (int64_t)c * n;
-    if (role == 0) {  // k0 = own
-      uint32_t wa[16];
-      mx::chacha_block(own, n_r0, B, wa);
-#pragma unroll
-      for (int part = 0; part < 4; ++part) {
-        const int64_t b = (int64_t)mx::ks_chunk(B, part);
-        if (b >= nb) break;
-        uint64_t al, ah;
-        mx::part_u64(wa, part, &al, &ah);
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-          const int64_t i = b * P + j;
-          if (i >= n) break;
-          msg[base + i] = mxf::trunc_mask0<T>(s0[base + i], s1[base + i], mxd::pick<T>(al, ah, j));
-        }
-      }
-    } else if (role == 1) {  // k2 = next
-      uint32_t wa[16];
-      mx::chacha_block(nxt, n_r1, B, wa);
-#pragma unroll
-      for (int part = 0; part < 4; ++part) {
-        const int64_t b = (int64_t)mx::ks_chunk(B, part);
-        if (b >= nb) break;
-        uint64_t al, ah;
-        mx::part_u64(wa, part, &al, &ah);
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-          const int64_t i = b * P + j;
-          if (i >= n) break;
-          msg[base + i] = s1[base + i] + mxd::pick<T>(al, ah, j);
-        }
-      }
-    } else if (role == 2) {  // k2 = own, k0 = next
-      // streams r0, r1, t, m, z0, z2
-      uint32_t w[6][16];
-      mx::chacha_block(nxt, n_r0, B, w[0]);
-      mx::chacha_block(own, n_r1, B, w[1]);
-      mx::chacha_block(nxt, n_t, B, w[2]);
-      mx::chacha_block(nxt, n_m, B, w[3]);
-      mx::chacha_block(nxt, n_z0, B, w[4]);
-      mx::chacha_block(own, n_z2, B, w[5]);
-#pragma unroll
-      for (int part = 0; part < 4; ++part) {
-        const int64_t b = (int64_t)mx::ks_chunk(B, part);
-        if (b >= nb) break;
-        uint64_t lo[6], hi[6];
-#pragma unroll
-        for (int q = 0; q < 6; ++q) mx::part_u64(w[q], part, &lo[q], &hi[q]);
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-          const int64_t i = b * P + j;
-          if (i >= n) break;
-          T rt1;
-          u64 rm1;
-          mxf::trunc_dealer<T>(mxd::pick<T>(lo[0], hi[0], j), mxd::pick<T>(lo[1], hi[1], j),
-                               mxd::pick<T>(lo[2], hi[2], j), mxd::pick<T>(lo[3], hi[3], j), m,
-                               &rt1, &rm1);
-          msg[base + i] = rt1;
-          msg_rm[base + i] = rm1;
-          out0[base + i] = mxd::pick<T>(lo[5], hi[5], j);
-          out1[base + i] = mxd::pick<T>(lo[4], hi[4], j);
-        }
-      }
+    if (role == 0 || role == 1) {  // P0's part of the value is x0 + x1, P1's x2
+      mxp::main_r0<T, false>(
+          role, own, nxt, 0, nr, B, nb, n,
+          [&](int64_t i) MX_LAMBDA_INLINE {
+            return role == 0 ? (T)(s0[base + i] + s1[base + i]) : s1[base + i];
+          },
+          [&](int64_t i) MX_LAMBDA_INLINE -> T& { return msg[base + i]; });
+    } else if (role == 2) {
+      mxp::dealer_r0<T>(own, nxt, nn, m, B, nb, n,
+                        [&](int64_t i, const mxf::TruncDeal<T>& d) MX_LAMBDA_INLINE {
+                          msg[base + i] = d.rt1;
+                          msg_rm[base + i] = d.rm1;
+                          out0[base + i] = d.s0;
+                          out1[base + i] = d.s1;
+                        });
     }
   }
 }
@@ -139,6 +88,53 @@ __global__ void __launch_bounds__(256) k_trunc_party_r0(int64_t n, int m, Roles 
                       n_z0, n_z2, ncomp);
 }
 
+// Round 1 of every stacked component in role 0 / 1.  at(c): the component's R1Args; a null
+// z2m is TruncPr's own two-term opening c = mine + other, else the dot tail's three-term one.
+template <class T>
+struct R1Args {
+  const T* mine;
+  const T* other;
+  const T* z2m;
+  const T* rt;
+  const u64* rm;
+  T* w;
+  T* o0;
+  T* o1;
+};
+
+template <class T, class At>
+__device__ __forceinline__ void party_round1(int64_t n, int m, const Roles& roles,
+                                             const mxd::KeySrc& keys, uint64_t n_t, uint64_t n_m,
+                                             uint64_t n_z0, uint64_t n_z2, int ncomp, At&& at) {
+  __shared__ uint32_t rks[mxd::kMaxKeySlots][mxd::kKeyWords];
+  mxd::stage_keys(rks, keys, 2 * ncomp);
+  const int64_t nb = mxp::chunks_of<T>(n);
+  const uint64_t nn[4] = {n_t, n_m, n_z0, n_z2};
+  MX_PARTY_WALK(nb, ncomp) {
+    const int c = (int)(g / nblk);
+    const uint64_t B = (uint64_t)(g - c * nblk);
+    const int role = roles.r[c];
+    if (role != 0 && role != 1) continue;
+    const R1Args<T> a = at(c);
+    T* o = role == 0 ? a.o0 : a.o1;
+    mxp::round1<T>(
+        role, rks[2 * c], rks[2 * c + 1], nn, m, B, nb, n,
+        [&](int64_t i) MX_LAMBDA_INLINE {
+          T cc = a.mine[i] + a.other[i];
+          if (a.z2m != nullptr) cc += a.z2m[i];
+          return cc;
+        },
+        [&](int64_t i, T* rt, T* rm) MX_LAMBDA_INLINE {
+          *rt = a.rt[i];
+          *rm = (T)a.rm[i];
+        },
+        [&](int64_t i, T w, T z) MX_LAMBDA_INLINE {
+          a.w[i] = w;
+          o[i] = z;
+        });
+  }
+}
+
 template <class T>
 __device__ __forceinline__ void d_trunc_party_r1(int64_t n, int m, const Roles& roles,
                                                  const T* __restrict__ msg,
@@ -149,63 +145,11 @@ __device__ __forceinline__ void d_trunc_party_r1(int64_t n, int m, const Roles& 
                                                  const mxd::KeySrc& keys, uint64_t n_t,
                                                  uint64_t n_m, uint64_t n_z0, uint64_t n_z2,
                                                  int ncomp) {
-  __shared__ uint32_t rks[mxd::kMaxKeySlots][mxd::kKeyWords];
-  mxd::stage_keys(rks, keys, 2 * ncomp);
-  constexpr int P = mxd::Lane<T>::kPer;
-  const int64_t nb = (n + P - 1) / P;
-  MX_PARTY_WALK(nb, ncomp) {
-    const int c = (int)(g / nblk);
-    const uint64_t B = (uint64_t)(g - c * nblk);
-    const int role = roles.r[c];
+  party_round1<T>(n, m, roles, keys, n_t, n_m, n_z0, n_z2, ncomp, [&](int c) {
     const int64_t base = (int64_t)c * n;
-    if (role == 0) {
-      const uint32_t* k0 = rks[2 * c];
-      uint32_t wt[16], wm[16], wz[16];
-      mx::chacha_block(k0, n_t, B, wt);
-      mx::chacha_block(k0, n_m, B, wm);
-      mx::chacha_block(k0, n_z0, B, wz);
-#pragma unroll
-      for (int part = 0; part < 4; ++part) {
-        const int64_t b = (int64_t)mx::ks_chunk(B, part);
-        if (b >= nb) break;
-        uint64_t tl, th, ml, mh, zl, zh;
-        mx::part_u64(wt, part, &tl, &th);
-        mx::part_u64(wm, part, &ml, &mh);
-        mx::part_u64(wz, part, &zl, &zh);
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-          const int64_t i = b * P + j;
-          if (i >= n) break;
-          const T cc = msg[base + i] + rmk[base + i];
-          const T z0 = mxd::pick<T>(zl, zh, j);
-          const T y0 = mxf::trunc_y<T>(cc, mxd::pick<T>(tl, th, j), mxd::pick<T>(ml, mh, j), m, true);
-          w[base + i] = y0 - z0;
-          out0[base + i] = z0;
-        }
-      }
-    } else if (role == 1) {
-      const uint32_t* k2 = rks[2 * c + 1];
-      uint32_t wz[16];
-      mx::chacha_block(k2, n_z2, B, wz);
-#pragma unroll
-      for (int part = 0; part < 4; ++part) {
-        const int64_t b = (int64_t)mx::ks_chunk(B, part);
-        if (b >= nb) break;
-        uint64_t zl, zh;
-        mx::part_u64(wz, part, &zl, &zh);
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-          const int64_t i = b * P + j;
-          if (i >= n) break;
-          const T cc = msg[base + i] + rmk[base + i];
-          const T z2 = mxd::pick<T>(zl, zh, j);
-          const T y1 = mxf::trunc_y<T>(cc, rrt[base + i], (T)rrm[base + i], m, false);
-          w[base + i] = y1 - z2;
-          out1[base + i] = z2;
-        }
-      }
-    }
-  }
+    return R1Args<T>{msg + base, rmk + base, nullptr,     rrt + base,
+                     rrm + base, w + base,   out0 + base, out1 + base};
+  });
 }
 
 template <class T>
@@ -222,8 +166,8 @@ __global__ void __launch_bounds__(256) k_trunc_party_r1(int64_t n, int m, Roles 
                       ncomp);
 }
 
-// Ring extension Z_2^64 -> Z_2^128 (dealer P2; rss_fused.h: ring_extend_dealer / _mask0 / _y),
-// rounds as TruncPr's:
+// Ring extension Z_2^64 -> Z_2^128 (dealer P2; rss_fused.h: ring_extend_deal / _mask0 /
+// _round1_w), rounds and streams as TruncPr's:
 //   r0: P0 msg = x0 + x1 + 2^62 + r0 (u64)        -> P1
 //       P1 msg = x2 + r1 (u64)                     -> P0
 //       P2 R1 (u128), M1 (u64)                     -> P1;  P2's new shares (z2, z0)
@@ -240,6 +184,7 @@ __device__ __forceinline__ void d_ring_extend_party_r0(
     uint64_t n_r1, uint64_t n_R, uint64_t n_M, uint64_t n_z0, uint64_t n_z2, int ncomp) {
   __shared__ uint32_t rks[mxd::kMaxKeySlots][mxd::kKeyWords];
   mxd::stage_keys(rks, keys, 2 * ncomp);
+  const uint64_t nn[6] = {n_r0, n_r1, n_R, n_M, n_z0, n_z2};
   MX_PARTY_WALK(n, ncomp) {
     const int c = (int)(g / nblk);
     const uint64_t B = (uint64_t)(g - c * nblk);
@@ -247,52 +192,27 @@ __device__ __forceinline__ void d_ring_extend_party_r0(
     const uint32_t* own = rks[2 * c];
     const uint32_t* nxt = rks[2 * c + 1];
     const int64_t base = (int64_t)c * n;
-    if (role == 0) {  // k0 = own
+    if (role == 0 || role == 1) {  // r0 under k0 = P0's own, r1 under k2 = P1's next
       uint32_t wa[16];
-      mx::chacha_block(own, n_r0, B, wa);
-#pragma unroll
-      for (int part = 0; part < 4; ++part) {
-        const int64_t i = (int64_t)mx::ks_chunk(B, part);
-        if (i >= n) break;
-        uint64_t al, ah;
-        mx::part_u64(wa, part, &al, &ah);
-        msg[base + i] = mxf::ring_extend_mask0(s0[base + i], s1[base + i], al);
-      }
-    } else if (role == 1) {  // k2 = next
-      uint32_t wa[16];
-      mx::chacha_block(nxt, n_r1, B, wa);
-#pragma unroll
-      for (int part = 0; part < 4; ++part) {
-        const int64_t i = (int64_t)mx::ks_chunk(B, part);
-        if (i >= n) break;
-        uint64_t al, ah;
-        mx::part_u64(wa, part, &al, &ah);
-        msg[base + i] = s1[base + i] + al;
-      }
-    } else if (role == 2) {  // k2 = own, k0 = next
-      // streams r0, r1, R0, M0, z0, z2
-      uint32_t w[6][16];
-      mx::chacha_block(nxt, n_r0, B, w[0]);
-      mx::chacha_block(own, n_r1, B, w[1]);
-      mx::chacha_block(nxt, n_R, B, w[2]);
-      mx::chacha_block(nxt, n_M, B, w[3]);
-      mx::chacha_block(nxt, n_z0, B, w[4]);
-      mx::chacha_block(own, n_z2, B, w[5]);
-#pragma unroll
-      for (int part = 0; part < 4; ++part) {
-        const int64_t i = (int64_t)mx::ks_chunk(B, part);
-        if (i >= n) break;
-        uint64_t lo[6], hi[6];
-#pragma unroll
-        for (int q = 0; q < 6; ++q) mx::part_u64(w[q], part, &lo[q], &hi[q]);
-        u128 R1;
-        u64 M1;
-        mxf::ring_extend_dealer(lo[0], lo[1], mxd::pick<u128>(lo[2], hi[2], 0), lo[3], &R1, &M1);
-        msg_R[base + i] = R1;
-        msg_M[base + i] = M1;
-        out0[base + i] = mxd::pick<u128>(lo[5], hi[5], 0);
-        out1[base + i] = mxd::pick<u128>(lo[4], hi[4], 0);
-      }
+      mx::chacha_block(role == 0 ? own : nxt, role == 0 ? n_r0 : n_r1, B, wa);
+      mxp::walk_block<1>(B, n, n, [&](auto part, auto, int64_t i) MX_LAMBDA_INLINE {
+        const u64 r = (u64)mxp::draw<u128>(wa, part, 0);
+        msg[base + i] = role == 0 ? mxf::ring_extend_mask0(s0[base + i], s1[base + i], r)
+                                  : s1[base + i] + r;
+      });
+    } else if (role == 2) {
+      mxp::DealerBlocks w;
+      mxp::draw_dealer(own, nxt, nn, B, w);
+      mxp::walk_block<1>(B, n, n, [&](auto part, auto, int64_t i) MX_LAMBDA_INLINE {
+        const mxf::RingExtendDeal d = mxf::ring_extend_deal(
+            mxp::draw<u128>(w.r0, part, 0), mxp::draw<u128>(w.r1, part, 0),
+            mxp::draw<u128>(w.t, part, 0), mxp::draw<u128>(w.m, part, 0),
+            mxp::draw<u128>(w.z0, part, 0), mxp::draw<u128>(w.z2, part, 0));
+        msg_R[base + i] = d.R1;
+        msg_M[base + i] = d.M1;
+        out0[base + i] = d.s0;
+        out1[base + i] = d.s1;
+      });
     }
   }
 }
@@ -318,40 +238,33 @@ __device__ __forceinline__ void d_ring_extend_party_r1(
     const uint64_t B = (uint64_t)(g - c * nblk);
     const int role = roles.r[c];
     const int64_t base = (int64_t)c * n;
-    if (role == 0) {
+    if (role == 0) {  // R0, M0, z0 under its own k0
       const uint32_t* k0 = rks[2 * c];
       uint32_t wR[16], wM[16], wz[16];
       mx::chacha_block(k0, n_R, B, wR);
       mx::chacha_block(k0, n_M, B, wM);
       mx::chacha_block(k0, n_z0, B, wz);
-#pragma unroll
-      for (int part = 0; part < 4; ++part) {
-        const int64_t i = (int64_t)mx::ks_chunk(B, part);
-        if (i >= n) break;
+      mxp::walk_block<1>(B, n, n, [&](auto part, auto, int64_t i) MX_LAMBDA_INLINE {
+        const int64_t k = base + i;
+        const u64 cc = msg[k] + rmk[k];
         uint64_t Rl, Rh, ml, mh, zl, zh;
         mx::part_u64(wR, part, &Rl, &Rh);
         mx::part_u64(wM, part, &ml, &mh);
         mx::part_u64(wz, part, &zl, &zh);
-        const u64 cc = msg[base + i] + rmk[base + i];
         const u128 z0 = mxd::pick<u128>(zl, zh, 0);
-        w[base + i] = mxf::ring_extend_y(cc, mxd::pick<u128>(Rl, Rh, 0), ml, true) - z0;
-        out0[base + i] = z0;
-      }
-    } else if (role == 1) {
-      const uint32_t* k2 = rks[2 * c + 1];
+        w[k] = mxf::ring_extend_round1_w(0, cc, mxd::pick<u128>(Rl, Rh, 0), ml, z0);
+        out0[k] = z0;
+      });
+    } else if (role == 1) {  // z2 under its next k2
       uint32_t wz[16];
-      mx::chacha_block(k2, n_z2, B, wz);
-#pragma unroll
-      for (int part = 0; part < 4; ++part) {
-        const int64_t i = (int64_t)mx::ks_chunk(B, part);
-        if (i >= n) break;
-        uint64_t zl, zh;
-        mx::part_u64(wz, part, &zl, &zh);
-        const u64 cc = msg[base + i] + rmk[base + i];
-        const u128 z2 = mxd::pick<u128>(zl, zh, 0);
-        w[base + i] = mxf::ring_extend_y(cc, rR[base + i], rM[base + i], false) - z2;
-        out1[base + i] = z2;
-      }
+      mx::chacha_block(rks[2 * c + 1], n_z2, B, wz);
+      mxp::walk_block<1>(B, n, n, [&](auto part, auto, int64_t i) MX_LAMBDA_INLINE {
+        const int64_t k = base + i;
+        const u64 cc = msg[k] + rmk[k];
+        const u128 z2 = mxp::draw<u128>(wz, part, 0);
+        w[k] = mxf::ring_extend_round1_w(1, cc, rR[k], rM[k], z2);
+        out1[k] = z2;
+      });
     }
   }
 }
@@ -382,8 +295,7 @@ __device__ __forceinline__ void d_share_party(int kind, int64_t n, const Roles& 
   // slot j+1 = PRF(k_{j+1}) (rel 0: next, rel 1: own), slot j = x - slot j+1 (sent to
   // P_{j+2}), slot j+2 = 0, so rel 2 draws nothing
   mxd::stage_keys(rks, keys, 2 * ncomp);
-  constexpr int P = mxd::Lane<T>::kPer;
-  const int64_t nb = (n + P - 1) / P;
+  const int64_t nb = mxp::chunks_of<T>(n);
   MX_PARTY_WALK(nb, ncomp) {
     const int c = (int)(g / nblk);
     const uint64_t B = (uint64_t)(g - c * nblk);
@@ -398,32 +310,23 @@ __device__ __forceinline__ void d_share_party(int kind, int64_t n, const Roles& 
     const bool draws = mir ? r != 2 : r != 1;
     uint32_t wa[16];
     if (draws) mx::chacha_block(rks[2 * c], n1, B, wa);
-#pragma unroll
-    for (int part = 0; part < 4; ++part) {
-      const int64_t b = (int64_t)mx::ks_chunk(B, part);
-      if (b >= nb) break;
-      uint64_t al = 0, ah = 0;
-      if (draws) mx::part_u64(wa, part, &al, &ah);
-#pragma unroll
-      for (int j = 0; j < P; ++j) {
-        const int64_t i = b * P + j;
-        if (i >= n) break;
-        const T rr = mxd::pick<T>(al, ah, j);
-        if (r == 0) {  // owner: (PRF(k_j), x - PRF(k_j)); mirrored (x - PRF(k_{j+1}), PRF)
-          const T xi = kind == MX_SHARE_F64 ? mxr::f64_to_ring<T>(xf[i] * scale) : x[i];
-          const T v = kind == MX_CROSS_BOOL ? (T)(xi ^ rr) : (T)(xi - rr);
-          out0[base + i] = mir ? v : rr;
-          out1[base + i] = mir ? rr : v;
-          if (fwd >= 0) (mir ? out1 : out0)[(int64_t)fwd * n + i] = v;
-        } else if (r == 1) {  // P_{j+1}: (received, 0); mirrored (PRF(k_{j+1}), 0)
-          if (mir) out0[base + i] = rr;
-          out1[base + i] = 0;
-        } else {  // P_{j+2}: (0, PRF(k_j)); mirrored (0, received)
-          out0[base + i] = 0;
-          if (!mir) out1[base + i] = rr;
-        }
+    constexpr int P = mxd::Lane<T>::kPer;
+    mxp::walk_block<P>(B, nb, n, [&](auto part, auto j, int64_t i) MX_LAMBDA_INLINE {
+      const T rr = draws ? mxp::draw<T>(wa, part, j) : (T)0;
+      if (r == 0) {  // owner: (PRF(k_j), x - PRF(k_j)); mirrored (x - PRF(k_{j+1}), PRF)
+        const T xi = kind == MX_SHARE_F64 ? mxr::f64_to_ring<T>(xf[i] * scale) : x[i];
+        const T v = kind == MX_CROSS_BOOL ? (T)(xi ^ rr) : (T)(xi - rr);
+        out0[base + i] = mir ? v : rr;
+        out1[base + i] = mir ? rr : v;
+        if (fwd >= 0) (mir ? out1 : out0)[(int64_t)fwd * n + i] = v;
+      } else if (r == 1) {  // P_{j+1}: (received, 0); mirrored (PRF(k_{j+1}), 0)
+        if (mir) out0[base + i] = rr;
+        out1[base + i] = 0;
+      } else {  // P_{j+2}: (0, PRF(k_j)); mirrored (0, received)
+        out0[base + i] = 0;
+        if (!mir) out1[base + i] = rr;
       }
-    }
+    });
   }
 }
 
@@ -436,28 +339,13 @@ __global__ void __launch_bounds__(256) k_share_party(int kind, int64_t n, Roles 
   d_share_party<T>(kind, n, rel, xv, out0, out1, keys, n1, na, ncomp);
 }
 
-inline Roles roles_of(const int* r, int ncomp) {
-  Roles o;
-  for (int c = 0; c < 3; ++c) o.r[c] = c < ncomp ? r[c] : -1;
-  return o;
-}
-
-
 // ---------------------------------------------------------------------------------------
-// Fixed-point dot tail (rep.dot_trunc) for parties on different GPUs.  Input: each party's
-// local cross products (the RSS dot's GEMM output).  The reshare of rep.dot is folded into
-// TruncPr's first round: P_p's product masked by the zero share is z_p (3-out-of-3
-// additive), and the opening c = x + r + 2^(k-2) of TruncPr is assembled from
-//   P0: m0 = z0 + 2^(k-2) + r0   -> P1
-//   P1: m1 = z1 + r1              -> P0
-//   P2: z2                        -> P0 and P1        (+ the dealer's rt1, rm1 -> P1)
-// so both P0 and P1 get c = m0 + m1 + z2 in ONE round (the generic path needs the
-// reshare round plus the P0 <-> P1 round).  c is the same value, and every output share
-// depends on the input only through c, so the shares are bitwise equal to reshare +
-// TruncPr (and to the stacked fused kernel).  Round 1 is k_trunc_party_r1's with the
-// three-term c; round 2 adds the exchanged w's.  Every array argument is a per-component
-// pointer triple (component slots need not be adjacent: rows of a larger stack, buffers
-// received from other GPUs, or -- one party per process at N = 1 -- the sender's buffer).
+// Fixed-point dot tail (rep.dot_trunc; party_rounds.h) for parties on different GPUs.
+// Input: each party's local cross products (the RSS dot's GEMM output).  Round 1 is
+// TruncPr's with the three-term c; round 2 adds the exchanged w's.  Every array argument is
+// a per-component pointer triple (component slots need not be adjacent: rows of a larger
+// stack, buffers received from other GPUs, or -- one party per process at N = 1 -- the
+// sender's buffer).
 // ---------------------------------------------------------------------------------------
 struct CP3 {
   const void* p[3];
@@ -484,8 +372,8 @@ __device__ __forceinline__ void d_dot_tail_r0(int64_t n, int m, const Roles& rol
                                               uint64_t n_z0, uint64_t n_z2, int ncomp) {
   __shared__ uint32_t rks[mxd::kMaxKeySlots][mxd::kKeyWords];
   mxd::stage_keys(rks, keys, 2 * ncomp);
-  constexpr int P = mxd::Lane<T>::kPer;
-  const int64_t nb = (n + P - 1) / P;
+  const int64_t nb = mxp::chunks_of<T>(n);
+  const uint64_t nn[6] = {n_r0, n_r1, n_t, n_m, n_z0, n_z2}, nr[2] = {n_r0, n_r1};
   MX_PARTY_WALK(nb, ncomp) {
     const int c = (int)(g / nblk);
     const uint64_t B = (uint64_t)(g - c * nblk);
@@ -497,72 +385,22 @@ __device__ __forceinline__ void d_dot_tail_r0(int64_t n, int m, const Roles& rol
     T* mo = wp<T>(msg, c);
     // no cross (null): the dealer part only, launched before the product exists, so P2's
     // rt1 / rm1 travel while the GEMM runs; no msg_rt (null): no dealer part
-    if (x != nullptr) {
-      // zero share alpha: P0 f(k0), P1 -f(k2), P2 f(k2) - f(k0) (f = PRF at nonce n_a; sums
-      // to zero).  z2 (sent to P0 and P1) is masked by f(k2) against P0 and f(k0) against
-      // P1, m0 / m1 by the opening masks r0 / r1: every view is as with the textbook
-      // alpha_p = f(k_p) - f(k_{p+1}), with one PRF stream less at P0 and at P1
-      uint32_t wa[16], wb[16], wr[16];
-      if (role != 1) mx::chacha_block(own, n_a, B, wa);
-      if (role != 0) mx::chacha_block(nxt, n_a, B, wb);
-      if (role == 0) mx::chacha_block(own, n_r0, B, wr);
-      if (role == 1) mx::chacha_block(nxt, n_r1, B, wr);
-#pragma unroll
-      for (int part = 0; part < 4; ++part) {
-        const int64_t b = (int64_t)mx::ks_chunk(B, part);
-        if (b >= nb) break;
-        uint64_t al = 0, ah = 0, bl = 0, bh = 0, rl = 0, rh = 0;
-        if (role != 1) mx::part_u64(wa, part, &al, &ah);
-        if (role != 0) mx::part_u64(wb, part, &bl, &bh);
-        if (role != 2) mx::part_u64(wr, part, &rl, &rh);
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-          const int64_t i = b * P + j;
-          if (i >= n) break;
-          const T z = x[i] + mxd::pick<T>(al, ah, j) - mxd::pick<T>(bl, bh, j);
-          if (role == 0)
-            mo[i] = mxf::trunc_mask0<T>(z, (T)0, mxd::pick<T>(rl, rh, j));
-          else if (role == 1)
-            mo[i] = z + mxd::pick<T>(rl, rh, j);
-          else
-            mo[i] = z;
-        }
-      }
-    }
-    if (role == 2 && msg_rt.p[c] != nullptr) {  // dealer (as k_trunc_party_r0): r0, r1, t, m, z0, z2
-      uint32_t w[6][16];
-      mx::chacha_block(nxt, n_r0, B, w[0]);
-      mx::chacha_block(own, n_r1, B, w[1]);
-      mx::chacha_block(nxt, n_t, B, w[2]);
-      mx::chacha_block(nxt, n_m, B, w[3]);
-      mx::chacha_block(nxt, n_z0, B, w[4]);
-      mx::chacha_block(own, n_z2, B, w[5]);
+    if (x != nullptr)
+      mxp::main_r0<T, true>(
+          role, own, nxt, n_a, nr, B, nb, n, [&](int64_t i) MX_LAMBDA_INLINE { return x[i]; },
+          [&](int64_t i) MX_LAMBDA_INLINE -> T& { return mo[i]; });
+    if (role == 2 && msg_rt.p[c] != nullptr) {
       T* rt = wp<T>(msg_rt, c);
       u64* rm = wp<u64>(msg_rm, c);
       T* o0 = wp<T>(out0, c);
       T* o1 = wp<T>(out1, c);
-#pragma unroll
-      for (int part = 0; part < 4; ++part) {
-        const int64_t b = (int64_t)mx::ks_chunk(B, part);
-        if (b >= nb) break;
-        uint64_t lo[6], hi[6];
-#pragma unroll
-        for (int q = 0; q < 6; ++q) mx::part_u64(w[q], part, &lo[q], &hi[q]);
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-          const int64_t i = b * P + j;
-          if (i >= n) break;
-          T rt1;
-          u64 rm1;
-          mxf::trunc_dealer<T>(mxd::pick<T>(lo[0], hi[0], j), mxd::pick<T>(lo[1], hi[1], j),
-                               mxd::pick<T>(lo[2], hi[2], j), mxd::pick<T>(lo[3], hi[3], j), m,
-                               &rt1, &rm1);
-          rt[i] = rt1;
-          rm[i] = rm1;
-          o0[i] = mxd::pick<T>(lo[5], hi[5], j);
-          o1[i] = mxd::pick<T>(lo[4], hi[4], j);
-        }
-      }
+      mxp::dealer_r0<T>(own, nxt, nn, m, B, nb, n,
+                        [&](int64_t i, const mxf::TruncDeal<T>& d) MX_LAMBDA_INLINE {
+                          rt[i] = d.rt1;
+                          rm[i] = d.rm1;
+                          o0[i] = d.s0;
+                          o1[i] = d.s1;
+                        });
     }
   }
 }
@@ -578,8 +416,7 @@ __global__ void __launch_bounds__(256) k_dot_tail_r0(int64_t n, int m, Roles rol
                    n_m, n_z0, n_z2, ncomp);
 }
 
-// P0 / P1: c = own message + the other's + z2 (rz may be null: the two-term opening of
-// k_trunc_party_r0's protocol), then y, w = y - z and the PRF share of the new sharing.
+// P0 / P1: c = own message + the other's + z2 (a null rz component: the two-term opening)
 template <class T>
 __device__ __forceinline__ void d_dot_tail_r1(int64_t n, int m, const Roles& roles, const CP3& msg,
                                               const CP3& rmk, const CP3& rz, const CP3& rrt,
@@ -587,57 +424,10 @@ __device__ __forceinline__ void d_dot_tail_r1(int64_t n, int m, const Roles& rol
                                               const WP3& out1, const mxd::KeySrc& keys,
                                               uint64_t n_t, uint64_t n_m, uint64_t n_z0,
                                               uint64_t n_z2, int ncomp) {
-  __shared__ uint32_t rks[mxd::kMaxKeySlots][mxd::kKeyWords];
-  mxd::stage_keys(rks, keys, 2 * ncomp);
-  constexpr int P = mxd::Lane<T>::kPer;
-  const int64_t nb = (n + P - 1) / P;
-  MX_PARTY_WALK(nb, ncomp) {
-    const int c = (int)(g / nblk);
-    const uint64_t B = (uint64_t)(g - c * nblk);
-    const int role = roles.r[c];
-    if (role != 0 && role != 1) continue;
-    const T* mine = cp<T>(msg, c);
-    const T* other = cp<T>(rmk, c);
-    const T* z2m = cp<T>(rz, c);
-    T* wo = wp<T>(w, c);
-    uint32_t wt[16], wm[16], wz[16];
-    if (role == 0) {
-      const uint32_t* k0 = rks[2 * c];
-      mx::chacha_block(k0, n_t, B, wt);
-      mx::chacha_block(k0, n_m, B, wm);
-      mx::chacha_block(k0, n_z0, B, wz);
-    } else {
-      mx::chacha_block(rks[2 * c + 1], n_z2, B, wz);
-    }
-    const T* rt = cp<T>(rrt, c);
-    const u64* rm = cp<u64>(rrm, c);
-    T* o = role == 0 ? wp<T>(out0, c) : wp<T>(out1, c);
-#pragma unroll
-    for (int part = 0; part < 4; ++part) {
-      const int64_t b = (int64_t)mx::ks_chunk(B, part);
-      if (b >= nb) break;
-      uint64_t tl = 0, th = 0, ml = 0, mh = 0, zl, zh;
-      if (role == 0) {
-        mx::part_u64(wt, part, &tl, &th);
-        mx::part_u64(wm, part, &ml, &mh);
-      }
-      mx::part_u64(wz, part, &zl, &zh);
-#pragma unroll
-      for (int j = 0; j < P; ++j) {
-        const int64_t i = b * P + j;
-        if (i >= n) break;
-        T cc = mine[i] + other[i];
-        if (z2m != nullptr) cc += z2m[i];
-        const T z = mxd::pick<T>(zl, zh, j);
-        const T y = role == 0
-                        ? mxf::trunc_y<T>(cc, mxd::pick<T>(tl, th, j), mxd::pick<T>(ml, mh, j), m,
-                                          true)
-                        : mxf::trunc_y<T>(cc, rt[i], (T)rm[i], m, false);
-        wo[i] = y - z;
-        o[i] = z;
-      }
-    }
-  }
+  party_round1<T>(n, m, roles, keys, n_t, n_m, n_z0, n_z2, ncomp, [&](int c) {
+    return R1Args<T>{cp<T>(msg, c),   cp<T>(rmk, c), cp<T>(rz, c),   cp<T>(rrt, c),
+                     cp<u64>(rrm, c), wp<T>(w, c),   wp<T>(out0, c), wp<T>(out1, c)};
+  });
 }
 
 template <class T>
@@ -700,6 +490,23 @@ inline WP3 wp3(void* const* a, int ncomp) {
   return o;
 }
 
+// The head of every entry point: the launch's roles and key source (slots may be null: a
+// kernel without PRF).  False: the entry point returns *rc (nothing to do, bad ncomp).
+inline bool party_args(int64_t n, int ncomp, const int* roles, const uint32_t* const* slots,
+                       Roles* rr, mxd::KeySrc* keys, int* rc) {
+  *rc = n == 0 ? 0 : -3;
+  if (n == 0 || ncomp < 1 || ncomp > 3) return false;
+  if (slots != nullptr) *keys = mxd::keysrc_slots(slots, 2 * ncomp);
+  for (int c = 0; c < 3; ++c) rr->r[c] = c < ncomp ? roles[c] : -1;
+  return true;
+}
+
+// grid of a walk over the chunks of n elements of T for ncomp stacked components
+template <class T>
+inline dim3 party_grid(int64_t n, int ncomp) {
+  return dim3(mxd::grid_for_chunks(mxp::chunks_of<T>(n)) * ncomp);
+}
+
 }  // namespace
 
 extern "C" {
@@ -708,142 +515,103 @@ int mxh_trunc_party_r0(int words, int64_t n, int m, int ncomp, const int* roles,
                        const void* s0, const void* s1, void* msg, void* msg_rm, void* out0,
                        void* out1, const uint32_t* const* slots, const uint64_t* nn,
                        void* stream) {
-  if (n == 0) return 0;
-  if (ncomp < 1 || ncomp > 3) return -3;
-  const mxd::KeySrc k = mxd::keysrc_slots(slots, 2 * ncomp);
-  const Roles rr = roles_of(roles, ncomp);
-  hipStream_t st = (hipStream_t)stream;
-  if (words == 1) {
-    hipLaunchKernelGGL(k_trunc_party_r0<u64>, dim3(mxd::grid_for_chunks((n + 1) / 2) * ncomp),
-                       dim3(256), 0, st, n, m, rr, (const u64*)s0, (const u64*)s1, (u64*)msg,
-                       (u64*)msg_rm, (u64*)out0, (u64*)out1, k, nn[0], nn[1], nn[2], nn[3],
-                       nn[4], nn[5], ncomp);
-  } else if (words == 2) {
-    hipLaunchKernelGGL(k_trunc_party_r0<u128>, dim3(mxd::grid_for_chunks(n) * ncomp), dim3(256), 0, st,
-                       n, m, rr, (const u128*)s0, (const u128*)s1, (u128*)msg, (u64*)msg_rm,
-                       (u128*)out0, (u128*)out1, k, nn[0], nn[1], nn[2], nn[3], nn[4], nn[5],
-                       ncomp);
-  } else {
-    return -2;
-  }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -100 - (int)e;
+  Roles rr;
+  mxd::KeySrc k;
+  int rc;
+  if (!party_args(n, ncomp, roles, slots, &rr, &k, &rc)) return rc;
+  return mxp::for_width(words, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_trunc_party_r0<T>, party_grid<T>(n, ncomp), dim3(256), 0,
+                       (hipStream_t)stream, n, m, rr, (const T*)s0, (const T*)s1, (T*)msg,
+                       (u64*)msg_rm, (T*)out0, (T*)out1, k, nn[0], nn[1], nn[2], nn[3], nn[4],
+                       nn[5], ncomp);
+  });
 }
 
 int mxh_trunc_party_r1(int words, int64_t n, int m, int ncomp, const int* roles,
                        const void* msg, const void* rmk, const void* rrt, const void* rrm,
                        void* w, void* out0, void* out1, const uint32_t* const* slots,
                        const uint64_t* nn, void* stream) {
-  if (n == 0) return 0;
-  if (ncomp < 1 || ncomp > 3) return -3;
-  const mxd::KeySrc k = mxd::keysrc_slots(slots, 2 * ncomp);
-  const Roles rr = roles_of(roles, ncomp);
-  hipStream_t st = (hipStream_t)stream;
-  if (words == 1) {
-    hipLaunchKernelGGL(k_trunc_party_r1<u64>, dim3(mxd::grid_for_chunks((n + 1) / 2) * ncomp),
-                       dim3(256), 0, st, n, m, rr, (const u64*)msg, (const u64*)rmk,
-                       (const u64*)rrt, (const u64*)rrm, (u64*)w, (u64*)out0, (u64*)out1, k,
-                       nn[2], nn[3], nn[4], nn[5], ncomp);
-  } else if (words == 2) {
-    hipLaunchKernelGGL(k_trunc_party_r1<u128>, dim3(mxd::grid_for_chunks(n) * ncomp), dim3(256), 0, st,
-                       n, m, rr, (const u128*)msg, (const u128*)rmk, (const u128*)rrt,
-                       (const u64*)rrm, (u128*)w, (u128*)out0, (u128*)out1, k, nn[2], nn[3],
+  Roles rr;
+  mxd::KeySrc k;
+  int rc;
+  if (!party_args(n, ncomp, roles, slots, &rr, &k, &rc)) return rc;
+  return mxp::for_width(words, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_trunc_party_r1<T>, party_grid<T>(n, ncomp), dim3(256), 0,
+                       (hipStream_t)stream, n, m, rr, (const T*)msg, (const T*)rmk,
+                       (const T*)rrt, (const u64*)rrm, (T*)w, (T*)out0, (T*)out1, k, nn[2], nn[3],
                        nn[4], nn[5], ncomp);
-  } else {
-    return -2;
-  }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -100 - (int)e;
+  });
 }
 
 int mxh_ring_extend_party_r0(int64_t n, int ncomp, const int* roles, const void* s0,
                              const void* s1, void* msg, void* msg_R, void* msg_M, void* out0,
                              void* out1, const uint32_t* const* slots, const uint64_t* nn,
                              void* stream) {
-  if (n == 0) return 0;
-  if (ncomp < 1 || ncomp > 3) return -3;
-  const mxd::KeySrc k = mxd::keysrc_slots(slots, 2 * ncomp);
-  const Roles rr = roles_of(roles, ncomp);
-  hipLaunchKernelGGL(k_ring_extend_party_r0, dim3(mxd::grid_for_chunks(n) * ncomp), dim3(256), 0,
+  Roles rr;
+  mxd::KeySrc k;
+  int rc;
+  if (!party_args(n, ncomp, roles, slots, &rr, &k, &rc)) return rc;
+  hipLaunchKernelGGL(k_ring_extend_party_r0, party_grid<u128>(n, ncomp), dim3(256), 0,
                      (hipStream_t)stream, n, rr, (const u64*)s0, (const u64*)s1, (u64*)msg,
                      (u128*)msg_R, (u64*)msg_M, (u128*)out0, (u128*)out1, k, nn[0], nn[1], nn[2],
                      nn[3], nn[4], nn[5], ncomp);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -100 - (int)e;
+  return mxp::launch_status();
 }
 
 int mxh_ring_extend_party_r1(int64_t n, int ncomp, const int* roles, const void* msg,
                              const void* rmk, const void* rR, const void* rM, void* w,
                              void* out0, void* out1, const uint32_t* const* slots,
                              const uint64_t* nn, void* stream) {
-  if (n == 0) return 0;
-  if (ncomp < 1 || ncomp > 3) return -3;
-  const mxd::KeySrc k = mxd::keysrc_slots(slots, 2 * ncomp);
-  const Roles rr = roles_of(roles, ncomp);
-  hipLaunchKernelGGL(k_ring_extend_party_r1, dim3(mxd::grid_for_chunks(n) * ncomp), dim3(256), 0,
+  Roles rr;
+  mxd::KeySrc k;
+  int rc;
+  if (!party_args(n, ncomp, roles, slots, &rr, &k, &rc)) return rc;
+  hipLaunchKernelGGL(k_ring_extend_party_r1, party_grid<u128>(n, ncomp), dim3(256), 0,
                      (hipStream_t)stream, n, rr, (const u64*)msg, (const u64*)rmk,
                      (const u128*)rR, (const u64*)rM, (u128*)w, (u128*)out0, (u128*)out1, k,
                      nn[2], nn[3], nn[4], nn[5], ncomp);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -100 - (int)e;
+  return mxp::launch_status();
 }
 
 int mxh_share_party(int kind, int words, int64_t n, int ncomp, const int* rel, const void* x,
                     void* out0, void* out1, const uint32_t* const* slots, uint64_t n1,
                     uint64_t na, void* stream) {
-  if (n == 0) return 0;
-  if (ncomp < 1 || ncomp > 3) return -3;
-  const mxd::KeySrc k = mxd::keysrc_slots(slots, 2 * ncomp);
-  const Roles rr = roles_of(rel, ncomp);
+  Roles rr;
+  mxd::KeySrc k;
+  int rc;
+  if (!party_args(n, ncomp, rel, slots, &rr, &k, &rc)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  switch (words) {
-    case 0:
-      hipLaunchKernelGGL(k_share_party<uint8_t>, dim3(mxd::grid_for_chunks((n + 15) / 16) * ncomp),
-                         dim3(256), 0, st, kind, n, rr, (const uint8_t*)x, (uint8_t*)out0,
-                         (uint8_t*)out1, k, n1, na, ncomp);
-      break;
-    case 1:
-      hipLaunchKernelGGL(k_share_party<u64>, dim3(mxd::grid_for_chunks((n + 1) / 2) * ncomp), dim3(256),
-                         0, st, kind, n, rr, (const u64*)x, (u64*)out0, (u64*)out1, k, n1, na,
-                         ncomp);
-      break;
-    case 2:
-      hipLaunchKernelGGL(k_share_party<u128>, dim3(mxd::grid_for_chunks(n) * ncomp), dim3(256), 0, st,
-                         kind, n, rr, (const u128*)x, (u128*)out0, (u128*)out1, k, n1, na, ncomp);
-      break;
-    default:
-      return -2;
+  if (words == 0) {  // bits: no u64 / u128 pair
+    hipLaunchKernelGGL(k_share_party<uint8_t>, party_grid<uint8_t>(n, ncomp), dim3(256), 0, st,
+                       kind, n, rr, x, (uint8_t*)out0, (uint8_t*)out1, k, n1, na, ncomp);
+    return mxp::launch_status();
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -100 - (int)e;
+  return mxp::for_width(words, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_share_party<T>, party_grid<T>(n, ncomp), dim3(256), 0, st, kind, n, rr,
+                       x, (T*)out0, (T*)out1, k, n1, na, ncomp);
+  });
 }
-
 
 int mxh_dot_tail_r0(int words, int64_t n, int m, int ncomp, const int* roles,
                     const void* const* cross, void* const* msg, void* const* msg_rt,
                     void* const* msg_rm, void* const* out0, void* const* out1,
                     const uint32_t* const* slots, const uint64_t* nn, void* stream) {
-  if (n == 0) return 0;
-  if (ncomp < 1 || ncomp > 3) return -3;
-  const mxd::KeySrc k = mxd::keysrc_slots(slots, 2 * ncomp);
-  const Roles rr = roles_of(roles, ncomp);
-  hipStream_t st = (hipStream_t)stream;
+  Roles rr;
+  mxd::KeySrc k;
+  int rc;
+  if (!party_args(n, ncomp, roles, slots, &rr, &k, &rc)) return rc;
   const CP3 x = cp3(cross, ncomp);
   const WP3 mo = wp3(msg, ncomp), rt = wp3(msg_rt, ncomp), rm = wp3(msg_rm, ncomp),
             o0 = wp3(out0, ncomp), o1 = wp3(out1, ncomp);
-  if (words == 1) {
-    hipLaunchKernelGGL(k_dot_tail_r0<u64>, dim3(mxd::grid_for_chunks((n + 1) / 2) * ncomp),
-                       dim3(256), 0, st, n, m, rr, x, mo, rt, rm, o0, o1, k, nn[0], nn[1],
+  return mxp::for_width(words, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_dot_tail_r0<T>, party_grid<T>(n, ncomp), dim3(256), 0,
+                       (hipStream_t)stream, n, m, rr, x, mo, rt, rm, o0, o1, k, nn[0], nn[1],
                        nn[2], nn[3], nn[4], nn[5], nn[6], ncomp);
-  } else if (words == 2) {
-    hipLaunchKernelGGL(k_dot_tail_r0<u128>, dim3(mxd::grid_for_chunks(n) * ncomp), dim3(256), 0,
-                       st, n, m, rr, x, mo, rt, rm, o0, o1, k, nn[0], nn[1], nn[2], nn[3], nn[4],
-                       nn[5], nn[6], ncomp);
-  } else {
-    return -2;
-  }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -100 - (int)e;
+  });
 }
 
 int mxh_dot_tail_r1(int words, int64_t n, int m, int ncomp, const int* roles,
@@ -851,46 +619,33 @@ int mxh_dot_tail_r1(int words, int64_t n, int m, int ncomp, const int* roles,
                     const void* const* rrt, const void* const* rrm, void* const* w,
                     void* const* out0, void* const* out1, const uint32_t* const* slots,
                     const uint64_t* nn, void* stream) {
-  if (n == 0) return 0;
-  if (ncomp < 1 || ncomp > 3) return -3;
-  const mxd::KeySrc k = mxd::keysrc_slots(slots, 2 * ncomp);
-  const Roles rr = roles_of(roles, ncomp);
-  hipStream_t st = (hipStream_t)stream;
+  Roles rr;
+  mxd::KeySrc k;
+  int rc;
+  if (!party_args(n, ncomp, roles, slots, &rr, &k, &rc)) return rc;
   const CP3 a = cp3(msg, ncomp), b = cp3(rmk, ncomp), z = cp3(rz, ncomp), t = cp3(rrt, ncomp),
             r = cp3(rrm, ncomp);
   const WP3 wo = wp3(w, ncomp), o0 = wp3(out0, ncomp), o1 = wp3(out1, ncomp);
-  if (words == 1) {
-    hipLaunchKernelGGL(k_dot_tail_r1<u64>, dim3(mxd::grid_for_chunks((n + 1) / 2) * ncomp),
-                       dim3(256), 0, st, n, m, rr, a, b, z, t, r, wo, o0, o1, k, nn[3], nn[4],
+  return mxp::for_width(words, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_dot_tail_r1<T>, party_grid<T>(n, ncomp), dim3(256), 0,
+                       (hipStream_t)stream, n, m, rr, a, b, z, t, r, wo, o0, o1, k, nn[3], nn[4],
                        nn[5], nn[6], ncomp);
-  } else if (words == 2) {
-    hipLaunchKernelGGL(k_dot_tail_r1<u128>, dim3(mxd::grid_for_chunks(n) * ncomp), dim3(256), 0,
-                       st, n, m, rr, a, b, z, t, r, wo, o0, o1, k, nn[3], nn[4], nn[5], nn[6],
-                       ncomp);
-  } else {
-    return -2;
-  }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -100 - (int)e;
+  });
 }
 
 int mxh_dot_tail_r2(int words, int64_t n, int ncomp, const int* roles, const void* const* a,
                     const void* const* b, void* const* out, void* stream) {
-  if (n == 0) return 0;
-  if (ncomp < 1 || ncomp > 3) return -3;
-  const Roles rr = roles_of(roles, ncomp);
-  hipStream_t st = (hipStream_t)stream;
+  Roles rr;
+  int rc;
+  if (!party_args(n, ncomp, roles, nullptr, &rr, nullptr, &rc)) return rc;
   const CP3 x = cp3(a, ncomp), y = cp3(b, ncomp);
   const WP3 o = wp3(out, ncomp);
-  const int grid = mxd::grid_for(n * ncomp);
-  if (words == 1)
-    hipLaunchKernelGGL(k_dot_tail_r2<u64>, dim3(grid), dim3(256), 0, st, n, rr, x, y, o, ncomp);
-  else if (words == 2)
-    hipLaunchKernelGGL(k_dot_tail_r2<u128>, dim3(grid), dim3(256), 0, st, n, rr, x, y, o, ncomp);
-  else
-    return -2;
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -100 - (int)e;
+  return mxp::for_width(words, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_dot_tail_r2<T>, dim3(mxd::grid_for(n * ncomp)), dim3(256), 0,
+                       (hipStream_t)stream, n, rr, x, y, o, ncomp);
+  });
 }
 
 }  // extern "C"

@@ -2,71 +2,29 @@
 // points that dispatch host / device.  Key slots are MX_KEY_SLOT_WORDS-word images whose
 // first four words are the raw AES key.
 #include <cmath>
-#include <functional>
-#include <vector>
 
 #include "moosex.h"
+#include "party_abi.h"
+#include "party_rounds_cpu.h"
 #include "ring_common.h"
 #include "rss_fused.h"
-
-void mx_cpu_prf_range(const uint8_t* key, uint64_t nonce, int words, int64_t i0, int64_t n,
-                      void* out);
-void mx_cpu_parallel_for(int64_t n, int64_t grain,
-                         const std::function<void(int64_t, int64_t)>& f);
-
-extern "C" {
-int mxh_trunc_party_r0(int words, int64_t n, int m, int ncomp, const int* roles,
-                       const void* s0, const void* s1, void* msg, void* msg_rm, void* out0,
-                       void* out1, const uint32_t* const* slots, const uint64_t* nn,
-                       void* stream);
-int mxh_trunc_party_r1(int words, int64_t n, int m, int ncomp, const int* roles,
-                       const void* msg, const void* rmk, const void* rrt, const void* rrm,
-                       void* w, void* out0, void* out1, const uint32_t* const* slots,
-                       const uint64_t* nn, void* stream);
-int mxh_ring_extend_party_r0(int64_t n, int ncomp, const int* roles, const void* s0,
-                             const void* s1, void* msg, void* msg_R, void* msg_M, void* out0,
-                             void* out1, const uint32_t* const* slots, const uint64_t* nn,
-                             void* stream);
-int mxh_ring_extend_party_r1(int64_t n, int ncomp, const int* roles, const void* msg,
-                             const void* rmk, const void* rR, const void* rM, void* w,
-                             void* out0, void* out1, const uint32_t* const* slots,
-                             const uint64_t* nn, void* stream);
-int mxh_share_party(int kind, int words, int64_t n, int ncomp, const int* rel, const void* x,
-                    void* out0, void* out1, const uint32_t* const* slots, uint64_t n1,
-                    uint64_t na, void* stream);
-int mxh_dot_tail_r0(int words, int64_t n, int m, int ncomp, const int* roles,
-                    const void* const* cross, void* const* msg, void* const* msg_rt,
-                    void* const* msg_rm, void* const* out0, void* const* out1,
-                    const uint32_t* const* slots, const uint64_t* nn, void* stream);
-int mxh_dot_tail_r1(int words, int64_t n, int m, int ncomp, const int* roles,
-                    const void* const* msg, const void* const* rmk, const void* const* rz,
-                    const void* const* rrt, const void* const* rrm, void* const* w,
-                    void* const* out0, void* const* out1, const uint32_t* const* slots,
-                    const uint64_t* nn, void* stream);
-int mxh_dot_tail_r2(int words, int64_t n, int ncomp, const int* roles, const void* const* a,
-                    const void* const* b, void* const* out, void* stream);
-}
 
 namespace {
 
 using u64 = uint64_t;
 using u128 = unsigned __int128;
+using mxc::for_chunks;
+using mxc::prf;
 
-const uint8_t* key_of(const uint32_t* slot) { return (const uint8_t*)slot; }
-
-// chunked element loop with up to six PRF streams per chunk
-template <class T, class F>
-void for_chunks(int64_t n, F&& f) {
-  mx_cpu_parallel_for(n, 1 << 12, [&](int64_t s, int64_t e) {
-    const int64_t CH = 512;
-    for (int64_t c = s; c < e; c += CH) f(c, std::min(CH, e - c));
-  });
-}
-
+// the dealer's outputs of one component
 template <class T>
-void prf(const uint32_t* slot, uint64_t nonce, int64_t i0, int64_t len, T* out) {
-  const int words = sizeof(T) == 1 ? 0 : (int)(sizeof(T) / 8);
-  mx_cpu_prf_range(key_of(slot), nonce, words, i0, len, out);
+auto deal_out(T* rt, u64* rm, T* o0, T* o1) {
+  return [=](int64_t i, const mxf::TruncDeal<T>& d) {
+    rt[i] = d.rt1;
+    rm[i] = d.rm1;
+    o0[i] = d.s0;
+    o1[i] = d.s1;
+  };
 }
 
 template <class T>
@@ -77,34 +35,54 @@ int trunc_r0(int64_t n, int m, int ncomp, const int* roles, const T* s0, const T
     const uint32_t* own = slots[2 * c];
     const uint32_t* nxt = slots[2 * c + 1];
     const int64_t base = (int64_t)c * n;
-    for_chunks<T>(n, [&](int64_t i0, int64_t len) {
-      std::vector<T> a(len), b(len), t(len), mm(len), z0(len), z2(len);
-      if (role == 0) {
-        prf<T>(own, nn[0], i0, len, a.data());
-        for (int64_t q = 0; q < len; ++q) {
-          const int64_t i = base + i0 + q;
-          msg[i] = mxf::trunc_mask0<T>(s0[i], s1[i], a[q]);
-        }
-      } else if (role == 1) {
-        prf<T>(nxt, nn[1], i0, len, a.data());
-        for (int64_t q = 0; q < len; ++q) {
-          const int64_t i = base + i0 + q;
-          msg[i] = s1[i] + a[q];
-        }
-      } else if (role == 2) {
-        prf<T>(nxt, nn[0], i0, len, a.data());
-        prf<T>(own, nn[1], i0, len, b.data());
-        prf<T>(nxt, nn[2], i0, len, t.data());
-        prf<T>(nxt, nn[3], i0, len, mm.data());
-        prf<T>(nxt, nn[4], i0, len, z0.data());
-        prf<T>(own, nn[5], i0, len, z2.data());
-        for (int64_t q = 0; q < len; ++q) {
-          const int64_t i = base + i0 + q;
-          mxf::trunc_dealer<T>(a[q], b[q], t[q], mm[q], m, &msg[i], &msg_rm[i]);
-          out0[i] = z2[q];
-          out1[i] = z0[q];
-        }
-      }
+    for_chunks(n, [&](int64_t i0, int64_t len) {
+      if (role == 0 || role == 1)  // P0's part of the value is x0 + x1, P1's x2
+        mxc::main_r0<T>(
+            false, role, own, nxt, 0, nn, i0, len,
+            [&](int64_t i) { return role == 0 ? (T)(s0[base + i] + s1[base + i]) : s1[base + i]; },
+            [&](int64_t i) -> T& { return msg[base + i]; });
+      else if (role == 2)
+        mxc::dealer_r0<T>(own, nxt, nn, m, i0, len,
+                          deal_out<T>(msg + base, msg_rm + base, out0 + base, out1 + base));
+    });
+  }
+  return 0;
+}
+
+// Round 1 of every component in role 0 / 1 (rss_party.hip party_round1): a null z2m is
+// TruncPr's own two-term opening, else the dot tail's three-term one.
+template <class T>
+struct R1Args {
+  const T* mine;
+  const T* other;
+  const T* z2m;
+  const T* rt;
+  const u64* rm;
+  T* w;
+  T* o0;
+  T* o1;
+};
+
+template <class T, class At>
+int party_round1(int64_t n, int m, int ncomp, const int* roles, const uint32_t* const* slots,
+                 const uint64_t* nn, At&& at) {
+  for (int c = 0; c < ncomp; ++c) {
+    const int role = roles[c];
+    if (role != 0 && role != 1) continue;
+    const R1Args<T> a = at(c);
+    T* o = role == 0 ? a.o0 : a.o1;
+    for_chunks(n, [&](int64_t i0, int64_t len) {
+      mxc::round1<T>(
+          role, slots[2 * c], slots[2 * c + 1], nn, m, i0, len,
+          [&](int64_t i) { return (T)(a.mine[i] + a.other[i] + (a.z2m ? a.z2m[i] : (T)0)); },
+          [&](int64_t i, T* rt, T* rm) {
+            *rt = a.rt[i];
+            *rm = (T)a.rm[i];
+          },
+          [&](int64_t i, T w, T z) {
+            a.w[i] = w;
+            o[i] = z;
+          });
     });
   }
   return 0;
@@ -114,34 +92,11 @@ template <class T>
 int trunc_r1(int64_t n, int m, int ncomp, const int* roles, const T* msg, const T* rmk,
              const T* rrt, const u64* rrm, T* w, T* out0, T* out1,
              const uint32_t* const* slots, const uint64_t* nn) {
-  for (int c = 0; c < ncomp; ++c) {
-    const int role = roles[c];
+  return party_round1<T>(n, m, ncomp, roles, slots, nn + 2, [&](int c) {
     const int64_t base = (int64_t)c * n;
-    for_chunks<T>(n, [&](int64_t i0, int64_t len) {
-      std::vector<T> t(len), mm(len), z(len);
-      if (role == 0) {
-        const uint32_t* k0 = slots[2 * c];
-        prf<T>(k0, nn[2], i0, len, t.data());
-        prf<T>(k0, nn[3], i0, len, mm.data());
-        prf<T>(k0, nn[4], i0, len, z.data());
-        for (int64_t q = 0; q < len; ++q) {
-          const int64_t i = base + i0 + q;
-          const T y0 = mxf::trunc_y<T>(msg[i] + rmk[i], t[q], mm[q], m, true);
-          w[i] = y0 - z[q];
-          out0[i] = z[q];
-        }
-      } else if (role == 1) {
-        prf<T>(slots[2 * c + 1], nn[5], i0, len, z.data());
-        for (int64_t q = 0; q < len; ++q) {
-          const int64_t i = base + i0 + q;
-          const T y1 = mxf::trunc_y<T>(msg[i] + rmk[i], rrt[i], (T)rrm[i], m, false);
-          w[i] = y1 - z[q];
-          out1[i] = z[q];
-        }
-      }
-    });
-  }
-  return 0;
+    return R1Args<T>{msg + base, rmk + base, nullptr,     rrt + base,
+                     rrm + base, w + base,   out0 + base, out1 + base};
+  });
 }
 
 // Ring extension Z_2^64 -> Z_2^128 (k_ring_extend_party_r0 / r1): every stream at 128-bit
@@ -154,32 +109,23 @@ int ring_extend_r0(int64_t n, int ncomp, const int* roles, const u64* s0, const 
     const uint32_t* own = slots[2 * c];
     const uint32_t* nxt = slots[2 * c + 1];
     const int64_t base = (int64_t)c * n;
-    for_chunks<u128>(n, [&](int64_t i0, int64_t len) {
-      std::vector<u128> a(len), b(len), R(len), mm(len), z0(len), z2(len);
-      if (role == 0) {
-        prf<u128>(own, nn[0], i0, len, a.data());
+    for_chunks(n, [&](int64_t i0, int64_t len) {
+      if (role == 0 || role == 1) {  // r0 under k0 = P0's own, r1 under k2 = P1's next
+        const std::vector<u128> r = prf<u128>(role == 0 ? own : nxt, nn[role], i0, len);
         for (int64_t q = 0; q < len; ++q) {
           const int64_t i = base + i0 + q;
-          msg[i] = mxf::ring_extend_mask0(s0[i], s1[i], (u64)a[q]);
-        }
-      } else if (role == 1) {
-        prf<u128>(nxt, nn[1], i0, len, a.data());
-        for (int64_t q = 0; q < len; ++q) {
-          const int64_t i = base + i0 + q;
-          msg[i] = s1[i] + (u64)a[q];
+          msg[i] = role == 0 ? mxf::ring_extend_mask0(s0[i], s1[i], (u64)r[q]) : s1[i] + (u64)r[q];
         }
       } else if (role == 2) {
-        prf<u128>(nxt, nn[0], i0, len, a.data());
-        prf<u128>(own, nn[1], i0, len, b.data());
-        prf<u128>(nxt, nn[2], i0, len, R.data());
-        prf<u128>(nxt, nn[3], i0, len, mm.data());
-        prf<u128>(nxt, nn[4], i0, len, z0.data());
-        prf<u128>(own, nn[5], i0, len, z2.data());
+        const mxc::DealerDraws<u128> w(own, nxt, nn, i0, len);
         for (int64_t q = 0; q < len; ++q) {
           const int64_t i = base + i0 + q;
-          mxf::ring_extend_dealer((u64)a[q], (u64)b[q], R[q], (u64)mm[q], &msg_R[i], &msg_M[i]);
-          out0[i] = z2[q];
-          out1[i] = z0[q];
+          const mxf::RingExtendDeal d =
+              mxf::ring_extend_deal(w.r0[q], w.r1[q], w.t[q], w.m[q], w.z0[q], w.z2[q]);
+          msg_R[i] = d.R1;
+          msg_M[i] = d.M1;
+          out0[i] = d.s0;
+          out1[i] = d.s1;
         }
       }
     });
@@ -192,26 +138,17 @@ int ring_extend_r1(int64_t n, int ncomp, const int* roles, const u64* msg, const
                    const uint32_t* const* slots, const uint64_t* nn) {
   for (int c = 0; c < ncomp; ++c) {
     const int role = roles[c];
+    if (role != 0 && role != 1) continue;
     const int64_t base = (int64_t)c * n;
-    for_chunks<u128>(n, [&](int64_t i0, int64_t len) {
-      std::vector<u128> R(len), mm(len), z(len);
-      if (role == 0) {
-        const uint32_t* k0 = slots[2 * c];
-        prf<u128>(k0, nn[2], i0, len, R.data());
-        prf<u128>(k0, nn[3], i0, len, mm.data());
-        prf<u128>(k0, nn[4], i0, len, z.data());
-        for (int64_t q = 0; q < len; ++q) {
-          const int64_t i = base + i0 + q;
-          w[i] = mxf::ring_extend_y(msg[i] + rmk[i], R[q], (u64)mm[q], true) - z[q];
-          out0[i] = z[q];
-        }
-      } else if (role == 1) {
-        prf<u128>(slots[2 * c + 1], nn[5], i0, len, z.data());
-        for (int64_t q = 0; q < len; ++q) {
-          const int64_t i = base + i0 + q;
-          w[i] = mxf::ring_extend_y(msg[i] + rmk[i], rR[i], rM[i], false) - z[q];
-          out1[i] = z[q];
-        }
+    u128* o = role == 0 ? out0 : out1;
+    for_chunks(n, [&](int64_t i0, int64_t len) {
+      const mxc::Round1Draws<u128> k(role, slots[2 * c], slots[2 * c + 1], nn + 2, i0, len);
+      for (int64_t q = 0; q < len; ++q) {
+        const int64_t i = base + i0 + q;
+        const u128 R = role == 0 ? k.t[q] : rR[i];
+        const u64 M = role == 0 ? (u64)k.m[q] : rM[i];
+        w[i] = mxf::ring_extend_round1_w(role, msg[i] + rmk[i], R, M, k.z[q]);
+        o[i] = k.z[q];
       }
     });
   }
@@ -232,9 +169,9 @@ int share_party(int kind, int64_t n, int ncomp, const int* rel, const void* xp, 
     const int r = code & 3, fwd = (code >> 2) - 1;
     const int64_t base = (int64_t)c * n;
     if (r > 2) continue;
-    for_chunks<T>(n, [&](int64_t i0, int64_t len) {
+    for_chunks(n, [&](int64_t i0, int64_t len) {
       std::vector<T> a(len);
-      if (mir ? r != 2 : r != 1) prf<T>(slots[2 * c], n1, i0, len, a.data());
+      if (mir ? r != 2 : r != 1) mxc::prf_into<T>(slots[2 * c], n1, i0, len, a.data());
       for (int64_t q = 0; q < len; ++q) {
         const int64_t i = base + i0 + q;
         if (r == 0) {
@@ -271,39 +208,15 @@ int dot_tail_r0(int64_t n, int m, int ncomp, const int* roles, const void* const
     const T* x = (const T*)cross[c];
     T* mo = (T*)msg[c];
     // as k_dot_tail_r0: no cross -> the dealer part only; no msg_rt -> no dealer part
-    const bool main_part = x != nullptr;
     const bool dealer = role == 2 && msg_rt[c] != nullptr;
-    for_chunks<T>(n, [&](int64_t i0, int64_t len) {
-      if (main_part) {
-        // zero share: P0 f(k0), P1 -f(k2), P2 f(k2) - f(k0) (rss_party.hip)
-        std::vector<T> a(len, (T)0), b(len, (T)0), r(len);
-        if (role != 1) prf<T>(own, nn[0], i0, len, a.data());
-        if (role != 0) prf<T>(nxt, nn[0], i0, len, b.data());
-        if (role == 0) prf<T>(own, nn[1], i0, len, r.data());
-        if (role == 1) prf<T>(nxt, nn[2], i0, len, r.data());
-        for (int64_t q = 0; q < len; ++q) {
-          const int64_t i = i0 + q;
-          const T z = x[i] + a[q] - b[q];
-          mo[i] = role == 0 ? mxf::trunc_mask0<T>(z, (T)0, r[q]) : role == 1 ? (T)(z + r[q]) : z;
-        }
-      }
-      if (dealer) {
-        std::vector<T> r0(len), r1(len), t(len), mm(len), z0(len), z2(len);
-        prf<T>(nxt, nn[1], i0, len, r0.data());
-        prf<T>(own, nn[2], i0, len, r1.data());
-        prf<T>(nxt, nn[3], i0, len, t.data());
-        prf<T>(nxt, nn[4], i0, len, mm.data());
-        prf<T>(nxt, nn[5], i0, len, z0.data());
-        prf<T>(own, nn[6], i0, len, z2.data());
-        T* rt = (T*)msg_rt[c];
-        u64* rm = (u64*)msg_rm[c];
-        for (int64_t q = 0; q < len; ++q) {
-          const int64_t i = i0 + q;
-          mxf::trunc_dealer<T>(r0[q], r1[q], t[q], mm[q], m, &rt[i], &rm[i]);
-          ((T*)out0[c])[i] = z2[q];
-          ((T*)out1[c])[i] = z0[q];
-        }
-      }
+    for_chunks(n, [&](int64_t i0, int64_t len) {
+      if (x != nullptr)
+        mxc::main_r0<T>(
+            true, role, own, nxt, nn[0], nn + 1, i0, len, [&](int64_t i) { return x[i]; },
+            [&](int64_t i) -> T& { return mo[i]; });
+      if (dealer)
+        mxc::dealer_r0<T>(own, nxt, nn + 1, m, i0, len,
+                          deal_out<T>((T*)msg_rt[c], (u64*)msg_rm[c], (T*)out0[c], (T*)out1[c]));
     });
   }
   return 0;
@@ -314,36 +227,11 @@ int dot_tail_r1(int64_t n, int m, int ncomp, const int* roles, const void* const
                 const void* const* rmk, const void* const* rz, const void* const* rrt,
                 const void* const* rrm, void* const* w, void* const* out0, void* const* out1,
                 const uint32_t* const* slots, const uint64_t* nn) {
-  for (int c = 0; c < ncomp; ++c) {
-    const int role = roles[c];
-    if (role != 0 && role != 1) continue;
-    const T* mine = (const T*)msg[c];
-    const T* other = (const T*)rmk[c];
-    const T* z2m = rz ? (const T*)rz[c] : nullptr;
-    T* wo = (T*)w[c];
-    T* o = role == 0 ? (T*)out0[c] : (T*)out1[c];
-    for_chunks<T>(n, [&](int64_t i0, int64_t len) {
-      std::vector<T> t(len), mm(len), z(len);
-      if (role == 0) {
-        prf<T>(slots[2 * c], nn[3], i0, len, t.data());
-        prf<T>(slots[2 * c], nn[4], i0, len, mm.data());
-        prf<T>(slots[2 * c], nn[5], i0, len, z.data());
-      } else {
-        prf<T>(slots[2 * c + 1], nn[6], i0, len, z.data());
-      }
-      for (int64_t q = 0; q < len; ++q) {
-        const int64_t i = i0 + q;
-        T cc = mine[i] + other[i];
-        if (z2m) cc += z2m[i];
-        const T y = role == 0 ? mxf::trunc_y<T>(cc, t[q], mm[q], m, true)
-                              : mxf::trunc_y<T>(cc, ((const T*)rrt[c])[i],
-                                                (T)((const u64*)rrm[c])[i], m, false);
-        wo[i] = y - z[q];
-        o[i] = z[q];
-      }
-    });
-  }
-  return 0;
+  return party_round1<T>(n, m, ncomp, roles, slots, nn + 3, [&](int c) {
+    return R1Args<T>{(const T*)msg[c],   (const T*)rmk[c], rz ? (const T*)rz[c] : nullptr,
+                     (const T*)rrt[c],   (const u64*)rrm[c], (T*)w[c],
+                     (T*)out0[c],        (T*)out1[c]};
+  });
 }
 
 template <class T>

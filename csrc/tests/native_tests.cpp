@@ -154,6 +154,61 @@ TEST(ring, zero_share_sums_to_zero) {
   for (int64_t i = 0; i < n; ++i) CHECK((zb[i] ^ zb[n + i] ^ zb[2 * n + i]) == 0);
 }
 
+TEST(ring, party_dot_tail_three_rounds_truncate) {
+  // the per-party dot tail's three host rounds (rss_party_cpu.cpp over party_rounds_cpu.h),
+  // the three roles stacked: the new sharing opens to the product shifted right by m, +-1
+  const int64_t n = 37;
+  const int m = 23;
+  uint8_t raw[48];
+  for (auto& b : raw) b = (uint8_t)rng();
+  std::vector<uint32_t> img(3 * MX_KEY_SLOT_WORDS);
+  mx_key_slots(raw, 3, img.data());
+  const int roles[3] = {0, 1, 2};
+  const uint32_t* slots[6];
+  for (int p = 0; p < 3; ++p) {  // role p holds (own k_p, next k_{p+1})
+    slots[2 * p] = img.data() + p * MX_KEY_SLOT_WORDS;
+    slots[2 * p + 1] = img.data() + ((p + 1) % 3) * MX_KEY_SLOT_WORDS;
+  }
+  const uint64_t nn[7] = {11, 12, 13, 14, 15, 16, 17};
+  std::vector<__int128> v(n);
+  std::vector<u128> x[3], msg[3], w[3], o0[3], o1[3], rt(n);
+  std::vector<uint64_t> rm(n);
+  for (int p = 0; p < 3; ++p)
+    for (auto* t : {&x[p], &msg[p], &w[p], &o0[p], &o1[p]}) t->assign(n, 0);
+  for (int64_t i = 0; i < n; ++i) {
+    v[i] = (__int128)(int64_t)rng() * (1 << 20);
+    x[0][i] = ((u128)rng() << 64) | rng();
+    x[1][i] = ((u128)rng() << 64) | rng();
+    x[2][i] = (u128)v[i] - x[0][i] - x[1][i];
+  }
+  const void* cross[3] = {x[0].data(), x[1].data(), x[2].data()};
+  void* mo[3] = {msg[0].data(), msg[1].data(), msg[2].data()};
+  void* prt[3] = {nullptr, nullptr, rt.data()};
+  void* prm[3] = {nullptr, nullptr, rm.data()};
+  void* p0[3] = {o0[0].data(), o0[1].data(), o0[2].data()};
+  void* p1[3] = {o1[0].data(), o1[1].data(), o1[2].data()};
+  CHECK(mx_dot_tail_r0(0, 2, n, m, 3, roles, cross, mo, prt, prm, p0, p1, slots, nn, nullptr) == 0);
+  // round A: m0 <-> m1, z2 to both, the dealer's rt1 / rm1 to P1
+  const void* mine[3] = {msg[0].data(), msg[1].data(), nullptr};
+  const void* other[3] = {msg[1].data(), msg[0].data(), nullptr};
+  const void* z2[3] = {msg[2].data(), msg[2].data(), nullptr};
+  const void* rrt[3] = {nullptr, rt.data(), nullptr};
+  const void* rrm[3] = {nullptr, rm.data(), nullptr};
+  void* wo[3] = {w[0].data(), w[1].data(), nullptr};
+  CHECK(mx_dot_tail_r1(0, 2, n, m, 3, roles, mine, other, z2, rrt, rrm, wo, p0, p1, slots, nn,
+                       nullptr) == 0);
+  // round B: w0 <-> w1; P0's s1 = P1's s0 = w0 + w1
+  const void* wa[3] = {w[0].data(), w[1].data(), nullptr};
+  const void* wb[3] = {w[1].data(), w[0].data(), nullptr};
+  void* sum[3] = {o1[0].data(), o0[1].data(), nullptr};
+  CHECK(mx_dot_tail_r2(0, 2, n, 3, roles, wa, wb, sum, nullptr) == 0);
+  for (int64_t i = 0; i < n; ++i) {
+    CHECK(o1[0][i] == o0[1][i] && o1[1][i] == o0[2][i] && o1[2][i] == o0[0][i]);
+    const __int128 got = (__int128)(o0[0][i] + o0[1][i] + o0[2][i]), want = v[i] >> m;
+    CHECK(got - want >= -1 && got - want <= 1);
+  }
+}
+
 TEST(ring, fixedpoint_encode_decode_roundtrip) {
   const int64_t n = 64;
   std::vector<double> x(n), y(n);
