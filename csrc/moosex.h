@@ -87,6 +87,14 @@ int mx_mul_trunc3_kv(int dev, int words, const void* x0, const void* x1, const v
                      const void* y1, void* out0, void* out1, int64_t n, int64_t ostride,
                      const uint32_t* slots, uint64_t nmul, int m, const uint64_t* nonces,
                      const int64_t* views, void* stream);
+// The tail of a fixed-point dot whose result is only revealed: mx_mul_trunc3_kv's zero share
+// + reshare + TruncPr of the parties' local products x ([3] slots, xstride elements apart:
+// a stack, or rows of a larger one), same keys and nonces, and the new shares opened at
+// once -- out[i] = signed(Z0 + Z1 + Z2)[i] / 2^frac, bitwise mx_addn_decode of those shares,
+// which are not written.  Host and device, every size.
+int mx_mul_trunc3_open(int dev, int words, const void* x, int64_t xstride, double* out,
+                       int64_t n, const uint32_t* slots, uint64_t nmul, int m,
+                       const uint64_t* nonces, int frac, void* stream);
 // out = a + b + c elementwise (mod 2^w)
 int mx_ew_add3(int dev, int words, const void* a, const void* b, const void* c, void* out,
                int64_t n, void* stream);

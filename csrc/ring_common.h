@@ -253,6 +253,9 @@ int mxh_mul_trunc3_kv(int words, const void* x0, const void* x1, const void* y0,
                       void* out0, void* out1, int64_t n, int64_t ostride, const uint32_t* slots,
                       uint64_t nmul, int m, const uint64_t* nn, const int64_t* views,
                       void* stream);
+int mxh_mul_trunc3_open(int words, const void* x, int64_t xstride, double* out, int64_t n,
+                        const uint32_t* slots, uint64_t nmul, int m, const uint64_t* nn, int frac,
+                        void* stream);
 int mxh_ew_unary2(int op, int words, const void* a0, void* out0, const void* a1, void* out1,
                   int64_t n, int64_t param, void* stream);
 int mxh_transpose2(int words, const void* a0, void* out0, const void* a1, void* out1,

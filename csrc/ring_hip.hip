@@ -1521,15 +1521,49 @@ __global__ void __launch_bounds__(256) k_rss_cross_ring3_lat(int kind, const T* 
   }
 }
 
+// Where the fixed-point product kernels below put element e's new shares (Z0, Z1, Z2).
+// TailShares: both share vectors at party stride os (the ordinary tail).
+template <class T>
+struct TailShares {
+  T* __restrict__ out0;
+  T* __restrict__ out1;
+  int64_t os;
+  __device__ __forceinline__ void operator()(int64_t e, T Z0, T Z1, T Z2) const {
+    out0[e] = Z0;
+    out0[os + e] = Z1;
+    out0[2 * os + e] = Z2;
+    if (out1 != out0 + os) {  // else a 4-slot ring: out1's slots 0, 1 are out0's 1, 2
+      out1[e] = Z1;
+      out1[os + e] = Z2;
+    }
+    out1[2 * os + e] = Z0;
+  }
+};
+
+// TailOpen: the product is only revealed -- the shares' sum decoded as d_addn_decode does
+// it (ring add, signed conversion, * scale), so the shares never go to memory.
+template <class T>
+struct TailOpen {
+  double* __restrict__ out;
+  double scale;
+  __device__ __forceinline__ void operator()(int64_t e, T Z0, T Z1, T Z2) const {
+    const T v = Z0 + Z1 + Z2;
+    if constexpr (sizeof(T) == 8)
+      out[e] = (double)(int64_t)v * scale;
+    else
+      out[e] = mxr::i128_to_f64(v) * scale;
+  }
+};
+
 // Fixed-point product of a latency-bound launch in ONE kernel: the stacked RSS product
 // with its zero share (as k_rss_cross_ring3_lat) and the TruncPr of the reshared product
 // (as k_trunc_pr3_lat) -- the product never leaves registers.  Nine keystream chunks per
 // chunk position: the product's zero share (k0, k1, k2 at nmul) and the TruncPr's r0, r1,
 // t, m, z0, z2 (keys k0 / k2, as in k_trunc_pr3).  Bitwise equal to the two kernels.
-template <class T, int EPB>
+template <class T, int EPB, class Sink>
 __device__ __forceinline__ void mul_trunc3_lat_body(
     const T* __restrict__ x0, const T* __restrict__ x1, const T* __restrict__ y0,
-    const T* __restrict__ y1, T* __restrict__ out0, T* __restrict__ out1, int64_t n, int64_t os,
+    const T* __restrict__ y1, const Sink& sink, int64_t n,
     const uint32_t (&rks)[3][kKeyWords], uint64_t (&kl)[9][EPB], uint64_t (&kh)[9][EPB],
     uint64_t nmul, int m, uint64_t nr0, uint64_t nr1, uint64_t nt, uint64_t nm, uint64_t nz0,
     uint64_t nz2, const Views& vw) {
@@ -1583,14 +1617,7 @@ __device__ __forceinline__ void mul_trunc3_lat_body(
             z[0], z[1], z[2], pick<T>(kl[3][tid], kh[3][tid], j),
             pick<T>(kl[4][tid], kh[4][tid], j), pick<T>(kl[5][tid], kh[5][tid], j),
             pick<T>(kl[6][tid], kh[6][tid], j), Z0, Z2, m);
-        out0[e] = Z0;
-        out0[os + e] = Z1;
-        out0[2 * os + e] = Z2;
-        if (out1 != out0 + os) {  // else a 4-slot ring: out1's slots 0, 1 are out0's 1, 2
-          out1[e] = Z1;
-          out1[os + e] = Z2;
-        }
-        out1[2 * os + e] = Z0;
+        sink(e, Z0, Z1, Z2);
       }
     }
     __syncthreads();
@@ -1612,8 +1639,24 @@ __global__ void __launch_bounds__(256) k_mul_trunc3_lat(
   __shared__ uint32_t rks[3][kKeyWords];
   __shared__ uint64_t kl[9][EPB], kh[9][EPB];
   stage_keys(rks, keys, 3);
-  mul_trunc3_lat_body<T, EPB>(x0, x1, y0, y1, out0, out1, n, os, rks, kl, kh, nmul, m, nr0,
-                              nr1, nt, nm, nz0, nz2, vw);
+  mul_trunc3_lat_body<T, EPB>(x0, x1, y0, y1, TailShares<T>{out0, out1, os}, n, rks, kl, kh,
+                              nmul, m, nr0, nr1, nt, nm, nz0, nz2, vw);
+}
+
+// k_mul_trunc3_lat of given local products ``x`` (party stride xs), opened: see
+// k_mul_trunc3_open.
+template <class T>
+__global__ void __launch_bounds__(256) k_mul_trunc3_lat_open(
+    const T* __restrict__ x, double* __restrict__ out, double scale, int64_t n, KeySrc keys,
+    uint64_t nmul, int m, uint64_t nr0, uint64_t nr1, uint64_t nt, uint64_t nm, uint64_t nz0,
+    uint64_t nz2, Views vw) {
+  constexpr int EPB = 256 / 9;
+  __shared__ uint32_t rks[3][kKeyWords];
+  __shared__ uint64_t kl[9][EPB], kh[9][EPB];
+  stage_keys(rks, keys, 3);
+  mul_trunc3_lat_body<T, EPB>(x, (const T*)nullptr, (const T*)nullptr, (const T*)nullptr,
+                              TailOpen<T>{out, scale}, n, rks, kl, kh, nmul, m, nr0, nr1, nt,
+                              nm, nz0, nz2, vw);
 }
 
 // Two independent products of one placement (same keys) in one launch: blockIdx.y picks the
@@ -1640,23 +1683,22 @@ __global__ void __launch_bounds__(256) k_mul_trunc3_lat2(MT2<T> a, KeySrc keys) 
   __shared__ uint64_t kl[9][EPB], kh[9][EPB];
   stage_keys(rks, keys, 3);
   const int y = blockIdx.y;
-  mul_trunc3_lat_body<T, EPB>(a.x0[y], a.x1[y], a.y0[y], a.y1[y], a.out0[y], a.out1[y], a.n[y],
-                              a.os[y], rks, kl, kh, a.nmul[y], a.m[y], a.nn[y][0], a.nn[y][1],
-                              a.nn[y][2], a.nn[y][3], a.nn[y][4], a.nn[y][5], a.vw[y]);
+  mul_trunc3_lat_body<T, EPB>(a.x0[y], a.x1[y], a.y0[y], a.y1[y],
+                              TailShares<T>{a.out0[y], a.out1[y], a.os[y]}, a.n[y], rks, kl, kh,
+                              a.nmul[y], a.m[y], a.nn[y][0], a.nn[y][1], a.nn[y][2], a.nn[y][3],
+                              a.nn[y][4], a.nn[y][5], a.vw[y]);
 }
 
-// Throughput form of k_mul_trunc3_lat: one ChaCha block of each of the nine streams per
+// Throughput form of mul_trunc3_lat_body: one ChaCha block of each of the nine streams per
 // thread (walk_chunks), same shares.  y0 == nullptr: x0 already holds the three parties'
 // local products (a GEMM's) -- the zero share + reshare + TruncPr tail of a fixed-point dot
 // in one pass, the reshared product never written.
-template <class T>
-__global__ void __launch_bounds__(256) k_mul_trunc3(
+template <class T, class Sink>
+__device__ __forceinline__ void mul_trunc3_body(
     const T* __restrict__ x0, const T* __restrict__ x1, const T* __restrict__ y0,
-    const T* __restrict__ y1, T* __restrict__ out0, T* __restrict__ out1, int64_t n, int64_t os,
-    KeySrc keys, uint64_t nmul, int m, uint64_t nr0, uint64_t nr1, uint64_t nt, uint64_t nm,
-    uint64_t nz0, uint64_t nz2, Views vw) {
-  __shared__ uint32_t rks[3][kKeyWords];
-  stage_keys(rks, keys, 3);
+    const T* __restrict__ y1, const Sink& sink, int64_t n, const uint32_t (&rks)[3][kKeyWords],
+    uint64_t nmul, int m, uint64_t nr0, uint64_t nr1, uint64_t nt, uint64_t nm, uint64_t nz0,
+    uint64_t nz2, const Views& vw) {
   constexpr int P = Lane<T>::kPer;
   const int64_t nb = (n + P - 1) / P;
   // streams as k_mul_trunc3_lat: product zero share (k0, k1, k2), r0 (k0), r1 (k2), t (k0),
@@ -1686,16 +1728,36 @@ __global__ void __launch_bounds__(256) k_mul_trunc3(
       const T Z1 = mxf::trunc_pr_z1<T>(z[0], z[1], z[2], pick<T>(lo[3], hi[3], j),
                                        pick<T>(lo[4], hi[4], j), pick<T>(lo[5], hi[5], j),
                                        pick<T>(lo[6], hi[6], j), Z0, Z2, m);
-      out0[e] = Z0;
-      out0[os + e] = Z1;
-      out0[2 * os + e] = Z2;
-      if (out1 != out0 + os) {
-        out1[e] = Z1;
-        out1[os + e] = Z2;
-      }
-      out1[2 * os + e] = Z0;
+      sink(e, Z0, Z1, Z2);
     }
   });
+}
+
+template <class T>
+__global__ void __launch_bounds__(256) k_mul_trunc3(
+    const T* __restrict__ x0, const T* __restrict__ x1, const T* __restrict__ y0,
+    const T* __restrict__ y1, T* __restrict__ out0, T* __restrict__ out1, int64_t n, int64_t os,
+    KeySrc keys, uint64_t nmul, int m, uint64_t nr0, uint64_t nr1, uint64_t nt, uint64_t nm,
+    uint64_t nz0, uint64_t nz2, Views vw) {
+  __shared__ uint32_t rks[3][kKeyWords];
+  stage_keys(rks, keys, 3);
+  mul_trunc3_body<T>(x0, x1, y0, y1, TailShares<T>{out0, out1, os}, n, rks, nmul, m, nr0, nr1,
+                     nt, nm, nz0, nz2, vw);
+}
+
+// The tail of a fixed-point dot that is only revealed: k_mul_trunc3 on the given local
+// products ``x`` (party stride vw.ps[0]) with the same keys and nonces, but instead of the
+// share stores out[e] = decode(Z0 + Z1 + Z2) -- bitwise k_mul_trunc3 then k_addn_decode,
+// without 64 B of stores and 48 B of loads per (128-bit) element in between.
+template <class T>
+__global__ void __launch_bounds__(256) k_mul_trunc3_open(
+    const T* __restrict__ x, double* __restrict__ out, double scale, int64_t n, KeySrc keys,
+    uint64_t nmul, int m, uint64_t nr0, uint64_t nr1, uint64_t nt, uint64_t nm, uint64_t nz0,
+    uint64_t nz2, Views vw) {
+  __shared__ uint32_t rks[3][kKeyWords];
+  stage_keys(rks, keys, 3);
+  mul_trunc3_body<T>(x, (const T*)nullptr, (const T*)nullptr, (const T*)nullptr,
+                     TailOpen<T>{out, scale}, n, rks, nmul, m, nr0, nr1, nt, nm, nz0, nz2, vw);
 }
 
 template <class T>
@@ -2576,6 +2638,43 @@ int mxh_mul_trunc3_kv(int words, const void* x0, const void* x1, const void* y0,
                        (const T*)x0, (const T*)x1, (const T*)y0, (const T*)y1, (T*)out0,
                        (T*)out1, n, ostride, mxd::keysrc_slots(ptrs, 3), nmul, m, nn[0], nn[1],
                        nn[2], nn[3], nn[4], nn[5], vw);
+    MX_LAUNCH_CHECK();
+    return 0;
+  });
+}
+
+// mxh_mul_trunc3_kv on given local products x (party stride xstride elements), opened:
+// out[e] = decode(Z0 + Z1 + Z2, frac) as float64, the shares not written.  The same size
+// rule picks the latency or the throughput kernel.
+int mxh_mul_trunc3_open(int words, const void* x, int64_t xstride, double* out, int64_t n,
+                        const uint32_t* slots, uint64_t nmul, int m, const uint64_t* nn, int frac,
+                        void* stream) {
+  if (n == 0) return 0;
+  if (xstride < n) return -3;
+  const uint32_t* ptrs[3];
+  for (int i = 0; i < 3; ++i) ptrs[i] = slots + MX_KEY_SLOT_WORDS * i;
+  Views vw{};
+  if (xstride != n) {
+    vw.ps[0] = xstride;
+    vw.per[0] = n;
+    vw.strided = 1;
+  }
+  const double scale = ldexp(1.0, -frac);
+  DEV_DISPATCH(words, T, {
+    constexpr int P = 16 / (int)sizeof(T);
+    const int64_t blocks = (n + P - 1) / P;
+    if (blocks > 8192) {
+      hipLaunchKernelGGL(k_mul_trunc3_open<T>, dim3(mxd::grid_for_chunks(blocks)), dim3(kBlock),
+                         0, S(stream), (const T*)x, out, scale, n, mxd::keysrc_slots(ptrs, 3),
+                         nmul, m, nn[0], nn[1], nn[2], nn[3], nn[4], nn[5], vw);
+      MX_LAUNCH_CHECK();
+      return 0;
+    }
+    constexpr int EPB = 256 / 9;
+    const int64_t g = (blocks + EPB - 1) / EPB;
+    hipLaunchKernelGGL(k_mul_trunc3_lat_open<T>, dim3((unsigned)g), dim3(kBlock), 0, S(stream),
+                       (const T*)x, out, scale, n, mxd::keysrc_slots(ptrs, 3), nmul, m, nn[0],
+                       nn[1], nn[2], nn[3], nn[4], nn[5], vw);
     MX_LAUNCH_CHECK();
     return 0;
   });

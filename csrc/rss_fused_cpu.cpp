@@ -103,6 +103,45 @@ int trunc3_host(const T* s0, T* out0, T* out1, int64_t n, int m, const uint8_t* 
   return 0;
 }
 
+// The opened dot tail (moosex.h mx_mul_trunc3_open): the zero share of rss_cross_t on the
+// given products, trunc3_host's TruncPr of the result and the decode of the new shares' sum,
+// element by element.  x: three party slots xs elements apart; keys: k0, k1, k2.
+template <class T>
+int mul_trunc3_open_host(const T* x, int64_t xs, double* out, int64_t n, const uint8_t* const* k,
+                         uint64_t nmul, int m, const uint64_t* nn, int frac) {
+  const int words = sizeof(T) / 8;
+  const double scale = std::ldexp(1.0, -frac);
+  mx_cpu_parallel_for(n, 1 << 12, [&](int64_t s, int64_t e) {
+    const int64_t CH = 512;
+    std::vector<T> a[3], r0(CH), r1(CH), rt0(CH), rm0(CH), z0(CH), z2(CH);
+    for (auto& v : a) v.resize(CH);
+    for (int64_t c = s; c < e; c += CH) {
+      int64_t len = std::min(CH, e - c);
+      for (int p = 0; p < 3; ++p) mx_cpu_prf_range(k[p], nmul, words, c, len, a[p].data());
+      mx_cpu_prf_range(k[0], nn[0], words, c, len, r0.data());
+      mx_cpu_prf_range(k[2], nn[1], words, c, len, r1.data());
+      mx_cpu_prf_range(k[0], nn[2], words, c, len, rt0.data());
+      mx_cpu_prf_range(k[0], nn[3], words, c, len, rm0.data());
+      mx_cpu_prf_range(k[0], nn[4], words, c, len, z0.data());
+      mx_cpu_prf_range(k[2], nn[5], words, c, len, z2.data());
+      for (int64_t t = 0; t < len; ++t) {
+        int64_t i = c + t;
+        T z[3];
+        for (int p = 0; p < 3; ++p)
+          z[p] = mxr::zs_combine<T>(MX_CROSS_ARITH, x[p * xs + i], a[p][t], a[(p + 1) % 3][t]);
+        T z1 = mxf::trunc_pr_z1<T>(z[0], z[1], z[2], r0[t], r1[t], rt0[t], rm0[t], z0[t], z2[t],
+                                   m);
+        const T v = z0[t] + z1 + z2[t];
+        if constexpr (sizeof(T) == 8)
+          out[i] = (double)(int64_t)v * scale;
+        else
+          out[i] = mxr::i128_to_f64(v) * scale;
+      }
+    }
+  });
+  return 0;
+}
+
 template <class T>
 int share3_host(int kind, const void* xv, T* out0, T* out1, int64_t n, int j, const uint8_t* kn,
                 const uint8_t* /*ka: unused*/, uint64_t n1, uint64_t na) {
@@ -224,6 +263,23 @@ int mx_trunc_pr3_kmo(int dev, int words, const void* s0, void* out0, void* out1,
                            ostride, stream);
   }
   return -2;
+}
+
+int mx_mul_trunc3_open(int dev, int words, const void* x, int64_t xstride, double* out,
+                       int64_t n, const uint32_t* slots, uint64_t nmul, int m,
+                       const uint64_t* nonces, int frac, void* stream) {
+  if (words != 1 && words != 2) return -2;
+  if (m < 1 || m > 63) return -3;
+  if (dev) return mxh_mul_trunc3_open(words, x, xstride, out, n, slots, nmul, m, nonces, frac,
+                                      stream);
+  if (xstride < n) return -3;
+  const uint8_t* k[3];
+  for (int i = 0; i < 3; ++i) k[i] = (const uint8_t*)(slots + MX_KEY_SLOT_WORDS * i);
+  if (words == 1)
+    return mul_trunc3_open_host<uint64_t>((const uint64_t*)x, xstride, out, n, k, nmul, m,
+                                          nonces, frac);
+  return mul_trunc3_open_host<unsigned __int128>((const unsigned __int128*)x, xstride, out, n, k,
+                                                 nmul, m, nonces, frac);
 }
 
 int mx_ring_extend3_k(int dev, const void* s0, void* out0, void* out1, int64_t n,

@@ -40,6 +40,9 @@ _SIGS = {
                                    c_i64, c_int, c_int, c_int, c_vp]),
     "mx_mul_trunc3_kv": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
                                  c_vp, c_u64, c_int, c_vp, c_vp, c_vp]),
+    # (dev, words, x, xstride, out, n, slots, nmul, m, nonces[6], frac, stream)
+    "mx_mul_trunc3_open": (c_int, [c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_u64, c_int,
+                                   c_vp, c_int, c_vp]),
     "mx_ew_add3": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "mx_lincomb2": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64,
                             c_int, c_int, c_int, c_vp]),

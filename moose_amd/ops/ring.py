@@ -618,6 +618,11 @@ def share_source(x: RT, kind: str):
 
 
 def decode(a: RT, frac: int) -> torch.Tensor:
+    if isinstance(a, OpenedTail) and a.pending():  # tail + reveal + decode: one kernel
+        out = a.src.open(frac)
+        if out is not None:
+            return out
+        a = a.shares()  # the shares exist by now: the ordinary reveal of them
     if isinstance(a, Opened) and a.pending():  # the reveal's add fused into the decode
         _join(a.stream)
         d = [t.data.contiguous() for t in a.parts]
@@ -1611,6 +1616,31 @@ def zs_trunc3_k(z: RT, slot_ptr: int, nmul: int, m: int, nonces):
     return o0, o1
 
 
+def zs_trunc3_open(z: RT, slot_ptr: int, nmul: int, m: int, nonces, frac: int):
+    """decode(reveal(zs_trunc3_k(z, ...)), frac) in one kernel (mx_mul_trunc3_open): the tail
+    of a dot that is only revealed.  Same keys and nonces as zs_trunc3_k, so bitwise the
+    decode of the sum of its shares -- which are not written.  ``z``: [3, ...] local
+    products, dense or party slots of a larger stack.  Returns the float64 tensor, or None
+    when the layout does not apply."""
+    bits = z.bits
+    if bits not in (64, 128):
+        return None
+    pv = _party_view(z)
+    n = math.prod(z.shape) // 3
+    if pv is None or pv[1] != n or pv[0] < n:
+        d, xs = z.data.contiguous(), n
+    else:
+        d, xs = z.data, pv[0]
+    if n == 0:
+        return None
+    out = torch.empty(z.shape[1:], dtype=torch.float64, device=d.device)
+    nn = (ctypes.c_uint64 * 6)(*[v & MASK64 for v in nonces])
+    nat.check(nat.lib().mx_mul_trunc3_open(
+        nat.dev_of(d), _words(bits), nat.ptr(d), xs, nat.ptr(out), n, ctypes.c_void_p(slot_ptr),
+        nmul & MASK64, int(m), nn, int(frac), nat.stream_of(d)), "zs_trunc3_open")
+    return out
+
+
 def zs_trunc3_rows(z: RT, slot_ptr: int, nmul: int, m: int, nonces, buf4, r0: int):
     """zs_trunc3_k for the row block [r0, r0 + rows) of a pipelined product: ``z`` =
     [3, rows, N] local products, the shares written straight into rows of ``buf4`` (the
@@ -1736,6 +1766,50 @@ class Opened(RT):
     @property
     def device(self):
         return self.parts[0].device if self.pending() else self.data.device
+
+
+class OpenedTail(RT):
+    """The opened value of a fixed-point dot whose tail has not run (``src``: a
+    protocols/replicated.StackedTail, revealed to its party ``j``).  A decode of it runs the
+    tail and the reveal as one kernel (``src.open``: mx_mul_trunc3_open) -- the new shares
+    never go to memory.  Any other use, or a decode after something read the shares, takes
+    the ordinary tail and an :class:`Opened` of its shares: the same value bitwise."""
+
+    __slots__ = ("src", "j")
+
+    def __init__(self, src, j: int, shape):
+        _RT_DATA.__set__(self, None)
+        self.bits = src.bits
+        self._shape = tuple(shape)
+        self.src = src
+        self.j = j
+
+    def pending(self) -> bool:
+        return _RT_DATA.__get__(self) is None
+
+    def shares(self) -> RT:
+        """The ordinary reveal: an Opened of party j's two shares and P_{j+1}'s second."""
+        v0, v1 = self.src.s0.v, self.src.s1.v
+        j, j1 = self.j, (self.j + 1) % 3
+        return opened(RT(v0.data[j], v0.bits), RT(v1.data[j], v1.bits),
+                      RT(v1.data[j1], v1.bits))
+
+    @property
+    def data(self):
+        d = _RT_DATA.__get__(self)
+        if d is None:
+            d = self.shares().data
+            _RT_DATA.__set__(self, d)
+            self.src = None
+        return d
+
+    @data.setter
+    def data(self, v):
+        _RT_DATA.__set__(self, v)
+
+    @property
+    def device(self):
+        return self.src.device if self.pending() else self.data.device
 
 
 def opened(a: RT, b: RT, c: RT, d: RT = None) -> RT:

@@ -219,10 +219,62 @@ class PendingTrunc(RepTensor):
         self._s1 = v
 
 
+class StackedTail(RepTensor):
+    """A fixed-point dot of a stacked device session whose tail (zero share + reshare +
+    TruncPr by m, one kernel) has not run: the GEMM's local products ``v`` and the tail's
+    nonces, drawn and accounted when the dot was issued (session ``p_zs_trunc_issue``).
+    Reading the shares runs the ordinary tail once.  A reveal to a member that comes first
+    is an ``ops.ring.OpenedTail``: its decode runs tail, reveal and decode as one kernel
+    (:meth:`open`) and the shares are never written; if they are read later the ordinary
+    tail runs then, on the same keys and nonces -- the very shares the opened value sums."""
+
+    def __init__(self, sess, plc, bits, v, m, nonces):
+        self._sess, self.v, self.m, self._nonces = sess, v, m, nonces
+        self._stream = R._stream_of(v.v.data)
+        self.device = v.v.device
+        super().__init__(plc, bits, "arith", None, None)
+
+    @property
+    def done(self) -> bool:
+        return self._s0 is not None
+
+    def finish(self):
+        if self._s0 is None:
+            R._join(self._stream)
+            self._s0, self._s1 = self._sess.p_zs_trunc_run(self.plc, self.v, self.m,
+                                                          self._nonces)
+            self.v = None
+
+    def open(self, frac: int):
+        """decode(reveal(self), frac) without the shares; None once they exist."""
+        if self._s0 is not None:
+            return None
+        R._join(self._stream)
+        return self._sess.p_zs_trunc_open(self.plc, self.v, self.m, self._nonces, frac)
+
+    @property
+    def s0(self):
+        self.finish()
+        return self._s0
+
+    @s0.setter
+    def s0(self, v):
+        self._s0 = v
+
+    @property
+    def s1(self):
+        self.finish()
+        return self._s1
+
+    @s1.setter
+    def s1(self, v):
+        self._s1 = v
+
+
 def lazy(x) -> bool:
     """A replicated value with message rounds still pending (read-completed)."""
     return ((isinstance(x, PendingTrunc) and (not x.completed or x._rb is not None))
-            or isinstance(x, DeferredRep))
+            or isinstance(x, DeferredRep) or (isinstance(x, StackedTail) and not x.done))
 
 
 def settle(x):
@@ -233,6 +285,8 @@ def settle(x):
         x._complete()
     elif isinstance(x, DeferredRep):
         x._tail.finish()
+    elif isinstance(x, StackedTail):
+        x.finish()
 
 
 def _reveal_pending(sess, x: PendingTrunc, host):
@@ -351,6 +405,10 @@ def reveal(sess, x: RepTensor, host: str) -> HV:
     with span("rep.reveal"):
         if isinstance(x, PendingTrunc) and not x.completed:
             r = _reveal_pending(sess, x, host)
+            if r is not None:
+                return r
+        if isinstance(x, StackedTail) and not x.done:
+            r = sess.p_reveal_tail(x, host)  # to a member: tail and reveal in one kernel
             if r is not None:
                 return r
         tail = getattr(x, "_tail", None)
@@ -844,6 +902,11 @@ def dot_trunc(sess, x: RepTensor, y: RepTensor, m: int, nbatch: int = 0) -> RepT
             with span("rep.dot_trunc_fused"):
                 v = _zero_slot_cross(sess, x, y) or sess.p_dot_cross(x.plc, x.s0, x.s1, y.s0,
                                                                         y.s1)
+                issue = getattr(sess, "p_zs_trunc_issue", None)
+                if (issue is not None and x.bits in (64, 128)
+                        and os.environ.get("MOOSEX_DOT_OPEN", "1") != "0"):
+                    # the tail waits for its first reader: a reveal opens it in one kernel
+                    return StackedTail(sess, x.plc, x.bits, v, m, issue(x.plc, v))
                 s0, s1 = tail(x.plc, v, m)  # zero share + reshare + TruncPr: one kernel
                 return RepTensor(x.plc, x.bits, "arith", s0, s1)
         if use_party:  # the per-party tail: reshare folded into TruncPr (2 rounds)

@@ -736,16 +736,47 @@ class StackedSession(Session):
         nonces in the same order as the two steps, so the same shares.  None on the host."""
         if self.device.type != "cuda" or z.v.bits not in (64, 128) or not m:
             return None
+        return self.p_zs_trunc_run(plc, z, m, self.p_zs_trunc_issue(plc, z))
+
+    def p_zs_trunc_issue(self, plc, z):
+        """What p_zs_trunc does when the dot is issued, whenever its kernel runs
+        (rep.StackedTail): the tail's nonces (nmul, the six of TruncPr), drawn in order, and
+        its traffic."""
         nmul = self.nonce(plc)
         nonces = tuple(self.nonce(plc) for _ in range(6))
-        r = R.zs_trunc3_k(z.v, self.key_ptr(plc, 0), nmul, m, nonces)
-        if r is None:  # nonces are drawn: never fall back silently
-            raise RuntimeError("zs_trunc3 declined on a device session")
         from moose_amd.parallel.party import record_tail_traffic
 
         # the messages of the per-party protocol (reshare folded into TruncPr, 2 rounds)
-        record_tail_traffic(self.stats, plc, _nbytes(r[0]) // 3)
+        record_tail_traffic(self.stats, plc, _nbytes(z.v) // 3)
+        return nmul, nonces
+
+    def p_zs_trunc_run(self, plc, z, m, issued):
+        """p_zs_trunc's kernel on the nonces of p_zs_trunc_issue."""
+        nmul, nonces = issued
+        r = R.zs_trunc3_k(z.v, self.key_ptr(plc, 0), nmul, m, nonces)
+        if r is None:  # nonces are drawn: never fall back silently
+            raise RuntimeError("zs_trunc3 declined on a device session")
         return PV(plc, r[0]), PV(plc, r[1])
+
+    def p_zs_trunc_open(self, plc, z, m, issued, frac):
+        """decode(reveal(p_zs_trunc_run(...)), frac) as one kernel, the shares not written
+        (mx_mul_trunc3_open): a float64 tensor."""
+        nmul, nonces = issued
+        out = R.zs_trunc3_open(z.v, self.key_ptr(plc, 0), nmul, m, nonces, frac)
+        if out is None:
+            raise RuntimeError("zs_trunc3_open declined on a device session")
+        return out
+
+    def p_reveal_tail(self, x, host):
+        """p_reveal of a dot whose tail has not run (rep.StackedTail) to a member P_j: the
+        same message accounted, the value an R.OpenedTail; None for outsiders (generic)."""
+        if host not in x.plc.owners:
+            return None
+        j = x.plc.owners.index(host)
+        shape = x.v.v.shape[1:]
+        self.stats.record_send(x.plc.owners[(j + 1) % 3], host,
+                               math.prod(shape) * (x.bits // 8))
+        return HV(host, R.OpenedTail(x, j, shape))
 
     def p_zs_trunc_rows(self, plc, z, m, buf4, r0):
         """p_zs_trunc of a row block of a pipelined product (rep.dot_trunc with
