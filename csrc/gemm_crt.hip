@@ -43,6 +43,8 @@
 
 #include "hip_attr.h"
 #include "moosex.h"
+#include "prf_dev.h"
+#include "rss_fused.h"
 
 void mx_ws_note(int dev, int64_t want, bool ok);  // gemm_mfma.hip: workspace bookkeeping
 bool mx_ws_malloc(void** p, int64_t bytes);       // gemm_mfma.hip: allocation (capture-safe)
@@ -385,6 +387,162 @@ __global__ void __launch_bounds__(256)
         }
       }
       emit(ob + src.dual[b] + boff);
+    }
+  }
+}
+
+// A share source: an operand of run_crt_asym that is still the plain input of its sharing
+// (k_share3 has not run).  The prep forms the three slots itself (mxf::share_plain /
+// share_masked: slot jr = r, slot jv = x - r, the third 0) and writes the side's four images.
+struct ShareSrc {
+  const void* x = nullptr;  // plain operand: float64 (MX_SHARE_F64) or ring data
+  int kind = 0;             // MX_CROSS_ARITH or MX_SHARE_F64, | MX_SHARE_MIRROR
+  int frac = 0;             // MX_SHARE_F64: fractional bits
+  int j0 = 0;               // owner slot
+  uint64_t nonce = 0;
+  mxd::KeySrc key;          // one key: the stream of r
+};
+// Kernel form.  The thread holds ONE image's 16 elements and turns them into the next in
+// place: phase 0 = r, 1 = x - r, 2 = the sum of the two, 3 = zero.  Image e of the side
+// (byte offset off[e]) is emitted in phase ph[e]; a sum with the zero slot is its other slot.
+struct SrcPlan {
+  const void* x;
+  int kind, pad;
+  double scale;
+  uint64_t nonce;
+  int ph[4];
+  int64_t off[4];
+};
+
+// k_crt_prep for a share source over Z_2^128, every image of the side from one thread.
+// Element i draws keystream chunk i = part (i >> 6) & 3 of ChaCha block ((i >> 8) << 6) |
+// (i & 63) (prf_core.h), so a thread's 16 elements lie in 16 blocks, of which it needs one
+// quarter each; the other quarters belong to the elements 64, 128 and 192 further on: the
+// next three k-steps of the row (A', K % 256 == 0) or the columns +64, +128, +192 (B',
+// N % 256 == 0).  The four owners are the lanes of one quad (p = lane & 3): each generates 4
+// of the 16 blocks and the quad trades quarters through a wave-private LDS slice (no
+// workgroup barrier: a wave's LDS operations complete in order), so every block is
+// generated once.  A wave is 4 rows x 4 chunks x 4 owners: per modulus it stores four 256 B
+// runs (k_crt_prep: one of 1 KB).  Rows past R hold zeros, as k_crt_prep's.
+template <bool TRANS, int ROWS, bool PK>
+__global__ void __launch_bounds__(256)
+    k_crt_prep_src(const SrcPlan s, const mxd::KeySrc keys, int64_t R, int64_t K,
+                   int8_t* __restrict__ out, int64_t tiles, int64_t nkb, const PrepTab tab) {
+  using T = u128;
+  constexpr int NW = 4;
+  __shared__ uint32_t rks[1][mxd::kKeyWords];
+  __shared__ uint4 xch[4][4][64];  // [wave][part][lane ^ part]: conflict-free both ways
+  mxd::stage_keys(rks, keys, 1);
+  const int lane = threadIdx.x & 63;
+  const int p = lane & 3;
+  uint4(*xw)[64] = xch[threadIdx.x >> 6];
+  const int n = tab.n;
+  const int64_t plane = tiles * nkb * (int64_t)(ROWS * BK);
+  const int64_t total = tiles * ROWS * nkb * 4;  // a multiple of 64: waves stay whole
+  for (int64_t g = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; g < total;
+       g += (int64_t)gridDim.x * blockDim.x) {
+    const int c = (int)((g >> 2) & 3);
+    const int rlow = (int)((g >> 4) & 3);
+    const int64_t rest = g >> 6;
+    int64_t row, kb, i0, istep;  // element j: i0 + j * istep, + 64 p for the thread's own
+    if (!TRANS) {
+      const int64_t q = rest / (ROWS / 4);
+      kb = 4 * (q % (nkb / 4)) + p;
+      row = (q / (nkb / 4)) * ROWS + (rest % (ROWS / 4)) * 4 + rlow;
+      i0 = row * K + (kb - p) * BK + c * 16;
+      istep = 1;
+    } else {
+      const int64_t q = rest >> 4;
+      kb = q % nkb;
+      row = (q / nkb) * 256 + 64 * p + (rest & 15) * 4 + rlow;
+      i0 = (kb * BK + c * 16) * R + (row - 64 * p);
+      istep = R;
+    }
+    const bool live = row < R;
+    const int64_t t = row / ROWS;
+    const int r = (int)(row % ROWS);
+    uint32_t v[16][NW];
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {  // blocks of elements 4 jj + (0..3), one per lane of the quad
+      uint32_t w[16];
+      mx::chacha_block(rks[0], s.nonce, mx::ks_block_of((uint64_t)(i0 + (4 * jj + p) * istep)), w);
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        xw[q][lane ^ q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const uint4 e = xw[p][((lane & ~3) | u) ^ p];
+        v[4 * jj + u][0] = live ? e.x : 0u;
+        v[4 * jj + u][1] = live ? e.y : 0u;
+        v[4 * jj + u][2] = live ? e.z : 0u;
+        v[4 * jj + u][3] = live ? e.w : 0u;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    const int64_t boff = (t * nkb + kb) * (int64_t)(ROWS * BK) + img_off(r, c);
+    auto emit = [&](int8_t* base) __attribute__((always_inline)) {
+      {  // p = 256: the low byte (times the folded inverse)
+        int rr[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) rr[j] = (int)(v[j][0] * tab.mul0);
+        v4i o;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) o[u] = (int)pack4(rr[4 * u], rr[4 * u + 1], rr[4 * u + 2], rr[4 * u + 3]);
+        *(v4i*)base = o;
+      }
+      for (int i = 1; i < n; ++i) {
+        const uint32_t w[4] = {tab.w[i][0], tab.w[i][1], tab.w[i][2], tab.w[i][3]};
+        const uint32_t neg = tab.neg[i];
+        const float pf = (float)tab.p[i], rcp = tab.rcp[i];
+        int rr[16];
+        if constexpr (PK) {
+#pragma unroll
+          for (int j = 0; j < 16; j += 2)
+            residue2<NW>(v[j], v[j + 1], w, neg, pf, rcp, rr[j], rr[j + 1]);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 16; ++j) rr[j] = residue<NW>(v[j], w, neg, pf, rcp);
+        }
+        v4i o;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) o[u] = (int)pack4(rr[4 * u], rr[4 * u + 1], rr[4 * u + 2], rr[4 * u + 3]);
+        *(v4i*)(base + i * plane) = o;
+      }
+    };
+    // the held slot h becomes the other one, x - h (r and x - r are each other's mask), or
+    // the two slots' sum h + (x - h)
+    auto step = [&](bool sum) __attribute__((always_inline)) {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        T h = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) h |= (T)v[j][w] << (32 * w);
+        const T x = live ? mxf::share_plain<T>(s.kind, s.x, i0 + 64 * p + j * istep, s.scale) : (T)0;
+        const T other = mxf::share_masked<T>(s.kind, x, h);
+        h = sum ? (T)(h + other) : other;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) v[j][w] = (uint32_t)(h >> (32 * w));
+      }
+    };
+#pragma nounroll
+    for (int ph = 0; ph < 4; ++ph) {
+      if (s.ph[0] != ph && s.ph[1] != ph && s.ph[2] != ph && s.ph[3] != ph) continue;
+      if (ph == 1) step(false);
+      if (ph == 2) step(true);
+      if (ph == 3) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+#pragma unroll
+          for (int w = 0; w < NW; ++w) v[j][w] = 0;
+      }
+#pragma nounroll
+      for (int e = 0; e < 4; ++e)
+        if (s.ph[e] == ph) emit(out + s.off[e] + boff);
     }
   }
 }
@@ -1187,6 +1345,47 @@ void launch_prep(const CPlan& p, const Tables& tb, bool is_b, int64_t batch, int
                        out, tiles, nkb, nkb_s, tb.pb, src);
 }
 
+bool share_src_ok(const ShareSrc& s) {
+  const int kind = s.kind & ~MX_SHARE_MIRROR;
+  return s.x && (kind == MX_CROSS_ARITH || kind == MX_SHARE_F64) && s.j0 >= 0 && s.j0 < 3;
+}
+
+// The four K-residue images of one side of run_crt_asym's rolled product from a share source
+// (A: [x0 + x1, x2, x1, x0], B: [y0 + y1, y1 + y2, y2, y0]; entry e at out + e * entry).
+void launch_prep_src(const CPlan& p, const Tables& tb, bool is_b, const ShareSrc& src, int64_t R,
+                     int64_t K, int8_t* out, int64_t entry, hipStream_t st) {
+  static const int kSlotsA[4][2] = {{0, 1}, {2, -1}, {1, -1}, {0, -1}};
+  static const int kSlotsB[4][2] = {{0, 1}, {1, 2}, {2, -1}, {0, -1}};
+  const int kind = src.kind & ~MX_SHARE_MIRROR;
+  int jr, jv;
+  mxf::share_place(src.j0, (src.kind & MX_SHARE_MIRROR) != 0, &jr, &jv);
+  SrcPlan s;
+  s.x = src.x;
+  s.kind = kind;
+  s.pad = 0;
+  s.scale = kind == MX_SHARE_F64 ? std::ldexp(1.0, src.frac) : 0.0;
+  s.nonce = src.nonce;
+  for (int e = 0; e < 4; ++e) {
+    const int* sl = is_b ? kSlotsB[e] : kSlotsA[e];
+    const bool has_r = sl[0] == jr || sl[1] == jr, has_v = sl[0] == jv || sl[1] == jv;
+    s.ph[e] = has_r && has_v ? 2 : has_r ? 0 : has_v ? 1 : 3;
+    s.off[e] = e * entry;
+  }
+  const int64_t tiles = is_b ? p.tiles_n : p.tiles_m;
+  const int rows = is_b ? p.bn : BM;
+  const int64_t work = tiles * rows * p.a_nkb * 4;
+  const dim3 grid((unsigned)std::min<int64_t>(work / 256, 16384));
+  if (!is_b)
+    hipLaunchKernelGGL((k_crt_prep_src<false, BM, true>), grid, dim3(256), 0, st, s, src.key, R, K,
+                       out, tiles, p.a_nkb, tb.pa);
+  else if (rows == 256)
+    hipLaunchKernelGGL((k_crt_prep_src<true, 256, false>), grid, dim3(256), 0, st, s, src.key, R,
+                       K, out, tiles, p.a_nkb, tb.pb);
+  else
+    hipLaunchKernelGGL((k_crt_prep_src<true, 128, false>), grid, dim3(256), 0, st, s, src.key, R,
+                       K, out, tiles, p.a_nkb, tb.pb);
+}
+
 // MOOSEX_CRT_DMA_MASK (timing experiments, wrong results): bit 0 = stream A, bit 1 = B,
 // bit 2 = skip the epilogue reduction, bit 3 = no LDS fragment reads in the main loop
 int dma_mask() {
@@ -1360,9 +1559,16 @@ int run_crt(int64_t batch, int64_t M, int64_t N, int64_t K, const T* A0, const T
 // [3][K][N] share stacks; rolled: S1[p] = S0[p + 1] and T1[p] = T0[p + 1] (a stacked
 // session's pair; S1/T1 may be null) -- party 1's b and party 2's a are then the same
 // share x_2, whose residues are prepared once (four K-long A' images instead of five).
+//
+// xs / ys: the operand is a share source instead (ShareSrc; S0 / T0 unused) -- its prep
+// shares the plain input in registers (k_crt_prep_src) and the shares are never written.
+// Z_2^128, rolled with the dual images, K % 256 == 0 (xs) / N % 256 == 0 (ys) only: -7
+// otherwise, nothing launched.  The residue images are byte for byte those of k_share3
+// followed by k_crt_prep; the GEMM and the reconstruction do not know the difference.
 template <class T>
 int run_crt_asym(int64_t M, int64_t N, int64_t K, const T* S0, const T* S1, const T* T0,
-                 const T* T1, int rolled, T* C, hipStream_t st) {
+                 const T* T1, int rolled, T* C, hipStream_t st, const ShareSrc* xs = nullptr,
+                 const ShareSrc* ys = nullptr) {
   constexpr int words = sizeof(T) / 8;
   if (K % BK || !crt_mfma16()) return -7;
   if (2 * K > (1 << 15)) return -6;  // exact epilogue rounding bound
@@ -1414,6 +1620,11 @@ int run_crt_asym(int64_t M, int64_t N, int64_t K, const T* S0, const T* S1, cons
   }();
   // rolled: the sums ride on the share images' threads (dual) -- no separate sum pass
   const bool duals = rolled && dual;
+  if (xs || ys) {
+    if (words != 2 || !duals) return -7;
+    if (xs && (K % 256 || !share_src_ok(*xs))) return -7;
+    if (ys && (N % 256 || !share_src_ok(*ys))) return -7;
+  }
   const int64_t sum_bytes = asum && !duals ? round_up(sa * (int64_t)sizeof(T), 256) : 0;
   int8_t* ws = (int8_t*)workspace(ra_bytes + rb_bytes + p.cr_bytes + sum_bytes, st);
   if (!ws) return -4;
@@ -1444,10 +1655,16 @@ int run_crt_asym(int64_t M, int64_t N, int64_t K, const T* S0, const T* S1, cons
     put(sa_, a[0], b[0], 0, -3 * a_entry);    // E3 = x0, dual E0 = x0 + x1
     put(sb_, d[1], c[1], 0, -b_entry);        // F2 = y2, dual F1 = y2 + y1
     put(sb_, d[2], d[0], 0, -3 * b_entry);    // F3 = y0, dual F0 = y0 + y1
-    launch_prep<T>(p, tb, true, sb_.n, N, K, 0, nullptr, nullptr, 0, rb + 2 * b_entry, st, kn,
-                   kn, sb_);
-    launch_prep<T>(p, tb, false, sa_.n, M, K, 0, nullptr, nullptr, 0, ra + a_entry, st, kn, kn,
-                   sa_);
+    if (ys)
+      launch_prep_src(p, tb, true, *ys, N, K, rb, b_entry, st);
+    else
+      launch_prep<T>(p, tb, true, sb_.n, N, K, 0, nullptr, nullptr, 0, rb + 2 * b_entry, st, kn,
+                     kn, sb_);
+    if (xs)
+      launch_prep_src(p, tb, false, *xs, M, K, ra, a_entry, st);
+    else
+      launch_prep<T>(p, tb, false, sa_.n, M, K, 0, nullptr, nullptr, 0, ra + a_entry, st, kn, kn,
+                     sa_);
   } else {
     if (a01)
       put(sa_, a01, a01, 0);
@@ -1489,6 +1706,35 @@ int mx_gemm_asym(int words, int64_t M, int64_t N, int64_t K, const void* S0, con
     return run_crt_asym<u128>(M, N, K, (const u128*)S0, (const u128*)S1, (const u128*)T0,
                               (const u128*)T1, rolled, (u128*)C, st);
   return -2;
+}
+
+// mx_gemm_asym, rolled, over Z_2^128 with one or both operands given as a share source
+// instead of a share stack (run_crt_asym's xs / ys): xsrc / ysrc null (then S0 / T0 is the
+// [3][..] stack) or six words {plain operand, kind (| MX_SHARE_MIRROR), fractional bits,
+// owner slot j0, key slot (device memory, as mx_share3_k's slot_next), nonce} -- the
+// arguments of the mx_share3_k launch that would have written the stack.  -7: not
+// applicable, nothing launched (the caller writes the shares and runs mx_gemm_asym).
+int mx_gemm_asym_src(int words, int64_t M, int64_t N, int64_t K, const void* S0, const void* T0,
+                     const int64_t* xsrc, const int64_t* ysrc, void* C, void* stream) {
+  if (M == 0 || N == 0) return 0;
+  if (words != 2) return -7;
+  if ((!xsrc && !S0) || (!ysrc && !T0)) return -2;
+  ShareSrc sx, sy;
+  auto fill = [](ShareSrc& s, const int64_t* a) {
+    s.x = (const void*)(intptr_t)a[0];
+    s.kind = (int)a[1];
+    s.frac = (int)a[2];
+    s.j0 = (int)a[3];
+    const uint32_t* slot[1] = {(const uint32_t*)(intptr_t)a[4]};
+    s.key = mxd::keysrc_slots(slot, 1);
+    s.nonce = (uint64_t)a[5];
+  };
+  if (xsrc) fill(sx, xsrc);
+  if (ysrc) fill(sy, ysrc);
+  if ((xsrc && !sx.key.slot[0]) || (ysrc && !sy.key.slot[0])) return -2;
+  return run_crt_asym<u128>(M, N, K, (const u128*)S0, nullptr, (const u128*)T0, nullptr, 1,
+                            (u128*)C, (hipStream_t)stream, xsrc ? &sx : nullptr,
+                            ysrc ? &sy : nullptr);
 }
 
 // Moduli count for a K' (= K, or 2K in mode 1) inner dimension; -1 if out of range.

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "aes_core.h"
+#include "moosex.h"
 #include "ring_common.h"
 
 namespace mxf {
@@ -44,6 +45,34 @@ MX_HD inline T trunc_pr_z1(T x0, T x1, T x2, T r0, T r1, T rt0, T rm0, T z0, T z
   T ov1 = rm1 - shl<T>(c_msb * rm1, 1);
   T y1 = shl<T>(ov1, k - m) - rt1;
   return (y0 - z0) + (y1 - z2);
+}
+
+// ---------------------------------------------------------------------------------------
+// Input sharing by the member P_j0 (k_share3, its host twin, and the sharing CRT operand prep
+// of gemm_crt.hip): slot j0 = r (one PRF draw), slot j0 + 1 = x - r, slot j0 + 2 = 0;
+// mirrored (MX_SHARE_MIRROR) the first two are swapped.  ``kind`` is without the mirror flag.
+// ---------------------------------------------------------------------------------------
+// the plain element i: ring data, or a float64 encoded as RingFixedpointEncode (scale = 2^frac)
+template <class T>
+MX_HD inline T share_plain(int kind, const void* xv, int64_t i, double scale) {
+  return kind == MX_SHARE_F64 ? mxr::f64_to_ring<T>(((const double*)xv)[i] * scale)
+                              : ((const T*)xv)[i];
+}
+template <class T>
+MX_HD inline T share_masked(int kind, T x, T r) {
+  return kind == MX_CROSS_BOOL ? (T)(x ^ r) : (T)(x - r);
+}
+// the slots that hold r and the masked value (the third one is zero)
+MX_HD inline void share_place(int j0, bool mir, int* jr, int* jv) {
+  *jr = mir ? (j0 + 1) % 3 : j0;
+  *jv = mir ? j0 : (j0 + 1) % 3;
+}
+template <class T>
+MX_HD inline void share_slots(int kind, T x, T r, int j0, bool mir, T (&slot)[3]) {
+  const T v = share_masked<T>(kind, x, r);
+  slot[j0] = mir ? v : r;
+  slot[(j0 + 1) % 3] = mir ? r : v;
+  slot[(j0 + 2) % 3] = 0;
 }
 
 // ---------------------------------------------------------------------------------------

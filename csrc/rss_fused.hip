@@ -272,8 +272,7 @@ __global__ void __launch_bounds__(256) k_share3(int kind, const void* __restrict
                          uint64_t na) {
   const bool mir = kind & MX_SHARE_MIRROR;
   kind &= ~MX_SHARE_MIRROR;
-  const T* x = (const T*)xv;
-  const double* xf = (const double*)xv;  // kind MX_SHARE_F64: encode in the kernel
+  // kind MX_SHARE_F64: encode in the kernel (mxf::share_plain)
   const double scale = kind == MX_SHARE_F64 ? ldexp(1.0, (int)na) : 0.0;
   __shared__ uint32_t rks[1][mxd::kKeyWords];
   mxd::stage_keys(rks, keys, 1);
@@ -287,12 +286,8 @@ __global__ void __launch_bounds__(256) k_share3(int kind, const void* __restrict
       const int64_t i = b * P + j;
       if (i >= n) break;
       const T r = mxd::pick<T>(lo[0], hi[0], j);
-      const T xi = kind == MX_SHARE_F64 ? mxr::f64_to_ring<T>(xf[i] * scale) : x[i];
-      const T v = kind == MX_CROSS_BOOL ? (T)(xi ^ r) : (T)(xi - r);
       T slot[3];
-      slot[j0] = mir ? v : r;
-      slot[(j0 + 1) % 3] = mir ? r : v;
-      slot[(j0 + 2) % 3] = 0;
+      mxf::share_slots<T>(kind, mxf::share_plain<T>(kind, xv, i, scale), r, j0, mir, slot);
       const bool ring4 = out1 == out0 + n;  // 4-slot ring: out1's slots 0, 1 are out0's 1, 2
 #pragma unroll
       for (int p = 0; p < 3; ++p) {

@@ -148,8 +148,7 @@ int share3_host(int kind, const void* xv, T* out0, T* out1, int64_t n, int j, co
   const bool mir = kind & MX_SHARE_MIRROR;
   kind &= ~MX_SHARE_MIRROR;
   const int words = sizeof(T) == 1 ? 0 : (int)(sizeof(T) / 8);
-  const T* x = (const T*)xv;
-  const double* xf = (const double*)xv;  // kind MX_SHARE_F64 (moosex.h)
+  // kind MX_SHARE_F64 (moosex.h): encoded by mxf::share_plain
   const double scale = kind == MX_SHARE_F64 ? std::ldexp(1.0, (int)na) : 0.0;
   mx_cpu_parallel_for(n, 1 << 12, [&](int64_t s, int64_t e) {
     const int64_t CH = 512;
@@ -159,12 +158,8 @@ int share3_host(int kind, const void* xv, T* out0, T* out1, int64_t n, int j, co
       mx_cpu_prf_range(kn, n1, words, c, len, r1.data());
       for (int64_t t = 0; t < len; ++t) {
         int64_t i = c + t;
-        const T xi = kind == MX_SHARE_F64 ? mxr::f64_to_ring<T>(xf[i] * scale) : x[i];
-        const T v = kind == MX_CROSS_BOOL ? (T)(xi ^ r1[t]) : (T)(xi - r1[t]);
         T slot[3];
-        slot[j] = mir ? v : r1[t];
-        slot[(j + 1) % 3] = mir ? r1[t] : v;
-        slot[(j + 2) % 3] = 0;
+        mxf::share_slots<T>(kind, mxf::share_plain<T>(kind, xv, i, scale), r1[t], j, mir, slot);
         for (int p = 0; p < 3; ++p) {
           out0[p * n + i] = slot[p];
           out1[p * n + i] = slot[(p + 1) % 3];

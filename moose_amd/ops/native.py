@@ -271,6 +271,10 @@ _SIGS = {
     "mx_gemm_asym": (
         c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp],
     ),
+    # (words, M, N, K, S0, T0, xsrc[6], ysrc[6], C, stream): operands as share sources
+    "mx_gemm_asym_src": (
+        c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    ),
     "mx_gemm_roll": (
         c_int,
         [c_int, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int,

@@ -1142,6 +1142,43 @@ def dot_cross_asym(x0: RT, x1: RT, y0: RT, y1: RT, rolled: bool = False) -> RT:
     return dot_cross(A0, A1, B0, B1, nb=1)
 
 
+def dot_cross_asym_src(x0, y0, xsrc, ysrc, M: int, K: int, N: int):
+    """dot_cross_asym over Z_2^128 (rolled) with one or both operands still the plain input
+    of their sharing: ``xsrc`` / ``ysrc`` is None (then ``x0`` / ``y0`` is the [3, ..] share
+    stack) or the arguments of the mx_share3_k launch that would write the stack -- (kind
+    code | SHARE_MIRROR, plain device tensor, fractional bits, owner slot, key slot, nonce).
+    The operand prep shares such an input in registers (mx_gemm_asym_src); the product is
+    bitwise that of the written shares.  None when the native form does not apply (nothing
+    has run: the caller writes the shares and takes dot_cross_asym)."""
+    ts = [None if t is None else t.data for t in (x0, y0)]
+    if any(t is not None and not t.is_contiguous() for t in ts):
+        return None
+    words = []
+    for s in (xsrc, ysrc):
+        if s is None:
+            words.append(None)
+            continue
+        code, d, frac, j0, slot, nonce = s
+        if not d.is_cuda or not d.is_contiguous():
+            return None
+        words.append((ctypes.c_int64 * 6)(d.data_ptr(), code, int(frac or 0), j0, int(slot),
+                                          _i64(nonce)))
+    anyt = next(s[1] for s in (xsrc, ysrc) if s is not None)
+    out = empty((3, M, N), 128, anyt.device)
+    rc = nat.lib().mx_gemm_asym_src(2, M, N, K, nat.ptr(ts[0]), nat.ptr(ts[1]), words[0],
+                                    words[1], nat.ptr(out.data), nat.stream_of(anyt))
+    if rc == -7:
+        return None
+    nat.check(rc, "gemm_asym_src")
+    return out
+
+
+def _i64(v: int) -> int:
+    """A 64-bit pattern as the signed value ctypes' c_int64 takes."""
+    v &= (1 << 64) - 1
+    return v - (1 << 64) if v >> 63 else v
+
+
 def _party_batch_strides(t: RT):
     """(party stride, batch stride) in ring elements of a [P, B, *inner] device tensor whose
     inner dims are contiguous (e.g. an expanded, stride-0 stack of one operand); None if

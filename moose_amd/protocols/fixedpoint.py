@@ -264,6 +264,8 @@ def shape_of(sess, x):
         return tuple(t.v.shape)
     if isinstance(t, rep.PendingTrunc) and not t.completed:  # without completing it
         return sess.p_shape(PV(t.plc, t.v_add))
+    if isinstance(t, rep.LazyShare) and not t.done:  # without writing the shares
+        return t.shape
     return sess.p_shape(t.s0)
 
 

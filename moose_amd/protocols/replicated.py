@@ -271,10 +271,62 @@ class StackedTail(RepTensor):
         self._s1 = v
 
 
+class LazyShare(RepTensor):
+    """A member's input sharing on a stacked device session whose kernel has not run: the
+    plain input, key, nonce and share direction, drawn and accounted when the sharing was
+    issued (session ``fused_share_issue``).  A fused stacked dot that reads it first shares
+    it inside its CRT operand prep (session ``p_dot_cross_src``) and the shares are never
+    written; any other reader, before or after, writes them with the ordinary share kernel
+    on the same key and nonce -- the very shares the product used."""
+
+    def __init__(self, sess, plc, bits, kind, issued, zero_slot):
+        self._sess, self._issued = sess, issued
+        self._stream = R._stream_of(issued[1])
+        super().__init__(plc, bits, kind, None, None, zero_slot=zero_slot)
+
+    @property
+    def done(self) -> bool:
+        return self._s0 is not None
+
+    @property
+    def shape(self):
+        """The shared value's shape (while the shares do not exist)."""
+        return tuple(self._issued[6])
+
+    def source(self):
+        """The sharing's launch arguments while the shares do not exist, else None."""
+        return None if self.done else self._issued
+
+    def finish(self):
+        if self._s0 is None:
+            R._join(self._stream)
+            self._s0, self._s1 = self._sess.fused_share_run(self.plc, self._issued)
+            self._issued = None
+
+    @property
+    def s0(self):
+        self.finish()
+        return self._s0
+
+    @s0.setter
+    def s0(self, v):
+        self._s0 = v
+
+    @property
+    def s1(self):
+        self.finish()
+        return self._s1
+
+    @s1.setter
+    def s1(self, v):
+        self._s1 = v
+
+
 def lazy(x) -> bool:
     """A replicated value with message rounds still pending (read-completed)."""
     return ((isinstance(x, PendingTrunc) and (not x.completed or x._rb is not None))
-            or isinstance(x, DeferredRep) or (isinstance(x, StackedTail) and not x.done))
+            or isinstance(x, DeferredRep)
+            or (isinstance(x, (StackedTail, LazyShare)) and not x.done))
 
 
 def settle(x):
@@ -285,7 +337,7 @@ def settle(x):
         x._complete()
     elif isinstance(x, DeferredRep):
         x._tail.finish()
-    elif isinstance(x, StackedTail):
+    elif isinstance(x, (StackedTail, LazyShare)):
         x.finish()
 
 
@@ -352,6 +404,10 @@ def share(sess, plc, x: HV, kind="arith") -> RepTensor:
         j1, j2 = (j + 1) % 3, (j + 2) % 3
         n1, na = sess.nonce(plc), sess.nonce(plc)
         if getattr(sess, "fused", False):
+            prep = getattr(sess, "share_prep", None)
+            if prep is not None and prep(x, kind):  # the share waits for its first reader
+                return LazyShare(sess, plc, bits, kind,
+                                 sess.fused_share_issue(plc, x, j, kind, n1, na), j2)
             s0, s1 = sess.fused_share(plc, x, j, kind, n1, na)
             return RepTensor(plc, bits, kind, s0, s1, zero_slot=j2)
         party = getattr(sess, "party_share", None)
@@ -834,6 +890,15 @@ def _zero_slot_cross(sess, x: RepTensor, y: RepTensor):
     return PV(x.plc, R.dot(R.RT(A, bits), R.RT(B, bits), nb=1))
 
 
+def _dot_cross_src(sess, x: RepTensor, y: RepTensor):
+    """The local products of the fused stacked dot when it is the first reader of a fresh
+    input sharing (LazyShare); None otherwise, with the sharings untouched."""
+    if not any(isinstance(t, LazyShare) and not t.done for t in (x, y)):
+        return None
+    fn = getattr(sess, "p_dot_cross_src", None)
+    return fn(x.plc, x, y) if fn is not None else None
+
+
 def dot(sess, x: RepTensor, y: RepTensor, nbatch: int = 0) -> RepTensor:
     """Matrix product: z_p = x_p.(y_p + y_{p+1}) + x_{p+1}.y_p as ONE K-doubled MFMA
     GEMM (all parties batched when stacked), + zero share, + reshare.  ``nbatch``
@@ -900,8 +965,8 @@ def dot_trunc(sess, x: RepTensor, y: RepTensor, m: int, nbatch: int = 0) -> RepT
                 and getattr(sess, "device", None) is not None and sess.device.type == "cuda"
                 and os.environ.get("MOOSEX_DOT_TAIL", "1") != "0"):
             with span("rep.dot_trunc_fused"):
-                v = _zero_slot_cross(sess, x, y) or sess.p_dot_cross(x.plc, x.s0, x.s1, y.s0,
-                                                                        y.s1)
+                v = (_zero_slot_cross(sess, x, y) or _dot_cross_src(sess, x, y)
+                     or sess.p_dot_cross(x.plc, x.s0, x.s1, y.s0, y.s1))
                 issue = getattr(sess, "p_zs_trunc_issue", None)
                 if (issue is not None and x.bits in (64, 128)
                         and os.environ.get("MOOSEX_DOT_OPEN", "1") != "0"):

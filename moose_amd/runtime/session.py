@@ -1055,25 +1055,68 @@ class StackedSession(Session):
         st.record_round(2 * nbytes, count=2)
 
     def fused_share(self, plc, x: HV, j, kind, n1, na):
+        return self.fused_share_run(plc, self.fused_share_issue(plc, x, j, kind, n1, na))
+
+    # a fresh input sharing waits for its first reader (rep.LazyShare): the fused dot shares
+    # it inside its operand prep and the shares are never written (MOOSEX_SHARE_PREP=0: off)
+    def share_prep(self, x: HV, kind) -> bool:
+        return (self.device.type == "cuda" and kind == "arith" and x.v.bits == 128
+                and len(x.v.shape) == 2 and self.pair_rolled and self.dot_asym
+                and not _lanes.ACTIVE
+                and os.environ.get("MOOSEX_SHARE_PREP", "1") != "0")
+
+    def fused_share_issue(self, plc, x: HV, j, kind, n1, na):
+        """What fused_share does when the sharing is issued, whenever its kernel runs: the
+        source (a pending encoding is shared unencoded), the share direction and key, and
+        the message accounted.  The arguments of fused_share_run."""
+        code, xd, aux = R.share_source(x.v, kind)  # a pending encoding: encoded in-kernel
+        d = self.share_dir(plc, j)
+        self.stats.record_send(x.host, plc.owners[(j + d) % 3], _nbytes(x.v))
+        return (code | (R.SHARE_MIRROR if d == 2 else 0), xd, na if aux is None else aux, j,
+                self.key_ptr(plc, (j + d - 1) % 3), n1, tuple(x.v.shape), x.v.bits)
+
+    def fused_share_run(self, plc, issued):
+        """fused_share's kernel on the arguments of fused_share_issue."""
         import ctypes
 
         from moose_amd.ops import native as nat
 
-        code, xd, aux = R.share_source(x.v, kind)  # a pending encoding: encoded in-kernel
-        d = self.share_dir(plc, j)
-        out0, out1 = (t.data for t in R.ring4((3,) + tuple(x.v.shape), x.v.bits, xd.device))
+        code, xd, na, j, slot, n1, shape, bits = issued
+        out0, out1 = (t.data for t in R.ring4((3,) + shape, bits, xd.device))
         nat.check(
             nat.lib().mx_share3_k(
-                nat.dev_of(xd), code | (R.SHARE_MIRROR if d == 2 else 0), R._words(x.v.bits),
-                nat.ptr(xd), nat.ptr(out0), nat.ptr(out1), x.v.numel(), j,
-                ctypes.c_void_p(self.key_ptr(plc, (j + d - 1) % 3)),
-                ctypes.c_void_p(self.key_ptr(plc, 3)), n1, na if aux is None else aux,
-                nat.stream_of(xd),
+                nat.dev_of(xd), code, R._words(bits), nat.ptr(xd), nat.ptr(out0), nat.ptr(out1),
+                math.prod(shape), j, ctypes.c_void_p(slot),
+                ctypes.c_void_p(self.key_ptr(plc, 3)), n1, na, nat.stream_of(xd),
             ),
             "share3",
         )
-        self.stats.record_send(x.host, plc.owners[(j + d) % 3], _nbytes(x.v))
-        return PV(plc, R.RT(out0, x.v.bits)), PV(plc, R.RT(out1, x.v.bits))
+        return PV(plc, R.RT(out0, bits)), PV(plc, R.RT(out1, bits))
+
+    def p_dot_cross_src(self, plc, x, y):
+        """p_dot_cross of the fused stacked dot when an operand is a fresh input sharing
+        whose kernel has not run (rep.LazyShare): the product's operand prep shares it.
+        None when that form does not apply -- nothing has run, and p_dot_cross's read of
+        the shares writes them."""
+        srcs = [t.source() if hasattr(t, "source") else None for t in (x, y)]
+        if (srcs[0] is None and srcs[1] is None) or x.bits != 128 or _lanes.ACTIVE:
+            return None
+        shp = [tuple(s[6]) if s is not None else tuple(t.s0.v.shape[1:])
+               for s, t in zip(srcs, (x, y))]
+        if len(shp[0]) != 2 or len(shp[1]) != 2 or shp[0][1] != shp[1][0]:
+            return None
+        (M, K), (_, N) = shp
+        if min(M, K, N) < 256:  # _asym_applies: smaller products keep the symmetric split
+            return None
+        stacks = [None if s is not None else t.s0.v for s, t in zip(srcs, (x, y))]
+        if not all(s is None or isinstance(s, R.RT) for s in stacks):
+            return None
+        for s, t in zip(srcs, (x, y)):
+            if s is not None:
+                R._join(t._stream)
+        out = R.dot_cross_asym_src(stacks[0], stacks[1],
+                                   *[None if s is None else s[:6] for s in srcs], M, K, N)
+        return None if out is None else PV(plc, out)
 
     def mirror(self, x: HV, plc):
         """Host value -> mirrored (public on the 3 hosts of ``plc``)."""
