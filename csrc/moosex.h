@@ -74,6 +74,20 @@ int mx_im2col(int dev, int elem_bytes, const void* in, void* out, int64_t slots,
               int64_t in_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH,
               int64_t KW, int64_t sh, int64_t sw, int64_t pt, int64_t pl, int64_t dh,
               int64_t dw, int64_t OH, int64_t OW, int nhwc, void* stream);
+// Depthwise 2-D convolution in Z_2^64 / Z_2^128 (elem_bytes 8 / 16), wrapping:
+//   out[s][n, oh, ow, c*mult + j] = sum_{kh,kw} X[s][n, oh*sh + kh*dh - pt, ow*sw + kw*dw - pl, c]
+//                                               * Wt[s][c*mult + j, kh, kw]
+// over x[slots, N, C, H, W] (nhwc: [slots, N, H, W, C]) and the dense ONNX depthwise weight
+// w[slots, C*mult, 1, KH, KW]; the output has the input's layout with C*mult channels, dense
+// slots.  Taps in the padding contribute zero and are not loaded.  x1 == w1 == null: plain,
+// X.Wt = x0.w0.  Otherwise the replicated local product x0.(w0 + w1) + x1.w0 in one pass
+// (x1 / w1: the next party's components).  Slots of x0 / x1 are x_slot_stride elements apart,
+// of w0 / w1 w_slot_stride; either may be 0 (a public operand read in place by every slot).
+int mx_dwconv(int dev, int elem_bytes, const void* x0, const void* x1, const void* w0,
+              const void* w1, void* out, int64_t slots, int64_t x_slot_stride,
+              int64_t w_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t mult,
+              int64_t KH, int64_t KW, int64_t sh, int64_t sw, int64_t pt, int64_t pl,
+              int64_t dh, int64_t dw, int64_t OH, int64_t OW, int nhwc, void* stream);
 // mx_ew_binary_slot on a0 (slot which0) and a1 (slot which1) with one public b
 int mx_ew_binary_slot2(int dev, int op, int words, const void* a0, const void* a1,
                        const void* b, int64_t nb, void* out0, void* out1, int64_t m,

@@ -349,6 +349,56 @@ void im2col_cpu(const T* in, T* out, int64_t slots, int64_t in_slot_stride, int6
   });
 }
 
+// depthwise convolution (moosex.h mx_dwconv): the arithmetic of k_dwconv in plain loops; the
+// cross mode's w0 + w1 is formed once per weight element
+template <class T>
+void dwconv_cpu(const T* x0, const T* x1, const T* w0, const T* w1, T* out, int64_t slots,
+                int64_t x_slot_stride, int64_t w_slot_stride, int64_t N, int64_t C, int64_t H,
+                int64_t W, int64_t mult, int64_t KH, int64_t KW, int64_t sh, int64_t sw,
+                int64_t pt, int64_t pl, int64_t dh, int64_t dw, int64_t OH, int64_t OW,
+                int nhwc) {
+  const int64_t OC = C * mult, taps = KH * KW, rows = N * OH * OW;
+  const int64_t sN = C * H * W, sH = nhwc ? W * C : W, sW = nhwc ? C : 1, sC = nhwc ? 1 : H * W;
+  const bool cross = x1 != nullptr;
+  std::vector<T> wsum;
+  if (cross) {
+    const int64_t wslots = w_slot_stride ? slots : 1;
+    wsum.resize((size_t)(wslots * OC * taps));
+    for (int64_t s = 0; s < wslots; ++s)
+      for (int64_t i = 0; i < OC * taps; ++i)
+        wsum[s * OC * taps + i] = w0[s * w_slot_stride + i] + w1[s * w_slot_stride + i];
+  }
+  const T* ws = wsum.data();
+  parallel_for(slots * rows, std::max<int64_t>(1, 4096 / (OC * taps)), [=](int64_t b, int64_t e) {
+    for (int64_t g = b; g < e; ++g) {
+      const int64_t s = g / rows, row = g - s * rows;
+      const int64_t ow = row % OW, oh = (row / OW) % OH, n = row / (OW * OH);
+      const int64_t xb = s * x_slot_stride + n * sN;
+      const T* wa = w0 + s * w_slot_stride;
+      const T* wb = cross ? ws + (w_slot_stride ? s * OC * taps : 0) : nullptr;
+      for (int64_t oc = 0; oc < OC; ++oc) {
+        const int64_t c = oc / mult;
+        T acc = 0;
+        for (int64_t kh = 0; kh < KH; ++kh) {
+          const int64_t iy = oh * sh + kh * dh - pt;
+          if (iy < 0 || iy >= H) continue;
+          for (int64_t kw = 0; kw < KW; ++kw) {
+            const int64_t ix = ow * sw + kw * dw - pl;
+            if (ix < 0 || ix >= W) continue;
+            const int64_t xi = xb + c * sC + iy * sH + ix * sW, wi = (oc * KH + kh) * KW + kw;
+            if (cross)
+              acc += x0[xi] * wb[wi] + x1[xi] * wa[wi];
+            else
+              acc += x0[xi] * wa[wi];
+          }
+        }
+        const int64_t oi = nhwc ? row * OC + oc : ((n * OC + oc) * OH + oh) * OW + ow;
+        out[s * rows * OC + oi] = acc;
+      }
+    }
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -476,6 +526,44 @@ int mx_im2col(int dev, int elem_bytes, const void* in, void* out, int64_t slots,
     case 16:
       im2col_cpu((const u128*)in, (u128*)out, slots, in_slot_stride, N, C, H, W, KH, KW, sh,
                  sw, pt, pl, dh, dw, OH, OW, nhwc);
+      return 0;
+    default: return -2;
+  }
+}
+
+int mx_dwconv(int dev, int elem_bytes, const void* x0, const void* x1, const void* w0,
+              const void* w1, void* out, int64_t slots, int64_t x_slot_stride,
+              int64_t w_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t mult,
+              int64_t KH, int64_t KW, int64_t sh, int64_t sw, int64_t pt, int64_t pl,
+              int64_t dh, int64_t dw, int64_t OH, int64_t OW, int nhwc, void* stream) {
+  if (OH <= 0 || OW <= 0 || KH <= 0 || KW <= 0 || sh <= 0 || sw <= 0 || dh <= 0 || dw <= 0 ||
+      pt < 0 || pl < 0 || N < 0 || C < 0 || H < 0 || W < 0 || mult <= 0 || slots < 0 ||
+      x_slot_stride < 0 || w_slot_stride < 0)
+    return -3;
+  if ((x1 == nullptr) != (w1 == nullptr)) return -3;  // cross mode takes both second components
+  // every tap coordinate and channel index has to fit an int: the kernels compute them in
+  // 32 bits
+  const int64_t lim = 0x7fffffff;
+  const int64_t dims[] = {N, C, H, W, mult, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW};
+  for (int64_t d : dims)
+    if (d > lim) return -3;
+  if ((OH - 1) * sh + (KH - 1) * dh > lim || (OW - 1) * sw + (KW - 1) * dw > lim ||
+      C * mult > lim || KH * KW > lim)
+    return -3;
+  if (dev)
+    return mxh_dwconv(elem_bytes, x0, x1, w0, w1, out, slots, x_slot_stride, w_slot_stride, N, C,
+                      H, W, mult, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW, nhwc, stream);
+  if (slots * N * OH * OW * C == 0) return 0;
+  switch (elem_bytes) {
+    case 8:
+      dwconv_cpu((const u64*)x0, (const u64*)x1, (const u64*)w0, (const u64*)w1, (u64*)out, slots,
+                 x_slot_stride, w_slot_stride, N, C, H, W, mult, KH, KW, sh, sw, pt, pl, dh, dw,
+                 OH, OW, nhwc);
+      return 0;
+    case 16:
+      dwconv_cpu((const u128*)x0, (const u128*)x1, (const u128*)w0, (const u128*)w1, (u128*)out,
+                 slots, x_slot_stride, w_slot_stride, N, C, H, W, mult, KH, KW, sh, sw, pt, pl,
+                 dh, dw, OH, OW, nhwc);
       return 0;
     default: return -2;
   }

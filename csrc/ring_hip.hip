@@ -1892,6 +1892,161 @@ static int im2col_launch(const void* in, void* out, int64_t slots, int64_t in_sl
   return 0;
 }
 
+// Depthwise convolution over shares (moosex.h mx_dwconv): a memory-bound stencil, output-
+// stationary like k_im2col.  The output is rows x inner: inner = the C*mult channels (NHWC,
+// rows (n, oh, ow)) or the OW columns of one channel (NCHW, rows (n, oh)); a lane owns V
+// adjacent inner outputs of a row (V = 2 for u64 with an even inner extent: every store is 16
+// bytes), adjacent lanes are adjacent in c (NHWC) or ow (NCHW), and the lane strides over
+// rows.  A block is blockDim.x inner lanes x 256 / blockDim.x rows; blockIdx.x picks its
+// inner tile: a run of blockDim.x * V channels (NHWC), or one channel and a run of OW (NCHW).
+// The weights of the block's channels -- all KH*KW taps, in cross mode w0 + w1 (formed here,
+// once per element) and w0 -- are staged in LDS once, laid out [tap][channel] so a lane's
+// read is its own 16 bytes (NHWC) or a broadcast (NCHW).  Per output: KH*KW wrapping
+// multiply-adds (two in cross mode, x0.(w0 + w1) + x1.w0) on inputs read once; a tap in the
+// padding is skipped without a load.  Slots are blockIdx.z.  I: the index type, 32-bit when
+// every extent is below 2^31.
+template <class I>
+struct DwconvP {
+  I x_slot, w_slot, o_slot;  // slot strides in elements
+  I sN, sH, sW, sC;          // input strides in elements (format-dependent)
+  I rows;
+  int H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW, OC, mult, nhwc;
+  int tiles;  // NCHW: inner tiles per channel
+};
+
+template <class T, class I, int V, bool CROSS>
+__global__ void __launch_bounds__(256) k_dwconv(const T* __restrict__ x0,
+                                                const T* __restrict__ x1,
+                                                const T* __restrict__ w0,
+                                                const T* __restrict__ w1, T* __restrict__ out,
+                                                DwconvP<I> p) {
+  using U = typename std::make_unsigned<I>::type;
+  extern __shared__ __align__(16) unsigned char dwconv_lds[];
+  T* __restrict__ wl = reinterpret_cast<T*>(dwconv_lds);
+  const int taps = p.KH * p.KW;
+  const int bx = (int)blockDim.x, by = (int)blockDim.y;
+  const int cw = p.nhwc ? bx * V : 1;  // channels of this block
+  int oc_base, ow_base = 0;
+  if (p.nhwc) {
+    oc_base = (int)blockIdx.x * cw;
+  } else {
+    oc_base = (int)(blockIdx.x / (unsigned)p.tiles);
+    ow_base = (int)(blockIdx.x - (unsigned)oc_base * (unsigned)p.tiles) * bx * V;
+  }
+  {
+    const int nch = min(cw, p.OC - oc_base);
+    const I woff = (I)blockIdx.z * p.w_slot + (I)oc_base * (I)taps;
+    const int nw = nch * taps;
+    for (int i = (int)(threadIdx.y * bx + threadIdx.x); i < nw; i += bx * by) {
+      const int cl = i / taps, tap = i - cl * taps;
+      const T a = w0[woff + i];
+      if (CROSS) {
+        wl[tap * cw + cl] = a + w1[woff + i];
+        wl[(taps + tap) * cw + cl] = a;
+      } else {
+        wl[tap * cw + cl] = a;
+      }
+    }
+  }
+  __syncthreads();
+  const int l0 = (int)threadIdx.x * V;
+  // V == 2 only with an even inner extent: both outputs are inside, or neither
+  if ((p.nhwc ? oc_base + l0 >= p.OC : ow_base + l0 >= p.OW)) return;
+  I coff[V];  // the input channel's offset
+  int wcol[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    const int oc = p.nhwc ? oc_base + l0 + j : oc_base;
+    coff[j] = (I)(oc / p.mult) * p.sC;
+    wcol[j] = p.nhwc ? l0 + j : 0;
+  }
+  const T* __restrict__ xs0 = x0 + (I)blockIdx.z * p.x_slot;
+  const T* __restrict__ xs1 = CROSS ? x1 + (I)blockIdx.z * p.x_slot : nullptr;
+  T* __restrict__ dst = out + (I)blockIdx.z * p.o_slot;
+  for (I row = (I)(blockIdx.y * by + threadIdx.y); row < p.rows; row += (I)(gridDim.y * by)) {
+    U n;
+    int oh, ow;
+    I oidx;
+    if (p.nhwc) {
+      const U q = (U)row / (U)p.OW;
+      ow = (int)((U)row - q * (U)p.OW);
+      n = q / (U)p.OH;
+      oh = (int)(q - n * (U)p.OH);
+      oidx = row * (I)p.OC + (I)(oc_base + l0);
+    } else {
+      n = (U)row / (U)p.OH;
+      oh = (int)((U)row - n * (U)p.OH);
+      ow = ow_base + l0;
+      oidx = (((I)n * (I)p.OC + (I)oc_base) * (I)p.OH + (I)oh) * (I)p.OW + (I)ow;
+    }
+    const I base = (I)n * p.sN;
+    const int y0 = oh * p.sh - p.pt;
+    Im2colVec<T, V> acc;
+#pragma unroll
+    for (int j = 0; j < V; ++j) acc.v[j] = (T)0;
+    for (int kh = 0; kh < p.KH; ++kh) {
+      const int iy = y0 + kh * p.dh;
+      if (iy < 0 || iy >= p.H) continue;
+      const I rbase = base + (I)iy * p.sH;
+      for (int kw = 0; kw < p.KW; ++kw) {
+        const int tap = kh * p.KW + kw;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          const int ix = (p.nhwc ? ow : ow + j) * p.sw - p.pl + kw * p.dw;
+          if (ix < 0 || ix >= p.W) continue;
+          const I xi = rbase + coff[j] + (I)ix * p.sW;
+          acc.v[j] += xs0[xi] * wl[tap * cw + wcol[j]];
+          if (CROSS) acc.v[j] += xs1[xi] * wl[(taps + tap) * cw + wcol[j]];
+        }
+      }
+    }
+    *reinterpret_cast<Im2colVec<T, V>*>(dst + oidx) = acc;
+  }
+}
+
+template <class T, class I, int V, bool CROSS>
+static int dwconv_launch(const void* x0, const void* x1, const void* w0, const void* w1,
+                         void* out, int64_t slots, int64_t x_slot_stride, int64_t w_slot_stride,
+                         int64_t N, int64_t C, int64_t H, int64_t W, int64_t mult, int64_t KH,
+                         int64_t KW, int64_t sh, int64_t sw, int64_t pt, int64_t pl, int64_t dh,
+                         int64_t dw, int64_t OH, int64_t OW, int nhwc, void* stream) {
+  const int64_t OC = C * mult, taps = KH * KW;
+  const int64_t inner = nhwc ? OC : OW, rows = nhwc ? N * OH * OW : N * OH;
+  // inner lanes of a block: no more than the inner extent needs, and few enough that the
+  // block's weights fit 64 KB of LDS (NHWC: bx * V channels; NCHW: one channel)
+  const int64_t per = taps * (int64_t)sizeof(T) * (CROSS ? 2 : 1);
+  int bx = 64;
+  while (bx > 1 && (bx / 2) * V >= inner) bx /= 2;
+  while (bx > 1 && nhwc && per * bx * V > 65536) bx /= 2;
+  const int64_t lds = per * (nhwc ? bx * V : 1);
+  if (lds > 65536) return -3;
+  const int by = 256 / bx;
+  const int64_t tiles = (inner + (int64_t)bx * V - 1) / ((int64_t)bx * V);
+  const int64_t gx = nhwc ? tiles : OC * tiles;
+  if (gx > 0x7fffffff) return -3;
+  // rows per lane: one visit while that leaves the grid small, up to 8 on a large one (the
+  // staged weights serve them all); the row grid is capped at 65,536 rows, as k_im2col's
+  const int64_t gy_full = (rows + by - 1) / by;
+  const int64_t visits = std::max<int64_t>(1, std::min<int64_t>(8, gx * slots * gy_full / 4096));
+  const int64_t gy = std::min<int64_t>((gy_full + visits - 1) / visits, 65536 / by);
+  DwconvP<I> p;
+  p.x_slot = (I)x_slot_stride, p.w_slot = (I)w_slot_stride;
+  p.o_slot = (I)(N * OH * OW * OC);
+  p.sN = (I)(C * H * W);
+  p.sH = (I)(nhwc ? W * C : W);
+  p.sW = (I)(nhwc ? C : 1);
+  p.sC = (I)(nhwc ? 1 : H * W);
+  p.rows = (I)rows;
+  p.H = (int)H, p.W = (int)W, p.KH = (int)KH, p.KW = (int)KW, p.sh = (int)sh, p.sw = (int)sw;
+  p.pt = (int)pt, p.pl = (int)pl, p.dh = (int)dh, p.dw = (int)dw, p.OH = (int)OH;
+  p.OW = (int)OW, p.OC = (int)OC, p.mult = (int)mult, p.nhwc = nhwc, p.tiles = (int)tiles;
+  hipLaunchKernelGGL((k_dwconv<T, I, V, CROSS>), dim3((unsigned)gx, (unsigned)gy, (unsigned)slots),
+                     dim3(bx, by), (size_t)lds, S(stream), (const T*)x0, (const T*)x1,
+                     (const T*)w0, (const T*)w1, (T*)out, p);
+  MX_LAUNCH_CHECK();
+  return 0;
+}
+
 // party-batched twins of the per-party sessions' local kernels (party_batch.h)
 MX_X3_GS(k_binary2<u64>, d_binary2<u64>);
 MX_X3_GS(k_binary2<u128>, d_binary2<u128>);
@@ -2194,6 +2349,43 @@ int mxh_im2col(int elem_bytes, const void* in, void* out, int64_t slots, int64_t
     default: return -2;
   }
 #undef MX_IM2COL
+}
+
+int mxh_dwconv(int elem_bytes, const void* x0, const void* x1, const void* w0, const void* w1,
+               void* out, int64_t slots, int64_t x_slot_stride, int64_t w_slot_stride, int64_t N,
+               int64_t C, int64_t H, int64_t W, int64_t mult, int64_t KH, int64_t KW, int64_t sh,
+               int64_t sw, int64_t pt, int64_t pl, int64_t dh, int64_t dw, int64_t OH,
+               int64_t OW, int nhwc, void* stream) {
+  const int64_t OC = C * mult, taps = KH * KW, n_out = N * OH * OW * OC;
+  if (slots <= 0 || n_out <= 0) return 0;
+  const int64_t dims[] = {N, C, H, W, mult, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW, OC, taps};
+  for (int64_t d : dims)
+    if (d < 0 || d > 0x7fffffff) return -3;
+  if (mult <= 0 || taps <= 0 || slots > 65535 || x_slot_stride < 0 || w_slot_stride < 0)
+    return -3;
+  if ((x1 == nullptr) != (w1 == nullptr)) return -3;
+  const int64_t x_extent = (slots - 1) * x_slot_stride + N * C * H * W;
+  const int64_t w_extent = (slots - 1) * w_slot_stride + OC * taps;
+  // 32-bit indices below 2^31 elements, less the overshoot of a lane's last loop step
+  const int64_t lim = (1ll << 31) - (1ll << 23);
+  const bool small = x_extent < lim && w_extent < lim && slots * n_out < lim &&
+                     (nhwc ? N * OH * OW : N * OH) < lim;
+  const bool cross = x1 != nullptr;
+#define MX_DWCONV_I(T, I, V, X)                                                                \
+  dwconv_launch<T, I, V, X>(x0, x1, w0, w1, out, slots, x_slot_stride, w_slot_stride, N, C, H, \
+                            W, mult, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW, nhwc, stream)
+#define MX_DWCONV(T, V)                                                              \
+  return small ? (cross ? MX_DWCONV_I(T, int32_t, V, true) : MX_DWCONV_I(T, int32_t, V, false)) \
+               : (cross ? MX_DWCONV_I(T, int64_t, V, true) : MX_DWCONV_I(T, int64_t, V, false))
+  switch (elem_bytes) {
+    case 8:
+      if ((nhwc ? OC : OW) % 2 == 0 && ((uintptr_t)out & 15) == 0) { MX_DWCONV(u64, 2); }
+      MX_DWCONV(u64, 1);
+    case 16: MX_DWCONV(u128, 1);
+    default: return -2;
+  }
+#undef MX_DWCONV
+#undef MX_DWCONV_I
 }
 
 int mxh_ew_binary_slot2(int op, int words, const void* a0, const void* a1, const void* b,

@@ -82,6 +82,12 @@ _OPS = {
                    "data_format": o.data_format},
     ),
     "PermuteOperation": ("Permute", ["x"], lambda o: {"axes": list(o.axes)}),
+    "DepthwiseConvOperation": (
+        "DepthwiseConv",
+        ["x", "w"],
+        lambda o: {"strides": list(o.strides), "pads": list(o.pads),
+                   "dilations": list(o.dilations), "data_format": o.data_format},
+    ),
 }
 
 _NP_CONST = {

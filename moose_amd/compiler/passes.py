@@ -111,6 +111,17 @@ def _static_shape(op, shapes):
             g = R.im2col_geometry(ins[0], a["kernel_shape"], a["strides"], a["pads"],
                                   a["dilations"], a["data_format"])
             shp = (g[0] * g[-2] * g[-1], g[1] * g[4] * g[5])
+        elif kind == "DepthwiseConv":
+            if len(ins) != 2 or ins[1] is None or ins[1][:1] == ("shape",):
+                if len(ins[0]) != 4:
+                    raise ValueError(f"expects a rank-4 {a['data_format']} tensor, found shape "
+                                     f"{ins[0]}")
+                return
+            g = R.dwconv_geometry(ins[0], ins[1], a["strides"], a["pads"], a["dilations"],
+                                  a["data_format"])
+            oc = g[1] * g[4]
+            shp = (g[0], g[-2], g[-1], oc) if a["data_format"] == "NHWC" \
+                else (g[0], oc, g[-2], g[-1])
         elif kind == "Reshape" and len(ins) == 2 and ins[1] is not None and ins[1][0] == "shape":
             want, n = list(ins[1][1]), int(np.prod(ins[0]))
             if want.count(-1) == 1:

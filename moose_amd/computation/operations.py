@@ -85,6 +85,7 @@ OPERATION_TABLE = [
     ("TransposeOperation", []),
     ("Im2ColOperation", ["kernel_shape", "strides", "pads", "dilations", "data_format"]),
     ("PermuteOperation", ["axes"]),
+    ("DepthwiseConvOperation", ["strides", "pads", "dilations", "data_format"]),
 ]
 
 OPERATION_CLASSES = {}

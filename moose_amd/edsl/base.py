@@ -690,28 +690,101 @@ def _batch(n):
     return -1 if n is None else n
 
 
-def conv2d(x, w, bias=None, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1),
-           data_format="NCHW", placement=None, input_shape=None, weight_shape=None):
-    """2-D convolution (cross-correlation, as ONNX ``Conv``) of ``x`` (rank 4, ``data_format``)
-    with ``w`` of shape ``[OC, C, KH, KW]``: ``im2col`` + one ``dot`` (+ ``bias`` of shape
-    ``[OC]``); the result has the input's ``data_format``.  The static shapes come from the
-    expressions (constants, ``pm.Argument(shape=...)``) or from ``input_shape`` /
-    ``weight_shape``; only the batch size may be unknown (None).  ``groups`` is not
-    supported."""
-    if data_format not in ("NCHW", "NHWC"):
-        raise ValueError(f"`conv2d`: data_format must be 'NCHW' or 'NHWC', found {data_format!r}")
+def _weight_shape(fn, w, weight_shape, layout):
     ws = tuple(weight_shape) if weight_shape is not None else w.static_shape
     if ws is None:
-        raise ValueError("`conv2d` needs the static shape of `w`: pass `weight_shape=`")
+        raise ValueError(f"`{fn}` needs the static shape of `w`: pass `weight_shape=`")
     if len(ws) != 4 or None in ws:
-        raise ValueError(f"`conv2d` expects `w` of shape [OC, C, KH, KW], found {tuple(ws)}")
-    oc, wc, kh, kw = (int(s) for s in ws)
+        raise ValueError(f"`{fn}` expects `w` of shape {layout}, found {tuple(ws)}")
+    return tuple(int(s) for s in ws)
+
+
+def _channel_bias(bias, oc, data_format, placement):
+    """``bias`` ([OC]) shaped to broadcast over a rank-4 activation in ``data_format``."""
+    return bias if data_format == "NHWC" else reshape(bias, [oc, 1, 1], placement)
+
+
+def depthwise_conv2d(x, w, bias=None, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1),
+                     data_format="NCHW", placement=None, input_shape=None, weight_shape=None):
+    """Depthwise 2-D convolution (ONNX ``Conv`` with ``group = C``) of ``x`` (rank 4,
+    ``data_format``) with ``w`` of shape ``[C*mult, 1, KH, KW]``: output channel ``c*mult + j``
+    is input channel ``c`` filtered by ``w[c*mult + j, 0]`` (+ ``bias`` of shape ``[C*mult]``).
+    One ``DepthwiseConv`` operator -- a direct stencil over the shares, no patch matrix; the
+    result keeps the input's ``data_format`` and carries a static shape.  Static shapes as
+    :func:`conv2d`."""
+    if data_format not in ("NCHW", "NHWC"):
+        raise ValueError(f"`depthwise_conv2d`: data_format must be 'NCHW' or 'NHWC', found "
+                         f"{data_format!r}")
+    oc, w1, kh, kw = _weight_shape("depthwise_conv2d", w, weight_shape, "[C*mult, 1, KH, KW]")
+    xs = _window_input("depthwise_conv2d", x, input_shape, data_format)
+    c, _h, _w, oh, ow = _conv_geometry("depthwise_conv2d", xs, (kh, kw), strides, pads,
+                                       dilations, data_format)
+    if w1 != 1:
+        raise ValueError(f"`depthwise_conv2d` expects `w` of shape [C*mult, 1, KH, KW], found "
+                         f"{(oc, w1, kh, kw)} (w.shape[1] = {w1})")
+    if oc % c:
+        raise ValueError(f"`depthwise_conv2d`: `w` has {oc} output channels, not a multiple of "
+                         f"the input's {c} channels")
+    y = _expr("depthwise_conv", [x, w], x.vtype, placement, strides=list(strides),
+              pads=list(pads), dilations=list(dilations), data_format=data_format)
+    y.static_shape = (xs[0], oc, oh, ow) if data_format == "NCHW" else (xs[0], oh, ow, oc)
+    if bias is not None:
+        static = y.static_shape
+        y = add(y, _channel_bias(bias, oc, data_format, placement), placement)
+        y.static_shape = static
+    return y
+
+
+def conv2d(x, w, bias=None, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1),
+           data_format="NCHW", placement=None, input_shape=None, weight_shape=None, groups=1):
+    """2-D convolution (cross-correlation, as ONNX ``Conv``) of ``x`` (rank 4, ``data_format``)
+    with ``w`` of shape ``[OC, C // groups, KH, KW]`` (+ ``bias`` of shape ``[OC]``); the result
+    has the input's ``data_format``.  ``groups = 1``: ``im2col`` + one ``dot``.  ``groups = C``:
+    the depthwise operator (:func:`depthwise_conv2d`).  ``1 < groups < C``: a composition --
+    a channel slice of ``x`` and of ``w`` per group, ``im2col`` + ``dot`` on each, and
+    ``concatenate`` on the channel axis: ``groups`` products, not a fast path.  The static
+    shapes come from the expressions (constants, ``pm.Argument(shape=...)``) or from
+    ``input_shape`` / ``weight_shape``; only the batch size may be unknown (None)."""
+    if data_format not in ("NCHW", "NHWC"):
+        raise ValueError(f"`conv2d`: data_format must be 'NCHW' or 'NHWC', found {data_format!r}")
+    if not isinstance(groups, int) or isinstance(groups, bool) or groups < 1:
+        raise ValueError(f"`conv2d`: groups must be a positive int, found {groups!r}")
+    ws = _weight_shape("conv2d", w, weight_shape, "[OC, C, KH, KW] (C // groups with groups)")
+    oc, wc, kh, kw = ws
     xs = _window_input("conv2d", x, input_shape, data_format)
     c, _h, _w, oh, ow = _conv_geometry("conv2d", xs, (kh, kw), strides, pads, dilations,
                                        data_format)
-    if c != wc:
-        raise ValueError(f"`conv2d`: input has {c} channels but `w` {tuple(ws)} expects {wc} "
-                         "(groups are not supported)")
+    if groups > 1:
+        if c % groups:
+            raise ValueError(f"`conv2d`: groups = {groups} does not divide the input's {c} "
+                             "channels")
+        if oc % groups:
+            raise ValueError(f"`conv2d`: groups = {groups} does not divide the {oc} output "
+                             f"channels of `w` {ws}")
+    if c != wc * groups:
+        raise ValueError(f"`conv2d`: input has {c} channels and groups = {groups}, so `w` "
+                         f"must have {c // groups} input channels per group, but `w` {ws} has "
+                         f"{wc}")
+    if groups > 1 and groups == c:
+        return depthwise_conv2d(x, w, bias, strides, pads, dilations, data_format, placement,
+                                xs, ws)
+    if groups > 1:
+        cg, ocg = c // groups, oc // groups
+        cax = 1 if data_format == "NCHW" else 3
+        gshape = tuple(cg if i == cax else s for i, s in enumerate(xs))
+        parts = []
+        for g in range(groups):
+            sl = [slice(None)] * 4
+            sl[cax] = slice(g * cg, (g + 1) * cg)
+            xg = strided_slice(x, sl, placement)
+            wg = strided_slice(w, [slice(g * ocg, (g + 1) * ocg)] + [slice(None)] * 3, placement)
+            parts.append(conv2d(xg, wg, None, strides, pads, dilations, data_format, placement,
+                                gshape, (ocg, cg, kh, kw)))
+        y = concatenate(parts, axis=cax, placement=placement)
+        if bias is not None:
+            y = add(y, _channel_bias(bias, oc, data_format, placement), placement)
+        y.static_shape = (xs[0], oc, oh, ow) if data_format == "NCHW" else (xs[0], oh, ow, oc)
+        return y
     k = c * kh * kw
     cols = im2col(x, (kh, kw), strides, pads, dilations, data_format, placement, xs)
     if data_format == "NCHW":

@@ -58,6 +58,8 @@ _OPS = {
     "im2col": ("Im2ColOperation", ["x"], "im2col",
                ["kernel_shape", "strides", "pads", "dilations", "data_format"]),
     "permute": ("PermuteOperation", ["x"], "permute", ["axes"]),
+    "depthwise_conv": ("DepthwiseConvOperation", ["x", "w"], "depthwise_conv",
+                       ["strides", "pads", "dilations", "data_format"]),
     "shape": ("ShapeOperation", ["x"], "shape", []),
     "mux": ("MuxOperation", ["selector", "x", "y"], "mux", []),
     "load": ("LoadOperation", ["key", "query"], "load", []),

@@ -135,6 +135,12 @@ EXTENSION_OPERATORS = {
                ("dilations", "ints"), ("data_format", "str")],
     # general axis permutation (Transpose reverses all axes); share-wise
     "Permute": [("axes", "ints")],
+    # depthwise 2-D convolution of a rank-4 NCHW / NHWC x with the ONNX depthwise weight
+    # w = [C*mult, 1, KH, KW]: out[n, oh, ow, c*mult + j] = sum_taps x[n, ., ., c] * w[c*mult
+    # + j, 0, kh, kw], in the input's layout; pads as Im2Col.  A direct stencil kernel over
+    # shares (no patch matrix): secret x secret is the replicated local product + dot tail
+    "DepthwiseConv": [("strides", "ints"), ("pads", "ints"), ("dilations", "ints"),
+                      ("data_format", "str")],
 }
 
 ALL_OPERATORS = {**OPERATORS, **EXTENSION_OPERATORS}

@@ -1,7 +1,8 @@
 """Convolutional networks exported from PyTorch or Keras/tf2onnx.
 
 The reference has no convolution; this predictor is this framework's own.  A graph is a
-chain of ``Conv`` (``group = 1``), ``Relu`` / ``Sigmoid``, ``MaxPool`` / ``AveragePool``,
+chain of ``Conv`` (any ``group`` that divides the channels: ``group = C`` is the depthwise
+operator, other groups a composition of per-group products), ``Relu`` / ``Sigmoid``, ``MaxPool`` / ``AveragePool``,
 ``Flatten`` (or ``Reshape`` to ``[N, -1]``), ``Gemm`` / ``MatMul`` + ``Add`` and a final
 ``Softmax``.  The model input is rank 4, NCHW.  Inside the MPC the activations are NHWC from
 the first convolution on, so no permutation ever runs on shares: the first ``im2col`` reads
@@ -69,6 +70,7 @@ def conv_layers_from_onnx(model):
         raise ValueError(f"the model input's channel and image sizes must be static, found {chw}")
     init = dict(initializers(model))
     layers = []
+    channels = chw[0]  # of the activation that reaches the next Conv
     for node in model.graph.node:
         op = node.op_type
         if op == "Constant":
@@ -77,8 +79,7 @@ def conv_layers_from_onnx(model):
                 raise _unsupported(node, "a Constant without a tensor value")
             init[node.output[0]] = onnx_proto.to_array(t.t)
         elif op == "Conv":
-            if _int(node, "group", 1) != 1:
-                raise _unsupported(node, f"group={_int(node, 'group', 1)}")
+            group = _int(node, "group", 1)
             ap = find_attribute(node, "auto_pad", enforce=False)
             if ap is not None and ap.s not in (b"", b"NOTSET"):
                 raise _unsupported(node, f"auto_pad={ap.s.decode()}")
@@ -87,8 +88,15 @@ def conv_layers_from_onnx(model):
             w = np.asarray(init[node.input[1]], dtype=np.float64)
             if w.ndim != 4:
                 raise _unsupported(node, f"weight of shape {w.shape} is not 2-D")
+            if group < 1 or channels % group or w.shape[0] % group:
+                raise _unsupported(node, f"group={group} does not divide the {channels} input "
+                                         f"and {w.shape[0]} output channels")
+            if w.shape[1] * group != channels:
+                raise _unsupported(node, f"group={group} with a weight of shape {w.shape} does "
+                                         f"not match {channels} input channels")
+            channels = w.shape[0]
             b = init[node.input[2]] if len(node.input) > 2 else np.zeros(w.shape[0])
-            layers.append({"op": "conv", "w": w, "b": np.asarray(b, np.float64).reshape(-1),
+            layers.append({"op": "conv", "w": w, "group": group, "b": np.asarray(b, np.float64).reshape(-1),
                            "strides": _ints(node, "strides", (1, 1)),
                            "pads": _ints(node, "pads", (0, 0, 0, 0)),
                            "dilations": _ints(node, "dilations", (1, 1))})
@@ -171,10 +179,14 @@ class ConvNetwork(Predictor):
                 raise ValueError(f"unsupported ONNX graph: {op} after Flatten")
             if op == "conv":
                 oc, wc, kh, kw = l["w"].shape
-                if wc != c:
-                    raise ValueError(f"Conv weight {l['w'].shape} does not match {c} channels")
+                group = l.setdefault("group", 1)
+                if group < 1 or c % group or oc % group or wc * group != c:
+                    raise ValueError(f"Conv weight {l['w'].shape} with group={group} does not "
+                                     f"match {c} channels")
                 l.update(fmt=fmt, chw=(c, h, w), kernel=(kh, kw))
-                if fmt == "NCHW":  # columns (c, kh, kw): the ONNX weight as it is
+                if group > 1:  # the ONNX weight as it is: pm.conv2d(groups=) takes it
+                    pass
+                elif fmt == "NCHW":  # columns (c, kh, kw): the ONNX weight as it is
                     l["wm"] = l["w"].reshape(oc, -1).T
                 else:  # columns (kh, kw, c)
                     l["wm"] = l["w"].transpose(2, 3, 1, 0).reshape(-1, oc)
@@ -211,6 +223,17 @@ class ConvNetwork(Predictor):
             if op == "conv":
                 c, h, w = l["chw"]
                 shape = (None, c, h, w) if l["fmt"] == "NCHW" else (None, h, w, c)
+                if l["group"] > 1:
+                    # depthwise (group = C) is one operator; other groups compose.  The first
+                    # convolution reads NCHW and answers NCHW: one permutation to NHWC
+                    fn = pm.depthwise_conv2d if l["group"] == c else pm.conv2d
+                    kw = {} if l["group"] == c else {"groups": l["group"]}
+                    x = fn(x, const(l["w"]), const(l["b"]), l["strides"], l["pads"],
+                           l["dilations"], l["fmt"], input_shape=shape,
+                           weight_shape=l["w"].shape, **kw)
+                    if l["fmt"] == "NCHW":
+                        x = pm.permute(x, (0, 2, 3, 1))
+                    continue
                 cols = pm.im2col(x, l["kernel"], l["strides"], l["pads"], l["dilations"],
                                  l["fmt"], input_shape=shape)
                 y = pm.add(pm.dot(cols, const(l["wm"])), const(l["b"]))

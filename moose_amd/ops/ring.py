@@ -836,6 +836,106 @@ def im2col(a: RT, kernel_shape, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1,
     return out
 
 
+def dwconv_geometry(x_shape, w_shape, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1),
+                    data_format="NCHW"):
+    """Validate a depthwise convolution of a rank-4 ``x_shape`` with the ONNX depthwise weight
+    ``w_shape = [C*mult, 1, KH, KW]`` (as :func:`im2col_geometry`, plus the weight) and return
+    ``(N, C, H, W, mult, KH, KW, sh, sw, pt, pl, pb, pr, dh, dw, OH, OW)``."""
+    w_shape = tuple(int(s) for s in w_shape)
+    if len(w_shape) != 4:
+        raise ValueError("dwconv expects a rank-4 weight [C*mult, 1, KH, KW], found shape "
+                         f"{w_shape}")
+    try:
+        g = im2col_geometry(x_shape, w_shape[2:], strides, pads, dilations, data_format)
+    except ValueError as e:
+        raise ValueError(str(e).replace("im2col", "dwconv")) from None
+    N, C, H, W, KH, KW, sh, sw, pt, pl, pb, pr, dh, dw, OH, OW = g
+    if w_shape[1] != 1:
+        raise ValueError(f"dwconv: a depthwise weight is [C*mult, 1, KH, KW], found {w_shape} "
+                         f"(w.shape[1] = {w_shape[1]})")
+    if C <= 0 or w_shape[0] <= 0 or w_shape[0] % C:
+        raise ValueError(f"dwconv: the weight's {w_shape[0]} output channels are not a positive "
+                         f"multiple of the input's {C} channels")
+    return N, C, H, W, w_shape[0] // C, KH, KW, sh, sw, pt, pl, pb, pr, dh, dw, OH, OW
+
+
+def _dwconv_operand(t: RT, nb, rank4, lead, dense):
+    """(data, slot stride in elements) of a dwconv operand: a rank-4 tensor shared by every
+    slot (stride 0), a [slots, ...] view with dense slots read in place, or a dense copy."""
+    w = 2 if t.bits == 128 else 1
+    d = t.data
+    if len(t.shape) == 4 and nb:  # public: one image / weight for every slot
+        return d.contiguous(), 0
+    if tuple(t.shape[:nb]) != lead or tuple(t.shape[nb:]) != tuple(rank4):
+        raise ValueError(f"dwconv: operand of shape {tuple(t.shape)} does not match the batch "
+                         f"dims {lead} and the shape {tuple(rank4)}")
+    if not nb:
+        return d.contiguous(), dense
+    slots = math.prod(lead)
+    if nb == 1 and slots and d[0].is_contiguous() and d.stride(0) >= 0 and d.stride(0) % w == 0:
+        return d, d.stride(0) // w
+    return d.contiguous(), dense
+
+
+def _dwconv(x0, x1, w0, w1, strides, pads, dilations, data_format, nb):
+    bits = x0.bits
+    ops = [t for t in (x0, x1, w0, w1) if t is not None]
+    if bits not in (64, 128) or any(t.bits != bits for t in ops):
+        raise ValueError("dwconv is arithmetic only: operands over one of Z_2^64 / Z_2^128, "
+                         f"found {[t.bits for t in ops]} bits")
+    xpub, wpub = bool(nb) and len(x0.shape) == 4, bool(nb) and len(w0.shape) == 4
+    if xpub and wpub:
+        raise ValueError("dwconv: with batch dims, the image or the weight has to carry them")
+    lead = tuple((w0 if xpub else x0).shape[:nb])
+    xs = tuple(x0.shape) if xpub else tuple(x0.shape[nb:])
+    ws = tuple(w0.shape) if wpub else tuple(w0.shape[nb:])
+    geom = dwconv_geometry(xs, ws, strides, pads, dilations, data_format)
+    N, C, H, W, mult, KH, KW, sh, sw, pt, pl, _pb, _pr, dh, dw, OH, OW = geom
+    nhwc = data_format == "NHWC"
+    out_shape = lead + ((N, OH, OW, C * mult) if nhwc else (N, C * mult, OH, OW))
+    if x0.device.type == "meta":  # shape inference of the symbolic session
+        return empty(out_shape, bits, x0.device)
+    xd0, xst = _dwconv_operand(x0, nb, xs, lead, N * C * H * W)
+    wd0, wst = _dwconv_operand(w0, nb, ws, lead, C * mult * KH * KW)
+    xd1 = wd1 = None
+    if x1 is not None:
+        xd1, xst1 = _dwconv_operand(x1, nb, xs, lead, N * C * H * W)
+        wd1, wst1 = _dwconv_operand(w1, nb, ws, lead, C * mult * KH * KW)
+        if xst1 != xst:  # one stride serves both components
+            xd0, xd1, xst = xd0.contiguous(), xd1.contiguous(), (0 if xpub else N * C * H * W)
+        if wst1 != wst:
+            wd0, wd1 = wd0.contiguous(), wd1.contiguous()
+            wst = 0 if wpub else C * mult * KH * KW
+    out = empty(out_shape, bits, x0.device)
+    nat.check(
+        nat.lib().mx_dwconv(
+            nat.dev_of(out.data), 16 if bits == 128 else 8, nat.ptr(xd0),
+            nat.ptr(xd1) if xd1 is not None else None, nat.ptr(wd0),
+            nat.ptr(wd1) if wd1 is not None else None, nat.ptr(out.data), math.prod(lead),
+            xst, wst, N, C, H, W, mult, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW,
+            1 if nhwc else 0, nat.stream_of(out.data)),
+        "dwconv",
+    )
+    return out
+
+
+def dwconv(x: RT, w: RT, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1),
+           data_format="NCHW", nb=0) -> RT:
+    """Ring depthwise convolution of a rank-4 tensor after ``nb`` batch dims with the dense
+    weight ``[..., C*mult, 1, KH, KW]``: ``out[n, oh, ow, c*mult + j] = sum_taps x[n, ., ., c]
+    * w[c*mult + j, 0, kh, kw]`` (wrapping), in the input's layout.  One native launch over all
+    batch slots (``mx_dwconv``); a [slots, ...] view with dense slots is read in place, and a
+    rank-4 operand beside a batched one is public: every slot reads the one copy."""
+    return _dwconv(x, None, w, None, strides, pads, dilations, data_format, nb)
+
+
+def dwconv_cross(x0: RT, x1: RT, w0: RT, w1: RT, strides=(1, 1), pads=(0, 0, 0, 0),
+                 dilations=(1, 1), data_format="NCHW", nb=0) -> RT:
+    """RSS cross terms of a depthwise convolution, ``x0 * (w0 + w1) + x1 * w0`` summed over the
+    taps in one pass (:func:`dwconv`'s conventions; x1 / w1 are the next party's components)."""
+    return _dwconv(x0, x1, w0, w1, strides, pads, dilations, data_format, nb)
+
+
 def select_mask(a: RT, axis: int, mask: torch.Tensor, nb=0) -> RT:
     ax = _ax(a, axis, nb)
     keep = torch.nonzero(mask.reshape(-1).to(torch.bool)).reshape(-1).to(a.device)

@@ -124,6 +124,23 @@ def dot(sess, x, y, px=None, py=None, f=None):
     return _with(base, rep.trunc_pr(sess, z, f if f is not None else base.frac))
 
 
+def dwconv(sess, x, w, px=None, pw=None, f=None, **geom):
+    """Fixed-point depthwise convolution of the image ``x`` with the weight ``w`` ([C*mult, 1,
+    KH, KW]); ``geom``: strides, pads, dilations, data_format.  Secret x secret is
+    rep.dwconv_trunc; with a public (mirrored) weight ``pw`` or a public image ``px`` the plain
+    kernel runs share-wise on both components, then rep.trunc_pr.  (The per-party
+    one-component shortcut that secret x public dots take is not built for convolutions.)"""
+    if px is not None:
+        z = rep.dwconv_public(sess, w.t, _pub(px), geom, public_image=True)
+        base = w
+    elif pw is not None:
+        z = rep.dwconv_public(sess, x.t, _pub(pw), geom)
+        base = x
+    else:
+        return _with(x, rep.dwconv_trunc(sess, x.t, w.t, f if f is not None else x.frac, geom))
+    return _with(base, rep.trunc_pr(sess, z, f if f is not None else base.frac))
+
+
 def _dot_public_trunc_jobs(sess, x, y, px, py, m):
     """A secret x public fixed-point product on a per-party session: the GEMM of this
     party's FIRST share component only (an additive sharing of the product) and its TruncPr

@@ -1043,6 +1043,58 @@ def dot_trunc(sess, x: RepTensor, y: RepTensor, m: int, nbatch: int = 0) -> RepT
         return RepTensor(plc, bits, kind, PV(plc, R.RT(out0, bits)), PV(plc, R.RT(out1, bits)))
 
 
+def dwconv_trunc(sess, x: RepTensor, w: RepTensor, m: int, geom: dict) -> RepTensor:
+    """trunc_pr(depthwise_conv(x, w), m) -- the fixed-point depthwise convolution of a secret
+    image with a secret weight.  ``geom``: the operator's strides, pads, dilations and
+    data_format.  The local products z_p = x_p * (w_p + w_{p+1}) + x_{p+1} * w_p, summed over
+    the taps, come from one stencil kernel (session ``p_dwconv_cross``); the tail is the one
+    :func:`dot_trunc` selects for an unchunked product, on the same nonces in the same order:
+    the lazy one-kernel tail of a fused stacked device session, the per-party tail (reshare
+    folded into TruncPr) on seven nonces, else zero share + reshare + TruncPr."""
+    tail = getattr(sess, "p_zs_trunc", None)
+    if (tail is not None and m and x.kind == "arith" and getattr(sess, "fused", False)
+            and getattr(sess, "device", None) is not None and sess.device.type == "cuda"
+            and os.environ.get("MOOSEX_DOT_TAIL", "1") != "0"):
+        with span("rep.dwconv_trunc_fused"):
+            v = sess.p_dwconv_cross(x.plc, x.s0, x.s1, w.s0, w.s1, geom)
+            issue = getattr(sess, "p_zs_trunc_issue", None)
+            if (issue is not None and x.bits in (64, 128)
+                    and os.environ.get("MOOSEX_DOT_OPEN", "1") != "0"):
+                return StackedTail(sess, x.plc, x.bits, v, m, issue(x.plc, v))
+            s0, s1 = tail(x.plc, v, m)
+            return RepTensor(x.plc, x.bits, "arith", s0, s1)
+    party = getattr(sess, "party_dot_trunc", None)
+    if (party is not None and m and 0 < m <= 63 and x.kind == "arith" and x.bits in (64, 128)
+            and os.environ.get("MOOSEX_DOT_TAIL", "1") != "0"):
+        with span("rep.dwconv_trunc_party"):
+            nonces = tuple(sess.nonce(x.plc) for _ in range(7))  # as dot + trunc_pr
+            v = sess.p_dwconv_cross(x.plc, x.s0, x.s1, w.s0, w.s1, geom)
+            s0, s1 = party(x.plc, v, m, nonces)
+            return RepTensor(x.plc, x.bits, "arith", s0, s1)
+    with span("rep.dwconv"):
+        v = sess.p_dwconv_cross(x.plc, x.s0, x.s1, w.s0, w.s1, geom)
+        fused = getattr(sess, "p_zero_share_reshare", None)
+        if fused is not None and getattr(sess, "fused", False):
+            s0, s1 = fused(x.plc, v, x.kind)
+            z = RepTensor(x.plc, x.bits, x.kind, s0, s1)
+        else:
+            z = _reshare(sess, x.plc, sess.p_add_zero_share(x.plc, v, x.kind), x.bits, x.kind)
+    return trunc_pr(sess, z, m) if m else z  # m = 0: the ring convolution, as rep.dot
+
+
+def dwconv_public(sess, x: RepTensor, c, geom: dict, public_image=False) -> RepTensor:
+    """Depthwise convolution of a secret image with the public weight ``c`` (or, with
+    ``public_image``, of the public image ``c`` with a secret weight): the plain kernel
+    share-wise on both components -- one launch over the pair buffer where the session does
+    that (public weight) -- every slot reading the one public operand in place."""
+    pc = sess.public(x.plc, c)
+    if public_image:
+        return RepTensor(x.plc, x.bits, x.kind, sess.p("DepthwiseConv", x.plc, pc, x.s0, **geom),
+                         sess.p("DepthwiseConv", x.plc, pc, x.s1, **geom))
+    s0, s1 = _sharewise(sess, "DepthwiseConv", x.plc, (x.s0, x.s1), (pc, pc), **geom)
+    return RepTensor(x.plc, x.bits, x.kind, s0, s1)
+
+
 # ---------------------------------------------------------------------------
 # probabilistic truncation (dealer-assisted, P2 = dealer)
 # ---------------------------------------------------------------------------

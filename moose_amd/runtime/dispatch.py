@@ -111,6 +111,11 @@ def _pub(v):
     return v.v  # a host operand's ring tensor, used as a public value
 
 
+def _dwconv_geom(c):
+    return dict(strides=tuple(c.attr("strides")), pads=tuple(c.attr("pads")),
+                dilations=tuple(c.attr("dilations")), data_format=c.attr("data_format"))
+
+
 # --- replicated: arithmetic ---------------------------------------------------------------
 for _op, _f in (("Add", rep.add), ("Sub", rep.sub)):
     kernel(_op, "rep", "rep_ring", "rep_ring")(lambda c, x, y, f=_f: f(c.sess, x, y))
@@ -127,6 +132,12 @@ kernel("Dot", "rep", "rep_ring", "rep_ring")(lambda c, x, y: rep.dot(c.sess, x, 
 kernel("Dot", "rep", "rep_ring", "host_ring")(lambda c, x, y: rep.dot_public(c.sess, x, _pub(y)))
 kernel("Dot", "rep", "host_ring", "rep_ring")(
     lambda c, x, y: rep.dot_public(c.sess, y, _pub(x), public_left=True))
+kernel("DepthwiseConv", "rep", "rep_ring", "rep_ring")(
+    lambda c, x, w: rep.dwconv_trunc(c.sess, x, w, 0, _dwconv_geom(c)))
+kernel("DepthwiseConv", "rep", "rep_ring", "host_ring")(
+    lambda c, x, w: rep.dwconv_public(c.sess, x, _pub(w), _dwconv_geom(c)))
+kernel("DepthwiseConv", "rep", "host_ring", "rep_ring")(
+    lambda c, x, w: rep.dwconv_public(c.sess, w, _pub(x), _dwconv_geom(c), public_image=True))
 kernel("Neg", "rep", "rep_ring")(lambda c, x: rep.neg(c.sess, x))
 kernel("Sum", "rep", "rep_ring")(lambda c, x: rep.sum(c.sess, x, c.attr("axis")))
 kernel("AddN", "rep", "rep_ring", variadic=True)(lambda c, *xs: _add_n(c, xs))

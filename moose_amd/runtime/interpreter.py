@@ -1507,6 +1507,35 @@ class Interpreter:
                               strides=tuple(a["strides"]), pads=tuple(a["pads"]),
                               dilations=tuple(a["dilations"]), data_format=a["data_format"])
 
+    def op_DepthwiseConv(self, op, ins):
+        """Depthwise convolution: host tensors (float, or fixed point with the truncation
+        that Dot takes) through the primitive, replicated fixed point through
+        fixedpoint.dwconv (secret or mirrored image and weight)."""
+        a = op.attrs
+        geom = dict(strides=tuple(a["strides"]), pads=tuple(a["pads"]),
+                    dilations=tuple(a["dilations"]), data_format=a["data_format"])
+        x, w = (self.at(op, v) for v in ins)
+        dtype = x.dtype if x.dtype is not None else w.dtype
+        sess = self.sess
+
+        def on_host(host, xv, wv):
+            z = sess.h("DepthwiseConv", host, xv, wv, **geom)
+            if dtype is not None and dtype.is_fixed:
+                z = sess.h("Sar", host, z, amount=dtype.fractional_precision)
+            return z
+
+        if x.is_host:
+            return LV(x.plc, "tensor", dtype, on_host(x.host, x.v, w.v))
+        px, pw = self._public(x), self._public(w)
+        if x.is_mir or (px is not None and pw is not None):
+            host = x.plc.owners[0]
+            z = on_host(host, HV(host, px), HV(host, pw))
+            return LV(x.plc, "tensor", dtype, MV(x.plc, z.v))
+        if dtype is None or not dtype.is_fixed:
+            raise MooseRuntimeError(f"replicated DepthwiseConv on {dtype}")
+        r = fxp.dwconv(sess, x.v, w.v, px, pw, dtype.fractional_precision, **geom)
+        return LV(x.plc, "tensor", dtype, r)
+
     def op_Permute(self, op, ins):
         return self._shape_op(op, ins[0], "Permute", axes=tuple(op.attrs["axes"]))
 

@@ -328,6 +328,35 @@ def _im2col(nb, a, kernel_shape, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1
     return R.im2col_torch(a, geom, data_format, nb)
 
 
+@prim("DepthwiseConv")
+def _dwconv(nb, x, w, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1), data_format="NCHW"):
+    """Depthwise convolution of a rank-4 x with w = [C*mult, 1, KH, KW] (R.dwconv): ring
+    tensors through the native stencil kernel, plain float tensors through
+    ``torch.nn.functional.conv2d(groups=C)``."""
+    if _is_rt(x) or _is_rt(w):
+        if not (_is_rt(x) and _is_rt(w)):
+            raise TypeError("DepthwiseConv: a ring tensor and a plain tensor do not combine")
+        return R.dwconv(x, w, strides, pads, dilations, data_format, nb)
+    if nb:
+        raise ValueError("DepthwiseConv of plain tensors takes no batch dims")
+    g = R.dwconv_geometry(tuple(x.shape), tuple(w.shape), strides, pads, dilations, data_format)
+    C, (pt, pl, pb, pr) = g[1], g[9:13]
+    nhwc = data_format == "NHWC"
+    xc = x.permute(0, 3, 1, 2) if nhwc else x
+    xc = torch.nn.functional.pad(xc, (pl, pr, pt, pb))
+    y = torch.nn.functional.conv2d(xc, w.to(xc.dtype), stride=tuple(strides),
+                                   dilation=tuple(dilations), groups=C)
+    return y.permute(0, 2, 3, 1).contiguous() if nhwc else y
+
+
+@prim("DepthwiseConvCross")
+def _dwconv_cross(nb, x0, x1, w0, w1, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1),
+                  data_format="NCHW"):
+    """The replicated local product of a depthwise convolution, x0 * (w0 + w1) + x1 * w0 over
+    the taps in one pass (R.dwconv_cross)."""
+    return R.dwconv_cross(x0, x1, w0, w1, strides, pads, dilations, data_format, nb)
+
+
 @prim("StridedSlice")
 def _strided_slice(nb, a, slices):
     if _is_rt(a):

@@ -300,7 +300,7 @@ class StackedSession(Session):
     # per-party primitives that run over a pair-stacked base (every slot independent)
     _PAIR_SLOTWISE = ("WeightedSum", "BitExtract", "BitSplit", "Slice", "Im2Col", "Permute")
     # slot-wise with one public operand, the same for both share vectors
-    _PAIR_SLOTWISE_PUB = ("MulLeading",)
+    _PAIR_SLOTWISE_PUB = ("MulLeading", "DepthwiseConv")
 
     @staticmethod
     def _pair_base(v0, v1):
@@ -925,6 +925,12 @@ class StackedSession(Session):
             if v is not None:
                 return PV(plc, v)
         return PV(plc, R.dot_cross(x0.v, x1.v, y0.v, y1.v, nb=1 + nbatch))
+
+    def p_dwconv_cross(self, plc, x0, x1, w0, w1, geom):
+        """The three parties' local products of a depthwise convolution, x_p * (w_p + w_{p+1})
+        + x_{p+1} * w_p over the taps, in one launch (R.dwconv_cross): the share vectors --
+        the views of a share-pair buffer included -- are read in place."""
+        return PV(plc, R.dwconv_cross(x0.v, x1.v, w0.v, w1.v, nb=1, **geom))
 
     def end_evaluation(self, ok=True):
         """Drop per-evaluation caches (prepared GEMM operands hold device memory and must
