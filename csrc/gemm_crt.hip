@@ -246,23 +246,28 @@ struct Words<u128> {
 
 // centered residue of the signed element whose little-endian 32-bit words are x[0..NW-1]
 template <int NW>
-__device__ __forceinline__ int residue(const uint32_t (&x)[NW], const uint32_t (&w)[4],
-                                       uint32_t neg, float p, float rcp) {
+__device__ __forceinline__ float residue_f(const uint32_t (&x)[NW], const uint32_t (&w)[4],
+                                           uint32_t neg, float p, float rcp) {
   uint32_t s = (x[NW - 1] >> 31) * neg;
 #pragma unroll
   for (int q = 0; q < NW; ++q) s = __builtin_amdgcn_udot4(x[q], w[q], s, false);
   const float fs = (float)s;  // < 2^20: exact
   const float qt = __builtin_rintf(fs * rcp);  // p odd: s/p is never within 1/(2p) of k + 1/2
-  return (int)__builtin_fmaf(-qt, p, fs);      // in [-(p-1)/2, (p-1)/2]
+  return __builtin_fmaf(-qt, p, fs);           // in [-(p-1)/2, (p-1)/2]
+}
+template <int NW>
+__device__ __forceinline__ int residue(const uint32_t (&x)[NW], const uint32_t (&w)[4],
+                                       uint32_t neg, float p, float rcp) {
+  return (int)residue_f<NW>(x, w, neg, p, rcp);
 }
 
 // Two residues at once: the fp32 scaling and the multiply-subtract as packed instructions
 // (v_pk_mul_f32, v_pk_fma_f32: one issue for both elements); the same values as residue().
 typedef float f2 __attribute__((ext_vector_type(2)));
 template <int NW>
-__device__ __forceinline__ void residue2(const uint32_t (&xa)[NW], const uint32_t (&xb)[NW],
+__device__ __forceinline__ f2 residue2_f(const uint32_t (&xa)[NW], const uint32_t (&xb)[NW],
                                          const uint32_t (&w)[4], uint32_t neg, float p,
-                                         float rcp, int& ra, int& rb) {
+                                         float rcp) {
   uint32_t sa = 0, sb = 0;
 #pragma unroll
   for (int q = 0; q < NW; ++q) {
@@ -277,9 +282,47 @@ __device__ __forceinline__ void residue2(const uint32_t (&xa)[NW], const uint32_
   f2 qt = fs * (f2){rcp, rcp};
   qt.x = __builtin_rintf(qt.x);
   qt.y = __builtin_rintf(qt.y);
-  const f2 r = __builtin_elementwise_fma(-qt, (f2){p, p}, fs);
+  return __builtin_elementwise_fma(-qt, (f2){p, p}, fs);
+}
+template <int NW>
+__device__ __forceinline__ void residue2(const uint32_t (&xa)[NW], const uint32_t (&xb)[NW],
+                                         const uint32_t (&w)[4], uint32_t neg, float p,
+                                         float rcp, int& ra, int& rb) {
+  const f2 r = residue2_f<NW>(xa, xb, w, neg, p, rcp);
   ra = (int)r.x;
   rb = (int)r.y;
+}
+
+// The residue of a sum of two ring elements from the two elements' residues.  With S(.) the
+// signed representative the residues are taken of, S(a + b mod 2^w) = S(a) + S(b) + kappa 2^w,
+// kappa = top(a) + top(b) - carry - top(a + b) in {-1, 0, 1} (the carry out of bit w - 1
+// minus the carry into it), and 2^w = -neg (mod p) (PrepTab::neg, A's with the folded inverse).
+// So the sum's centred residue is that of ra + rb - kappa neg: an add, one fma and the
+// rounding of residue(), about half a residue pass; |ra + rb - kappa neg| <= 2 (p - 1) keeps
+// s/p at least 1/(2p) - 2^-21 from k + 1/2 for odd p.  p = 256 (neg = 0): a tie rounds to
+// either neighbour, both the same byte.
+__host__ __device__ inline int crt_sum_kappa(uint32_t ta, uint32_t tb, uint32_t ts) {  // top words
+  const uint32_t carry = ((ta & tb) | ((ta | tb) & ~ts)) >> 31;
+  return (int)(ta >> 31) + (int)(tb >> 31) - (int)carry - (int)(ts >> 31);
+}
+__host__ __device__ inline float crt_combine_f(float ra, float rb, float kappa, float neg,
+                                               float p, float rcp) {
+  const float fs = __builtin_fmaf(kappa, -neg, ra + rb);
+  const float qt = __builtin_rintf(fs * rcp);
+  return __builtin_fmaf(-qt, p, fs);
+}
+__host__ __device__ inline int crt_combine(int ra, int rb, int kappa, uint32_t neg, float p,
+                                           float rcp) {
+  return (int)crt_combine_f((float)ra, (float)rb, (float)kappa, (float)neg, p, rcp);
+}
+// two elements in packed instructions (the PK instance); the same values
+__host__ __device__ inline f2 crt_combine2(f2 ra, f2 rb, f2 kappa, float neg, float p,
+                                           float rcp) {
+  const f2 fs = __builtin_elementwise_fma(kappa, (f2){-neg, -neg}, ra + rb);
+  f2 qt = fs * (f2){rcp, rcp};
+  qt.x = __builtin_rintf(qt.x);
+  qt.y = __builtin_rintf(qt.y);
+  return __builtin_elementwise_fma(-qt, (f2){p, p}, fs);
 }
 
 // One thread = (tile, k-step, image row r, 16-byte chunk c) of every residue plane.
@@ -402,9 +445,9 @@ struct ShareSrc {
   uint64_t nonce = 0;
   mxd::KeySrc key;          // one key: the stream of r
 };
-// Kernel form.  The thread holds ONE image's 16 elements and turns them into the next in
-// place: phase 0 = r, 1 = x - r, 2 = the sum of the two, 3 = zero.  Image e of the side
-// (byte offset off[e]) is emitted in phase ph[e]; a sum with the zero slot is its other slot.
+// Kernel form.  Image e of the side (byte offset off[e]) holds phase ph[e]: 0 = r, 1 = x - r,
+// 2 = the sum of the two, 3 = zero; a sum with the zero slot is its other slot.  A phase may
+// belong to several images or to none.
 struct SrcPlan {
   const void* x;
   int kind, pad;
@@ -424,6 +467,10 @@ struct SrcPlan {
 // workgroup barrier: a wave's LDS operations complete in order), so every block is
 // generated once.  A wave is 4 rows x 4 chunks x 4 owners: per modulus it stores four 256 B
 // runs (k_crt_prep: one of 1 KB).  Rows past R hold zeros, as k_crt_prep's.
+// The thread holds r and v = x - r (the plain operand is read once) and walks the moduli
+// once: the residues of r and of v are full passes, the sum image's are combined from the
+// two (crt_combine, with the element's kappa), the zero image's are zero bytes; each goes
+// to every image of its phase.
 template <bool TRANS, int ROWS, bool PK>
 __global__ void __launch_bounds__(256)
     k_crt_prep_src(const SrcPlan s, const mxd::KeySrc keys, int64_t R, int64_t K,
@@ -461,7 +508,7 @@ __global__ void __launch_bounds__(256)
     const bool live = row < R;
     const int64_t t = row / ROWS;
     const int r = (int)(row % ROWS);
-    uint32_t v[16][NW];
+    uint32_t rr[16][NW], v[16][NW];
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {  // blocks of elements 4 jj + (0..3), one per lane of the quad
       uint32_t w[16];
@@ -475,74 +522,128 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const uint4 e = xw[p][((lane & ~3) | u) ^ p];
-        v[4 * jj + u][0] = live ? e.x : 0u;
-        v[4 * jj + u][1] = live ? e.y : 0u;
-        v[4 * jj + u][2] = live ? e.z : 0u;
-        v[4 * jj + u][3] = live ? e.w : 0u;
+        rr[4 * jj + u][0] = live ? e.x : 0u;
+        rr[4 * jj + u][1] = live ? e.y : 0u;
+        rr[4 * jj + u][2] = live ? e.z : 0u;
+        rr[4 * jj + u][3] = live ? e.w : 0u;
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
+    // the other slot v = x - r (r and x - r are each other's mask) and the kappa of r + v
+    // (the 16 plain values are loaded before any is encoded: the loads are in flight together)
+    float kf[16];
+    T xp[16];
+    if (s.kind == MX_SHARE_F64) {
+      double d[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        d[j] = live ? ((const double*)s.x)[i0 + 64 * p + j * istep] : 0.0;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) xp[j] = mxf::share_plain<T>(MX_SHARE_F64, d, j, s.scale);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        xp[j] = live ? mxf::share_plain<T>(s.kind, s.x, i0 + 64 * p + j * istep, s.scale) : (T)0;
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      T h = 0;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) h |= (T)rr[j][w] << (32 * w);
+      const T x = xp[j];
+      const T other = mxf::share_masked<T>(s.kind, x, h);
+#pragma unroll
+      for (int w = 0; w < NW; ++w) v[j][w] = (uint32_t)(other >> (32 * w));
+      kf[j] = (float)crt_sum_kappa(rr[j][NW - 1], v[j][NW - 1],
+                                   (uint32_t)((T)(h + other) >> (32 * (NW - 1))));
+    }
     const int64_t boff = (t * nkb + kb) * (int64_t)(ROWS * BK) + img_off(r, c);
-    auto emit = [&](int8_t* base) __attribute__((always_inline)) {
-      {  // p = 256: the low byte (times the folded inverse)
-        int rr[16];
+    bool has[4];  // the phases some image takes
 #pragma unroll
-        for (int j = 0; j < 16; ++j) rr[j] = (int)(v[j][0] * tab.mul0);
-        v4i o;
+    for (int ph = 0; ph < 4; ++ph)
+      has[ph] = s.ph[0] == ph || s.ph[1] == ph || s.ph[2] == ph || s.ph[3] == ph;
+    const bool do_r = has[0] || has[2], do_v = has[1] || has[2];
+    auto put = [&](int ph, int64_t ioff, const v4i o) __attribute__((always_inline)) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) o[u] = (int)pack4(rr[4 * u], rr[4 * u + 1], rr[4 * u + 2], rr[4 * u + 3]);
-        *(v4i*)base = o;
-      }
-      for (int i = 1; i < n; ++i) {
-        const uint32_t w[4] = {tab.w[i][0], tab.w[i][1], tab.w[i][2], tab.w[i][3]};
-        const uint32_t neg = tab.neg[i];
-        const float pf = (float)tab.p[i], rcp = tab.rcp[i];
-        int rr[16];
+      for (int e = 0; e < 4; ++e)
+        if (s.ph[e] == ph) *(v4i*)(out + s.off[e] + ioff + boff) = o;
+    };
+    auto pack16 = [](const int (&q)[16]) __attribute__((always_inline)) {
+      v4i o;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) o[u] = (int)pack4(q[4 * u], q[4 * u + 1], q[4 * u + 2], q[4 * u + 3]);
+      return o;
+    };
+    const v4i zero = {0, 0, 0, 0};
+    {  // p = 256: the low byte (times the folded inverse); the sum's is the low bytes' sum
+      int q[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) q[j] = (int)(rr[j][0] * tab.mul0);
+      put(0, 0, pack16(q));
+#pragma unroll
+      for (int j = 0; j < 16; ++j) q[j] = (int)(v[j][0] * tab.mul0);
+      put(1, 0, pack16(q));
+#pragma unroll
+      for (int j = 0; j < 16; ++j) q[j] = (int)((rr[j][0] + v[j][0]) * tab.mul0);
+      put(2, 0, pack16(q));
+      put(3, 0, zero);
+    }
+    for (int i = 1; i < n; ++i) {
+      const uint32_t w[4] = {tab.w[i][0], tab.w[i][1], tab.w[i][2], tab.w[i][3]};
+      const uint32_t neg = tab.neg[i];
+      const float pf = (float)tab.p[i], rcp = tab.rcp[i];
+      const int64_t ioff = i * plane;
+      const float nf = (float)neg;
+      auto res4 = [&](const uint32_t (&x)[16][NW], int u, float (&f)[4])
+                      __attribute__((always_inline)) {
         if constexpr (PK) {
 #pragma unroll
-          for (int j = 0; j < 16; j += 2)
-            residue2<NW>(v[j], v[j + 1], w, neg, pf, rcp, rr[j], rr[j + 1]);
+          for (int j = 0; j < 4; j += 2) {
+            const f2 g = residue2_f<NW>(x[4 * u + j], x[4 * u + j + 1], w, neg, pf, rcp);
+            f[j] = g.x;
+            f[j + 1] = g.y;
+          }
         } else {
 #pragma unroll
-          for (int j = 0; j < 16; ++j) rr[j] = residue<NW>(v[j], w, neg, pf, rcp);
+          for (int j = 0; j < 4; ++j) f[j] = residue_f<NW>(x[4 * u + j], w, neg, pf, rcp);
         }
-        v4i o;
+      };
+      // four elements at a time through all three, so that only their residues are held
+      v4i o_r, o_v, o_s;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) o[u] = (int)pack4(rr[4 * u], rr[4 * u + 1], rr[4 * u + 2], rr[4 * u + 3]);
-        *(v4i*)(base + i * plane) = o;
+      for (int u = 0; u < 4; ++u) {
+        float fr[4], fv[4], fs[4];
+        if (do_r) {
+          res4(rr, u, fr);
+          o_r[u] = (int)pack4((int)fr[0], (int)fr[1], (int)fr[2], (int)fr[3]);
+        }
+        if (do_v) {
+          res4(v, u, fv);
+          o_v[u] = (int)pack4((int)fv[0], (int)fv[1], (int)fv[2], (int)fv[3]);
+        }
+        if (has[2]) {  // both residues are at hand
+          if constexpr (PK) {
+#pragma unroll
+            for (int j = 0; j < 4; j += 2) {
+              const f2 g = crt_combine2((f2){fr[j], fr[j + 1]}, (f2){fv[j], fv[j + 1]},
+                                        (f2){kf[4 * u + j], kf[4 * u + j + 1]}, nf, pf, rcp);
+              fs[j] = g.x;
+              fs[j + 1] = g.y;
+            }
+          } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              fs[j] = crt_combine_f(fr[j], fv[j], kf[4 * u + j], nf, pf, rcp);
+          }
+          o_s[u] = (int)pack4((int)fs[0], (int)fs[1], (int)fs[2], (int)fs[3]);
+        }
       }
-    };
-    // the held slot h becomes the other one, x - h (r and x - r are each other's mask), or
-    // the two slots' sum h + (x - h)
-    auto step = [&](bool sum) __attribute__((always_inline)) {
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        T h = 0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) h |= (T)v[j][w] << (32 * w);
-        const T x = live ? mxf::share_plain<T>(s.kind, s.x, i0 + 64 * p + j * istep, s.scale) : (T)0;
-        const T other = mxf::share_masked<T>(s.kind, x, h);
-        h = sum ? (T)(h + other) : other;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) v[j][w] = (uint32_t)(h >> (32 * w));
-      }
-    };
-#pragma nounroll
-    for (int ph = 0; ph < 4; ++ph) {
-      if (s.ph[0] != ph && s.ph[1] != ph && s.ph[2] != ph && s.ph[3] != ph) continue;
-      if (ph == 1) step(false);
-      if (ph == 2) step(true);
-      if (ph == 3) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-#pragma unroll
-          for (int w = 0; w < NW; ++w) v[j][w] = 0;
-      }
-#pragma nounroll
-      for (int e = 0; e < 4; ++e)
-        if (s.ph[e] == ph) emit(out + s.off[e] + boff);
+      put(0, ioff, o_r);
+      put(1, ioff, o_v);
+      put(2, ioff, o_s);
+      put(3, ioff, zero);
     }
   }
 }
@@ -1777,6 +1878,29 @@ int mx_crt_tables4(int words, int n, uint32_t* wd_out, uint32_t* rd_out) {
     for (int d = 0; d < 3; ++d) rd_out[g * 3 + d] = t.r4.rd[g][d];
   }
   return t.r4.groups;
+}
+
+// Host run of the share-source prep's sum-image combine (tests check it against integers):
+// out[k] = the byte k_crt_prep_src stores for modulus i of the n from the residues ra[k],
+// rb[k] of the two slots and the element's kappa[k].  side 0: the A' tables and the packed
+// form (crt_combine2), side 1: the B' tables and the scalar form, as the kernel's instances.
+int mx_crt_combine(int words, int n, int side, int i, int64_t count, const int32_t* ra,
+                   const int32_t* rb, const int32_t* kappa, int8_t* out) {
+  if ((words != 1 && words != 2) || n < 1 || n > kMaxMod || i < 0 || i >= n || (side & ~1))
+    return -2;
+  const Tables& t = tables_for(words, n);
+  const PrepTab& tab = side ? t.pb : t.pa;
+  const float p = (float)tab.p[i], rcp = tab.rcp[i];
+  for (int64_t k = 0; k < count; ++k) {
+    if (side) {
+      out[k] = (int8_t)crt_combine(ra[k], rb[k], kappa[k], tab.neg[i], p, rcp);
+    } else {
+      const f2 f = crt_combine2((f2){(float)ra[k], 0.f}, (f2){(float)rb[k], 0.f},
+                                (f2){(float)kappa[k], 0.f}, (float)tab.neg[i], p, rcp);
+      out[k] = (int8_t)(int)f.x;
+    }
+  }
+  return 0;
 }
 
 int mxh_gemm_crt(int words, int64_t batch, int64_t M, int64_t N, int64_t K, const void* A0,

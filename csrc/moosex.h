@@ -225,6 +225,9 @@ void mx_set_gemm_crt(int mode);
 int mx_crt_moduli(int words, int64_t kprime);
 int mx_crt_tables(int words, int n, int32_t* p, uint8_t* wa, uint8_t* wb, int32_t* nega,
                   int32_t* negb, uint16_t* W, uint16_t* Mw);
+// host run of the share-source prep's sum-image combine for modulus i (side 0: A', 1: B')
+int mx_crt_combine(int words, int n, int side, int i, int64_t count, const int32_t* ra,
+                   const int32_t* rb, const int32_t* kappa, int8_t* out);
 
 // Fused stacked-session protocols (rss_fused.h).  s0/out0/out1 are [3, n] slot
 // vectors (party p holds out0[p] = z_p and out1[p] = z_{p+1}).
