@@ -74,6 +74,17 @@ int mx_im2col(int dev, int elem_bytes, const void* in, void* out, int64_t slots,
               int64_t in_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH,
               int64_t KW, int64_t sh, int64_t sw, int64_t pt, int64_t pl, int64_t dh,
               int64_t dw, int64_t OH, int64_t OW, int nhwc, void* stream);
+// col2im, the exact adjoint of mx_im2col and the scatter-sum of a transposed convolution:
+// in[slots, N*OH*OW, C*KH*KW] (im2col's row and column order) of elem_bytes-wide ring elements
+// (8 or 16; 1-byte bit tensors return -2) -> out[slots, N, C, H, W] (nhwc: [slots, N, H, W,
+// C]), out[n, c, y, x] = the wrapping sum of in[(n, oh, ow), (c, kh, kw)] over the taps with
+// oh*sh + kh*dh - pt == y and ow*sw + kw*dw - pl == x.  Entries whose tap lies in the padding
+// are dropped; a pixel no window reaches is zero.  Input slots are in_slot_stride elements
+// apart (a slot view of a larger buffer is read in place), output slots are dense.
+int mx_col2im(int dev, int elem_bytes, const void* in, void* out, int64_t slots,
+              int64_t in_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH,
+              int64_t KW, int64_t sh, int64_t sw, int64_t pt, int64_t pl, int64_t dh,
+              int64_t dw, int64_t OH, int64_t OW, int nhwc, void* stream);
 // Depthwise 2-D convolution in Z_2^64 / Z_2^128 (elem_bytes 8 / 16), wrapping:
 //   out[s][n, oh, ow, c*mult + j] = sum_{kh,kw} X[s][n, oh*sh + kh*dh - pt, ow*sw + kw*dw - pl, c]
 //                                               * Wt[s][c*mult + j, kh, kw]

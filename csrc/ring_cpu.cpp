@@ -349,6 +349,39 @@ void im2col_cpu(const T* in, T* out, int64_t slots, int64_t in_slot_stride, int6
   });
 }
 
+// col2im (moosex.h mx_col2im): every image pixel gathers the patch-matrix entries whose tap
+// lands on it; parallel over the image rows (s, n, y)
+template <class T>
+void col2im_cpu(const T* in, T* out, int64_t slots, int64_t in_slot_stride, int64_t N,
+                int64_t C, int64_t H, int64_t W, int64_t KH, int64_t KW, int64_t sh, int64_t sw,
+                int64_t pt, int64_t pl, int64_t dh, int64_t dw, int64_t OH, int64_t OW,
+                int nhwc) {
+  const int64_t K = C * KH * KW;
+  const int64_t sN = C * H * W, sH = nhwc ? W * C : W, sW = nhwc ? C : 1, sC = nhwc ? 1 : H * W;
+  parallel_for(slots * N * H, std::max<int64_t>(1, 4096 / (W * K)), [=](int64_t b, int64_t e) {
+    for (int64_t g = b; g < e; ++g) {
+      const int64_t y = g % H, n = (g / H) % N, s = g / (H * N);
+      const T* src = in + s * in_slot_stride + n * OH * OW * K;
+      T* dst = out + (s * N + n) * sN + y * sH;
+      for (int64_t x = 0; x < W; ++x)
+        for (int64_t c = 0; c < C; ++c) {
+          T acc = 0;
+          for (int64_t kh = 0; kh < KH; ++kh) {
+            const int64_t ty = y + pt - kh * dh;
+            if (ty < 0 || ty % sh || ty / sh >= OH) continue;
+            for (int64_t kw = 0; kw < KW; ++kw) {
+              const int64_t tx = x + pl - kw * dw;
+              if (tx < 0 || tx % sw || tx / sw >= OW) continue;
+              const int64_t col = nhwc ? (kh * KW + kw) * C + c : (c * KH + kh) * KW + kw;
+              acc += src[(ty / sh * OW + tx / sw) * K + col];
+            }
+          }
+          dst[x * sW + c * sC] = acc;
+        }
+    }
+  });
+}
+
 // depthwise convolution (moosex.h mx_dwconv): the arithmetic of k_dwconv in plain loops; the
 // cross mode's w0 + w1 is formed once per weight element
 template <class T>
@@ -529,6 +562,36 @@ int mx_im2col(int dev, int elem_bytes, const void* in, void* out, int64_t slots,
       return 0;
     default: return -2;
   }
+}
+
+int mx_col2im(int dev, int elem_bytes, const void* in, void* out, int64_t slots,
+              int64_t in_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH,
+              int64_t KW, int64_t sh, int64_t sw, int64_t pt, int64_t pl, int64_t dh,
+              int64_t dw, int64_t OH, int64_t OW, int nhwc, void* stream) {
+  if (OH <= 0 || OW <= 0 || KH <= 0 || KW <= 0 || sh <= 0 || sw <= 0 || dh <= 0 || dw <= 0 ||
+      pt < 0 || pl < 0 || N < 0 || C < 0 || H < 0 || W < 0 || slots < 0 || in_slot_stride < 0)
+    return -3;
+  if (elem_bytes != 8 && elem_bytes != 16) return -2;
+  // every tap coordinate y + pt - kh*dh (and its w twin) has to fit an int: the kernels
+  // compute them in 32 bits
+  const int64_t lim = 0x7fffffff;
+  const int64_t dims[] = {N, C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW};
+  for (int64_t d : dims)
+    if (d > lim) return -3;
+  if (H + pt > lim || W + pl > lim || (KH - 1) * dh > lim || (KW - 1) * dw > lim ||
+      KH * KW > lim)
+    return -3;
+  if (dev)
+    return mxh_col2im(elem_bytes, in, out, slots, in_slot_stride, N, C, H, W, KH, KW, sh, sw, pt,
+                      pl, dh, dw, OH, OW, nhwc, stream);
+  if (slots * N * C * H * W == 0) return 0;
+  if (elem_bytes == 8)
+    col2im_cpu((const u64*)in, (u64*)out, slots, in_slot_stride, N, C, H, W, KH, KW, sh, sw, pt,
+               pl, dh, dw, OH, OW, nhwc);
+  else
+    col2im_cpu((const u128*)in, (u128*)out, slots, in_slot_stride, N, C, H, W, KH, KW, sh, sw,
+               pt, pl, dh, dw, OH, OW, nhwc);
+  return 0;
 }
 
 int mx_dwconv(int dev, int elem_bytes, const void* x0, const void* x1, const void* w0,

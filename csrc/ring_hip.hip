@@ -2047,6 +2047,116 @@ static int dwconv_launch(const void* x0, const void* x1, const void* w0, const v
   return 0;
 }
 
+// col2im (moosex.h mx_col2im): the adjoint of k_im2col, as an output-stationary gather -- no
+// atomics and no scatter, so the wrapping sums equal the CPU twin's bit for bit.  The output
+// image is rows x inner: inner = the C channels (NHWC, rows (n, y, x)) or the W columns of one
+// channel (NCHW, rows (n, c, y)); a lane owns V adjacent inner outputs of a row (V = 2 for u64
+// with an even inner extent: every store is 16 bytes), adjacent lanes are adjacent in c (NHWC)
+// or x (NCHW), and the lane strides over rows.  Per output the lane walks the KH*KW taps: a
+// tap contributes when y + pt - kh*dh is a non-negative multiple of sh whose quotient oh is
+// below OH (and its w twin).  NHWC: a wave reads contiguous channel runs of one patch-matrix
+// row, 16 bytes per lane; NCHW lanes read K elements apart (correct, uncoalesced).  A block is
+// blockDim.x inner lanes x 256 / blockDim.x rows.  Slots are blockIdx.z, read at in_slot and
+// written densely.  I: the index type, 32-bit when every extent is below 2^31.
+template <class I>
+struct Col2imP {
+  I in_slot, o_slot;  // slot strides in elements
+  I K, rows;          // patch-matrix row length; output rows
+  int C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW, nhwc;
+};
+
+template <class T, class I, int V>
+__global__ void __launch_bounds__(256) k_col2im(const T* __restrict__ in, T* __restrict__ out,
+                                                Col2imP<I> p) {
+  using U = typename std::make_unsigned<I>::type;
+  const unsigned bx = blockDim.x, by = blockDim.y;
+  const unsigned inner = (unsigned)(p.nhwc ? p.C : p.W);
+  // V == 2 only with an even inner extent: both outputs are inside, or neither
+  const unsigned i0 = (blockIdx.x * bx + threadIdx.x) * V;
+  if (i0 >= inner) return;
+  const T* __restrict__ src = in + (I)blockIdx.z * p.in_slot;
+  T* __restrict__ dst = out + (I)blockIdx.z * p.o_slot;
+  for (I row = (I)(blockIdx.y * by + threadIdx.y); row < p.rows; row += (I)(gridDim.y * by)) {
+    U n;
+    int y, x, c = 0;
+    if (p.nhwc) {
+      const U q = (U)row / (U)p.W;
+      x = (int)((U)row - q * (U)p.W);
+      n = q / (U)p.H;
+      y = (int)(q - n * (U)p.H);
+    } else {
+      const U q = (U)row / (U)p.H;
+      y = (int)((U)row - q * (U)p.H);
+      n = q / (U)p.C;
+      c = (int)(q - n * (U)p.C);
+      x = (int)i0;
+    }
+    const I nbase = (I)n * (I)p.OH * (I)p.OW;
+    Im2colVec<T, V> acc;
+#pragma unroll
+    for (int j = 0; j < V; ++j) acc.v[j] = (T)0;
+    for (int kh = 0; kh < p.KH; ++kh) {
+      const int ty = y + p.pt - kh * p.dh;
+      if (ty < 0) break;  // ty only falls with kh
+      const unsigned oh = (unsigned)ty / (unsigned)p.sh;
+      if (oh * (unsigned)p.sh != (unsigned)ty || oh >= (unsigned)p.OH) continue;
+      const I rbase = nbase + (I)oh * (I)p.OW;
+      if (p.nhwc) {
+        for (int kw = 0; kw < p.KW; ++kw) {
+          const int tx = x + p.pl - kw * p.dw;
+          if (tx < 0) break;
+          const unsigned ow = (unsigned)tx / (unsigned)p.sw;
+          if (ow * (unsigned)p.sw != (unsigned)tx || ow >= (unsigned)p.OW) continue;
+          const I si = (rbase + (I)ow) * p.K + (I)(kh * p.KW + kw) * (I)p.C + (I)i0;
+          const Im2colVec<T, V> r = *reinterpret_cast<const Im2colVec<T, V>*>(src + si);
+#pragma unroll
+          for (int j = 0; j < V; ++j) acc.v[j] += r.v[j];
+        }
+      } else {
+        const I cbase = ((I)c * (I)p.KH + (I)kh) * (I)p.KW;
+        for (int kw = 0; kw < p.KW; ++kw) {
+#pragma unroll
+          for (int j = 0; j < V; ++j) {
+            const int tx = x + j + p.pl - kw * p.dw;
+            if (tx < 0) continue;
+            const unsigned ow = (unsigned)tx / (unsigned)p.sw;
+            if (ow * (unsigned)p.sw != (unsigned)tx || ow >= (unsigned)p.OW) continue;
+            acc.v[j] += src[(rbase + (I)ow) * p.K + cbase + (I)kw];
+          }
+        }
+      }
+    }
+    *reinterpret_cast<Im2colVec<T, V>*>(dst + row * (I)inner + (I)i0) = acc;
+  }
+}
+
+template <class T, class I, int V>
+static int col2im_launch(const void* in, void* out, int64_t slots, int64_t in_slot_stride,
+                         int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH, int64_t KW,
+                         int64_t sh, int64_t sw, int64_t pt, int64_t pl, int64_t dh, int64_t dw,
+                         int64_t OH, int64_t OW, int nhwc, void* stream) {
+  const int64_t inner = nhwc ? C : W, rows = nhwc ? N * H * W : N * C * H;
+  // inner lanes of a block: no more than the inner extent needs
+  int bx = 64;
+  while (bx > 1 && (bx / 2) * V >= inner) bx /= 2;
+  const int by = 256 / bx;
+  const int64_t gx = (inner + (int64_t)bx * V - 1) / ((int64_t)bx * V);
+  // the row grid is capped at 65,536 rows, as k_im2col's; a lane strides over the rest
+  const int64_t gy = std::min<int64_t>((rows + by - 1) / by, 65536 / by);
+  Col2imP<I> p;
+  p.in_slot = (I)in_slot_stride;
+  p.o_slot = (I)(N * C * H * W);
+  p.K = (I)(C * KH * KW);
+  p.rows = (I)rows;
+  p.C = (int)C, p.H = (int)H, p.W = (int)W, p.KH = (int)KH, p.KW = (int)KW;
+  p.sh = (int)sh, p.sw = (int)sw, p.pt = (int)pt, p.pl = (int)pl, p.dh = (int)dh;
+  p.dw = (int)dw, p.OH = (int)OH, p.OW = (int)OW, p.nhwc = nhwc;
+  hipLaunchKernelGGL((k_col2im<T, I, V>), dim3((unsigned)gx, (unsigned)gy, (unsigned)slots),
+                     dim3(bx, by), 0, S(stream), (const T*)in, (T*)out, p);
+  MX_LAUNCH_CHECK();
+  return 0;
+}
+
 // party-batched twins of the per-party sessions' local kernels (party_batch.h)
 MX_X3_GS(k_binary2<u64>, d_binary2<u64>);
 MX_X3_GS(k_binary2<u128>, d_binary2<u128>);
@@ -2349,6 +2459,41 @@ int mxh_im2col(int elem_bytes, const void* in, void* out, int64_t slots, int64_t
     default: return -2;
   }
 #undef MX_IM2COL
+}
+
+int mxh_col2im(int elem_bytes, const void* in, void* out, int64_t slots, int64_t in_slot_stride,
+               int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH, int64_t KW, int64_t sh,
+               int64_t sw, int64_t pt, int64_t pl, int64_t dh, int64_t dw, int64_t OH,
+               int64_t OW, int nhwc, void* stream) {
+  const int64_t K = C * KH * KW, n_out = N * C * H * W;
+  if (slots <= 0 || n_out <= 0) return 0;
+  const int64_t dims[] = {N, C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW};
+  for (int64_t d : dims)
+    if (d < 0 || d > 0x7fffffff) return -3;
+  if (OH <= 0 || OW <= 0 || sh <= 0 || sw <= 0 || slots > 65535 || in_slot_stride < 0)
+    return -3;
+  const int64_t in_extent = (slots - 1) * in_slot_stride + N * OH * OW * K;
+  // 32-bit indices below 2^31 elements, less the overshoot of a lane's last loop step
+  const int64_t lim = (1ll << 31) - (1ll << 23);
+  const bool small = in_extent < lim && slots * n_out < lim;
+#define MX_COL2IM(T, V)                                                                       \
+  return small ? col2im_launch<T, int32_t, V>(in, out, slots, in_slot_stride, N, C, H, W, KH, \
+                                              KW, sh, sw, pt, pl, dh, dw, OH, OW, nhwc,       \
+                                              stream)                                         \
+               : col2im_launch<T, int64_t, V>(in, out, slots, in_slot_stride, N, C, H, W, KH, \
+                                              KW, sh, sw, pt, pl, dh, dw, OH, OW, nhwc, stream)
+  switch (elem_bytes) {
+    case 8:
+      // 16-byte stores need an even inner extent; NHWC's 16-byte loads an aligned input too
+      if ((nhwc ? C : W) % 2 == 0 && ((uintptr_t)out & 15) == 0 &&
+          (!nhwc || (((uintptr_t)in & 15) == 0 && in_slot_stride % 2 == 0))) {
+        MX_COL2IM(u64, 2);
+      }
+      MX_COL2IM(u64, 1);
+    case 16: MX_COL2IM(u128, 1);
+    default: return -2;
+  }
+#undef MX_COL2IM
 }
 
 int mxh_dwconv(int elem_bytes, const void* x0, const void* x1, const void* w0, const void* w1,

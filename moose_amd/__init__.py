@@ -83,7 +83,9 @@ from moose_amd.edsl.base import sum  # noqa: F401,A004
 from moose_amd.edsl.base import transpose  # noqa: F401
 from moose_amd.edsl.base import zeros  # noqa: F401
 from moose_amd.edsl.base import avg_pool2d  # noqa: F401
+from moose_amd.edsl.base import col2im  # noqa: F401
 from moose_amd.edsl.base import conv2d  # noqa: F401
+from moose_amd.edsl.base import conv_transpose2d  # noqa: F401
 from moose_amd.edsl.base import depthwise_conv2d  # noqa: F401
 from moose_amd.edsl.base import im2col  # noqa: F401
 from moose_amd.edsl.base import max_pool2d  # noqa: F401

@@ -81,6 +81,13 @@ _OPS = {
                    "pads": list(o.pads), "dilations": list(o.dilations),
                    "data_format": o.data_format},
     ),
+    "Col2ImOperation": (
+        "Col2Im",
+        ["x"],
+        lambda o: {"image_shape": list(o.image_shape), "kernel_shape": list(o.kernel_shape),
+                   "strides": list(o.strides), "pads": list(o.pads),
+                   "dilations": list(o.dilations), "data_format": o.data_format},
+    ),
     "PermuteOperation": ("Permute", ["x"], lambda o: {"axes": list(o.axes)}),
     "DepthwiseConvOperation": (
         "DepthwiseConv",

@@ -78,7 +78,8 @@ _SAME_SHAPE_OPS = {"Cast", "Identity", "Relu", "Sigmoid", "Abs", "Neg", "Exp", "
 def _static_shape(op, shapes):
     """Shape inference over what is statically known (tensor constants and the shape-class
     operators downstream of them), recorded in ``shapes``; rejects an Im2Col whose input is
-    not rank 4 or whose output would be empty, a Permute whose axes do not match the rank
+    not rank 4 or whose output would be empty, a Col2Im whose matrix does not match its
+    geometry, a Permute whose axes do not match the rank
     and a Dot whose inner dimensions differ (a convolution's channel mismatch)."""
     import numpy as np
 
@@ -111,6 +112,11 @@ def _static_shape(op, shapes):
             g = R.im2col_geometry(ins[0], a["kernel_shape"], a["strides"], a["pads"],
                                   a["dilations"], a["data_format"])
             shp = (g[0] * g[-2] * g[-1], g[1] * g[4] * g[5])
+        elif kind == "Col2Im":
+            g = R.col2im_geometry(ins[0], tuple(a["image_shape"]), a["kernel_shape"],
+                                  a["strides"], a["pads"], a["dilations"], a["data_format"])
+            shp = (g[0], g[2], g[3], g[1]) if a["data_format"] == "NHWC" \
+                else (g[0], g[1], g[2], g[3])
         elif kind == "DepthwiseConv":
             if len(ins) != 2 or ins[1] is None or ins[1][:1] == ("shape",):
                 if len(ins[0]) != 4:

@@ -84,6 +84,8 @@ OPERATION_TABLE = [
     ("SumOperation", ["axis"]),
     ("TransposeOperation", []),
     ("Im2ColOperation", ["kernel_shape", "strides", "pads", "dilations", "data_format"]),
+    ("Col2ImOperation", ["image_shape", "kernel_shape", "strides", "pads", "dilations",
+                         "data_format"]),
     ("PermuteOperation", ["axes"]),
     ("DepthwiseConvOperation", ["strides", "pads", "dilations", "data_format"]),
 ]

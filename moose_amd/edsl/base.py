@@ -801,6 +801,90 @@ def conv2d(x, w, bias=None, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1),
     return y
 
 
+def col2im(cols, image_shape, kernel_shape, strides=(1, 1), pads=(0, 0, 0, 0),
+           dilations=(1, 1), data_format="NCHW", placement=None):
+    """The exact adjoint of :func:`im2col`: the patch matrix ``cols`` (``[N*OH*OW, C*KH*KW]``,
+    im2col's row and column order) summed into the image ``[N, C, H, W]`` (NHWC: ``[N, H, W,
+    C]``) of ``image_shape = (C, H, W)``: every pixel is the sum of the entries whose tap lands
+    on it, entries in the padding are dropped and a pixel no window reaches is zero.  The
+    batch size comes from the rows."""
+    if not isinstance(image_shape, (tuple, list)) or len(image_shape) != 3 or \
+            not all(isinstance(i, int) and i > 0 for i in image_shape):
+        raise ValueError("`col2im`: `image_shape` must be 3 positive ints (C, H, W), found "
+                         f"{image_shape!r}")
+    c, h, w = image_shape
+    shape = (None, c, h, w) if data_format != "NHWC" else (None, h, w, c)
+    _c, _h, _w, oh, ow = _conv_geometry("col2im", shape, kernel_shape, strides, pads, dilations,
+                                        data_format)
+    n = None
+    cs = cols.static_shape
+    if cs is not None:
+        k = c * kernel_shape[0] * kernel_shape[1]
+        if len(cs) != 2 or (cs[1] is not None and cs[1] != k):
+            raise ValueError(f"`col2im` expects a patch matrix [N*{oh * ow}, {k}], found shape "
+                             f"{tuple(cs)}")
+        if cs[0] is not None and cs[0] >= 0:
+            if cs[0] % (oh * ow):
+                raise ValueError(f"`col2im`: {cs[0]} rows are not a multiple of the {oh}x{ow} "
+                                 f"windows of a {h}x{w} image")
+            n = cs[0] // (oh * ow)
+    e = _expr("col2im", [cols], cols.vtype, placement, image_shape=list(image_shape),
+              kernel_shape=list(kernel_shape), strides=list(strides), pads=list(pads),
+              dilations=list(dilations), data_format=data_format)
+    e.static_shape = (n, c, h, w) if data_format == "NCHW" else (n, h, w, c)
+    return e
+
+
+def conv_transpose2d(x, w, bias=None, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1),
+                     output_padding=(0, 0), data_format="NCHW", placement=None,
+                     input_shape=None, weight_shape=None):
+    """Transposed 2-D convolution (ONNX ``ConvTranspose``, ``group = 1``) of ``x`` (rank 4,
+    ``data_format``) with ``w`` of shape ``[C, OC, KH, KW]`` (+ ``bias`` of shape ``[OC]``); the
+    result has the input's ``data_format`` and the spatial size ``(H - 1)*sh + dh*(KH - 1) + 1
+    - pt - pb + output_padding[0]`` (width alike).  One ``dot`` of the pixels with the weight,
+    then :func:`col2im` -- the adjoint of the patch gather, a sum over shares -- into the
+    output image: the forward geometry of that image with the same attributes is exactly
+    ``H x W`` while ``output_padding < strides``.  Static shapes as :func:`conv2d`."""
+    if data_format not in ("NCHW", "NHWC"):
+        raise ValueError("`conv_transpose2d`: data_format must be 'NCHW' or 'NHWC', found "
+                         f"{data_format!r}")
+    wc, oc, kh, kw = _weight_shape("conv_transpose2d", w, weight_shape, "[C, OC, KH, KW]")
+    xs = _window_input("conv_transpose2d", x, input_shape, data_format)
+    _conv_geometry("conv_transpose2d", None, (kh, kw), strides, pads, dilations, data_format)
+    if not isinstance(output_padding, (tuple, list)) or len(output_padding) != 2 or \
+            not all(isinstance(i, int) for i in output_padding):
+        raise ValueError("`conv_transpose2d`: `output_padding` must be a list/tuple of 2 ints, "
+                         f"found {output_padding!r}")
+    if not all(0 <= o < s for o, s in zip(output_padding, strides)):
+        raise ValueError("`conv_transpose2d`: output_padding must be non-negative and below "
+                         f"the strides, found {tuple(output_padding)} with strides "
+                         f"{tuple(strides)}")
+    c, h, wd = (xs[1:] if data_format == "NCHW" else (xs[3], xs[1], xs[2]))
+    if c != wc:
+        raise ValueError(f"`conv_transpose2d`: input has {c} channels, but `w` "
+                         f"{(wc, oc, kh, kw)} expects {wc} (w.shape[0])")
+    (sh, sw), (pt, pl, pb, pr), (dh, dw) = strides, pads, dilations
+    oht = (h - 1) * sh + dh * (kh - 1) + 1 - pt - pb + output_padding[0]
+    owt = (wd - 1) * sw + dw * (kw - 1) + 1 - pl - pr + output_padding[1]
+    if oht <= 0 or owt <= 0:
+        raise ValueError(f"`conv_transpose2d`: pads {tuple(pads)} leave no output "
+                         f"({oht}x{owt})")
+    if data_format == "NCHW":
+        xr = reshape(permute(x, (0, 2, 3, 1), placement), [-1, c], placement)
+        wm = reshape(w, [c, oc * kh * kw], placement)
+    else:  # columns in the patch matrix's (kh, kw, oc) order
+        xr = reshape(x, [-1, c], placement)
+        wm = reshape(permute(w, (0, 2, 3, 1), placement), [c, kh * kw * oc], placement)
+    cols = dot(xr, wm, placement)
+    y = col2im(cols, (oc, oht, owt), (kh, kw), strides, pads, dilations, data_format, placement)
+    static = (xs[0], oc, oht, owt) if data_format == "NCHW" else (xs[0], oht, owt, oc)
+    y.static_shape = static
+    if bias is not None:
+        y = add(y, _channel_bias(bias, oc, data_format, placement), placement)
+        y.static_shape = static
+    return y
+
+
 def _pool_taps(fn, x, kernel_shape, strides, pads, data_format, placement, input_shape):
     """([M, KH*KW] or [M, KH*KW, C] tap matrix, tap axis, result builder) of a pooling."""
     strides = tuple(kernel_shape) if strides is None else strides

@@ -57,6 +57,8 @@ _OPS = {
     "strided_slice": ("StridedSliceOperation", ["x"], "strided_slice", ["slices"]),
     "im2col": ("Im2ColOperation", ["x"], "im2col",
                ["kernel_shape", "strides", "pads", "dilations", "data_format"]),
+    "col2im": ("Col2ImOperation", ["x"], "col2im",
+               ["image_shape", "kernel_shape", "strides", "pads", "dilations", "data_format"]),
     "permute": ("PermuteOperation", ["x"], "permute", ["axes"]),
     "depthwise_conv": ("DepthwiseConvOperation", ["x", "w"], "depthwise_conv",
                        ["strides", "pads", "dilations", "data_format"]),

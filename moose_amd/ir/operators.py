@@ -133,6 +133,12 @@ EXTENSION_OPERATORS = {
     # linear): the GEMM that follows is the ordinary fixed-point Dot
     "Im2Col": [("kernel_shape", "ints"), ("strides", "ints"), ("pads", "ints"),
                ("dilations", "ints"), ("data_format", "str")],
+    # the exact adjoint of Im2Col, and the scatter-sum of a transposed convolution: a patch
+    # matrix [N*OH*OW, C*KH*KW] in Im2Col's order -> the image [N, C, H, W] (NHWC: [N, H, W,
+    # C]) of image_shape = (C, H, W), every pixel the sum of the entries whose tap lands on
+    # it.  N comes from the rows.  Linear, so share-wise on replicated values
+    "Col2Im": [("image_shape", "ints"), ("kernel_shape", "ints"), ("strides", "ints"),
+               ("pads", "ints"), ("dilations", "ints"), ("data_format", "str")],
     # general axis permutation (Transpose reverses all axes); share-wise
     "Permute": [("axes", "ints")],
     # depthwise 2-D convolution of a rank-4 NCHW / NHWC x with the ONNX depthwise weight

@@ -2,7 +2,8 @@
 
 The reference has no convolution; this predictor is this framework's own.  A graph is a
 chain of ``Conv`` (any ``group`` that divides the channels: ``group = C`` is the depthwise
-operator, other groups a composition of per-group products), ``Relu`` / ``Sigmoid``, ``MaxPool`` / ``AveragePool``,
+operator, other groups a composition of per-group products), ``ConvTranspose`` (``group = 1``, explicit ``pads`` and ``output_padding``: a ``dot`` of the
+pixels followed by the ``col2im`` sum), ``Relu`` / ``Sigmoid``, ``MaxPool`` / ``AveragePool``,
 ``Flatten`` (or ``Reshape`` to ``[N, -1]``), ``Gemm`` / ``MatMul`` + ``Add`` and a final
 ``Softmax``.  The model input is rank 4, NCHW.  Inside the MPC the activations are NHWC from
 the first convolution on, so no permutation ever runs on shares: the first ``im2col`` reads
@@ -60,8 +61,9 @@ def hwc_rows(w, c, h, w_):
 
 
 def conv_layers_from_onnx(model):
-    """-> (input (C, H, W), layers): each layer a dict with ``op`` in conv / relu / sigmoid /
-    maxpool / avgpool / flatten / dense / softmax and its parameters (ONNX layouts)."""
+    """-> (input (C, H, W), layers): each layer a dict with ``op`` in conv / convtranspose /
+    relu / sigmoid / maxpool / avgpool / flatten / dense / softmax and its parameters (ONNX
+    layouts)."""
     dims = model.graph.input[0].type.tensor_type.shape.dim
     if len(dims) != 4:
         raise ValueError("a convolutional predictor expects a rank-4 [batch, C, H, W] model input")
@@ -100,6 +102,32 @@ def conv_layers_from_onnx(model):
                            "strides": _ints(node, "strides", (1, 1)),
                            "pads": _ints(node, "pads", (0, 0, 0, 0)),
                            "dilations": _ints(node, "dilations", (1, 1))})
+        elif op == "ConvTranspose":
+            group = _int(node, "group", 1)
+            if group != 1:
+                raise _unsupported(node, f"group={group}: only group=1 is supported")
+            ap = find_attribute(node, "auto_pad", enforce=False)
+            if ap is not None and ap.s not in (b"", b"NOTSET"):
+                raise _unsupported(node, f"auto_pad={ap.s.decode()}")
+            if _ints(node, "output_shape", ()):
+                raise _unsupported(node, "an explicit output_shape (give pads and "
+                                         "output_padding instead)")
+            if len(node.input) < 2 or node.input[1] not in init:
+                raise _unsupported(node, "its weight is not an initializer")
+            w = np.asarray(init[node.input[1]], dtype=np.float64)
+            if w.ndim != 4:
+                raise _unsupported(node, f"weight of shape {w.shape} is not 2-D")
+            if w.shape[0] != channels:
+                raise _unsupported(node, f"a weight of shape {w.shape} does not match "
+                                         f"{channels} input channels")
+            channels = w.shape[1]
+            b = init[node.input[2]] if len(node.input) > 2 else np.zeros(w.shape[1])
+            layers.append({"op": "convtranspose", "w": w,
+                           "b": np.asarray(b, np.float64).reshape(-1),
+                           "strides": _ints(node, "strides", (1, 1)),
+                           "pads": _ints(node, "pads", (0, 0, 0, 0)),
+                           "dilations": _ints(node, "dilations", (1, 1)),
+                           "output_padding": _ints(node, "output_padding", (0, 0))})
         elif op in ("Relu", "Sigmoid"):
             layers.append({"op": op.lower()})
         elif op == "MaxPool":
@@ -149,7 +177,7 @@ def conv_layers_from_onnx(model):
             raise _unsupported(node, "not an operator of a convolutional predictor")
     if any(l["op"] == "softmax" for l in layers[:-1]):
         raise ValueError("unsupported ONNX graph: Softmax is only supported as the final node")
-    if not any(l["op"] == "conv" for l in layers):
+    if not any(l["op"] in ("conv", "convtranspose") for l in layers):
         raise ValueError("no Conv node found in the ONNX graph")
     return chw, layers
 
@@ -175,7 +203,7 @@ class ConvNetwork(Predictor):
         fmt, flat = "NCHW", None
         for l in self.layers:
             op = l["op"]
-            if op in ("conv", "maxpool", "avgpool") and flat is not None:
+            if op in ("conv", "convtranspose", "maxpool", "avgpool") and flat is not None:
                 raise ValueError(f"unsupported ONNX graph: {op} after Flatten")
             if op == "conv":
                 oc, wc, kh, kw = l["w"].shape
@@ -191,6 +219,21 @@ class ConvNetwork(Predictor):
                 else:  # columns (kh, kw, c)
                     l["wm"] = l["w"].transpose(2, 3, 1, 0).reshape(-1, oc)
                 h, w = _out_hw(h, w, (kh, kw), l["strides"], l["pads"], l["dilations"])
+                c, fmt = oc, "NHWC"
+            elif op == "convtranspose":
+                wc, oc, kh, kw = l["w"].shape
+                if wc != c:
+                    raise ValueError(f"ConvTranspose weight {l['w'].shape} does not match {c} "
+                                     "channels")
+                l.update(fmt=fmt, chw=(c, h, w), kernel=(kh, kw))
+                # the pixels times [C, (kh, kw, oc)]: the NHWC patch matrix of the output
+                l["wm"] = l["w"].transpose(0, 2, 3, 1).reshape(c, -1)
+                h, w = _out_hw_t(h, w, (kh, kw), l["strides"], l["pads"], l["dilations"],
+                                 l.setdefault("output_padding", (0, 0)))
+                if not all(0 <= o < s for o, s in zip(l["output_padding"], l["strides"])):
+                    raise ValueError(f"ConvTranspose output_padding {l['output_padding']} is "
+                                     f"not below the strides {l['strides']}")
+                l["out_chw"] = (oc, h, w)
                 c, fmt = oc, "NHWC"
             elif op in ("maxpool", "avgpool"):
                 l.update(fmt=fmt, chw=(c, h, w))
@@ -239,6 +282,15 @@ class ConvNetwork(Predictor):
                 y = pm.add(pm.dot(cols, const(l["wm"])), const(l["b"]))
                 oh, ow = _out_hw(h, w, l["kernel"], l["strides"], l["pads"], l["dilations"])
                 x = pm.reshape(y, [-1, oh, ow, l["w"].shape[0]])
+            elif op == "convtranspose":
+                # pm.conv_transpose2d's composition on NHWC, the weight re-ordered at load: a
+                # dot of the pixels, then the col2im sum into the output image
+                if l["fmt"] == "NCHW":
+                    x = pm.permute(x, (0, 2, 3, 1))
+                cols = pm.dot(pm.reshape(x, [-1, l["chw"][0]]), const(l["wm"]))
+                y = pm.col2im(cols, l["out_chw"], l["kernel"], l["strides"], l["pads"],
+                              l["dilations"], "NHWC")
+                x = pm.add(y, const(l["b"]))
             elif op in ("maxpool", "avgpool"):
                 c, h, w = l["chw"]
                 shape = (None, c, h, w) if l["fmt"] == "NCHW" else (None, h, w, c)
@@ -266,6 +318,8 @@ class ConvNetwork(Predictor):
             if l["op"] == "conv":
                 h, w = _out_hw(h, w, l["kernel"], l["strides"], l["pads"], l["dilations"])
                 c = l["w"].shape[0]
+            elif l["op"] == "convtranspose":
+                c, h, w = l["out_chw"]
             elif l["op"] in ("maxpool", "avgpool"):
                 h, w = _out_hw(h, w, l["kernel"], l["strides"], l.get("pads", (0, 0, 0, 0)),
                                (1, 1))
@@ -278,3 +332,10 @@ def _out_hw(h, w, kernel, strides, pads, dilations):
     (kh, kw), (sh, sw), (pt, pl, pb, pr), (dh, dw) = kernel, strides, pads, dilations
     return ((h + pt + pb - dh * (kh - 1) - 1) // sh + 1,
             (w + pl + pr - dw * (kw - 1) - 1) // sw + 1)
+
+
+def _out_hw_t(h, w, kernel, strides, pads, dilations, output_padding):
+    """Spatial size of a ConvTranspose output."""
+    (kh, kw), (sh, sw), (pt, pl, pb, pr), (dh, dw) = kernel, strides, pads, dilations
+    return ((h - 1) * sh + dh * (kh - 1) + 1 - pt - pb + output_padding[0],
+            (w - 1) * sw + dw * (kw - 1) + 1 - pl - pr + output_padding[1])

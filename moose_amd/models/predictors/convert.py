@@ -2,8 +2,8 @@
 
 Parity: reference ``pymoose/pymoose/predictors/onnx_convert.py:8-92``: PyTorch and
 tf2onnx exports are neural networks (convolutional ones, which the reference does not have,
-when the graph has a ``Conv`` node); otherwise the single recognised ML operator
-(LinearRegressor / LinearClassifier / TreeEnsembleRegressor / TreeEnsembleClassifier)
+when the graph has a ``Conv`` or ``ConvTranspose`` node); otherwise the single recognised ML
+operator (LinearRegressor / LinearClassifier / TreeEnsembleRegressor / TreeEnsembleClassifier)
 decides, and graphs with several weight matrices are sklearn MLPs (classifiers have a
 ``ZipMap`` node).
 """
@@ -26,7 +26,7 @@ _SUPPORTED = {
 def from_onnx(model):
     model = load_onnx(model)
     if model.producer_name in ("pytorch", "tf2onnx"):
-        if any(n.op_type == "Conv" for n in model.graph.node):
+        if any(n.op_type in ("Conv", "ConvTranspose") for n in model.graph.node):
             return conv.ConvNetwork.from_onnx(model)
         return neural.NeuralNetwork.from_onnx(model)
     ops = [n.op_type for n in model.graph.node]

@@ -836,6 +836,93 @@ def im2col(a: RT, kernel_shape, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1,
     return out
 
 
+def col2im_geometry(cols_shape, image_chw, kernel_shape, strides=(1, 1), pads=(0, 0, 0, 0),
+                    dilations=(1, 1), data_format="NCHW"):
+    """Validate a col2im of a patch matrix ``cols_shape = [N*OH*OW, C*KH*KW]`` into an image
+    of ``image_chw = (C, H, W)`` and return :func:`im2col_geometry`'s tuple for that image,
+    with ``N`` read off the rows.  ``ValueError`` when the attributes are malformed, the
+    column count is not ``C*KH*KW`` or the rows are not a multiple of ``OH*OW``."""
+    cols_shape = tuple(int(s) for s in cols_shape)
+    if len(cols_shape) != 2:
+        raise ValueError(f"col2im expects a rank-2 patch matrix, found shape {cols_shape}")
+    if not isinstance(image_chw, (tuple, list)) or len(image_chw) != 3 or \
+            not all(isinstance(x, (int, np.integer)) and x > 0 for x in image_chw):
+        raise ValueError("col2im: `image_shape` must be 3 positive ints (C, H, W), found "
+                         f"{image_chw!r}")
+    C, H, W = (int(s) for s in image_chw)
+    shape = (1, C, H, W) if data_format != "NHWC" else (1, H, W, C)
+    try:
+        g = im2col_geometry(shape, kernel_shape, strides, pads, dilations, data_format)
+    except ValueError as e:
+        raise ValueError(str(e).replace("im2col", "col2im")) from None
+    KH, KW, OH, OW = g[4], g[5], g[14], g[15]
+    if cols_shape[1] != C * KH * KW:
+        raise ValueError(f"col2im: the patch matrix has {cols_shape[1]} columns, a {KH}x{KW} "
+                         f"kernel over {C} channels needs {C * KH * KW}")
+    if cols_shape[0] % (OH * OW):
+        raise ValueError(f"col2im: {cols_shape[0]} rows are not a multiple of the {OH}x{OW} "
+                         f"windows of a {H}x{W} image")
+    return (cols_shape[0] // (OH * OW),) + g[1:]
+
+
+def col2im_torch(d: torch.Tensor, geom, data_format, nb=0) -> torch.Tensor:
+    """col2im as a torch composition on a tensor of dims ``[nb batch dims, N*OH*OW,
+    C*KH*KW]``: ``F.fold`` into the padded image, then the crop ``[pt:pt+H, pl:pl+W]`` (which
+    takes asymmetric pads).  The path of plain host tensors."""
+    N, C, H, W, KH, KW, sh, sw, pt, pl, pb, pr, dh, dw, OH, OW = geom
+    lead = tuple(d.shape[:nb])
+    B = math.prod(lead) * N
+    if data_format == "NHWC":
+        m = d.reshape(B, OH * OW, KH * KW, C).permute(0, 3, 2, 1)
+    else:
+        m = d.reshape(B, OH * OW, C, KH * KW).permute(0, 2, 3, 1)
+    m = m.reshape(B, C * KH * KW, OH * OW)
+    img = torch.nn.functional.fold(m, (H + pt + pb, W + pl + pr), (KH, KW), dilation=(dh, dw),
+                                   padding=0, stride=(sh, sw))
+    img = img[:, :, pt:pt + H, pl:pl + W]
+    if data_format == "NHWC":
+        return img.permute(0, 2, 3, 1).reshape(lead + (N, H, W, C)).contiguous()
+    return img.reshape(lead + (N, C, H, W)).contiguous()
+
+
+def col2im(a: RT, image_chw, kernel_shape, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1),
+           data_format="NCHW", nb=0) -> RT:
+    """The exact adjoint of :func:`im2col`: the patch matrix ``[..., N*OH*OW, C*KH*KW]`` after
+    ``nb`` batch dims summed (wrapping) into the image ``[..., N, C, H, W]`` (NHWC: ``[..., N,
+    H, W, C]``) of ``image_chw = (C, H, W)``.  Entries whose tap lies in the padding are
+    dropped and a pixel no window reaches is zero.  One native launch over all batch slots
+    (``mx_col2im``), which reads a slot-strided view ([slots, ...] with dense slots) in
+    place."""
+    if a.bits not in (64, 128):
+        raise ValueError(f"col2im is arithmetic only: Z_2^64 / Z_2^128, found {a.bits} bits")
+    geom = col2im_geometry(a.shape[nb:], image_chw, kernel_shape, strides, pads, dilations,
+                           data_format)
+    N, C, H, W, KH, KW, sh, sw, pt, pl, _pb, _pr, dh, dw, OH, OW = geom
+    lead = tuple(a.shape[:nb])
+    nhwc = data_format == "NHWC"
+    out_shape = lead + ((N, H, W, C) if nhwc else (N, C, H, W))
+    if a.device.type == "meta":  # shape inference of the symbolic session
+        return empty(out_shape, a.bits, a.device)
+    d = a.data
+    w = 2 if a.bits == 128 else 1  # int64 words per element
+    slots = math.prod(lead)
+    slot = d[(0,) * nb] if nb and slots else d
+    if nb == 1 and slots and slot.is_contiguous() and d.stride(0) >= 0 and d.stride(0) % w == 0:
+        slot_stride = d.stride(0) // w
+    else:
+        d = d.contiguous()
+        slot_stride = N * OH * OW * C * KH * KW
+    out = empty(out_shape, a.bits, a.device)
+    nat.check(
+        nat.lib().mx_col2im(
+            nat.dev_of(d), 16 if a.bits == 128 else 8, nat.ptr(d), nat.ptr(out.data),
+            slots, slot_stride, N, C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW,
+            1 if nhwc else 0, nat.stream_of(d)),
+        "col2im",
+    )
+    return out
+
+
 def dwconv_geometry(x_shape, w_shape, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1),
                     data_format="NCHW"):
     """Validate a depthwise convolution of a rank-4 ``x_shape`` with the ONNX depthwise weight

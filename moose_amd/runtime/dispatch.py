@@ -210,6 +210,8 @@ for _op in ("Reshape", "ExpandDims", "Squeeze", "Transpose", "Slice", "IndexAxis
         lambda c, *xs, p=_op: _local(c, p, xs))
     kernel(_op, "rep", "rep_bit", variadic=_op == "Concat")(
         lambda c, *xs, p=_op: _local(c, p, xs))
+# Col2Im sums: arithmetic shares only
+kernel("Col2Im", "rep", "rep_ring")(lambda c, x: _local(c, "Col2Im", (x,)))
 
 
 def _local(c, prim, xs):

@@ -1507,6 +1507,13 @@ class Interpreter:
                               strides=tuple(a["strides"]), pads=tuple(a["pads"]),
                               dilations=tuple(a["dilations"]), data_format=a["data_format"])
 
+    def op_Col2Im(self, op, ins):
+        a = op.attrs
+        return self._shape_op(op, ins[0], "Col2Im", image_shape=tuple(a["image_shape"]),
+                              kernel_shape=tuple(a["kernel_shape"]),
+                              strides=tuple(a["strides"]), pads=tuple(a["pads"]),
+                              dilations=tuple(a["dilations"]), data_format=a["data_format"])
+
     def op_DepthwiseConv(self, op, ins):
         """Depthwise convolution: host tensors (float, or fixed point with the truncation
         that Dot takes) through the primitive, replicated fixed point through

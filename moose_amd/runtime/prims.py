@@ -328,6 +328,22 @@ def _im2col(nb, a, kernel_shape, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1
     return R.im2col_torch(a, geom, data_format, nb)
 
 
+@prim("Col2Im")
+def _col2im(nb, a, image_shape, kernel_shape, strides=(1, 1), pads=(0, 0, 0, 0),
+            dilations=(1, 1), data_format="NCHW"):
+    """Image [N, C, H, W] (NHWC: [N, H, W, C]) summed from the patch matrix [N*OH*OW,
+    C*KH*KW] (R.col2im, the adjoint of Im2Col): ring tensors through the native gather, plain
+    float tensors through F.fold + crop."""
+    image_shape = tuple(image_shape)
+    if _is_rt(a):
+        return R.col2im(a, image_shape, kernel_shape, strides, pads, dilations, data_format, nb)
+    if a.dtype == torch.bool:
+        raise ValueError("Col2Im sums its input: a bool tensor has no col2im")
+    geom = R.col2im_geometry(tuple(a.shape[nb:]), image_shape, kernel_shape, strides, pads,
+                             dilations, data_format)
+    return R.col2im_torch(a, geom, data_format, nb)
+
+
 @prim("DepthwiseConv")
 def _dwconv(nb, x, w, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1), data_format="NCHW"):
     """Depthwise convolution of a rank-4 x with w = [C*mult, 1, KH, KW] (R.dwconv): ring

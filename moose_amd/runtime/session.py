@@ -298,7 +298,8 @@ class StackedSession(Session):
     _PAIR_BIN = {"Add": "add", "Sub": "sub", "Xor": "xor", "And": "and", "Mul": "mul"}
 
     # per-party primitives that run over a pair-stacked base (every slot independent)
-    _PAIR_SLOTWISE = ("WeightedSum", "BitExtract", "BitSplit", "Slice", "Im2Col", "Permute")
+    _PAIR_SLOTWISE = ("WeightedSum", "BitExtract", "BitSplit", "Slice", "Im2Col", "Col2Im",
+                      "Permute")
     # slot-wise with one public operand, the same for both share vectors
     _PAIR_SLOTWISE_PUB = ("MulLeading", "DepthwiseConv")
 
