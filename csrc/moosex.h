@@ -85,6 +85,21 @@ int mx_col2im(int dev, int elem_bytes, const void* in, void* out, int64_t slots,
               int64_t in_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH,
               int64_t KW, int64_t sh, int64_t sw, int64_t pt, int64_t pl, int64_t dh,
               int64_t dw, int64_t OH, int64_t OW, int nhwc, void* stream);
+// 2-D image resize with public coordinates (nearest / bilinear), exact in the ring, no
+// truncation: in[slots, N, C, H, W] (nhwc: [slots, N, H, W, C]) of elem_bytes-wide ring
+// elements (8 or 16; 1-byte bit tensors return -2) -> out[slots, N, C, OH, OW] (nhwc: [slots,
+// N, OH, OW, C]),
+//   out[n, oy, ox, c] = sum_{a,b in {0,1}} wh_a[oy] * ww_b[ox] * in[n, ih_a[oy], iw_b[ox], c]
+// wrapping.  th / tw are the per-axis tables, int32 [3, OH] / [3, OW] holding the rows i0, i1,
+// w1 (on the device for dev != 0): w0 = 2^wb - w1 with wb = wbh / wbw (0..12), 0 <= w1 <=
+// 2^wb, and w1 = 0 where wb = 0.  wbh == wbw == 0 is a pure gather of in[.., i0h, i0w, ..].
+// The CPU entry checks the tables (-3 on an index outside the image or a weight out of
+// range); the device kernel clamps the indices.  Input slots are in_slot_stride elements
+// apart (a slot view of a larger buffer is read in place), output slots are dense.
+int mx_resize2d(int dev, int elem_bytes, const void* in, void* out, int64_t slots,
+                int64_t in_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t OH,
+                int64_t OW, const int32_t* th, const int32_t* tw, int wbh, int wbw, int nhwc,
+                void* stream);
 // Depthwise 2-D convolution in Z_2^64 / Z_2^128 (elem_bytes 8 / 16), wrapping:
 //   out[s][n, oh, ow, c*mult + j] = sum_{kh,kw} X[s][n, oh*sh + kh*dh - pt, ow*sw + kw*dw - pl, c]
 //                                               * Wt[s][c*mult + j, kh, kw]

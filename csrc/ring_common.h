@@ -271,6 +271,10 @@ int mxh_col2im(int elem_bytes, const void* in, void* out, int64_t slots, int64_t
                int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH, int64_t KW, int64_t sh,
                int64_t sw, int64_t pt, int64_t pl, int64_t dh, int64_t dw, int64_t OH,
                int64_t OW, int nhwc, void* stream);
+int mxh_resize2d(int elem_bytes, const void* in, void* out, int64_t slots,
+                 int64_t in_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t OH,
+                 int64_t OW, const int32_t* th, const int32_t* tw, int wbh, int wbw, int nhwc,
+                 void* stream);
 int mxh_dwconv(int elem_bytes, const void* x0, const void* x1, const void* w0, const void* w1,
                void* out, int64_t slots, int64_t x_slot_stride, int64_t w_slot_stride, int64_t N,
                int64_t C, int64_t H, int64_t W, int64_t mult, int64_t KH, int64_t KW, int64_t sh,

@@ -382,6 +382,41 @@ void col2im_cpu(const T* in, T* out, int64_t slots, int64_t in_slot_stride, int6
   });
 }
 
+// image resize (moosex.h mx_resize2d): every output pixel is the integer-weighted sum of its
+// four taps (one tap without a multiply when both weight widths are 0); parallel over the
+// output rows (s, n, oy)
+template <class T>
+void resize2d_cpu(const T* in, T* out, int64_t slots, int64_t in_slot_stride, int64_t N,
+                  int64_t C, int64_t H, int64_t W, int64_t OH, int64_t OW, const int32_t* th,
+                  const int32_t* tw, int wbh, int wbw, int nhwc) {
+  const int64_t sH = nhwc ? W * C : W, sW = nhwc ? C : 1, sC = nhwc ? 1 : H * W;
+  const int64_t oH = nhwc ? OW * C : OW, oW = nhwc ? C : 1, oC = nhwc ? 1 : OH * OW;
+  const bool nearest = wbh == 0 && wbw == 0;
+  parallel_for(slots * N * OH, std::max<int64_t>(1, 4096 / (OW * C)), [=](int64_t b, int64_t e) {
+    for (int64_t g = b; g < e; ++g) {
+      const int64_t oy = g % OH, n = (g / OH) % N, s = g / (OH * N);
+      const T* src = in + s * in_slot_stride + n * C * H * W;
+      T* dst = out + (s * N + n) * C * OH * OW + oy * oH;
+      const int64_t y0 = th[oy], y1 = th[OH + oy];
+      const uint32_t h1 = (uint32_t)th[2 * OH + oy], h0 = (1u << wbh) - h1;
+      for (int64_t ox = 0; ox < OW; ++ox) {
+        const int64_t x0 = tw[ox], x1 = tw[OW + ox];
+        const uint32_t w1 = (uint32_t)tw[2 * OW + ox], w0 = (1u << wbw) - w1;
+        for (int64_t c = 0; c < C; ++c) {
+          const T* p = src + c * sC;
+          T acc;
+          if (nearest)
+            acc = p[y0 * sH + x0 * sW];
+          else
+            acc = p[y0 * sH + x0 * sW] * (T)(h0 * w0) + p[y0 * sH + x1 * sW] * (T)(h0 * w1) +
+                  p[y1 * sH + x0 * sW] * (T)(h1 * w0) + p[y1 * sH + x1 * sW] * (T)(h1 * w1);
+          dst[ox * oW + c * oC] = acc;
+        }
+      }
+    }
+  });
+}
+
 // depthwise convolution (moosex.h mx_dwconv): the arithmetic of k_dwconv in plain loops; the
 // cross mode's w0 + w1 is formed once per weight element
 template <class T>
@@ -591,6 +626,40 @@ int mx_col2im(int dev, int elem_bytes, const void* in, void* out, int64_t slots,
   else
     col2im_cpu((const u128*)in, (u128*)out, slots, in_slot_stride, N, C, H, W, KH, KW, sh, sw,
                pt, pl, dh, dw, OH, OW, nhwc);
+  return 0;
+}
+
+int mx_resize2d(int dev, int elem_bytes, const void* in, void* out, int64_t slots,
+                int64_t in_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t OH,
+                int64_t OW, const int32_t* th, const int32_t* tw, int wbh, int wbw, int nhwc,
+                void* stream) {
+  if (N < 0 || C < 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || slots < 0 ||
+      in_slot_stride < 0 || wbh < 0 || wbh > 12 || wbw < 0 || wbw > 12)
+    return -3;
+  if (elem_bytes != 8 && elem_bytes != 16) return -2;
+  // the kernels hold every coordinate in 32 bits
+  const int64_t dims[] = {N, C, H, W, OH, OW};
+  for (int64_t d : dims)
+    if (d > 0x7fffffff) return -3;
+  if (slots * N * C == 0) return 0;
+  if (!th || !tw) return -3;
+  if (dev)
+    return mxh_resize2d(elem_bytes, in, out, slots, in_slot_stride, N, C, H, W, OH, OW, th, tw,
+                        wbh, wbw, nhwc, stream);
+  for (int64_t o = 0; o < OH; ++o)
+    if (th[o] < 0 || th[o] >= H || th[OH + o] < 0 || th[OH + o] >= H || th[2 * OH + o] < 0 ||
+        th[2 * OH + o] > (wbh ? 1 << wbh : 0))
+      return -3;
+  for (int64_t o = 0; o < OW; ++o)
+    if (tw[o] < 0 || tw[o] >= W || tw[OW + o] < 0 || tw[OW + o] >= W || tw[2 * OW + o] < 0 ||
+        tw[2 * OW + o] > (wbw ? 1 << wbw : 0))
+      return -3;
+  if (elem_bytes == 8)
+    resize2d_cpu((const u64*)in, (u64*)out, slots, in_slot_stride, N, C, H, W, OH, OW, th, tw,
+                 wbh, wbw, nhwc);
+  else
+    resize2d_cpu((const u128*)in, (u128*)out, slots, in_slot_stride, N, C, H, W, OH, OW, th, tw,
+                 wbh, wbw, nhwc);
   return 0;
 }
 

@@ -2157,6 +2157,118 @@ static int col2im_launch(const void* in, void* out, int64_t slots, int64_t in_sl
   return 0;
 }
 
+// image resize (moosex.h mx_resize2d), on k_col2im's plan: output-stationary, no atomics, so
+// the wrapping sums equal the CPU twin's bit for bit.  The output image is rows x inner: inner
+// = the C channels (NHWC, rows (n, oy, ox)) or the OW columns of one channel (NCHW, rows (n, c,
+// oy)); a lane owns V adjacent inner outputs of a row (V = 2 only for u64 in NHWC with an even
+// C: both outputs share their taps, every load and store is 16 bytes), adjacent lanes are
+// adjacent in c (NHWC: a wave reads contiguous channel runs of four input pixels) or in ox
+// (NCHW: a wave reads two input rows at the columns its width taps name -- neighbouring when
+// upsampling, strided when downsampling), and the lane strides over rows.  The tables th / tw
+// are int32 [3, O] (i0, i1, w1): NHWC reads both once per row, the same entries for all lanes
+// of the row; NCHW reads the width entries of its column once and the height entries per row.
+// The four weights wh_a * ww_b < 2^24 are 32-bit; with both weight widths 0 the lane copies its
+// one tap.  Indices are clamped to the image: a bad table reads a wrong pixel, never outside.
+// Slots are blockIdx.z, read at in_slot and written densely.  I: the index type, 32-bit when
+// every extent is below 2^31.
+template <class I>
+struct Resize2dP {
+  I in_slot, o_slot;  // slot strides in elements
+  I sN, sH, sW, sC;   // input strides in elements (format-dependent)
+  I rows;             // output rows
+  int C, H, W, OH, OW, wbh, wbw, nhwc;
+};
+
+template <class T, class I, int V>
+__global__ void __launch_bounds__(256) k_resize2d(const T* __restrict__ in, T* __restrict__ out,
+                                                  const int32_t* __restrict__ th,
+                                                  const int32_t* __restrict__ tw,
+                                                  Resize2dP<I> p) {
+  using U = typename std::make_unsigned<I>::type;
+  using Vec = Im2colVec<T, V>;
+  const unsigned bx = blockDim.x, by = blockDim.y;
+  const unsigned inner = (unsigned)(p.nhwc ? p.C : p.OW);
+  // V == 2 only with an even inner extent: both outputs are inside, or neither
+  const unsigned i0 = (blockIdx.x * bx + threadIdx.x) * V;
+  if (i0 >= inner) return;
+  const bool nearest = (p.wbh | p.wbw) == 0;
+  const unsigned hmax = (unsigned)p.H - 1u, wmax = (unsigned)p.W - 1u;
+  const T* __restrict__ src = in + (I)blockIdx.z * p.in_slot;
+  T* __restrict__ dst = out + (I)blockIdx.z * p.o_slot;
+  unsigned xa = 0, xb = 0, w1 = 0;
+  if (!p.nhwc) {  // the lane's column, and so its width taps, are fixed
+    xa = min((unsigned)tw[i0], wmax);
+    xb = min((unsigned)tw[(unsigned)p.OW + i0], wmax);
+    w1 = (unsigned)tw[2u * (unsigned)p.OW + i0];
+  }
+  for (I row = (I)(blockIdx.y * by + threadIdx.y); row < p.rows; row += (I)(gridDim.y * by)) {
+    unsigned oy;
+    I base;
+    if (p.nhwc) {
+      const U q = (U)row / (U)p.OW;
+      const unsigned ox = (unsigned)((U)row - q * (U)p.OW);
+      const U n = q / (U)p.OH;
+      oy = (unsigned)(q - n * (U)p.OH);
+      xa = min((unsigned)tw[ox], wmax);
+      xb = min((unsigned)tw[(unsigned)p.OW + ox], wmax);
+      w1 = (unsigned)tw[2u * (unsigned)p.OW + ox];
+      base = (I)n * p.sN + (I)i0;
+    } else {
+      const U q = (U)row / (U)p.OH;
+      oy = (unsigned)((U)row - q * (U)p.OH);
+      const U n = q / (U)p.C;
+      base = (I)n * p.sN + (I)(q - n * (U)p.C) * p.sC;
+    }
+    const unsigned ya = min((unsigned)th[oy], hmax);
+    const I ra = base + (I)ya * p.sH;
+    Vec acc = *reinterpret_cast<const Vec*>(src + ra + (I)xa * p.sW);
+    if (!nearest) {
+      const unsigned yb = min((unsigned)th[(unsigned)p.OH + oy], hmax);
+      const unsigned h1 = (unsigned)th[2u * (unsigned)p.OH + oy];
+      const unsigned h0 = (1u << p.wbh) - h1, w0 = (1u << p.wbw) - w1;
+      const I rb = base + (I)yb * p.sH;
+      const Vec r01 = *reinterpret_cast<const Vec*>(src + ra + (I)xb * p.sW);
+      const Vec r10 = *reinterpret_cast<const Vec*>(src + rb + (I)xa * p.sW);
+      const Vec r11 = *reinterpret_cast<const Vec*>(src + rb + (I)xb * p.sW);
+      const uint32_t c00 = h0 * w0, c01 = h0 * w1, c10 = h1 * w0, c11 = h1 * w1;
+#pragma unroll
+      for (int j = 0; j < V; ++j)
+        acc.v[j] = acc.v[j] * (T)c00 + r01.v[j] * (T)c01 + r10.v[j] * (T)c10 +
+                   r11.v[j] * (T)c11;
+    }
+    *reinterpret_cast<Vec*>(dst + row * (I)inner + (I)i0) = acc;
+  }
+}
+
+template <class T, class I, int V>
+static int resize2d_launch(const void* in, void* out, int64_t slots, int64_t in_slot_stride,
+                           int64_t N, int64_t C, int64_t H, int64_t W, int64_t OH, int64_t OW,
+                           const int32_t* th, const int32_t* tw, int wbh, int wbw, int nhwc,
+                           void* stream) {
+  const int64_t inner = nhwc ? C : OW, rows = nhwc ? N * OH * OW : N * C * OH;
+  // inner lanes of a block: no more than the inner extent needs
+  int bx = 64;
+  while (bx > 1 && (bx / 2) * V >= inner) bx /= 2;
+  const int by = 256 / bx;
+  const int64_t gx = (inner + (int64_t)bx * V - 1) / ((int64_t)bx * V);
+  // the row grid is capped at 65,536 rows, as k_im2col's; a lane strides over the rest
+  const int64_t gy = std::min<int64_t>((rows + by - 1) / by, 65536 / by);
+  Resize2dP<I> p;
+  p.in_slot = (I)in_slot_stride;
+  p.o_slot = (I)(N * C * OH * OW);
+  p.sN = (I)(C * H * W);
+  p.sH = (I)(nhwc ? W * C : W);
+  p.sW = (I)(nhwc ? C : 1);
+  p.sC = (I)(nhwc ? 1 : H * W);
+  p.rows = (I)rows;
+  p.C = (int)C, p.H = (int)H, p.W = (int)W, p.OH = (int)OH, p.OW = (int)OW;
+  p.wbh = wbh, p.wbw = wbw, p.nhwc = nhwc;
+  hipLaunchKernelGGL((k_resize2d<T, I, V>), dim3((unsigned)gx, (unsigned)gy, (unsigned)slots),
+                     dim3(bx, by), 0, S(stream), (const T*)in, (T*)out, th, tw, p);
+  MX_LAUNCH_CHECK();
+  return 0;
+}
+
 // party-batched twins of the per-party sessions' local kernels (party_batch.h)
 MX_X3_GS(k_binary2<u64>, d_binary2<u64>);
 MX_X3_GS(k_binary2<u128>, d_binary2<u128>);
@@ -2494,6 +2606,42 @@ int mxh_col2im(int elem_bytes, const void* in, void* out, int64_t slots, int64_t
     default: return -2;
   }
 #undef MX_COL2IM
+}
+
+int mxh_resize2d(int elem_bytes, const void* in, void* out, int64_t slots,
+                 int64_t in_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t OH,
+                 int64_t OW, const int32_t* th, const int32_t* tw, int wbh, int wbw, int nhwc,
+                 void* stream) {
+  const int64_t n_in = N * C * H * W, n_out = N * C * OH * OW;
+  if (slots <= 0 || n_out <= 0) return 0;
+  const int64_t dims[] = {N, C, H, W, OH, OW};
+  for (int64_t d : dims)
+    if (d <= 0 || d > 0x7fffffff) return -3;
+  if (slots > 65535 || in_slot_stride < 0 || !th || !tw || wbh < 0 || wbh > 12 || wbw < 0 ||
+      wbw > 12)
+    return -3;
+  const int64_t in_extent = (slots - 1) * in_slot_stride + n_in;
+  // 32-bit indices below 2^31 elements, less the overshoot of a lane's last loop step
+  const int64_t lim = (1ll << 31) - (1ll << 23);
+  const bool small = in_extent < lim && slots * n_out < lim;
+#define MX_RESIZE2D(T, V)                                                                      \
+  return small ? resize2d_launch<T, int32_t, V>(in, out, slots, in_slot_stride, N, C, H, W, OH, \
+                                                OW, th, tw, wbh, wbw, nhwc, stream)             \
+               : resize2d_launch<T, int64_t, V>(in, out, slots, in_slot_stride, N, C, H, W, OH, \
+                                                OW, th, tw, wbh, wbw, nhwc, stream)
+  switch (elem_bytes) {
+    case 8:
+      // two outputs per lane share their taps only in NHWC; 16-byte accesses need an even C
+      // and aligned buffers
+      if (nhwc && C % 2 == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)in & 15) == 0 &&
+          in_slot_stride % 2 == 0) {
+        MX_RESIZE2D(u64, 2);
+      }
+      MX_RESIZE2D(u64, 1);
+    case 16: MX_RESIZE2D(u128, 1);
+    default: return -2;
+  }
+#undef MX_RESIZE2D
 }
 
 int mxh_dwconv(int elem_bytes, const void* x0, const void* x1, const void* w0, const void* w1,

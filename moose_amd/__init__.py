@@ -89,6 +89,7 @@ from moose_amd.edsl.base import conv_transpose2d  # noqa: F401
 from moose_amd.edsl.base import depthwise_conv2d  # noqa: F401
 from moose_amd.edsl.base import im2col  # noqa: F401
 from moose_amd.edsl.base import max_pool2d  # noqa: F401
+from moose_amd.edsl.base import resize2d  # noqa: F401
 from moose_amd.edsl.base import permute  # noqa: F401
 from moose_amd.edsl.tracer import trace  # noqa: F401
 from moose_amd.edsl.tracer import trace_and_compile  # noqa: F401

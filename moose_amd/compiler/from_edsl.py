@@ -88,6 +88,14 @@ _OPS = {
                    "strides": list(o.strides), "pads": list(o.pads),
                    "dilations": list(o.dilations), "data_format": o.data_format},
     ),
+    "ResizeOperation": (
+        "Resize",
+        ["x"],
+        lambda o: {"sizes": list(o.sizes), "mode": o.mode,
+                   "coordinate_transformation_mode": o.coordinate_transformation_mode,
+                   "nearest_mode": o.nearest_mode, "scales": list(o.scales),
+                   "weight_bits": list(o.weight_bits), "data_format": o.data_format},
+    ),
     "PermuteOperation": ("Permute", ["x"], lambda o: {"axes": list(o.axes)}),
     "DepthwiseConvOperation": (
         "DepthwiseConv",

@@ -79,7 +79,7 @@ def _static_shape(op, shapes):
     """Shape inference over what is statically known (tensor constants and the shape-class
     operators downstream of them), recorded in ``shapes``; rejects an Im2Col whose input is
     not rank 4 or whose output would be empty, a Col2Im whose matrix does not match its
-    geometry, a Permute whose axes do not match the rank
+    geometry, a Resize whose input is not rank 4 or whose attributes are malformed, a Permute whose axes do not match the rank
     and a Dot whose inner dimensions differ (a convolution's channel mismatch)."""
     import numpy as np
 
@@ -117,6 +117,12 @@ def _static_shape(op, shapes):
                                   a["strides"], a["pads"], a["dilations"], a["data_format"])
             shp = (g[0], g[2], g[3], g[1]) if a["data_format"] == "NHWC" \
                 else (g[0], g[1], g[2], g[3])
+        elif kind == "Resize":
+            g = R.resize_geometry(ins[0], a["sizes"], a["mode"],
+                                  a["coordinate_transformation_mode"], a["nearest_mode"],
+                                  a["scales"], a["weight_bits"], a["data_format"])
+            shp = (g[0], g[4], g[5], g[1]) if a["data_format"] == "NHWC" \
+                else (g[0], g[1], g[4], g[5])
         elif kind == "DepthwiseConv":
             if len(ins) != 2 or ins[1] is None or ins[1][:1] == ("shape",):
                 if len(ins[0]) != 4:

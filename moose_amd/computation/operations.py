@@ -86,6 +86,8 @@ OPERATION_TABLE = [
     ("Im2ColOperation", ["kernel_shape", "strides", "pads", "dilations", "data_format"]),
     ("Col2ImOperation", ["image_shape", "kernel_shape", "strides", "pads", "dilations",
                          "data_format"]),
+    ("ResizeOperation", ["sizes", "mode", "coordinate_transformation_mode", "nearest_mode",
+                         "scales", "weight_bits", "data_format"]),
     ("PermuteOperation", ["axes"]),
     ("DepthwiseConvOperation", ["strides", "pads", "dilations", "data_format"]),
 ]

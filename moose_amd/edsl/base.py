@@ -885,6 +885,99 @@ def conv_transpose2d(x, w, bias=None, strides=(1, 1), pads=(0, 0, 0, 0), dilatio
     return y
 
 
+def resize2d(x, sizes=None, scales=None, mode="nearest",
+             coordinate_transformation_mode="half_pixel", nearest_mode="round_prefer_floor",
+             data_format="NCHW", weight_bits=None, placement=None, input_shape=None):
+    """Resize the spatial axes of ``x`` (rank 4, ``data_format``) as ONNX ``Resize`` does, in
+    ``nearest`` or (bi)``linear`` mode.  Exactly one of ``sizes = (OH, OW)`` and ``scales =
+    (scale_h, scale_w)`` is given; with ``scales`` the output size is ``floor(I * scale)`` and
+    the coordinates use the given scale.  The coordinates are public, so on a replicated
+    placement the operator is local on the shares; ``linear`` on fixed point multiplies by
+    integer weights of ``weight_bits = (wbh, wbw)`` bits per axis and truncates once by ``wbh
+    + wbw``.  The default ``weight_bits`` is, per axis, the smallest width in 0..12 at which
+    every weight is exact (2x ``half_pixel``: 2; an axis that keeps its size: 0), else 12: an
+    inexact weight is off by at most ``2^-(wb + 1)``.  Static shapes as :func:`conv2d`."""
+    from moose_amd.ops import ring as R
+
+    fn = "resize2d"
+    if data_format not in ("NCHW", "NHWC"):
+        raise ValueError(f"`{fn}`: data_format must be 'NCHW' or 'NHWC', found {data_format!r}")
+    if mode not in R.RESIZE_MODES:
+        raise ValueError(f"`{fn}`: `mode` must be one of {R.RESIZE_MODES}, found {mode!r}")
+    if coordinate_transformation_mode not in R.RESIZE_COORDS:
+        raise ValueError(f"`{fn}`: `coordinate_transformation_mode` must be one of "
+                         f"{R.RESIZE_COORDS}, found {coordinate_transformation_mode!r}")
+    if nearest_mode not in R.RESIZE_NEAREST:
+        raise ValueError(f"`{fn}`: `nearest_mode` must be one of {R.RESIZE_NEAREST}, found "
+                         f"{nearest_mode!r}")
+    if (sizes is None) == (scales is None):
+        raise ValueError(f"`{fn}`: exactly one of `sizes` and `scales` must be given, found "
+                         f"sizes={sizes!r} and scales={scales!r}")
+    xs = _window_input(fn, x, input_shape, data_format)
+    h, w = (xs[2], xs[3]) if data_format == "NCHW" else (xs[1], xs[2])
+    fracs = (None, None)
+    if sizes is not None:
+        if not isinstance(sizes, (tuple, list)) or len(sizes) != 2 or \
+                not all(isinstance(i, int) and not isinstance(i, bool) for i in sizes):
+            raise ValueError(f"`{fn}`: `sizes` must be a list/tuple of 2 ints (OH, OW), found "
+                             f"{sizes!r}")
+        if builtins.min(sizes) <= 0:
+            raise ValueError(f"`{fn}`: `sizes` must be positive, found {tuple(sizes)}")
+        oh, ow = sizes
+    else:
+        if not isinstance(scales, (tuple, list)) or len(scales) != 2 or \
+                not all(isinstance(s, (int, float)) and not isinstance(s, bool)
+                        for s in scales):
+            raise ValueError(f"`{fn}`: `scales` must be a list/tuple of 2 numbers (scale_h, "
+                             f"scale_w), found {scales!r}")
+        if not all(s > 0 and s == s and s != float("inf") for s in scales):
+            raise ValueError(f"`{fn}`: `scales` must be positive and finite, found "
+                             f"{tuple(scales)}")
+        fracs = tuple(R.resize_scale(s) for s in scales)
+        oh, ow = (int(i * s) for i, s in zip((h, w), fracs))  # floor of the exact product
+        if oh <= 0 or ow <= 0:
+            raise ValueError(f"`{fn}`: `scales` {tuple(scales)} leave no output ({oh}x{ow}) of "
+                             f"a {h}x{w} image")
+        if builtins.max(f.numerator.bit_length() for f in fracs) > 62 or \
+                builtins.max(f.denominator.bit_length() for f in fracs) > 62:
+            raise ValueError(f"`{fn}`: `scales` {tuple(scales)} are not representable as "
+                             "ratios of 62-bit integers")
+    axes = ((h, oh, fracs[0]), (w, ow, fracs[1]))
+    if weight_bits is None:
+        weight_bits = tuple(R.resize_weight_bits(i, o, mode, coordinate_transformation_mode,
+                                                 nearest_mode, s) for i, o, s in axes)
+    elif not isinstance(weight_bits, (tuple, list)) or len(weight_bits) != 2 or \
+            not all(isinstance(b, int) and not isinstance(b, bool) and
+                    0 <= b <= R.RESIZE_MAX_WEIGHT_BITS for b in weight_bits):
+        raise ValueError(f"`{fn}`: `weight_bits` must be 2 ints in 0.."
+                         f"{R.RESIZE_MAX_WEIGHT_BITS} (height, width), found {weight_bits!r}")
+    if mode == "nearest":
+        weight_bits = (0, 0)
+    dtype = x.vtype.dtype if isinstance(x.vtype, ty.TensorType) else None
+    wb = builtins.sum(weight_bits)
+    if wb and dtype is not None and dtype.is_fixedpoint:
+        # the truncation protocol is valid for |x| < 2^(k - 2); an unpinned dtype is checked
+        # against the widest ring here and against the run's ring when it is evaluated
+        ring = dtype.ring or 128
+        need = dtype.integral_precision + dtype.fractional_precision + wb
+        if need > ring - 2:
+            raise ValueError(
+                f"`{fn}`: {dtype.integral_precision} integral + {dtype.fractional_precision} "
+                f"fractional + {wb} weight bits = {need} exceed the {ring - 2} bits a "
+                f"truncation in Z_2^{ring} can take: pass a smaller `weight_bits`")
+    if wb and dtype is not None and dtype.is_boolean:
+        raise ValueError(f"`{fn}`: `mode` 'linear' on a bool tensor: a weighted sum of bits is "
+                         "not a bit")
+    sc = [] if scales is None else [fracs[0].numerator, fracs[0].denominator,
+                                    fracs[1].numerator, fracs[1].denominator]
+    e = _expr("resize", [x], x.vtype, placement, sizes=[oh, ow], mode=mode,
+              coordinate_transformation_mode=coordinate_transformation_mode,
+              nearest_mode=nearest_mode, scales=sc, weight_bits=list(weight_bits),
+              data_format=data_format)
+    e.static_shape = (xs[0], xs[1], oh, ow) if data_format == "NCHW" else (xs[0], oh, ow, xs[3])
+    return e
+
+
 def _pool_taps(fn, x, kernel_shape, strides, pads, data_format, placement, input_shape):
     """([M, KH*KW] or [M, KH*KW, C] tap matrix, tap axis, result builder) of a pooling."""
     strides = tuple(kernel_shape) if strides is None else strides

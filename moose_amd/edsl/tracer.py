@@ -59,6 +59,9 @@ _OPS = {
                ["kernel_shape", "strides", "pads", "dilations", "data_format"]),
     "col2im": ("Col2ImOperation", ["x"], "col2im",
                ["image_shape", "kernel_shape", "strides", "pads", "dilations", "data_format"]),
+    "resize": ("ResizeOperation", ["x"], "resize",
+               ["sizes", "mode", "coordinate_transformation_mode", "nearest_mode", "scales",
+                "weight_bits", "data_format"]),
     "permute": ("PermuteOperation", ["x"], "permute", ["axes"]),
     "depthwise_conv": ("DepthwiseConvOperation", ["x", "w"], "depthwise_conv",
                        ["strides", "pads", "dilations", "data_format"]),

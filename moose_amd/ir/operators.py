@@ -139,6 +139,16 @@ EXTENSION_OPERATORS = {
     # it.  N comes from the rows.  Linear, so share-wise on replicated values
     "Col2Im": [("image_shape", "ints"), ("kernel_shape", "ints"), ("strides", "ints"),
                ("pads", "ints"), ("dilations", "ints"), ("data_format", "str")],
+    # 2-D image resize with public coordinates (ONNX Resize: nearest / linear): a rank-4
+    # NCHW / NHWC tensor -> spatial size sizes = (OH, OW), every output the exact integer-
+    # weighted sum of its (up to) four taps, weights of weight_bits = (wbh, wbw) bits per
+    # axis (moose_amd.ops.ring.resize_tables).  The leaf does not truncate: a fixed-point
+    # linear result is truncated by wbh + wbw afterwards.  scales is empty (the scale is O/I)
+    # or the two given scales as exact rationals [num_h, den_h, num_w, den_w].  Linear, so
+    # share-wise on replicated values
+    "Resize": [("sizes", "ints"), ("mode", "str"), ("coordinate_transformation_mode", "str"),
+               ("nearest_mode", "str"), ("scales", "ints"), ("weight_bits", "ints"),
+               ("data_format", "str")],
     # general axis permutation (Transpose reverses all axes); share-wise
     "Permute": [("axes", "ints")],
     # depthwise 2-D convolution of a rank-4 NCHW / NHWC x with the ONNX depthwise weight

@@ -3,7 +3,9 @@
 The reference has no convolution; this predictor is this framework's own.  A graph is a
 chain of ``Conv`` (any ``group`` that divides the channels: ``group = C`` is the depthwise
 operator, other groups a composition of per-group products), ``ConvTranspose`` (``group = 1``, explicit ``pads`` and ``output_padding``: a ``dot`` of the
-pixels followed by the ``col2im`` sum), ``Relu`` / ``Sigmoid``, ``MaxPool`` / ``AveragePool``,
+pixels followed by the ``col2im`` sum), ``Resize`` (opset 11+) / ``Upsample`` (opset 7, 9) in
+``nearest`` or ``linear`` mode with constant ``scales`` / ``sizes`` (``pm.resize2d`` in the
+activation's layout), ``Relu`` / ``Sigmoid``, ``MaxPool`` / ``AveragePool``,
 ``Flatten`` (or ``Reshape`` to ``[N, -1]``), ``Gemm`` / ``MatMul`` + ``Add`` and a final
 ``Softmax``.  The model input is rank 4, NCHW.  Inside the MPC the activations are NHWC from
 the first convolution on, so no permutation ever runs on shares: the first ``im2col`` reads
@@ -53,6 +55,79 @@ def _window_attrs(node):
     return kernel, _ints(node, "strides", (1, 1)), _ints(node, "pads", (0, 0, 0, 0))
 
 
+def _str(node, name, default):
+    a = find_attribute(node, name, enforce=False)
+    return a.s.decode() if a is not None and a.s else default
+
+
+def _opset(model):
+    """Version of the default ONNX operator set the model imports (0: not stated)."""
+    return max((int(o.version) for o in model.opset_import if o.domain in ("", "ai.onnx")),
+               default=0)
+
+
+def _resize_operand(node, init, index, what):
+    """The constant input ``index`` of a Resize / Upsample node as a flat array; None when
+    it is absent, empty-named or empty."""
+    if len(node.input) <= index or not node.input[index]:
+        return None
+    if node.input[index] not in init:
+        raise _unsupported(node, f"its `{what}` input is not an initializer or a Constant")
+    v = np.asarray(init[node.input[index]]).reshape(-1)
+    return v if v.size else None
+
+
+def _resize_layer(node, init, opset):
+    """The ``resize`` layer of an ONNX ``Resize`` (opset 11+) or ``Upsample`` (7, 9) node."""
+    mode = _str(node, "mode", "nearest")
+    if node.op_type == "Upsample":
+        ctm, nearest = "asymmetric", "floor"
+        mode = "linear" if mode == "bilinear" else mode
+        a = find_attribute(node, "scales", enforce=False)
+        if a is not None and list(a.floats):  # opset 7: an attribute
+            scales, sizes = np.asarray(list(a.floats), dtype=np.float32), None
+        else:  # opset 9: an input
+            scales, sizes = _resize_operand(node, init, 1, "scales"), None
+    else:
+        if opset and opset < 11:
+            raise _unsupported(node, f"Resize of opset {opset}: opset 11 or later is supported")
+        ctm = _str(node, "coordinate_transformation_mode", "half_pixel")
+        nearest = _str(node, "nearest_mode", "round_prefer_floor")
+        if ctm == "tf_crop_and_resize":
+            raise _unsupported(node, "coordinate_transformation_mode=tf_crop_and_resize")
+        if _int(node, "antialias"):
+            raise _unsupported(node, "antialias=1")
+        if _int(node, "exclude_outside"):
+            raise _unsupported(node, "exclude_outside=1")
+        if _ints(node, "axes", ()):
+            raise _unsupported(node, "an `axes` attribute (give all four scales or sizes)")
+        policy = _str(node, "keep_aspect_ratio_policy", "stretch")
+        if policy != "stretch":
+            raise _unsupported(node, f"keep_aspect_ratio_policy={policy}")
+        scales = _resize_operand(node, init, 2, "scales")  # input 1 is roi: ignored
+        sizes = _resize_operand(node, init, 3, "sizes")
+    if mode not in ("nearest", "linear"):
+        raise _unsupported(node, f"mode={mode}: nearest and linear are supported")
+    if ctm not in ("half_pixel", "pytorch_half_pixel", "align_corners", "asymmetric"):
+        raise _unsupported(node, f"coordinate_transformation_mode={ctm}")
+    if nearest not in ("round_prefer_floor", "round_prefer_ceil", "floor", "ceil"):
+        raise _unsupported(node, f"nearest_mode={nearest}")
+    if (scales is None) == (sizes is None):
+        raise _unsupported(node, "exactly one of `scales` and `sizes` must be given")
+    given = scales if scales is not None else sizes
+    if len(given) != 4:
+        raise _unsupported(node, f"{len(given)} scales / sizes: a rank-4 input needs 4")
+    layer = {"op": "resize", "mode": mode, "ctm": ctm, "nearest_mode": nearest}
+    if scales is not None:
+        if float(scales[0]) != 1 or float(scales[1]) != 1:
+            raise _unsupported(node, f"batch / channel scales {tuple(map(float, scales[:2]))} "
+                                     "are not 1")
+        layer["scales"] = (float(scales[2]), float(scales[3]))
+    else:
+        layer["sizes_nchw"] = tuple(int(s) for s in sizes)
+    return layer
+
+
 def hwc_rows(w, c, h, w_):
     """Rows of a dense weight ``[c*h*w_, out]`` moved from the (c, h, w) flatten order of an
     NCHW activation to the (h, w, c) order of its NHWC form."""
@@ -62,7 +137,7 @@ def hwc_rows(w, c, h, w_):
 
 def conv_layers_from_onnx(model):
     """-> (input (C, H, W), layers): each layer a dict with ``op`` in conv / convtranspose /
-    relu / sigmoid / maxpool / avgpool / flatten / dense / softmax and its parameters (ONNX
+    resize / relu / sigmoid / maxpool / avgpool / flatten / dense / softmax and its parameters (ONNX
     layouts)."""
     dims = model.graph.input[0].type.tensor_type.shape.dim
     if len(dims) != 4:
@@ -71,6 +146,7 @@ def conv_layers_from_onnx(model):
     if min(chw) <= 0:
         raise ValueError(f"the model input's channel and image sizes must be static, found {chw}")
     init = dict(initializers(model))
+    opset = _opset(model)
     layers = []
     channels = chw[0]  # of the activation that reaches the next Conv
     for node in model.graph.node:
@@ -128,6 +204,15 @@ def conv_layers_from_onnx(model):
                            "pads": _ints(node, "pads", (0, 0, 0, 0)),
                            "dilations": _ints(node, "dilations", (1, 1)),
                            "output_padding": _ints(node, "output_padding", (0, 0))})
+        elif op in ("Resize", "Upsample"):
+            layer = _resize_layer(node, init, opset)
+            nc = layer.pop("sizes_nchw", None)
+            if nc is not None:
+                if nc[1] != channels:
+                    raise _unsupported(node, f"sizes {nc} change the {channels} channels "
+                                             "(batch / channel scales are not 1)")
+                layer["sizes"] = nc[2:]  # (the batch entry is the export's; the batch is free)
+            layers.append(layer)
         elif op in ("Relu", "Sigmoid"):
             layers.append({"op": op.lower()})
         elif op == "MaxPool":
@@ -203,7 +288,8 @@ class ConvNetwork(Predictor):
         fmt, flat = "NCHW", None
         for l in self.layers:
             op = l["op"]
-            if op in ("conv", "convtranspose", "maxpool", "avgpool") and flat is not None:
+            if op in ("conv", "convtranspose", "resize", "maxpool", "avgpool") and \
+                    flat is not None:
                 raise ValueError(f"unsupported ONNX graph: {op} after Flatten")
             if op == "conv":
                 oc, wc, kh, kw = l["w"].shape
@@ -235,6 +321,10 @@ class ConvNetwork(Predictor):
                                      f"not below the strides {l['strides']}")
                 l["out_chw"] = (oc, h, w)
                 c, fmt = oc, "NHWC"
+            elif op == "resize":
+                l.update(fmt=fmt, chw=(c, h, w))
+                h, w = _resize_hw(h, w, l)
+                l["out_hw"] = (h, w)
             elif op in ("maxpool", "avgpool"):
                 l.update(fmt=fmt, chw=(c, h, w))
                 h, w = _out_hw(h, w, l["kernel"], l["strides"], l.get("pads", (0, 0, 0, 0)),
@@ -291,6 +381,14 @@ class ConvNetwork(Predictor):
                 y = pm.col2im(cols, l["out_chw"], l["kernel"], l["strides"], l["pads"],
                               l["dilations"], "NHWC")
                 x = pm.add(y, const(l["b"]))
+            elif op == "resize":
+                # in the activation's own layout: no permutation runs on shares
+                c, h, w = l["chw"]
+                shape = (None, c, h, w) if l["fmt"] == "NCHW" else (None, h, w, c)
+                x = pm.resize2d(x, sizes=l.get("sizes"), scales=l.get("scales"), mode=l["mode"],
+                                coordinate_transformation_mode=l["ctm"],
+                                nearest_mode=l["nearest_mode"], data_format=l["fmt"],
+                                weight_bits=l.get("weight_bits"), input_shape=shape)
             elif op in ("maxpool", "avgpool"):
                 c, h, w = l["chw"]
                 shape = (None, c, h, w) if l["fmt"] == "NCHW" else (None, h, w, c)
@@ -320,6 +418,8 @@ class ConvNetwork(Predictor):
                 c = l["w"].shape[0]
             elif l["op"] == "convtranspose":
                 c, h, w = l["out_chw"]
+            elif l["op"] == "resize":
+                h, w = l["out_hw"]
             elif l["op"] in ("maxpool", "avgpool"):
                 h, w = _out_hw(h, w, l["kernel"], l["strides"], l.get("pads", (0, 0, 0, 0)),
                                (1, 1))
@@ -332,6 +432,20 @@ def _out_hw(h, w, kernel, strides, pads, dilations):
     (kh, kw), (sh, sw), (pt, pl, pb, pr), (dh, dw) = kernel, strides, pads, dilations
     return ((h + pt + pb - dh * (kh - 1) - 1) // sh + 1,
             (w + pl + pr - dw * (kw - 1) - 1) // sw + 1)
+
+
+def _resize_hw(h, w, l):
+    """Spatial size of a resize layer's output: its sizes, or floor(I * scale) with the scale
+    taken as its exact binary value (as pm.resize2d does)."""
+    if l.get("sizes") is not None:
+        oh, ow = (int(s) for s in l["sizes"])
+    else:
+        from fractions import Fraction
+
+        oh, ow = (int(i * Fraction(s)) for i, s in zip((h, w), l["scales"]))
+    if min(oh, ow) <= 0:
+        raise ValueError(f"Resize leaves an empty {oh}x{ow} image")
+    return oh, ow
 
 
 def _out_hw_t(h, w, kernel, strides, pads, dilations, output_padding):

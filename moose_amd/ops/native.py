@@ -38,6 +38,10 @@ _SIGS = {
     "mx_im2col": (c_int, [c_int, c_int, c_vp, c_vp, c_i64, c_i64] + [c_i64] * 14 + [c_int, c_vp]),
     # mx_im2col's parameters; in is the patch matrix, out the image
     "mx_col2im": (c_int, [c_int, c_int, c_vp, c_vp, c_i64, c_i64] + [c_i64] * 14 + [c_int, c_vp]),
+    # (dev, elem_bytes, in, out, slots, in_slot_stride, N C H W, OH OW, th, tw, wbh, wbw, nhwc,
+    #  stream)
+    "mx_resize2d": (c_int, [c_int, c_int, c_vp, c_vp, c_i64, c_i64] + [c_i64] * 6
+                    + [c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     # (dev, elem_bytes, x0 x1 w0 w1 out, slots, x_slot_stride, w_slot_stride, N C H W mult,
     #  KH KW, sh sw, pt pl, dh dw, OH OW, nhwc, stream)
     "mx_dwconv": (c_int, [c_int, c_int] + [c_vp] * 5 + [c_i64] * 3 + [c_i64] * 15

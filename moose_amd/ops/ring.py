@@ -20,9 +20,11 @@ from __future__ import annotations
 
 import builtins
 import ctypes
+import functools
 import math
 import os
 import threading
+from fractions import Fraction
 from typing import List
 from typing import Sequence
 
@@ -919,6 +921,294 @@ def col2im(a: RT, image_chw, kernel_shape, strides=(1, 1), pads=(0, 0, 0, 0), di
             slots, slot_stride, N, C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW,
             1 if nhwc else 0, nat.stream_of(d)),
         "col2im",
+    )
+    return out
+
+
+RESIZE_MODES = ("nearest", "linear")
+RESIZE_COORDS = ("half_pixel", "pytorch_half_pixel", "align_corners", "asymmetric")
+RESIZE_NEAREST = ("round_prefer_floor", "round_prefer_ceil", "floor", "ceil")
+RESIZE_MAX_WEIGHT_BITS = 12
+
+
+def resize_scale(scale):
+    """A resize scale as the exact rational of its binary value; ``None`` stays ``None`` (the
+    scale is then O/I).  Accepts a float, an int, a ``Fraction`` or a ``(num, den)`` pair."""
+    if scale is None:
+        return None
+    if isinstance(scale, (tuple, list)):
+        scale = Fraction(int(scale[0]), int(scale[1]))
+    s = Fraction(scale)
+    if s <= 0:
+        raise ValueError(f"resize: `scales` must be positive, found {scale!r}")
+    return s
+
+
+@functools.lru_cache(maxsize=1024)
+def _resize_coords(I, O, mode, ctm, nearest_mode, scale):  # noqa: E741
+    """Per output index of one axis: (i0, t) with the source coordinate i0 + t, 0 <= t < 1, per
+    the ONNX ``Resize`` definition in exact rational arithmetic, clamped to [0, I - 1].  In
+    nearest mode i0 is the chosen pixel and t is 0."""
+    s = scale if scale is not None else Fraction(O, I)
+    half = Fraction(1, 2)
+    out = []
+    for o in range(O):
+        if ctm == "half_pixel":
+            x = (o + half) / s - half
+        elif ctm == "pytorch_half_pixel":
+            x = (o + half) / s - half if O > 1 else Fraction(0)
+        elif ctm == "align_corners":
+            x = Fraction(o * (I - 1), O - 1) if O > 1 else Fraction(0)
+        else:  # asymmetric
+            x = o / s
+        x = min(max(x, Fraction(0)), Fraction(I - 1))
+        i0 = math.floor(x)
+        t = x - i0
+        if mode == "nearest":
+            if nearest_mode == "round_prefer_floor":
+                i0 += 1 if t > half else 0
+            elif nearest_mode == "round_prefer_ceil":
+                i0 += 1 if t >= half else 0
+            elif nearest_mode == "ceil":
+                i0 += 1 if t > 0 else 0
+            t = Fraction(0)
+        out.append((i0, t))
+    return tuple(out)
+
+
+def _resize_check_axis(I, O, mode, ctm, nearest_mode):  # noqa: E741
+    if mode not in RESIZE_MODES:
+        raise ValueError(f"resize: `mode` must be one of {RESIZE_MODES}, found {mode!r}")
+    if ctm not in RESIZE_COORDS:
+        raise ValueError("resize: `coordinate_transformation_mode` must be one of "
+                         f"{RESIZE_COORDS}, found {ctm!r}")
+    if nearest_mode not in RESIZE_NEAREST:
+        raise ValueError(f"resize: `nearest_mode` must be one of {RESIZE_NEAREST}, found "
+                         f"{nearest_mode!r}")
+    if I <= 0 or O <= 0:
+        raise ValueError(f"resize: sizes must be positive, found {I} -> {O}")
+
+
+def resize_weight_bits(I, O, mode="linear", coordinate_transformation_mode="half_pixel",  # noqa: E741
+                       nearest_mode="round_prefer_floor", scale=None):
+    """The smallest weight width in 0..12 at which every interpolation weight of one axis is
+    exact (2x ``half_pixel``: t in {1/4, 3/4}, so 2; nearest and an axis that keeps its size:
+    0), else 12."""
+    I, O = int(I), int(O)  # noqa: E741
+    _resize_check_axis(I, O, mode, coordinate_transformation_mode, nearest_mode)
+    coords = _resize_coords(I, O, mode, coordinate_transformation_mode, nearest_mode,
+                            resize_scale(scale))
+    for wb in range(RESIZE_MAX_WEIGHT_BITS + 1):
+        if all((t * (1 << wb)).denominator == 1 for _i, t in coords):
+            return wb
+    return RESIZE_MAX_WEIGHT_BITS
+
+
+@functools.lru_cache(maxsize=1024)
+def _resize_tables(I, O, mode, ctm, nearest_mode, scale, wb):  # noqa: E741
+    coords = _resize_coords(I, O, mode, ctm, nearest_mode, scale)
+    tab = np.zeros((3, O), dtype=np.int32)
+    for o, (i0, t) in enumerate(coords):
+        w1 = math.floor(t * (1 << wb) + Fraction(1, 2))
+        if wb == 0 and w1:  # the whole weight on the upper tap: it becomes the one tap
+            i0, w1 = min(i0 + 1, I - 1), 0
+        tab[:, o] = (i0, min(i0 + 1, I - 1), w1)
+    tab.setflags(write=False)
+    return tab
+
+
+def resize_tables(I, O, mode="linear", coordinate_transformation_mode="half_pixel",  # noqa: E741
+                  nearest_mode="round_prefer_floor", scale=None, weight_bits=0):
+    """The table of one resized axis, int32 ``[3, O]`` with the rows ``i0``, ``i1``, ``w1``:
+    output ``o`` is ``(2^wb - w1) * x[i0] + w1 * x[i1]`` with ``wb = weight_bits``.  The only
+    place that turns resize attributes into numbers -- the CPU twin, the gfx950 kernel, the
+    torch composition, shape inference and the tests' integer model all read it.  Source
+    coordinates follow the ONNX ``Resize`` definition in exact rational arithmetic (a float
+    ``scale`` is taken as its exact binary value; ``None``: O/I), are clamped to ``[0, I -
+    1]``, ``i1 = min(i0 + 1, I - 1)`` and ``w1 = floor(t * 2^wb + 1/2)``: the same table on
+    every machine.  Nearest mode has ``w1 = 0`` and ``i0`` the chosen pixel, whatever
+    ``weight_bits`` says; so has a table of width 0 (a weight that rounds to the upper tap
+    moves ``i0`` there).  The array is shared and read-only."""
+    I, O, wb = int(I), int(O), int(weight_bits)  # noqa: E741
+    _resize_check_axis(I, O, mode, coordinate_transformation_mode, nearest_mode)
+    if not 0 <= wb <= RESIZE_MAX_WEIGHT_BITS:
+        raise ValueError(f"resize: `weight_bits` must be in 0..{RESIZE_MAX_WEIGHT_BITS}, found "
+                         f"{weight_bits!r}")
+    if mode == "nearest":
+        wb = 0
+    return _resize_tables(I, O, mode, coordinate_transformation_mode, nearest_mode,
+                          resize_scale(scale), wb)
+
+
+def resize_geometry(shape, sizes, mode="nearest", coordinate_transformation_mode="half_pixel",
+                    nearest_mode="round_prefer_floor", scales=(), weight_bits=(0, 0),
+                    data_format="NCHW"):
+    """Validate a resize of a rank-4 ``shape`` to ``sizes = (OH, OW)`` and return ``(N, C, H,
+    W, OH, OW, wbh, wbw, sh, sw)``: the weight widths as the tables use them (0 in nearest
+    mode) and the two scales as exact rationals or ``None``.  ``scales`` is empty, or one
+    scale per axis (floats, or ``(num, den)`` pairs flattened to four ints, the form the
+    serialised operator carries).  ``ValueError`` names the malformed argument."""
+    if data_format not in ("NCHW", "NHWC"):
+        raise ValueError(f"resize: data_format must be 'NCHW' or 'NHWC', found {data_format!r}")
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 4:
+        raise ValueError(f"resize expects a rank-4 {data_format} tensor, found shape {shape}")
+    for name, v in (("sizes", sizes), ("weight_bits", weight_bits)):
+        if not isinstance(v, (tuple, list)) or len(v) != 2 or \
+                not all(isinstance(x, (int, np.integer)) for x in v):
+            raise ValueError(f"resize: `{name}` must be 2 ints, found {v!r}")
+    OH, OW = (int(s) for s in sizes)
+    if OH <= 0 or OW <= 0:
+        raise ValueError(f"resize: `sizes` must be positive, found {tuple(sizes)}")
+    if not isinstance(scales, (tuple, list)) or len(scales) not in (0, 2, 4):
+        raise ValueError(f"resize: `scales` must be empty or one scale per axis, found "
+                         f"{scales!r}")
+    if len(scales) == 4:
+        scales = (tuple(scales[0:2]), tuple(scales[2:4]))
+    sh, sw = (resize_scale(s) for s in scales) if len(scales) else (None, None)
+    N, C, H, W = shape if data_format == "NCHW" else (shape[0], shape[3], shape[1], shape[2])
+    if H <= 0 or W <= 0:
+        raise ValueError(f"resize: the image is empty ({H}x{W})")
+    wbh, wbw = (int(b) for b in weight_bits)
+    for I, O in ((H, OH), (W, OW)):  # noqa: E741
+        _resize_check_axis(I, O, mode, coordinate_transformation_mode, nearest_mode)
+    if not (0 <= wbh <= RESIZE_MAX_WEIGHT_BITS and 0 <= wbw <= RESIZE_MAX_WEIGHT_BITS):
+        raise ValueError(f"resize: `weight_bits` must be in 0..{RESIZE_MAX_WEIGHT_BITS}, found "
+                         f"{tuple(weight_bits)}")
+    if mode == "nearest":
+        wbh = wbw = 0
+    return N, C, H, W, OH, OW, wbh, wbw, sh, sw
+
+
+def _resize_axis_tables(geom, mode, ctm, nearest_mode):
+    N, C, H, W, OH, OW, wbh, wbw, sh, sw = geom
+    return (resize_tables(H, OH, mode, ctm, nearest_mode, sh, wbh),
+            resize_tables(W, OW, mode, ctm, nearest_mode, sw, wbw))
+
+
+def resize_torch(d: torch.Tensor, geom, mode="nearest",
+                 coordinate_transformation_mode="half_pixel",
+                 nearest_mode="round_prefer_floor", data_format="NCHW", nb=0,
+                 bits=None) -> torch.Tensor:
+    """Resize as a torch composition on a tensor of dims ``[nb batch dims, N, C, H, W,
+    trailing...]`` (or N, H, W, C): ``index_select`` of the two taps on each axis, multiply by
+    the table's weights, add.  Integer tensors (the int64 of Z_2^64, wrapping) get the integer
+    weights -- the arithmetic of the ring kernel, its A/B baseline; ``bits=128`` says that the
+    trailing dim holds the (lo, hi) words of Z_2^128, which are then summed as four 32-bit
+    limbs (a limb's weighted sum stays below 2^56) with one carry pass at the end.  Float
+    tensors get the same weights over ``2^wb``; bool and uint8 (bit) tensors only the gather
+    of nearest mode."""
+    N, C, H, W, OH, OW, wbh, wbw, _sh, _sw = geom
+    th, tw = _resize_axis_tables(geom, mode, coordinate_transformation_mode, nearest_mode)
+    hax = nb + (1 if data_format == "NHWC" else 2)
+    x = d
+    exact = not x.dtype.is_floating_point
+    limbs = bits == 128 and wbh + wbw > 0
+    if limbs:  # [..., 2] words -> [..., 4] limbs of 32 bits
+        x = torch.stack((x[..., 0] & 0xffffffff, (x[..., 0] >> 32) & 0xffffffff,
+                         x[..., 1] & 0xffffffff, (x[..., 1] >> 32) & 0xffffffff), dim=-1)
+    for ax, tab, wb in ((hax, th, wbh), (hax + 1, tw, wbw)):
+        i0 = to_device(torch.from_numpy(tab[0].astype(np.int64)), x.device)
+        a = x.index_select(ax, i0)
+        if tab[2].any():
+            if x.dtype in (torch.bool, torch.uint8):
+                raise ValueError("resize: a weighted sum of bits is not a bit; `linear` needs "
+                                 "an arithmetic tensor")
+            i1 = to_device(torch.from_numpy(tab[1].astype(np.int64)), x.device)
+            view = [1] * x.dim()
+            view[ax] = -1
+            w1 = torch.from_numpy(tab[2].astype(np.int64))
+            w0 = (1 << wb) - w1
+            if not exact:
+                w0, w1 = (w.to(x.dtype) / (1 << wb) for w in (w0, w1))
+            w0, w1 = (to_device(w, x.device).reshape(view) for w in (w0, w1))
+            a = a * w0 + x.index_select(ax, i1) * w1
+        elif wb and exact:
+            a = a * (1 << wb)
+        x = a
+    if limbs:
+        v0 = x[..., 0]
+        v1 = x[..., 1] + (v0 >> 32)
+        v2 = x[..., 2] + (v1 >> 32)
+        v3 = x[..., 3] + (v2 >> 32)
+        x = torch.stack(((v0 & 0xffffffff) | (v1 << 32), (v2 & 0xffffffff) | (v3 << 32)),
+                        dim=-1)
+    return x.contiguous()
+
+
+# The device default of resize: the stencil kernel, or the torch composition when False
+# (benchmarks/resize.py measures both; profiles/resize.md has the numbers)
+RESIZE_KERNEL = True
+
+_RESIZE_TABLES = {}
+
+
+def _resize_device_tables(key, tabs, device):
+    """The two axis tables on ``device``, made once per (geometry, device) and shared (no
+    upload per evaluation, so none inside a captured hipGraph; not cached while one is being
+    captured: the tensors would live in the graph's pool)."""
+    device = torch.device(device)
+    if device.type == "cpu":
+        return tabs
+    key = key + (str(device),)
+    hit = _RESIZE_TABLES.get(key)
+    if hit is not None:
+        return hit
+    t = tuple(to_device(torch.from_numpy(t.copy()), device) for t in tabs)
+    if not torch.cuda.is_current_stream_capturing():
+        _cache_put(_RESIZE_TABLES, key, t, 4096)
+    return t
+
+
+def _table_ptr(t):
+    return t.ctypes.data if isinstance(t, np.ndarray) else t.data_ptr()
+
+
+def resize(a: RT, sizes, mode="nearest", coordinate_transformation_mode="half_pixel",
+           nearest_mode="round_prefer_floor", scales=(), weight_bits=(0, 0),
+           data_format="NCHW", nb=0) -> RT:
+    """Resize the rank-4 ring tensor after ``nb`` batch dims to ``sizes = (OH, OW)``, exactly:
+    ``out = sum_{a,b} wh_a * ww_b * x[ih_a, iw_b]`` (wrapping) with the integer weights of
+    :func:`resize_tables`, so a ``linear`` result carries ``wbh + wbw`` more fractional bits
+    (the leaf does not truncate).  One native launch over all batch slots (``mx_resize2d``),
+    which reads a slot-strided view ([slots, ...] with dense slots) in place.  Bit tensors:
+    nearest only, through the torch gather."""
+    geom = resize_geometry(a.shape[nb:], sizes, mode, coordinate_transformation_mode,
+                           nearest_mode, scales, weight_bits, data_format)
+    N, C, H, W, OH, OW, wbh, wbw, sh, sw = geom
+    lead = tuple(a.shape[:nb])
+    nhwc = data_format == "NHWC"
+    out_shape = lead + ((N, OH, OW, C) if nhwc else (N, C, OH, OW))
+    if a.bits == 1 and mode != "nearest":
+        raise ValueError("resize: a weighted sum of bits is not a bit; `linear` needs an "
+                         "arithmetic tensor")
+    if a.device.type == "meta":  # shape inference of the symbolic session
+        return empty(out_shape, a.bits, a.device)
+    if a.bits == 1 or (a.device.type == "cuda" and not RESIZE_KERNEL):
+        return RT(resize_torch(a.data, geom, mode, coordinate_transformation_mode,
+                               nearest_mode, data_format, nb, a.bits), a.bits)
+    d = a.data
+    w = 2 if a.bits == 128 else 1  # int64 words per element
+    slots = math.prod(lead)
+    slot = d[(0,) * nb] if nb and slots else d
+    if nb == 1 and slots and slot.is_contiguous() and d.stride(0) >= 0 and d.stride(0) % w == 0:
+        slot_stride = d.stride(0) // w
+    else:
+        d = d.contiguous()
+        slot_stride = N * C * H * W
+    out = empty(out_shape, a.bits, a.device)
+    if out.data.numel() == 0:
+        return out
+    key = (H, W, OH, OW, mode, coordinate_transformation_mode, nearest_mode, sh, sw, wbh, wbw)
+    th, tw = _resize_device_tables(
+        key, _resize_axis_tables(geom, mode, coordinate_transformation_mode, nearest_mode),
+        a.device)
+    nat.check(
+        nat.lib().mx_resize2d(
+            nat.dev_of(d), 16 if a.bits == 128 else 8, nat.ptr(d), nat.ptr(out.data), slots,
+            slot_stride, N, C, H, W, OH, OW, _table_ptr(th), _table_ptr(tw), wbh, wbw,
+            1 if nhwc else 0, nat.stream_of(d)),
+        "resize2d",
     )
     return out
 

@@ -210,6 +210,9 @@ for _op in ("Reshape", "ExpandDims", "Squeeze", "Transpose", "Slice", "IndexAxis
         lambda c, *xs, p=_op: _local(c, p, xs))
     kernel(_op, "rep", "rep_bit", variadic=_op == "Concat")(
         lambda c, *xs, p=_op: _local(c, p, xs))
+# Resize: bit shares too (nearest is a gather; linear on bits raises in the primitive)
+kernel("Resize", "rep", "rep_ring")(lambda c, x: _local(c, "Resize", (x,)))
+kernel("Resize", "rep", "rep_bit")(lambda c, x: _local(c, "Resize", (x,)))
 # Col2Im sums: arithmetic shares only
 kernel("Col2Im", "rep", "rep_ring")(lambda c, x: _local(c, "Col2Im", (x,)))
 

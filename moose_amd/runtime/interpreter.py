@@ -1514,6 +1514,38 @@ class Interpreter:
                               strides=tuple(a["strides"]), pads=tuple(a["pads"]),
                               dilations=tuple(a["dilations"]), data_format=a["data_format"])
 
+    def op_Resize(self, op, ins):
+        """Image resize: the exact leaf on every kind of value (share-wise on replicated
+        ones), then, for fixed point in linear mode, the truncation by the weights' wbh + wbw
+        bits -- rep.trunc_pr on shares, Sar on a host.  Float host tensors take the weights as
+        floats in the primitive."""
+        a = op.attrs
+        attrs = dict(sizes=tuple(a["sizes"]), mode=a["mode"],
+                     coordinate_transformation_mode=a["coordinate_transformation_mode"],
+                     nearest_mode=a["nearest_mode"], scales=tuple(a["scales"]),
+                     weight_bits=tuple(a["weight_bits"]), data_format=a["data_format"])
+        y = self._shape_op(op, ins[0], "Resize", **attrs)
+        m = 0 if a["mode"] == "nearest" else int(a["weight_bits"][0]) + int(a["weight_bits"][1])
+        # (a value without a dtype is a raw ring tensor: the leaf's exact sum is its result)
+        if m == 0 or y.kind == "shape" or y.dtype is None or \
+                y.dtype.kind in ("Float32", "Float64"):
+            return y
+        if not y.dtype.is_fixed:
+            raise MooseRuntimeError(f"linear Resize with weights of {m} bits on {y.dtype}: "
+                                    "only float and fixed-point tensors")
+        bits = y.dtype.ring_bits
+        if y.dtype.integral_precision + y.dtype.fractional_precision + m > bits - 2:
+            raise MooseRuntimeError(
+                f"{op.name}: Resize of {y.dtype} with weights of {m} bits leaves no headroom "
+                f"for the truncation in Z_2^{bits}: pass a smaller `weight_bits`")
+        if y.is_host:
+            return LV(y.plc, "tensor", y.dtype, self.sess.h("Sar", y.host, y.v, amount=m))
+        if isinstance(y.v, MV):  # mirrored: a public value, truncated as on a host
+            host = y.plc.owners[0]
+            z = self.sess.h("Sar", host, HV(host, y.v.v), amount=m)
+            return LV(y.plc, "tensor", y.dtype, MV(y.plc, z.v))
+        return LV(y.plc, "tensor", y.dtype, fxp._with(y.v, rep.trunc_pr(self.sess, y.v.t, m)))
+
     def op_DepthwiseConv(self, op, ins):
         """Depthwise convolution: host tensors (float, or fixed point with the truncation
         that Dot takes) through the primitive, replicated fixed point through

@@ -344,6 +344,28 @@ def _col2im(nb, a, image_shape, kernel_shape, strides=(1, 1), pads=(0, 0, 0, 0),
     return R.col2im_torch(a, geom, data_format, nb)
 
 
+@prim("Resize")
+def _resize(nb, a, sizes, mode="nearest", coordinate_transformation_mode="half_pixel",
+            nearest_mode="round_prefer_floor", scales=(), weight_bits=(0, 0),
+            data_format="NCHW"):
+    """Rank-4 image resized to sizes = (OH, OW) with public coordinates (R.resize): ring
+    tensors through the native stencil, exactly and without truncation (a linear result has
+    weight_bits more fractional bits); plain tensors through the torch composition over the
+    same tables -- floats with the weights over 2^weight_bits, bools in nearest mode only."""
+    sizes, scales, weight_bits = tuple(sizes), tuple(scales), tuple(weight_bits)
+    if _is_rt(a):
+        return R.resize(a, sizes, mode, coordinate_transformation_mode, nearest_mode, scales,
+                        weight_bits, data_format, nb)
+    geom = R.resize_geometry(tuple(a.shape[nb:nb + 4]), sizes, mode,
+                             coordinate_transformation_mode, nearest_mode, scales, weight_bits,
+                             data_format)
+    if a.dtype == torch.bool and mode != "nearest":
+        raise ValueError("Resize: a weighted sum of bits is not a bit; `linear` on a bool "
+                         "tensor")
+    return R.resize_torch(a, geom, mode, coordinate_transformation_mode, nearest_mode,
+                          data_format, nb)
+
+
 @prim("DepthwiseConv")
 def _dwconv(nb, x, w, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1), data_format="NCHW"):
     """Depthwise convolution of a rank-4 x with w = [C*mult, 1, KH, KW] (R.dwconv): ring

@@ -299,7 +299,7 @@ class StackedSession(Session):
 
     # per-party primitives that run over a pair-stacked base (every slot independent)
     _PAIR_SLOTWISE = ("WeightedSum", "BitExtract", "BitSplit", "Slice", "Im2Col", "Col2Im",
-                      "Permute")
+                      "Resize", "Permute")
     # slot-wise with one public operand, the same for both share vectors
     _PAIR_SLOTWISE_PUB = ("MulLeading", "DepthwiseConv")
 
