@@ -114,6 +114,23 @@ int mx_dwconv(int dev, int elem_bytes, const void* x0, const void* x1, const voi
               int64_t w_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t mult,
               int64_t KH, int64_t KW, int64_t sh, int64_t sw, int64_t pt, int64_t pl,
               int64_t dh, int64_t dw, int64_t OH, int64_t OW, int nhwc, void* stream);
+// The local step of a secret piecewise-linear function in Z_2^64 / Z_2^128 (elem_bytes 8 /
+// 16), wrapping.  s0 / s1: one party's components of the k stacked flags [slots, k, n] (plane j
+// of a slot at element offset j*n), x0 / x1 of the input [slots, n]; da / db: k public ring
+// elements each and ak one, on the host, elem_bytes wide, little-endian words -- they travel in
+// the kernel's arguments, so nothing is uploaded.  With G0 = sum_j da[j]*s0[j,e] and G1 the
+// same over s1,
+//   out[s][e] = G0*(x0[e] + x1[e]) + G1*x0[e] + ak*x0[e] + sum_j db[j]*s0[j,e]
+// (mx_dwconv's cross convention: own times the sum, plus next times own; over the three
+// parties a 3-out-of-3 sharing of (ak + G)*x + H).  s1 == x1 == null: plain, G0*x0 + ak*x0 +
+// sum_j db[j]*s0[j,e].  0 <= k <= MX_PWL_MAX.  Slots of s0 / s1 are s_slot_stride elements
+// apart, of x0 / x1 x_slot_stride (views of a larger buffer are read in place); output slots
+// are dense.
+#define MX_PWL_MAX 8
+int mx_pwl_cross(int dev, int elem_bytes, const void* s0, const void* s1, const void* x0,
+                 const void* x1, void* out, int64_t slots, int64_t s_slot_stride,
+                 int64_t x_slot_stride, int64_t n, int k, const uint64_t* da, const uint64_t* db,
+                 const uint64_t* ak, void* stream);
 // mx_ew_binary_slot on a0 (slot which0) and a1 (slot which1) with one public b
 int mx_ew_binary_slot2(int dev, int op, int words, const void* a0, const void* a1,
                        const void* b, int64_t nb, void* out0, void* out1, int64_t m,

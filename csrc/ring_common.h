@@ -275,6 +275,10 @@ int mxh_resize2d(int elem_bytes, const void* in, void* out, int64_t slots,
                  int64_t in_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t OH,
                  int64_t OW, const int32_t* th, const int32_t* tw, int wbh, int wbw, int nhwc,
                  void* stream);
+int mxh_pwl_cross(int elem_bytes, const void* s0, const void* s1, const void* x0, const void* x1,
+                  void* out, int64_t slots, int64_t s_slot_stride, int64_t x_slot_stride,
+                  int64_t n, int k, const uint64_t* da, const uint64_t* db, const uint64_t* ak,
+                  void* stream);
 int mxh_dwconv(int elem_bytes, const void* x0, const void* x1, const void* w0, const void* w1,
                void* out, int64_t slots, int64_t x_slot_stride, int64_t w_slot_stride, int64_t N,
                int64_t C, int64_t H, int64_t W, int64_t mult, int64_t KH, int64_t KW, int64_t sh,

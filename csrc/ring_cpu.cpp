@@ -467,6 +467,36 @@ void dwconv_cpu(const T* x0, const T* x1, const T* w0, const T* w1, T* out, int6
   });
 }
 
+// piecewise-linear local step (moosex.h mx_pwl_cross): the arithmetic of k_pwl_cross in plain
+// loops, one output element at a time
+template <class T>
+void pwl_cross_cpu(const T* s0, const T* s1, const T* x0, const T* x1, T* out, int64_t slots,
+                   int64_t s_slot_stride, int64_t x_slot_stride, int64_t n, int k,
+                   const uint64_t* da, const uint64_t* db, const uint64_t* ak) {
+  T DA[MX_PWL_MAX], DB[MX_PWL_MAX], AK;
+  std::memcpy(DA, da, sizeof(T) * k);
+  std::memcpy(DB, db, sizeof(T) * k);
+  std::memcpy(&AK, ak, sizeof(T));
+  const bool cross = x1 != nullptr;
+  parallel_for(slots * n, 1 << 12, [&](int64_t b, int64_t e) {
+    for (int64_t g = b; g < e; ++g) {
+      const int64_t s = g / n, i = g - s * n;
+      const T* f0 = s0 + s * s_slot_stride + i;
+      const T* f1 = cross ? s1 + s * s_slot_stride + i : nullptr;
+      const T a0 = x0[s * x_slot_stride + i];
+      T g0 = 0, g1 = 0, h = 0;
+      for (int j = 0; j < k; ++j) {
+        g0 += DA[j] * f0[j * n];
+        h += DB[j] * f0[j * n];
+        if (cross) g1 += DA[j] * f1[j * n];
+      }
+      T v = g0 * (cross ? a0 + x1[s * x_slot_stride + i] : a0) + AK * a0 + h;
+      if (cross) v += g1 * a0;
+      out[g] = v;
+    }
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -699,6 +729,28 @@ int mx_dwconv(int dev, int elem_bytes, const void* x0, const void* x1, const voi
       return 0;
     default: return -2;
   }
+}
+
+int mx_pwl_cross(int dev, int elem_bytes, const void* s0, const void* s1, const void* x0,
+                 const void* x1, void* out, int64_t slots, int64_t s_slot_stride,
+                 int64_t x_slot_stride, int64_t n, int k, const uint64_t* da, const uint64_t* db,
+                 const uint64_t* ak, void* stream) {
+  if (slots < 0 || n < 0 || k < 0 || k > MX_PWL_MAX || s_slot_stride < 0 || x_slot_stride < 0)
+    return -3;
+  if ((s1 == nullptr) != (x1 == nullptr)) return -3;  // cross mode takes both next components
+  if (elem_bytes != 8 && elem_bytes != 16) return -2;
+  if (slots * n == 0) return 0;
+  if (!ak || (k && (!da || !db))) return -3;
+  if (dev)
+    return mxh_pwl_cross(elem_bytes, s0, s1, x0, x1, out, slots, s_slot_stride, x_slot_stride, n,
+                         k, da, db, ak, stream);
+  if (elem_bytes == 8)
+    pwl_cross_cpu((const u64*)s0, (const u64*)s1, (const u64*)x0, (const u64*)x1, (u64*)out, slots,
+                  s_slot_stride, x_slot_stride, n, k, da, db, ak);
+  else
+    pwl_cross_cpu((const u128*)s0, (const u128*)s1, (const u128*)x0, (const u128*)x1, (u128*)out,
+                  slots, s_slot_stride, x_slot_stride, n, k, da, db, ak);
+  return 0;
 }
 
 int mx_ew_unary2(int dev, int op, int words, const void* a0, void* out0, const void* a1,

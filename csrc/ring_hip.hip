@@ -2269,6 +2269,88 @@ static int resize2d_launch(const void* in, void* out, int64_t slots, int64_t in_
   return 0;
 }
 
+// piecewise-linear local step (moosex.h mx_pwl_cross), on k_col2im's plan with one row per
+// slot: a lane owns V adjacent outputs (one u128, or two u64 when n is even and every buffer
+// is 16-byte aligned, so every load and store is 16 bytes), adjacent lanes are adjacent in
+// memory, the lane strides over the slot by the grid, and slots are blockIdx.z, read at their
+// strides and written densely.  Per output: 2k + 2 reads (k + 1 in plain mode) and one write;
+// the flag planes of a slot are n elements apart.  The public tables arrive in the kernel's
+// arguments (scalar registers, no table in memory); the loop over the k planes is unrolled to
+// MX_PWL_MAX with a uniform exit.  Wrapping sums in the CPU twin's order, so the results
+// are equal bit for bit.  I: the index type, 32-bit when every extent is below 2^31.
+template <class T, class I>
+struct PwlP {
+  T da[MX_PWL_MAX], db[MX_PWL_MAX], ak;
+  I s_slot, x_slot, n;  // slot strides and slot length in elements
+  int k, cross;
+};
+
+template <class T, class I, int V>
+__global__ void __launch_bounds__(256) k_pwl_cross(const T* __restrict__ s0,
+                                                   const T* __restrict__ s1,
+                                                   const T* __restrict__ x0,
+                                                   const T* __restrict__ x1, T* __restrict__ out,
+                                                   PwlP<T, I> p) {
+  using Vec = Im2colVec<T, V>;
+  const I sb = (I)blockIdx.z * p.s_slot, xb = (I)blockIdx.z * p.x_slot;
+  T* __restrict__ dst = out + (I)blockIdx.z * p.n;
+  const I step = (I)(gridDim.x * 256u) * V;
+  // V == 2 only with an even n: both outputs are inside, or neither
+  for (I i = (I)(blockIdx.x * 256u + threadIdx.x) * V; i < p.n; i += step) {
+    const Vec a0 = *reinterpret_cast<const Vec*>(x0 + xb + i);
+    Vec g0, g1, h, a;
+#pragma unroll
+    for (int v = 0; v < V; ++v) g0.v[v] = g1.v[v] = h.v[v] = (T)0, a.v[v] = a0.v[v];
+    if (p.cross) {
+      const Vec a1 = *reinterpret_cast<const Vec*>(x1 + xb + i);
+#pragma unroll
+      for (int v = 0; v < V; ++v) a.v[v] += a1.v[v];
+    }
+#pragma unroll
+    for (int j = 0; j < MX_PWL_MAX; ++j) {
+      if (j >= p.k) break;
+      const I fi = sb + (I)j * p.n + i;
+      const Vec f0 = *reinterpret_cast<const Vec*>(s0 + fi);
+#pragma unroll
+      for (int v = 0; v < V; ++v) g0.v[v] += p.da[j] * f0.v[v], h.v[v] += p.db[j] * f0.v[v];
+      if (p.cross) {
+        const Vec f1 = *reinterpret_cast<const Vec*>(s1 + fi);
+#pragma unroll
+        for (int v = 0; v < V; ++v) g1.v[v] += p.da[j] * f1.v[v];
+      }
+    }
+    Vec o;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      o.v[v] = g0.v[v] * a.v[v] + p.ak * a0.v[v] + h.v[v];
+      if (p.cross) o.v[v] += g1.v[v] * a0.v[v];
+    }
+    *reinterpret_cast<Vec*>(dst + i) = o;
+  }
+}
+
+template <class T, class I, int V>
+static int pwl_cross_launch(const void* s0, const void* s1, const void* x0, const void* x1,
+                            void* out, int64_t slots, int64_t s_slot_stride,
+                            int64_t x_slot_stride, int64_t n, int k, const uint64_t* da,
+                            const uint64_t* db, const uint64_t* ak, void* stream) {
+  PwlP<T, I> p;
+  std::memset(&p, 0, sizeof(p));
+  std::memcpy(p.da, da, sizeof(T) * k);
+  std::memcpy(p.db, db, sizeof(T) * k);
+  std::memcpy(&p.ak, ak, sizeof(T));
+  p.s_slot = (I)s_slot_stride, p.x_slot = (I)x_slot_stride, p.n = (I)n;
+  p.k = k, p.cross = x1 != nullptr;
+  const int64_t lanes = (n + V - 1) / V;
+  // the grid is capped at 256 CUs x 8 blocks per slot; a lane strides over the rest
+  const int64_t gx = std::min<int64_t>((lanes + 255) / 256, 256 * 8);
+  hipLaunchKernelGGL((k_pwl_cross<T, I, V>), dim3((unsigned)gx, 1, (unsigned)slots), dim3(256), 0,
+                     S(stream), (const T*)s0, (const T*)s1, (const T*)x0, (const T*)x1, (T*)out,
+                     p);
+  MX_LAUNCH_CHECK();
+  return 0;
+}
+
 // party-batched twins of the per-party sessions' local kernels (party_batch.h)
 MX_X3_GS(k_binary2<u64>, d_binary2<u64>);
 MX_X3_GS(k_binary2<u128>, d_binary2<u128>);
@@ -2642,6 +2724,40 @@ int mxh_resize2d(int elem_bytes, const void* in, void* out, int64_t slots,
     default: return -2;
   }
 #undef MX_RESIZE2D
+}
+
+int mxh_pwl_cross(int elem_bytes, const void* s0, const void* s1, const void* x0, const void* x1,
+                  void* out, int64_t slots, int64_t s_slot_stride, int64_t x_slot_stride,
+                  int64_t n, int k, const uint64_t* da, const uint64_t* db, const uint64_t* ak,
+                  void* stream) {
+  if (slots <= 0 || n <= 0) return 0;
+  if (k < 0 || k > MX_PWL_MAX || slots > 65535 || s_slot_stride < 0 || x_slot_stride < 0 || !ak ||
+      (k && (!da || !db)) || (s1 == nullptr) != (x1 == nullptr))
+    return -3;
+  const int64_t s_extent = (slots - 1) * s_slot_stride + (int64_t)k * n;
+  const int64_t x_extent = (slots - 1) * x_slot_stride + n;
+  // 32-bit indices below 2^31 elements, less the overshoot of a lane's last loop step
+  const int64_t lim = (1ll << 31) - (1ll << 23);
+  const bool small = s_extent < lim && x_extent < lim && slots * n < lim;
+#define MX_PWL(T, V)                                                                           \
+  return small ? pwl_cross_launch<T, int32_t, V>(s0, s1, x0, x1, out, slots, s_slot_stride,    \
+                                                 x_slot_stride, n, k, da, db, ak, stream)      \
+               : pwl_cross_launch<T, int64_t, V>(s0, s1, x0, x1, out, slots, s_slot_stride,    \
+                                                 x_slot_stride, n, k, da, db, ak, stream)
+  switch (elem_bytes) {
+    case 8: {
+      // two outputs per lane: every plane, slot and buffer has to start on 16 bytes
+      const uintptr_t al = (uintptr_t)s0 | (uintptr_t)s1 | (uintptr_t)x0 | (uintptr_t)x1 |
+                           (uintptr_t)out;
+      if (n % 2 == 0 && (al & 15) == 0 && s_slot_stride % 2 == 0 && x_slot_stride % 2 == 0) {
+        MX_PWL(u64, 2);
+      }
+      MX_PWL(u64, 1);
+    }
+    case 16: MX_PWL(u128, 1);
+    default: return -2;
+  }
+#undef MX_PWL
 }
 
 int mxh_dwconv(int elem_bytes, const void* x0, const void* x1, const void* w0, const void* w1,

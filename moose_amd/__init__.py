@@ -90,6 +90,15 @@ from moose_amd.edsl.base import depthwise_conv2d  # noqa: F401
 from moose_amd.edsl.base import im2col  # noqa: F401
 from moose_amd.edsl.base import max_pool2d  # noqa: F401
 from moose_amd.edsl.base import resize2d  # noqa: F401
+from moose_amd.edsl.base import clip  # noqa: F401
+from moose_amd.edsl.base import hard_sigmoid  # noqa: F401
+from moose_amd.edsl.base import hard_swish  # noqa: F401
+from moose_amd.edsl.base import hard_tanh  # noqa: F401
+from moose_amd.edsl.base import leaky_relu  # noqa: F401
+from moose_amd.edsl.base import piecewise_linear  # noqa: F401
+from moose_amd.edsl.base import relu6  # noqa: F401
+from moose_amd.edsl.base import tanh  # noqa: F401
+from moose_amd.edsl.base import thresholded_relu  # noqa: F401
 from moose_amd.edsl.base import permute  # noqa: F401
 from moose_amd.edsl.tracer import trace  # noqa: F401
 from moose_amd.edsl.tracer import trace_and_compile  # noqa: F401

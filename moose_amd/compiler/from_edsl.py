@@ -97,6 +97,12 @@ _OPS = {
                    "weight_bits": list(o.weight_bits), "data_format": o.data_format},
     ),
     "PermuteOperation": ("Permute", ["x"], lambda o: {"axes": list(o.axes)}),
+    "PiecewiseLinearOperation": (
+        "PiecewiseLinear",
+        ["x"],
+        lambda o: {"breakpoints": list(o.breakpoints), "slopes": list(o.slopes),
+                   "intercepts": list(o.intercepts)},
+    ),
     "DepthwiseConvOperation": (
         "DepthwiseConv",
         ["x", "w"],

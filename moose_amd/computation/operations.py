@@ -90,6 +90,7 @@ OPERATION_TABLE = [
                          "scales", "weight_bits", "data_format"]),
     ("PermuteOperation", ["axes"]),
     ("DepthwiseConvOperation", ["strides", "pads", "dilations", "data_format"]),
+    ("PiecewiseLinearOperation", ["breakpoints", "slopes", "intercepts"]),
 ]
 
 OPERATION_CLASSES = {}

@@ -13,6 +13,7 @@ import functools as ft
 import inspect
 from dataclasses import dataclass
 from dataclasses import field
+from fractions import Fraction
 from typing import Any
 from typing import Dict
 from typing import List
@@ -269,7 +270,7 @@ def _check_arithmetickable(expr, fn_name):
 
 # builders whose result has the shape of their (first) operand
 _SAME_SHAPE = {"identity", "cast", "exp", "sqrt", "sigmoid", "relu", "log", "log2", "abs",
-               "softmax"}
+               "softmax", "piecewise_linear"}
 
 
 def _expr(kind, inputs, vtype, placement, **attrs):
@@ -555,6 +556,155 @@ log = _unary("log")
 log2 = _unary("log2")
 abs = _unary("abs")
 transpose = _unary("transpose")
+
+
+# ---------------------------------------------------------------------------
+# piecewise-linear activations (one PiecewiseLinear operator each)
+# ---------------------------------------------------------------------------
+PWL_MAX = 8  # breakpoints of one PiecewiseLinear operator (MX_PWL_MAX of the native leaf)
+
+
+def _pwl_dtype(fn, x):
+    d = x.vtype.dtype if isinstance(x, Expression) and isinstance(x.vtype, ty.TensorType) \
+        else None
+    if d is None or not d.is_fixedpoint:
+        raise TypeError(f"`{fn}` expects a fixed-point tensor (cast the input first), found "
+                        f"{getattr(x, 'vtype', type(x).__name__)}")
+    return d
+
+
+def _pwl_encode(fn, what, values, frac):
+    """Real numbers -> signed integers at ``frac`` fractional bits (round to nearest)."""
+    out = []
+    for v in values:
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating,
+                                                    Fraction)):
+            raise TypeError(f"`{fn}`: {what} must be real numbers, found {v!r}")
+        if isinstance(v, (float, np.floating)) and not np.isfinite(v):
+            raise ValueError(f"`{fn}`: {what} must be finite, found {v!r}")
+        v = float(v) if isinstance(v, np.floating) else int(v) if isinstance(v, np.integer) else v
+        out.append(int(round(Fraction(v) * (1 << frac))))
+    return out
+
+
+def _pwl_op(fn, x, breakpoints, slopes, intercepts, placement=None):
+    """The PiecewiseLinear operator from integer tables at the input's fractional precision."""
+    _pwl_dtype(fn, x)
+    k = len(breakpoints)
+    if not 1 <= k <= PWL_MAX:
+        raise ValueError(f"`{fn}`: between 1 and {PWL_MAX} breakpoints, found {k}")
+    if len(slopes) != k + 1 or len(intercepts) != k + 1:
+        raise ValueError(f"`{fn}`: {k} breakpoints take {k + 1} slopes and intercepts, found "
+                         f"{len(slopes)} and {len(intercepts)}")
+    for what, vals in (("breakpoints", breakpoints), ("slopes", slopes),
+                       ("intercepts", intercepts)):
+        for v in vals:
+            if not -(1 << 63) <= v < (1 << 63):
+                raise ValueError(f"`{fn}`: {what} entry {v} (at the input's fractional "
+                                 "precision) does not fit a signed 64-bit integer")
+    if any(b <= a for a, b in zip(breakpoints, breakpoints[1:])):
+        raise ValueError(f"`{fn}`: breakpoints must be strictly increasing at the input's "
+                         f"fractional precision, found {list(breakpoints)}")
+    return _expr("piecewise_linear", [x], x.vtype, placement, breakpoints=list(breakpoints),
+                 slopes=list(slopes), intercepts=list(intercepts))
+
+
+def piecewise_linear(x, breakpoints, slopes, intercepts, placement=None):
+    """Elementwise piecewise-linear function of a fixed-point ``x`` with public pieces: ``k``
+    increasing real ``breakpoints`` (at most ``PWL_MAX``) and ``k + 1`` ``slopes`` and
+    ``intercepts``; the result is ``slopes[i] * x + intercepts[i]`` for ``breakpoints[i-1] <= x
+    < breakpoints[i]``.  The numbers are rounded to the input's fractional precision.  On a
+    secret ``x`` all ``k`` comparisons are ONE sign extraction, followed by one multiplication
+    and one truncation -- the cost of a single ``relu`` whatever ``k``."""
+    fn = "piecewise_linear"
+    f = _pwl_dtype(fn, x).fractional_precision
+    return _pwl_op(fn, x, _pwl_encode(fn, "breakpoints", breakpoints, f),
+                   _pwl_encode(fn, "slopes", slopes, f),
+                   _pwl_encode(fn, "intercepts", intercepts, f), placement)
+
+
+def _clip(fn, x, lo, hi, placement):
+    f = _pwl_dtype(fn, x).fractional_precision
+    if lo is None and hi is None:
+        raise ValueError(f"`{fn}` needs a lower or an upper bound")
+    if lo is not None and hi is not None:
+        tl, th = _pwl_encode(fn, "bounds", (lo, hi), f)
+        if tl >= th:
+            raise ValueError(f"`{fn}`: the lower bound {lo} is not below the upper bound {hi} "
+                             "at the input's fractional precision")
+        return _pwl_op(fn, x, [tl, th], [0, 1 << f, 0], [tl, 0, th], placement)
+    if lo is not None:
+        (tl,) = _pwl_encode(fn, "bounds", (lo,), f)
+        return _pwl_op(fn, x, [tl], [0, 1 << f], [tl, 0], placement)
+    (th,) = _pwl_encode(fn, "bounds", (hi,), f)
+    return _pwl_op(fn, x, [th], [1 << f, 0], [0, th], placement)
+
+
+def clip(x, lo=None, hi=None, placement=None):
+    """``min(max(x, lo), hi)`` with public real bounds; either may be None (one-sided)."""
+    return _clip("clip", x, lo, hi, placement)
+
+
+def relu6(x, placement=None):
+    """``min(max(x, 0), 6)``."""
+    return _clip("relu6", x, 0, 6, placement)
+
+
+def hard_tanh(x, min_val=-1.0, max_val=1.0, placement=None):
+    """``min(max(x, min_val), max_val)``."""
+    return _clip("hard_tanh", x, min_val, max_val, placement)
+
+
+def leaky_relu(x, alpha=0.01, placement=None):
+    """``x`` where ``x >= 0``, else ``alpha * x``."""
+    fn = "leaky_relu"
+    f = _pwl_dtype(fn, x).fractional_precision
+    (a,) = _pwl_encode(fn, "alpha", (alpha,), f)
+    return _pwl_op(fn, x, [0], [a, 1 << f], [0, 0], placement)
+
+
+def _hard_sigmoid(fn, x, alpha, beta, placement):
+    f = _pwl_dtype(fn, x).fractional_precision
+    if not alpha > 0:
+        raise ValueError(f"`{fn}`: alpha must be positive, found {alpha!r}")
+    a, b = Fraction(alpha), Fraction(beta)
+    t = _pwl_encode(fn, "breakpoints", (-b / a, (1 - b) / a), f)
+    (ai,) = _pwl_encode(fn, "alpha", (alpha,), f)
+    (bi,) = _pwl_encode(fn, "beta", (beta,), f)
+    return _pwl_op(fn, x, t, [0, ai, 0], [0, bi, 1 << f], placement)
+
+
+def hard_sigmoid(x, alpha=0.2, beta=0.5, placement=None):
+    """``max(0, min(1, alpha * x + beta))`` (ONNX ``HardSigmoid``)."""
+    return _hard_sigmoid("hard_sigmoid", x, alpha, beta, placement)
+
+
+def thresholded_relu(x, alpha=1.0, placement=None):
+    """``x`` where ``x > alpha``, else 0 (ONNX ``ThresholdedRelu``; discontinuous at
+    ``alpha``)."""
+    fn = "thresholded_relu"
+    f = _pwl_dtype(fn, x).fractional_precision
+    (t,) = _pwl_encode(fn, "alpha", (alpha,), f)
+    # x > alpha is x >= alpha + one unit in the last place
+    return _pwl_op(fn, x, [t + 1], [0, 1 << f], [0, 0], placement)
+
+
+def hard_swish(x, placement=None):
+    """``x * hard_sigmoid(x, 1/6, 1/2)`` (ONNX ``HardSwish``)."""
+    y = mul(x, _hard_sigmoid("hard_swish", x, Fraction(1, 6), Fraction(1, 2), placement),
+            placement)
+    y.static_shape = x.static_shape
+    return y
+
+
+def tanh(x, placement=None):
+    """``tanh(x) = 2 * sigmoid(2x) - 1`` on the existing sigmoid."""
+    d = _pwl_dtype("tanh", x)
+    s = sigmoid(add(x, x, placement), placement)
+    one = constant(1.0, vtype=ty.TensorType(d), placement=placement)
+    y = sub(add(s, s, placement), one, placement)
+    y.static_shape = x.static_shape
+    return y
 
 
 def softmax(x, axis, upmost_index, placement=None):

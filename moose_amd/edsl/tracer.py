@@ -65,6 +65,8 @@ _OPS = {
     "permute": ("PermuteOperation", ["x"], "permute", ["axes"]),
     "depthwise_conv": ("DepthwiseConvOperation", ["x", "w"], "depthwise_conv",
                        ["strides", "pads", "dilations", "data_format"]),
+    "piecewise_linear": ("PiecewiseLinearOperation", ["x"], "piecewise_linear",
+                         ["breakpoints", "slopes", "intercepts"]),
     "shape": ("ShapeOperation", ["x"], "shape", []),
     "mux": ("MuxOperation", ["selector", "x", "y"], "mux", []),
     "load": ("LoadOperation", ["key", "query"], "load", []),

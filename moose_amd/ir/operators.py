@@ -157,6 +157,11 @@ EXTENSION_OPERATORS = {
     # shares (no patch matrix): secret x secret is the replicated local product + dot tail
     "DepthwiseConv": [("strides", "ints"), ("pads", "ints"), ("dilations", "ints"),
                       ("data_format", "str")],
+    # elementwise piecewise-linear function with public pieces: k sorted breakpoints and k + 1
+    # slopes and intercepts, signed integers at the input dtype's fractional precision;
+    # segment i is slopes[i] * x + intercepts[i] on [breakpoints[i-1], breakpoints[i]).  On a
+    # secret x: one stacked sign extraction for the k flags, one local kernel, one truncation
+    "PiecewiseLinear": [("breakpoints", "ints"), ("slopes", "ints"), ("intercepts", "ints")],
 }
 
 ALL_OPERATORS = {**OPERATORS, **EXTENSION_OPERATORS}

@@ -5,8 +5,11 @@ chain of ``Conv`` (any ``group`` that divides the channels: ``group = C`` is the
 operator, other groups a composition of per-group products), ``ConvTranspose`` (``group = 1``, explicit ``pads`` and ``output_padding``: a ``dot`` of the
 pixels followed by the ``col2im`` sum), ``Resize`` (opset 11+) / ``Upsample`` (opset 7, 9) in
 ``nearest`` or ``linear`` mode with constant ``scales`` / ``sizes`` (``pm.resize2d`` in the
-activation's layout), ``Relu`` / ``Sigmoid``, ``MaxPool`` / ``AveragePool``,
-``Flatten`` (or ``Reshape`` to ``[N, -1]``), ``Gemm`` / ``MatMul`` + ``Add`` and a final
+activation's layout), ``Relu`` / ``Sigmoid`` / ``Tanh``, the piecewise-linear activations ``Clip``
+(attribute or initializer bounds, one-sided included), ``LeakyRelu``, ``PRelu`` (one slope),
+``HardSigmoid``, ``HardSwish`` and ``ThresholdedRelu``, ``MaxPool`` / ``AveragePool``,
+``Flatten`` (or ``Reshape`` to ``[N, -1]``), ``Gemm`` / ``MatMul`` + ``Add``, a ``Reshape`` of a
+dense layer's output back to an image ``[N, C, H, W]`` (a decoder's first step) and a final
 ``Softmax``.  The model input is rank 4, NCHW.  Inside the MPC the activations are NHWC from
 the first convolution on, so no permutation ever runs on shares: the first ``im2col`` reads
 NCHW, the convolution weights are re-ordered to the patch matrix's (kh, kw, c) rows and the
@@ -58,6 +61,61 @@ def _window_attrs(node):
 def _str(node, name, default):
     a = find_attribute(node, name, enforce=False)
     return a.s.decode() if a is not None and a.s else default
+
+
+def _float(node, name, default):
+    a = find_attribute(node, name, enforce=False)
+    return float(a.f) if a is not None else default
+
+
+def _scalar_operand(node, init, index, what):
+    """The one-element constant input ``index`` of a node as a float; None when it is absent
+    or empty-named."""
+    if len(node.input) <= index or not node.input[index]:
+        return None
+    if node.input[index] not in init:
+        raise _unsupported(node, f"its `{what}` input is not an initializer or a Constant")
+    v = np.asarray(init[node.input[index]], dtype=np.float64).reshape(-1)
+    if v.size != 1:
+        raise _unsupported(node, f"its `{what}` input has {v.size} elements, not 1")
+    return float(v[0])
+
+
+def _activation_layer(node, init):
+    """The layer of a piecewise-linear activation node (or Tanh)."""
+    op = node.op_type
+    if op == "Clip":
+        lo = find_attribute(node, "min", enforce=False)  # opset < 11: attributes
+        hi = find_attribute(node, "max", enforce=False)
+        lo = float(lo.f) if lo is not None else _scalar_operand(node, init, 1, "min")
+        hi = float(hi.f) if hi is not None else _scalar_operand(node, init, 2, "max")
+        # float32's extremes stand for "no bound" in exported graphs
+        big = float(np.finfo(np.float32).max)
+        lo = None if lo is not None and lo <= -big else lo
+        hi = None if hi is not None and hi >= big else hi
+        if lo is None and hi is None:
+            raise _unsupported(node, "a Clip without bounds")
+        if lo is not None and hi is not None and not lo < hi:
+            raise _unsupported(node, f"min={lo} is not below max={hi}")
+        return {"op": "clip", "lo": lo, "hi": hi}
+    if op == "LeakyRelu":
+        return {"op": "leakyrelu", "alpha": _float(node, "alpha", 0.01)}
+    if op == "PRelu":
+        if len(node.input) < 2 or node.input[1] not in init:
+            raise _unsupported(node, "its slope is not an initializer or a Constant")
+        slope = np.asarray(init[node.input[1]], dtype=np.float64).reshape(-1)
+        if slope.size != 1:
+            raise _unsupported(node, f"a per-channel slope of {slope.size} elements: only a "
+                                     "one-element slope is supported")
+        return {"op": "leakyrelu", "alpha": float(slope[0])}
+    if op == "HardSigmoid":
+        alpha = _float(node, "alpha", 0.2)
+        if not alpha > 0:
+            raise _unsupported(node, f"alpha={alpha} is not positive")
+        return {"op": "hardsigmoid", "alpha": alpha, "beta": _float(node, "beta", 0.5)}
+    if op == "ThresholdedRelu":
+        return {"op": "thresholdedrelu", "alpha": _float(node, "alpha", 1.0)}
+    return {"op": op.lower()}  # HardSwish, Tanh
 
 
 def _opset(model):
@@ -137,8 +195,9 @@ def hwc_rows(w, c, h, w_):
 
 def conv_layers_from_onnx(model):
     """-> (input (C, H, W), layers): each layer a dict with ``op`` in conv / convtranspose /
-    resize / relu / sigmoid / maxpool / avgpool / flatten / dense / softmax and its parameters (ONNX
-    layouts)."""
+    resize / relu / sigmoid / tanh / clip / leakyrelu / hardsigmoid / hardswish /
+    thresholdedrelu / maxpool / avgpool / flatten / dense / unflatten / softmax and its
+    parameters (ONNX layouts)."""
     dims = model.graph.input[0].type.tensor_type.shape.dim
     if len(dims) != 4:
         raise ValueError("a convolutional predictor expects a rank-4 [batch, C, H, W] model input")
@@ -215,6 +274,9 @@ def conv_layers_from_onnx(model):
             layers.append(layer)
         elif op in ("Relu", "Sigmoid"):
             layers.append({"op": op.lower()})
+        elif op in ("Clip", "LeakyRelu", "PRelu", "HardSigmoid", "HardSwish",
+                    "ThresholdedRelu", "Tanh"):
+            layers.append(_activation_layer(node, init))
         elif op == "MaxPool":
             kernel, strides, pads = _window_attrs(node)
             if any(pads):
@@ -232,6 +294,11 @@ def conv_layers_from_onnx(model):
         elif op == "Reshape":
             shape = init.get(node.input[1]) if len(node.input) > 1 else None
             shape = None if shape is None else [int(s) for s in np.asarray(shape).reshape(-1)]
+            if (shape is not None and len(shape) == 4 and min(shape[1:]) > 0 and layers
+                    and layers[-1]["op"] == "dense"):  # a decoder: dense -> image
+                layers.append({"op": "unflatten", "out_chw": tuple(shape[1:])})
+                channels = shape[1]
+                continue
             if shape is None or len(shape) != 2 or -1 not in shape:
                 raise _unsupported(node, f"only a Reshape to [N, -1] is supported, found {shape}")
             layers.append({"op": "flatten"})
@@ -331,6 +398,12 @@ class ConvNetwork(Predictor):
                                (1, 1))
             elif op == "flatten":
                 flat = (fmt, c, h, w)
+            elif op == "unflatten":
+                c, h, w = l["out_chw"]
+                if flat is None or flat[0] is not None or self.n_outputs != c * h * w:
+                    raise ValueError(f"unsupported ONNX graph: a Reshape to the image {(c, h, w)} "
+                                     "has to follow a dense layer of as many outputs")
+                fmt, flat = "NCHW", None
             elif op == "dense":
                 if flat is None:
                     raise ValueError("unsupported ONNX graph: Gemm / MatMul before Flatten")
@@ -401,6 +474,20 @@ class ConvNetwork(Predictor):
                 x = pm.relu(x)
             elif op == "sigmoid":
                 x = pm.sigmoid(x)
+            elif op == "tanh":
+                x = pm.tanh(x)
+            elif op == "clip":
+                x = pm.clip(x, l["lo"], l["hi"])
+            elif op == "leakyrelu":
+                x = pm.leaky_relu(x, l["alpha"])
+            elif op == "hardsigmoid":
+                x = pm.hard_sigmoid(x, l["alpha"], l["beta"])
+            elif op == "hardswish":
+                x = pm.hard_swish(x)
+            elif op == "thresholdedrelu":
+                x = pm.thresholded_relu(x, l["alpha"])
+            elif op == "unflatten":
+                x = pm.reshape(x, [-1, *l["out_chw"]])
             elif op == "flatten":
                 c, h, w = self._flat_size()
                 x = pm.reshape(x, [-1, c * h * w])

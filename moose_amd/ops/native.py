@@ -42,6 +42,10 @@ _SIGS = {
     #  stream)
     "mx_resize2d": (c_int, [c_int, c_int, c_vp, c_vp, c_i64, c_i64] + [c_i64] * 6
                     + [c_vp, c_vp, c_int, c_int, c_int, c_vp]),
+    # (dev, elem_bytes, s0 s1 x0 x1 out, slots, s_slot_stride, x_slot_stride, n, k, da db ak,
+    #  stream)
+    "mx_pwl_cross": (c_int, [c_int, c_int] + [c_vp] * 5 + [c_i64] * 4 + [c_int] + [c_vp] * 3
+                     + [c_vp]),
     # (dev, elem_bytes, x0 x1 w0 w1 out, slots, x_slot_stride, w_slot_stride, N C H W mult,
     #  KH KW, sh sw, pt pl, dh dw, OH OW, nhwc, stream)
     "mx_dwconv": (c_int, [c_int, c_int] + [c_vp] * 5 + [c_i64] * 3 + [c_i64] * 15

@@ -1313,6 +1313,112 @@ def dwconv_cross(x0: RT, x1: RT, w0: RT, w1: RT, strides=(1, 1), pads=(0, 0, 0, 
     return _dwconv(x0, x1, w0, w1, strides, pads, dilations, data_format, nb)
 
 
+# ---------------------------------------------------------------------------
+# piecewise-linear local step
+# ---------------------------------------------------------------------------
+PWL_MAX = 8  # MX_PWL_MAX (moosex.h): the flag planes one launch takes
+
+# the device path of pwl / pwl_cross: the native kernel (True) or the torch composition
+# pwl_torch (False); a CPU tensor always takes the native loops
+PWL_KERNEL = True
+
+
+@functools.lru_cache(maxsize=1024)
+def _pwl_tables(da, db, ak, bits):
+    return _ring_words(da, bits), _ring_words(db, bits), _ring_words((ak,), bits)
+
+
+def _pwl_check(s0, s1, x0, x1, da, db, nb):
+    k = len(da)
+    if not 1 <= k <= PWL_MAX or len(db) != k:
+        raise ValueError(f"pwl: between 1 and {PWL_MAX} flag planes with one DA and one DB entry "
+                         f"each, found {k} and {len(db)}")
+    if (s1 is None) != (x1 is None):
+        raise ValueError("pwl: the cross form takes both next components")
+    ops = [t for t in (s0, s1, x0, x1) if t is not None]
+    bits = x0.bits
+    if bits not in (64, 128) or any(t.bits != bits for t in ops):
+        raise ValueError("pwl is arithmetic only: operands over one of Z_2^64 / Z_2^128, found "
+                         f"{[t.bits for t in ops]} bits")
+    if nb not in (0, 1):
+        raise ValueError("pwl takes at most one batch dim")
+    lead, shape = tuple(x0.shape[:nb]), tuple(x0.shape[nb:])
+    for t, want in ((s0, lead + (k,) + shape), (s1, lead + (k,) + shape), (x1, lead + shape)):
+        if t is not None and tuple(t.shape) != want:
+            raise ValueError(f"pwl: operand of shape {tuple(t.shape)}, expected {want}")
+    return k, bits, lead, shape
+
+
+def _pwl_operand(t: RT, nb, dense):
+    """(data, slot stride in elements): a [slots, ...] view with dense slots is read in place."""
+    d, w = t.data, 2 if t.bits == 128 else 1
+    if not nb:
+        return d.contiguous(), dense
+    if d.shape[0] and d[0].is_contiguous() and d.stride(0) >= 0 and d.stride(0) % w == 0:
+        return d, d.stride(0) // w
+    return d.contiguous(), dense
+
+
+def pwl_torch(s0: RT, s1, x0: RT, x1, da, db, ak, nb=0) -> RT:
+    """:func:`pwl_cross` as a composition of the existing kernels (weighted sums of the flag
+    planes, then elementwise products and sums): the fallback and the benchmark's opponent."""
+    _pwl_check(s0, s1, x0, x1, da, db, nb)
+    g0, h = weighted_sum(s0, da, nb), weighted_sum(s0, db, nb)
+    v = binary("add", binary("mul", binary("add", g0, int(ak)), x0), h)
+    if s1 is not None:
+        g1 = weighted_sum(s1, da, nb)
+        v = binary("add", v, binary("add", binary("mul", g0, x1), binary("mul", g1, x0)))
+    return v
+
+
+def pwl_cross(s0: RT, s1, x0: RT, x1, da, db, ak, nb=0) -> RT:
+    """One party's local step of a secret piecewise-linear function, exact in the ring: with
+    the flag planes ``s0`` / ``s1`` ([.., k, *shape]), the input components ``x0`` / ``x1``
+    ([.., *shape]) and public python ints ``da[k]``, ``db[k]``, ``ak``,
+    ``G0 * (x0 + x1) + G1 * x0 + ak * x0 + sum_j db[j] * s0[j]`` where ``Gc = sum_j da[j] *
+    sc[j]`` (own times the sum plus next times own, as :func:`dwconv_cross`).  ``s1 = x1 =
+    None``: the plain form ``G0 * x0 + ak * x0 + sum_j db[j] * s0[j]``.  One native launch
+    over all batch slots (``mx_pwl_cross``); [slots, ...] views with dense slots are read in
+    place and the tables travel in the launch's arguments."""
+    k, bits, lead, shape = _pwl_check(s0, s1, x0, x1, da, db, nb)
+    if x0.device.type == "meta":  # shape inference of the symbolic session
+        return empty(lead + shape, bits, x0.device)
+    if x0.device.type == "cuda" and not PWL_KERNEL:
+        return pwl_torch(s0, s1, x0, x1, da, db, ak, nb)
+    n = math.prod(shape)
+    out = empty(lead + shape, bits, x0.device)
+    if out.data.numel() == 0:
+        return out
+    sd0, sst = _pwl_operand(s0, nb, k * n)
+    xd0, xst = _pwl_operand(x0, nb, n)
+    sd1 = xd1 = None
+    if s1 is not None:
+        sd1, sst1 = _pwl_operand(s1, nb, k * n)
+        xd1, xst1 = _pwl_operand(x1, nb, n)
+        if sst1 != sst:  # one stride serves both components
+            sd0, sd1, sst = sd0.contiguous(), sd1.contiguous(), k * n
+        if xst1 != xst:
+            xd0, xd1, xst = xd0.contiguous(), xd1.contiguous(), n
+    tda, tdb, tak = _pwl_tables(tuple(int(v) for v in da), tuple(int(v) for v in db), int(ak),
+                                bits)
+    nat.check(
+        nat.lib().mx_pwl_cross(
+            nat.dev_of(out.data), 16 if bits == 128 else 8, nat.ptr(sd0),
+            nat.ptr(sd1) if sd1 is not None else None, nat.ptr(xd0),
+            nat.ptr(xd1) if xd1 is not None else None, nat.ptr(out.data), math.prod(lead), sst,
+            xst, n, k, tda, tdb, tak, nat.stream_of(out.data)),
+        "pwl_cross",
+    )
+    return out
+
+
+def pwl(s: RT, x: RT, da, db, ak, nb=0) -> RT:
+    """The plain form of :func:`pwl_cross`: ``(ak + sum_j da[j] * s[j]) * x + sum_j db[j] *
+    s[j]`` over the flag planes ``s`` ([.., k, *shape]) -- a host's ring tensor, or slot-wise
+    use."""
+    return pwl_cross(s, None, x, None, da, db, ak, nb)
+
+
 def select_mask(a: RT, axis: int, mask: torch.Tensor, nb=0) -> RT:
     ax = _ax(a, axis, nb)
     keep = torch.nonzero(mask.reshape(-1).to(torch.bool)).reshape(-1).to(a.device)

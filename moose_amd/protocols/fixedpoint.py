@@ -367,6 +367,58 @@ def relu(sess, x: RepFixed) -> RepFixed:
     return _with(x, rep.sub(sess, x.t, rep.mul(sess, s, x.t)))
 
 
+def pwl_tables(breakpoints, slopes, intercepts, f: int, integ: int, bits: int, what="pwl"):
+    """The integer tables of a piecewise-linear function at ``f`` fractional bits: ``(T, DA,
+    DB, AK, BK)`` with DA[j] = a_j - a_{j+1}, DB[j] = (b_j - b_{j+1}) * 2^f (the intercepts
+    meet the product a * x at scale 2f), AK = a_k and BK = b_k (added after the truncation, so
+    the constant is counted once).  Checks that the product leaves the truncation its two
+    spare bits, as a fixed-point multiplication needs integ + 2f of them."""
+    T = [int(t) for t in breakpoints]
+    a, b = [int(v) for v in slopes], [int(v) for v in intercepts]
+    k = len(T)
+    if not 1 <= k <= R.PWL_MAX or len(a) != k + 1 or len(b) != k + 1:
+        raise ValueError(f"{what}: between 1 and {R.PWL_MAX} breakpoints with one more slope and "
+                         f"intercept, found {k}, {len(a)} and {len(b)}")
+    if any(t1 <= t0 for t0, t1 in zip(T, T[1:])):
+        raise ValueError(f"{what}: breakpoints must be strictly increasing, found {T}")
+    amax = max(abs(v) for v in a + [a[i] - a[i + 1] for i in range(k)])
+    bmax = max(abs(v) for v in b + [b[i] - b[i + 1] for i in range(k)])
+    need = max(integ + f + amax.bit_length(), f + bmax.bit_length()) + 1
+    if need > bits - 2:
+        raise ValueError(
+            f"{what}: slopes up to {amax} / 2^{f} on a fixed({integ}, {f}) value need {need} "
+            f"bits before the truncation (integral + 2 * fractional and the slope's integer "
+            f"part), but Z_2^{bits} leaves {bits - 2}")
+    DA = [a[j] - a[j + 1] for j in range(k)]
+    DB = [(b[j] - b[j + 1]) << f for j in range(k)]
+    return T, DA, DB, a[k], b[k]
+
+
+def pwl_shift(DB):
+    """(sh, DB >> sh): the power of two common to the intercept weights, taken out so that a
+    lowered graph's WeightedSum keeps small weights and shifts its sum instead."""
+    nz = [int(v) for v in DB if int(v)]
+    sh = min(((v & -v).bit_length() - 1 for v in nz), default=0)
+    return sh, [int(v) >> sh for v in DB]
+
+
+def piecewise_linear(sess, x: RepFixed, breakpoints, slopes, intercepts) -> RepFixed:
+    """Piecewise-linear function of a secret fixed-point ``x`` with public integer tables at
+    x's fractional precision (k breakpoints, k + 1 slopes and intercepts): rep.pwl_trunc --
+    one stacked sign extraction, one local kernel, one truncation by f -- then the last
+    segment's intercept with add_public."""
+    f = x.frac
+    T, DA, DB, AK, BK = pwl_tables(breakpoints, slopes, intercepts, f, x.integ, x.bits,
+                                   "piecewise_linear")
+    w = x.integ + f + 2  # x - t spans one bit more than x
+    width = w if SIGN_WIDTH and 2 < w < x.bits and all(abs(t) < (1 << (x.integ + f)) for t in T) \
+        else None
+    z = rep.pwl_trunc(sess, x.t, T, DA, DB, AK, f, width=width)
+    if BK:
+        z = rep.add_public(sess, z, R.fill((), BK, x.bits, sess.device))
+    return _with(x, z)
+
+
 def abs_(sess, x: RepFixed) -> RepFixed:
     s = sign_bit(sess, x)
     return _with(x, rep.negate_where(sess, s, x.t))

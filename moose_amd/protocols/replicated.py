@@ -1082,6 +1082,59 @@ def dwconv_trunc(sess, x: RepTensor, w: RepTensor, m: int, geom: dict) -> RepTen
     return trunc_pr(sess, z, m) if m else z  # m = 0: the ring convolution, as rep.dot
 
 
+def pwl_trunc(sess, x: RepTensor, T, DA, DB, AK, m: int, width=None) -> RepTensor:
+    """trunc_pr((AK + G) * x + H, m) with G = sum_j DA[j] * s_j, H = sum_j DB[j] * s_j and the
+    secret flags s_j = [x < T[j]] -- a piecewise-linear function of a secret ``x`` with public
+    breakpoints ``T`` (python ints, ring values) at the cost of ONE sign extraction and one
+    multiplication: the k shifted copies x - T[j] are stacked (one concat per share) and go
+    through less_than_zero_arith as one protocol instance; the local products come from one
+    kernel (session ``p_pwl_cross``); the tail is :func:`dwconv_trunc`'s selection, on the same
+    nonces in the same order.  ``width``: |x - T[j]| < 2^(width - 1) is known."""
+    plc, bits = x.plc, x.bits
+    with span("rep.pwl_flags"):
+        parts = [local(sess, sub_public(sess, x, R.fill((), int(t), bits, sess.device)),
+                       "ExpandDims", axis=[0]) for t in T]
+        if len(parts) == 1:
+            stack = parts[0]
+        else:
+            stack = RepTensor(plc, bits, "arith",
+                              sess.p("Concat", plc, *[p.s0 for p in parts], axis=0),
+                              sess.p("Concat", plc, *[p.s1 for p in parts], axis=0))
+        s = less_than_zero_arith(sess, stack, width=width)
+
+    def cross():
+        return sess.p_pwl_cross(plc, s.s0, s.s1, x.s0, x.s1, DA, DB, AK)
+
+    tail = getattr(sess, "p_zs_trunc", None)
+    if (tail is not None and m and getattr(sess, "fused", False)
+            and getattr(sess, "device", None) is not None and sess.device.type == "cuda"
+            and os.environ.get("MOOSEX_DOT_TAIL", "1") != "0"):
+        with span("rep.pwl_trunc_fused"):
+            v = cross()
+            issue = getattr(sess, "p_zs_trunc_issue", None)
+            if (issue is not None and bits in (64, 128)
+                    and os.environ.get("MOOSEX_DOT_OPEN", "1") != "0"):
+                return StackedTail(sess, plc, bits, v, m, issue(plc, v))
+            s0, s1 = tail(plc, v, m)
+            return RepTensor(plc, bits, "arith", s0, s1)
+    party = getattr(sess, "party_dot_trunc", None)
+    if (party is not None and m and 0 < m <= 63 and bits in (64, 128)
+            and os.environ.get("MOOSEX_DOT_TAIL", "1") != "0"):
+        with span("rep.pwl_trunc_party"):
+            nonces = tuple(sess.nonce(plc) for _ in range(7))  # as dot + trunc_pr
+            s0, s1 = party(plc, cross(), m, nonces)
+            return RepTensor(plc, bits, "arith", s0, s1)
+    with span("rep.pwl"):
+        v = cross()
+        fused = getattr(sess, "p_zero_share_reshare", None)
+        if fused is not None and getattr(sess, "fused", False):
+            s0, s1 = fused(plc, v, "arith")
+            z = RepTensor(plc, bits, "arith", s0, s1)
+        else:
+            z = _reshare(sess, plc, sess.p_add_zero_share(plc, v, "arith"), bits, "arith")
+    return trunc_pr(sess, z, m) if m else z
+
+
 def dwconv_public(sess, x: RepTensor, c, geom: dict, public_image=False) -> RepTensor:
     """Depthwise convolution of a secret image with the public weight ``c`` (or, with
     ``public_image``, of the public image ``c`` with a secret weight): the plain kernel

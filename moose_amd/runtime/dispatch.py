@@ -138,6 +138,19 @@ kernel("DepthwiseConv", "rep", "rep_ring", "host_ring")(
     lambda c, x, w: rep.dwconv_public(c.sess, x, _pub(w), _dwconv_geom(c)))
 kernel("DepthwiseConv", "rep", "host_ring", "rep_ring")(
     lambda c, x, w: rep.dwconv_public(c.sess, w, _pub(x), _dwconv_geom(c), public_image=True))
+
+
+def _pwl_ring(c, x):
+    """PiecewiseLinear on a raw ring sharing: the tables are ring integers (no fractional
+    bits), so the pieces are exact and nothing is truncated."""
+    T, a, b = (list(c.attr(n)) for n in ("breakpoints", "slopes", "intercepts"))
+    k = len(T)
+    z = rep.pwl_trunc(c.sess, x, T, [a[j] - a[j + 1] for j in range(k)],
+                      [b[j] - b[j + 1] for j in range(k)], a[k], 0)
+    return rep.add_public(c.sess, z, R.fill((), b[k], x.bits, c.sess.device)) if b[k] else z
+
+
+kernel("PiecewiseLinear", "rep", "rep_ring")(_pwl_ring)
 kernel("Neg", "rep", "rep_ring")(lambda c, x: rep.neg(c.sess, x))
 kernel("Sum", "rep", "rep_ring")(lambda c, x: rep.sum(c.sess, x, c.attr("axis")))
 kernel("AddN", "rep", "rep_ring", variadic=True)(lambda c, *xs: _add_n(c, xs))

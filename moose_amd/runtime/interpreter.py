@@ -1546,6 +1546,51 @@ class Interpreter:
             return LV(y.plc, "tensor", y.dtype, MV(y.plc, z.v))
         return LV(y.plc, "tensor", y.dtype, fxp._with(y.v, rep.trunc_pr(self.sess, y.v.t, m)))
 
+    def op_PiecewiseLinear(self, op, ins):
+        """Piecewise-linear activation of a fixed-point tensor: replicated values through
+        fixedpoint.piecewise_linear (one sign extraction, one local kernel, one truncation);
+        a host's or a mirrored value through the plain leaf on the ring tensor, its flags
+        the sign bits of x - t_j, then Sar by the fractional precision."""
+        a = op.attrs
+        tabs = (a["breakpoints"], a["slopes"], a["intercepts"])
+        x = self.at(op, ins[0])
+        d = x.dtype
+        if x.kind != "tensor" or d is None or not d.is_fixed:
+            raise MooseRuntimeError(
+                f"{op.name}: PiecewiseLinear expects a fixed-point tensor, got {d}; cast a "
+                "float tensor to fixed point first")
+        if x.is_host:
+            return LV(x.plc, "tensor", d, self._host_pwl(x.host, x.v, d, tabs))
+        if x.is_mir or (x.is_rep and isinstance(x.v, MV)):
+            host = x.plc.owners[0]
+            z = self._host_pwl(host, HV(host, x.v.v), d, tabs)
+            return LV(x.plc, "tensor", d, MV(x.plc, z.v))
+        return LV(x.plc, "tensor", d, fxp.piecewise_linear(self.sess, x.v, *tabs))
+
+    def _host_pwl(self, host, xv, d, tabs):
+        sess = self.sess
+        f = d.fractional_precision
+        bits = getattr(xv.v, "bits", None) or d.ring_bits
+        T_, DA, DB, AK, BK = fxp.pwl_tables(*tabs, f, d.integral_precision, bits,
+                                            "PiecewiseLinear")
+        dev = sess.device
+        flags = [sess.h("ExpandDims", host,
+                        sess.h("Shr", host, sess.h("Sub", host, xv, R.fill((), t, bits, dev)),
+                               amount=bits - 1), axis=[0]) for t in T_]
+        s = flags[0] if len(flags) == 1 else sess.h("Concat", host, *flags, axis=0)
+        if self.symbolic:  # a lowered graph takes no operator of its own
+            sh, dbs = fxp.pwl_shift(DB)
+            g = sess.h("Add", host, sess.h("WeightedSum", host, s, weights=DA, bits=bits),
+                       R.fill((), AK, bits, dev))
+            hh = sess.h("WeightedSum", host, s, weights=dbs, bits=bits)
+            if sh:
+                hh = sess.h("Shl", host, hh, amount=sh)
+            v = sess.h("Add", host, sess.h("Mul", host, g, xv), hh)
+        else:
+            v = sess.h("PwlPlain", host, s, xv, da=DA, db=DB, ak=AK)
+        z = sess.h("Sar", host, v, amount=f)
+        return sess.h("Add", host, z, R.fill((), BK, bits, dev)) if BK else z
+
     def op_DepthwiseConv(self, op, ins):
         """Depthwise convolution: host tensors (float, or fixed point with the truncation
         that Dot takes) through the primitive, replicated fixed point through

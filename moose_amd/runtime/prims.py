@@ -395,6 +395,13 @@ def _dwconv_cross(nb, x0, x1, w0, w1, strides=(1, 1), pads=(0, 0, 0, 0), dilatio
     return R.dwconv_cross(x0, x1, w0, w1, strides, pads, dilations, data_format, nb)
 
 
+@prim("PwlPlain")
+def _pwl_plain(nb, s, x, da, db, ak):
+    """The plain piecewise-linear leaf on ring tensors (R.pwl): (ak + sum_j da[j] * s[j]) * x +
+    sum_j db[j] * s[j] over the flag planes s stacked on the leading logical axis."""
+    return R.pwl(s, x, tuple(da), tuple(db), int(ak), nb)
+
+
 @prim("StridedSlice")
 def _strided_slice(nb, a, slices):
     if _is_rt(a):

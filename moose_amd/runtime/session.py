@@ -933,6 +933,12 @@ class StackedSession(Session):
         the views of a share-pair buffer included -- are read in place."""
         return PV(plc, R.dwconv_cross(x0.v, x1.v, w0.v, w1.v, nb=1, **geom))
 
+    def p_pwl_cross(self, plc, s0, s1, x0, x1, da, db, ak):
+        """The three parties' local steps of a piecewise-linear function (R.pwl_cross) in one
+        launch: the flag and input share vectors -- the views of a share-pair buffer included
+        -- are read in place."""
+        return PV(plc, R.pwl_cross(s0.v, s1.v, x0.v, x1.v, da, db, ak, nb=1))
+
     def end_evaluation(self, ok=True):
         """Drop per-evaluation caches (prepared GEMM operands hold device memory and must
         not outlive the evaluation whose values they were prepared from)."""
