@@ -448,14 +448,20 @@ struct ShareSrc {
 // Kernel form.  Image e of the side (byte offset off[e]) holds phase ph[e]: 0 = r, 1 = x - r,
 // 2 = the sum of the two, 3 = zero; a sum with the zero slot is its other slot.  A phase may
 // belong to several images or to none.
+// strip != 0: the zero phase has no image (its entries' ph is -1: nothing stored) -- every
+// (modulus, tile) strip of it would be the same nkb * ROWS * BK zero bytes, so the side holds
+// that strip once, at byte offset zoff, and k_crt_gemm16 reads it for every modulus and tile
+// (map entry kZeroStrip).
 struct SrcPlan {
   const void* x;
-  int kind, pad;
+  int kind, strip;
   double scale;
   uint64_t nonce;
   int ph[4];
   int64_t off[4];
+  int64_t zoff;
 };
+constexpr int kZeroStrip = 7;  // amap / bmap entry: the side's zero strip (images: 0..4)
 
 // k_crt_prep for a share source over Z_2^128, every image of the side from one thread.
 // Element i draws keystream chunk i = part (i >> 6) & 3 of ChaCha block ((i >> 8) << 6) |
@@ -470,7 +476,7 @@ struct SrcPlan {
 // The thread holds r and v = x - r (the plain operand is read once) and walks the moduli
 // once: the residues of r and of v are full passes, the sum image's are combined from the
 // two (crt_combine, with the element's kappa), the zero image's are zero bytes; each goes
-// to every image of its phase.
+// to every image of its phase.  s.strip: the zero phase is one strip instead (SrcPlan).
 template <bool TRANS, int ROWS, bool PK>
 __global__ void __launch_bounds__(256)
     k_crt_prep_src(const SrcPlan s, const mxd::KeySrc keys, int64_t R, int64_t K,
@@ -589,6 +595,9 @@ __global__ void __launch_bounds__(256)
       for (int j = 0; j < 16; ++j) q[j] = (int)((rr[j][0] + v[j][0]) * tab.mul0);
       put(2, 0, pack16(q));
       put(3, 0, zero);
+      // the zero strip: tile 0's threads, here only (boff is their offset in the strip); the
+      // workspace is shared with other products, so it is written by every call
+      if (s.strip && t == 0) *(v4i*)(out + s.zoff + boff) = zero;
     }
     for (int i = 1; i < n; ++i) {
       const uint32_t w[4] = {tab.w[i][0], tab.w[i][1], tab.w[i][2], tab.w[i][3]};
@@ -950,12 +959,16 @@ __global__ void __launch_bounds__(64 * WR * WC, MINW)
     const int sh = 8 * (g / ep.n);
     const int e1 = (amap >> sh) & 7, e2 = (amap >> (sh + 3)) & 7;
     const int f1 = (bmap >> sh) & 7, f2 = (bmap >> (sh + 3)) & 7;
-    ga = RA + ((int64_t)(e1 * ep.n + mi) * tiles_m + tm) * a_nkb * (int64_t)kImg;
-    ga2 = RA + ((int64_t)(e2 * ep.n + mi) * tiles_m + tm) * a_nkb * (int64_t)kImg -
-          (int64_t)a_nkb * kImg;
-    gb = RB + ((int64_t)(f1 * ep.n + mi) * tiles_n + tn) * a_nkb * (int64_t)kImgB;
-    gb2 = RB + ((int64_t)(f2 * ep.n + mi) * tiles_n + tn) * a_nkb * (int64_t)kImgB -
-          (int64_t)a_nkb * kImgB;
+    // Entry kZeroStrip: an all-zero image, held as one (modulus, tile) strip of a_nkb
+    // k-steps right below the side's images and read for every modulus and tile (a fresh
+    // sharing's zero slot, run_crt_asym); ga2 / gb2 keep their bias of a_nkb k-steps.
+    const int64_t sa_ = (int64_t)a_nkb * kImg, sb_ = (int64_t)a_nkb * kImgB;
+    ga = e1 == kZeroStrip ? RA - sa_ : RA + ((int64_t)(e1 * ep.n + mi) * tiles_m + tm) * sa_;
+    ga2 = (e2 == kZeroStrip ? RA - sa_ : RA + ((int64_t)(e2 * ep.n + mi) * tiles_m + tm) * sa_) -
+          sa_;
+    gb = f1 == kZeroStrip ? RB - sb_ : RB + ((int64_t)(f1 * ep.n + mi) * tiles_n + tn) * sb_;
+    gb2 = (f2 == kZeroStrip ? RB - sb_ : RB + ((int64_t)(f2 * ep.n + mi) * tiles_n + tn) * sb_) -
+          sb_;
     khalf = a_nkb;
     if ((amap >> (sh + 6)) & 1) nkb = a_nkb;
   }
@@ -1451,26 +1464,39 @@ bool share_src_ok(const ShareSrc& s) {
   return s.x && (kind == MX_CROSS_ARITH || kind == MX_SHARE_F64) && s.j0 >= 0 && s.j0 < 3;
 }
 
-// The four K-residue images of one side of run_crt_asym's rolled product from a share source
-// (A: [x0 + x1, x2, x1, x0], B: [y0 + y1, y1 + y2, y2, y0]; entry e at out + e * entry).
-void launch_prep_src(const CPlan& p, const Tables& tb, bool is_b, const ShareSrc& src, int64_t R,
-                     int64_t K, int8_t* out, int64_t entry, hipStream_t st) {
+// The phase (SrcPlan) of each of the four K-residue images of one side of run_crt_asym's
+// rolled product from a share source (A: [x0 + x1, x2, x1, x0], B: [y0 + y1, y1 + y2, y2, y0]).
+void src_phases(bool is_b, const ShareSrc& src, int (&ph)[4]) {
   static const int kSlotsA[4][2] = {{0, 1}, {2, -1}, {1, -1}, {0, -1}};
   static const int kSlotsB[4][2] = {{0, 1}, {1, 2}, {2, -1}, {0, -1}};
-  const int kind = src.kind & ~MX_SHARE_MIRROR;
   int jr, jv;
   mxf::share_place(src.j0, (src.kind & MX_SHARE_MIRROR) != 0, &jr, &jv);
-  SrcPlan s;
-  s.x = src.x;
-  s.kind = kind;
-  s.pad = 0;
-  s.scale = kind == MX_SHARE_F64 ? std::ldexp(1.0, src.frac) : 0.0;
-  s.nonce = src.nonce;
   for (int e = 0; e < 4; ++e) {
     const int* sl = is_b ? kSlotsB[e] : kSlotsA[e];
     const bool has_r = sl[0] == jr || sl[1] == jr, has_v = sl[0] == jv || sl[1] == jv;
-    s.ph[e] = has_r && has_v ? 2 : has_r ? 0 : has_v ? 1 : 3;
-    s.off[e] = e * entry;
+    ph[e] = has_r && has_v ? 2 : has_r ? 0 : has_v ? 1 : 3;
+  }
+}
+
+// Those images in one launch: entry e of phase ph[e] at out + at[e] * entry.  at[e] ==
+// kZeroStrip (zero phase only): no image -- the prep writes the side's one zero strip at
+// out + zoff instead, which the GEMM reads for every modulus and tile of such an entry.
+void launch_prep_src(const CPlan& p, const Tables& tb, bool is_b, const ShareSrc& src, int64_t R,
+                     int64_t K, int8_t* out, int64_t entry, const int (&ph)[4],
+                     const int (&at)[4], int64_t zoff, hipStream_t st) {
+  const int kind = src.kind & ~MX_SHARE_MIRROR;
+  SrcPlan s;
+  s.x = src.x;
+  s.kind = kind;
+  s.strip = 0;
+  s.scale = kind == MX_SHARE_F64 ? std::ldexp(1.0, src.frac) : 0.0;
+  s.nonce = src.nonce;
+  s.zoff = zoff;
+  for (int e = 0; e < 4; ++e) {
+    const bool z = at[e] == kZeroStrip;
+    s.ph[e] = z ? -1 : ph[e];
+    s.off[e] = z ? 0 : at[e] * entry;
+    s.strip |= z;
   }
   const int64_t tiles = is_b ? p.tiles_n : p.tiles_m;
   const int rows = is_b ? p.bn : BM;
@@ -1665,7 +1691,8 @@ int run_crt(int64_t batch, int64_t M, int64_t N, int64_t K, const T* A0, const T
 // shares the plain input in registers (k_crt_prep_src) and the shares are never written.
 // Z_2^128, rolled with the dual images, K % 256 == 0 (xs) / N % 256 == 0 (ys) only: -7
 // otherwise, nothing launched.  The residue images are byte for byte those of k_share3
-// followed by k_crt_prep; the GEMM and the reconstruction do not know the difference.
+// followed by k_crt_prep, except that the zero slot's image is held as one zero strip (below);
+// the GEMM reads the same bytes and the reconstruction does not know the difference.
 template <class T>
 int run_crt_asym(int64_t M, int64_t N, int64_t K, const T* S0, const T* S1, const T* T0,
                  const T* T1, int rolled, T* C, hipStream_t st, const ShareSrc* xs = nullptr,
@@ -1710,7 +1737,6 @@ int run_crt_asym(int64_t M, int64_t N, int64_t K, const T* S0, const T* S1, cons
     amap = pmap(0, 1, 2, 3, 4);
     bmap = pmap(0, 1, 2, 3, 4);
   }
-  const int64_t ra_bytes = na * a_entry, rb_bytes = nb * b_entry;
   static const bool asum = [] {  // MOOSEX_CRT_ASUM=0: the sum inside the prep (mode 2)
     const char* e = std::getenv("MOOSEX_CRT_ASUM");
     return !(e && e[0] == '0');
@@ -1726,12 +1752,36 @@ int run_crt_asym(int64_t M, int64_t N, int64_t K, const T* S0, const T* S1, cons
     if (xs && (K % 256 || !share_src_ok(*xs))) return -7;
     if (ys && (N % 256 || !share_src_ok(*ys))) return -7;
   }
+  // A share source's zero slot: every (modulus, tile) strip of its image would be the same
+  // zero bytes, so the side keeps one strip right below its images instead (k_crt_gemm16's
+  // entry kZeroStrip) -- the other images close up, the maps follow, and the GEMM streams
+  // the strip from L2 where it fetched a whole image.  All five products still run.
+  static const bool zstrip = [] {  // MOOSEX_ZERO_STRIP=0: the full zero image
+    const char* e = std::getenv("MOOSEX_ZERO_STRIP");
+    return !(e && e[0] == '0');
+  }();
+  int aph[4], bph[4], aat[4] = {0, 1, 2, 3}, bat[4] = {0, 1, 2, 3};
+  int64_t a_strip = 0, b_strip = 0;
+  auto plan_src = [&](bool is_b, const ShareSrc& s, int (&ph)[4], int (&at)[4], int& n, int& map,
+                      int64_t& strip) {
+    src_phases(is_b, s, ph);
+    int m = 0;
+    for (int e = 0; e < 4; ++e) at[e] = zstrip && ph[e] == 3 ? kZeroStrip : m++;
+    if (m == n) return;  // no zero image on this side (y owned by slot 1, or switched off)
+    n = m;
+    strip = p.a_nkb * (int64_t)(is_b ? p.bn * BK : kImg);
+    for (int sh : {0, 8, 11, 16, 19}) map = (map & ~(7 << sh)) | (at[(map >> sh) & 7] << sh);
+  };
+  if (xs) plan_src(false, *xs, aph, aat, na, amap, a_strip);
+  if (ys) plan_src(true, *ys, bph, bat, nb, bmap, b_strip);
+  const int64_t ra_bytes = na * a_entry, rb_bytes = nb * b_entry;
   const int64_t sum_bytes = asum && !duals ? round_up(sa * (int64_t)sizeof(T), 256) : 0;
-  int8_t* ws = (int8_t*)workspace(ra_bytes + rb_bytes + p.cr_bytes + sum_bytes, st);
+  int8_t* ws = (int8_t*)workspace(
+      a_strip + ra_bytes + p.cr_bytes + b_strip + rb_bytes + sum_bytes, st);
   if (!ws) return -4;
-  int8_t* ra = ws;
+  int8_t* ra = ws + a_strip;
   int8_t* cr = ra + ra_bytes;
-  int8_t* rb = cr + p.cr_bytes;
+  int8_t* rb = cr + p.cr_bytes + b_strip;
   T* a01 = sum_bytes ? (T*)(rb + rb_bytes) : nullptr;
   if (a01)
     hipLaunchKernelGGL((k_add_pair<T>), dim3((unsigned)std::min<int64_t>((sa + 255) / 256, 65536)),
@@ -1757,12 +1807,12 @@ int run_crt_asym(int64_t M, int64_t N, int64_t K, const T* S0, const T* S1, cons
     put(sb_, d[1], c[1], 0, -b_entry);        // F2 = y2, dual F1 = y2 + y1
     put(sb_, d[2], d[0], 0, -3 * b_entry);    // F3 = y0, dual F0 = y0 + y1
     if (ys)
-      launch_prep_src(p, tb, true, *ys, N, K, rb, b_entry, st);
+      launch_prep_src(p, tb, true, *ys, N, K, rb, b_entry, bph, bat, -b_strip, st);
     else
       launch_prep<T>(p, tb, true, sb_.n, N, K, 0, nullptr, nullptr, 0, rb + 2 * b_entry, st, kn,
                      kn, sb_);
     if (xs)
-      launch_prep_src(p, tb, false, *xs, M, K, ra, a_entry, st);
+      launch_prep_src(p, tb, false, *xs, M, K, ra, a_entry, aph, aat, -a_strip, st);
     else
       launch_prep<T>(p, tb, false, sa_.n, M, K, 0, nullptr, nullptr, 0, ra + a_entry, st, kn, kn,
                      sa_);
