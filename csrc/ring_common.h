@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include "aes_core.h"
+#include "img_geom.h"
 #include "moosex.h"
 
 namespace mxr {
@@ -263,27 +264,21 @@ int mxh_transpose2(int words, const void* a0, void* out0, const void* a1, void* 
 int mxh_ew_binary_slot2(int op, int words, const void* a0, const void* a1, const void* b,
                         int64_t nb, void* out0, void* out1, int64_t m, int nparties, int which0,
                         int which1, void* stream);
+// the image leaves: g is validated and filled by img_geom_check (img_geom.h)
 int mxh_im2col(int elem_bytes, const void* in, void* out, int64_t slots, int64_t in_slot_stride,
-               int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH, int64_t KW, int64_t sh,
-               int64_t sw, int64_t pt, int64_t pl, int64_t dh, int64_t dw, int64_t OH,
-               int64_t OW, int nhwc, void* stream);
+               const mxr::ImgGeom& g, void* stream);
 int mxh_col2im(int elem_bytes, const void* in, void* out, int64_t slots, int64_t in_slot_stride,
-               int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH, int64_t KW, int64_t sh,
-               int64_t sw, int64_t pt, int64_t pl, int64_t dh, int64_t dw, int64_t OH,
-               int64_t OW, int nhwc, void* stream);
+               const mxr::ImgGeom& g, void* stream);
 int mxh_resize2d(int elem_bytes, const void* in, void* out, int64_t slots,
-                 int64_t in_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t OH,
-                 int64_t OW, const int32_t* th, const int32_t* tw, int wbh, int wbw, int nhwc,
-                 void* stream);
+                 int64_t in_slot_stride, const mxr::ImgGeom& g, const int32_t* th,
+                 const int32_t* tw, void* stream);
 int mxh_pwl_cross(int elem_bytes, const void* s0, const void* s1, const void* x0, const void* x1,
                   void* out, int64_t slots, int64_t s_slot_stride, int64_t x_slot_stride,
                   int64_t n, int k, const uint64_t* da, const uint64_t* db, const uint64_t* ak,
                   void* stream);
 int mxh_dwconv(int elem_bytes, const void* x0, const void* x1, const void* w0, const void* w1,
-               void* out, int64_t slots, int64_t x_slot_stride, int64_t w_slot_stride, int64_t N,
-               int64_t C, int64_t H, int64_t W, int64_t mult, int64_t KH, int64_t KW, int64_t sh,
-               int64_t sw, int64_t pt, int64_t pl, int64_t dh, int64_t dw, int64_t OH,
-               int64_t OW, int nhwc, void* stream);
+               void* out, int64_t slots, int64_t x_slot_stride, int64_t w_slot_stride,
+               const mxr::ImgGeom& g, void* stream);
 int mxh_ks_cross1(int words, const void* g0, const void* g1, const void* p0, const void* p1,
                   void* z, int64_t n, int d, int both, const uint8_t* keys16, uint64_t nonce,
                   void* stream);

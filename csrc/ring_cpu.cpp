@@ -322,15 +322,26 @@ void mx_cpu_parallel_for(int64_t n, int64_t grain,
     default: return -2;                               \
   }
 
+// the arithmetic element widths of the image leaves (moosex.h): 8 or 16 bytes
+#define DISPATCH_ELEM(elem_bytes, T, ...)      \
+  switch (elem_bytes) {                        \
+    case 8: { using T = u64; __VA_ARGS__; }    \
+    case 16: { using T = u128; __VA_ARGS__; }  \
+    default: return -2;                        \
+  }
+
 namespace {
 
+using mxr::ImgGeom;
+
+// The image leaves take the record img_geom_check (img_geom.h) filled; their loops read its
+// attributes, strides and counts under the names of moosex.h.
 template <class T>
-void im2col_cpu(const T* in, T* out, int64_t slots, int64_t in_slot_stride, int64_t N,
-                       int64_t C, int64_t H, int64_t W, int64_t KH, int64_t KW, int64_t sh,
-                       int64_t sw, int64_t pt, int64_t pl, int64_t dh, int64_t dw, int64_t OH,
-                       int64_t OW, int nhwc) {
-  const int64_t K = C * KH * KW, rows = N * OH * OW;
-  const int64_t sN = C * H * W, sH = nhwc ? W * C : W, sW = nhwc ? C : 1, sC = nhwc ? 1 : H * W;
+void im2col_cpu(const T* in, T* out, int64_t slots, int64_t in_slot_stride, const ImgGeom& geom) {
+  const int64_t C = geom.C, H = geom.H, W = geom.W, KH = geom.KH, KW = geom.KW, sh = geom.sh, sw = geom.sw;
+  const int64_t pt = geom.pt, pl = geom.pl, dh = geom.dh, dw = geom.dw, OH = geom.OH, OW = geom.OW;
+  const int64_t K = geom.K, rows = geom.rows, sN = geom.sN, sH = geom.sH, sW = geom.sW, sC = geom.sC;
+  const bool nhwc = geom.nhwc;
   parallel_for(slots * rows, std::max<int64_t>(1, 4096 / K), [=](int64_t b, int64_t e) {
     for (int64_t g = b; g < e; ++g) {
       const int64_t s = g / rows, row = g - s * rows;
@@ -352,12 +363,11 @@ void im2col_cpu(const T* in, T* out, int64_t slots, int64_t in_slot_stride, int6
 // col2im (moosex.h mx_col2im): every image pixel gathers the patch-matrix entries whose tap
 // lands on it; parallel over the image rows (s, n, y)
 template <class T>
-void col2im_cpu(const T* in, T* out, int64_t slots, int64_t in_slot_stride, int64_t N,
-                int64_t C, int64_t H, int64_t W, int64_t KH, int64_t KW, int64_t sh, int64_t sw,
-                int64_t pt, int64_t pl, int64_t dh, int64_t dw, int64_t OH, int64_t OW,
-                int nhwc) {
-  const int64_t K = C * KH * KW;
-  const int64_t sN = C * H * W, sH = nhwc ? W * C : W, sW = nhwc ? C : 1, sC = nhwc ? 1 : H * W;
+void col2im_cpu(const T* in, T* out, int64_t slots, int64_t in_slot_stride, const ImgGeom& geom) {
+  const int64_t N = geom.N, C = geom.C, H = geom.H, W = geom.W, KH = geom.KH, KW = geom.KW, sh = geom.sh, sw = geom.sw;
+  const int64_t pt = geom.pt, pl = geom.pl, dh = geom.dh, dw = geom.dw, OH = geom.OH, OW = geom.OW;
+  const int64_t K = geom.K, sN = geom.sN, sH = geom.sH, sW = geom.sW, sC = geom.sC;
+  const bool nhwc = geom.nhwc;
   parallel_for(slots * N * H, std::max<int64_t>(1, 4096 / (W * K)), [=](int64_t b, int64_t e) {
     for (int64_t g = b; g < e; ++g) {
       const int64_t y = g % H, n = (g / H) % N, s = g / (H * N);
@@ -386,10 +396,12 @@ void col2im_cpu(const T* in, T* out, int64_t slots, int64_t in_slot_stride, int6
 // four taps (one tap without a multiply when both weight widths are 0); parallel over the
 // output rows (s, n, oy)
 template <class T>
-void resize2d_cpu(const T* in, T* out, int64_t slots, int64_t in_slot_stride, int64_t N,
-                  int64_t C, int64_t H, int64_t W, int64_t OH, int64_t OW, const int32_t* th,
-                  const int32_t* tw, int wbh, int wbw, int nhwc) {
-  const int64_t sH = nhwc ? W * C : W, sW = nhwc ? C : 1, sC = nhwc ? 1 : H * W;
+void resize2d_cpu(const T* in, T* out, int64_t slots, int64_t in_slot_stride, const ImgGeom& geom,
+                  const int32_t* th, const int32_t* tw) {
+  const int64_t N = geom.N, C = geom.C, H = geom.H, W = geom.W, OH = geom.OH, OW = geom.OW;
+  const int64_t sH = geom.sH, sW = geom.sW, sC = geom.sC;
+  const int wbh = geom.wbh, wbw = geom.wbw;
+  const bool nhwc = geom.nhwc;
   const int64_t oH = nhwc ? OW * C : OW, oW = nhwc ? C : 1, oC = nhwc ? 1 : OH * OW;
   const bool nearest = wbh == 0 && wbw == 0;
   parallel_for(slots * N * OH, std::max<int64_t>(1, 4096 / (OW * C)), [=](int64_t b, int64_t e) {
@@ -421,12 +433,12 @@ void resize2d_cpu(const T* in, T* out, int64_t slots, int64_t in_slot_stride, in
 // cross mode's w0 + w1 is formed once per weight element
 template <class T>
 void dwconv_cpu(const T* x0, const T* x1, const T* w0, const T* w1, T* out, int64_t slots,
-                int64_t x_slot_stride, int64_t w_slot_stride, int64_t N, int64_t C, int64_t H,
-                int64_t W, int64_t mult, int64_t KH, int64_t KW, int64_t sh, int64_t sw,
-                int64_t pt, int64_t pl, int64_t dh, int64_t dw, int64_t OH, int64_t OW,
-                int nhwc) {
-  const int64_t OC = C * mult, taps = KH * KW, rows = N * OH * OW;
-  const int64_t sN = C * H * W, sH = nhwc ? W * C : W, sW = nhwc ? C : 1, sC = nhwc ? 1 : H * W;
+                int64_t x_slot_stride, int64_t w_slot_stride, const ImgGeom& geom) {
+  const int64_t H = geom.H, W = geom.W, mult = geom.mult, KH = geom.KH, KW = geom.KW, sh = geom.sh, sw = geom.sw;
+  const int64_t pt = geom.pt, pl = geom.pl, dh = geom.dh, dw = geom.dw, OH = geom.OH, OW = geom.OW;
+  const int64_t OC = geom.OC, taps = KH * KW, rows = geom.N * OH * OW;
+  const int64_t sN = geom.sN, sH = geom.sH, sW = geom.sW, sC = geom.sC;
+  const bool nhwc = geom.nhwc;
   const bool cross = x1 != nullptr;
   std::vector<T> wsum;
   if (cross) {
@@ -598,84 +610,47 @@ int mx_im2col(int dev, int elem_bytes, const void* in, void* out, int64_t slots,
               int64_t in_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH,
               int64_t KW, int64_t sh, int64_t sw, int64_t pt, int64_t pl, int64_t dh,
               int64_t dw, int64_t OH, int64_t OW, int nhwc, void* stream) {
-  if (OH <= 0 || OW <= 0 || KH <= 0 || KW <= 0 || sh <= 0 || sw <= 0 || dh <= 0 || dw <= 0 ||
-      pt < 0 || pl < 0 || N < 0 || C < 0 || H < 0 || W < 0 || slots < 0)
-    return -3;
-  // every tap coordinate oh*sh + kh*dh - pt (and its w twin) has to fit an int: the kernels
-  // compute them in 32 bits
-  const int64_t lim = 0x7fffffff;
-  const int64_t dims[] = {N, C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW};
-  for (int64_t d : dims)
-    if (d > lim) return -3;
-  if ((OH - 1) * sh + (KH - 1) * dh > lim || (OW - 1) * sw + (KW - 1) * dw > lim) return -3;
-  if (dev)
-    return mxh_im2col(elem_bytes, in, out, slots, in_slot_stride, N, C, H, W, KH, KW, sh, sw, pt,
-                      pl, dh, dw, OH, OW, nhwc, stream);
-  if (slots * N * OH * OW * C * KH * KW == 0) return 0;
-  switch (elem_bytes) {
-    case 1:
-      im2col_cpu((const uint8_t*)in, (uint8_t*)out, slots, in_slot_stride, N, C, H, W, KH, KW,
-                 sh, sw, pt, pl, dh, dw, OH, OW, nhwc);
-      return 0;
-    case 8:
-      im2col_cpu((const u64*)in, (u64*)out, slots, in_slot_stride, N, C, H, W, KH, KW, sh, sw,
-                 pt, pl, dh, dw, OH, OW, nhwc);
-      return 0;
-    case 16:
-      im2col_cpu((const u128*)in, (u128*)out, slots, in_slot_stride, N, C, H, W, KH, KW, sh,
-                 sw, pt, pl, dh, dw, OH, OW, nhwc);
-      return 0;
-    default: return -2;
+  ImgGeom g{N, C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW};
+  g.nhwc = nhwc;
+  const int rc = mxr::img_geom_check(g, mxr::kIm2colLeaf, elem_bytes, slots, in_slot_stride);
+  if (rc <= 0) return rc;
+  if (dev) return mxh_im2col(elem_bytes, in, out, slots, in_slot_stride, g, stream);
+  if (elem_bytes == 1) {  // bit tensors: the one leaf that moves them
+    im2col_cpu((const uint8_t*)in, (uint8_t*)out, slots, in_slot_stride, g);
+    return 0;
   }
+  DISPATCH_ELEM(elem_bytes, T, {
+    im2col_cpu((const T*)in, (T*)out, slots, in_slot_stride, g);
+    return 0;
+  });
 }
 
 int mx_col2im(int dev, int elem_bytes, const void* in, void* out, int64_t slots,
               int64_t in_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH,
               int64_t KW, int64_t sh, int64_t sw, int64_t pt, int64_t pl, int64_t dh,
               int64_t dw, int64_t OH, int64_t OW, int nhwc, void* stream) {
-  if (OH <= 0 || OW <= 0 || KH <= 0 || KW <= 0 || sh <= 0 || sw <= 0 || dh <= 0 || dw <= 0 ||
-      pt < 0 || pl < 0 || N < 0 || C < 0 || H < 0 || W < 0 || slots < 0 || in_slot_stride < 0)
-    return -3;
-  if (elem_bytes != 8 && elem_bytes != 16) return -2;
-  // every tap coordinate y + pt - kh*dh (and its w twin) has to fit an int: the kernels
-  // compute them in 32 bits
-  const int64_t lim = 0x7fffffff;
-  const int64_t dims[] = {N, C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW};
-  for (int64_t d : dims)
-    if (d > lim) return -3;
-  if (H + pt > lim || W + pl > lim || (KH - 1) * dh > lim || (KW - 1) * dw > lim ||
-      KH * KW > lim)
-    return -3;
-  if (dev)
-    return mxh_col2im(elem_bytes, in, out, slots, in_slot_stride, N, C, H, W, KH, KW, sh, sw, pt,
-                      pl, dh, dw, OH, OW, nhwc, stream);
-  if (slots * N * C * H * W == 0) return 0;
-  if (elem_bytes == 8)
-    col2im_cpu((const u64*)in, (u64*)out, slots, in_slot_stride, N, C, H, W, KH, KW, sh, sw, pt,
-               pl, dh, dw, OH, OW, nhwc);
-  else
-    col2im_cpu((const u128*)in, (u128*)out, slots, in_slot_stride, N, C, H, W, KH, KW, sh, sw,
-               pt, pl, dh, dw, OH, OW, nhwc);
-  return 0;
+  ImgGeom g{N, C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW};
+  g.nhwc = nhwc;
+  const int rc = mxr::img_geom_check(g, mxr::kCol2imLeaf, elem_bytes, slots, in_slot_stride);
+  if (rc <= 0) return rc;
+  if (dev) return mxh_col2im(elem_bytes, in, out, slots, in_slot_stride, g, stream);
+  DISPATCH_ELEM(elem_bytes, T, {
+    col2im_cpu((const T*)in, (T*)out, slots, in_slot_stride, g);
+    return 0;
+  });
 }
 
 int mx_resize2d(int dev, int elem_bytes, const void* in, void* out, int64_t slots,
                 int64_t in_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t OH,
                 int64_t OW, const int32_t* th, const int32_t* tw, int wbh, int wbw, int nhwc,
                 void* stream) {
-  if (N < 0 || C < 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || slots < 0 ||
-      in_slot_stride < 0 || wbh < 0 || wbh > 12 || wbw < 0 || wbw > 12)
-    return -3;
-  if (elem_bytes != 8 && elem_bytes != 16) return -2;
-  // the kernels hold every coordinate in 32 bits
-  const int64_t dims[] = {N, C, H, W, OH, OW};
-  for (int64_t d : dims)
-    if (d > 0x7fffffff) return -3;
-  if (slots * N * C == 0) return 0;
+  ImgGeom g{N, C, H, W, 1, 1, 1, 1, 0, 0, 1, 1, OH, OW};  // a 1 x 1 window
+  g.wbh = wbh, g.wbw = wbw, g.nhwc = nhwc;
+  const int rc = mxr::img_geom_check(g, mxr::kResize2dLeaf, elem_bytes, slots, in_slot_stride);
+  if (rc <= 0) return rc;
   if (!th || !tw) return -3;
-  if (dev)
-    return mxh_resize2d(elem_bytes, in, out, slots, in_slot_stride, N, C, H, W, OH, OW, th, tw,
-                        wbh, wbw, nhwc, stream);
+  if (dev) return mxh_resize2d(elem_bytes, in, out, slots, in_slot_stride, g, th, tw, stream);
+  // the tables are checked on the host only: the kernel clamps what it reads from them
   for (int64_t o = 0; o < OH; ++o)
     if (th[o] < 0 || th[o] >= H || th[OH + o] < 0 || th[OH + o] >= H || th[2 * OH + o] < 0 ||
         th[2 * OH + o] > (wbh ? 1 << wbh : 0))
@@ -684,13 +659,10 @@ int mx_resize2d(int dev, int elem_bytes, const void* in, void* out, int64_t slot
     if (tw[o] < 0 || tw[o] >= W || tw[OW + o] < 0 || tw[OW + o] >= W || tw[2 * OW + o] < 0 ||
         tw[2 * OW + o] > (wbw ? 1 << wbw : 0))
       return -3;
-  if (elem_bytes == 8)
-    resize2d_cpu((const u64*)in, (u64*)out, slots, in_slot_stride, N, C, H, W, OH, OW, th, tw,
-                 wbh, wbw, nhwc);
-  else
-    resize2d_cpu((const u128*)in, (u128*)out, slots, in_slot_stride, N, C, H, W, OH, OW, th, tw,
-                 wbh, wbw, nhwc);
-  return 0;
+  DISPATCH_ELEM(elem_bytes, T, {
+    resize2d_cpu((const T*)in, (T*)out, slots, in_slot_stride, g, th, tw);
+    return 0;
+  });
 }
 
 int mx_dwconv(int dev, int elem_bytes, const void* x0, const void* x1, const void* w0,
@@ -698,37 +670,20 @@ int mx_dwconv(int dev, int elem_bytes, const void* x0, const void* x1, const voi
               int64_t w_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t mult,
               int64_t KH, int64_t KW, int64_t sh, int64_t sw, int64_t pt, int64_t pl,
               int64_t dh, int64_t dw, int64_t OH, int64_t OW, int nhwc, void* stream) {
-  if (OH <= 0 || OW <= 0 || KH <= 0 || KW <= 0 || sh <= 0 || sw <= 0 || dh <= 0 || dw <= 0 ||
-      pt < 0 || pl < 0 || N < 0 || C < 0 || H < 0 || W < 0 || mult <= 0 || slots < 0 ||
-      x_slot_stride < 0 || w_slot_stride < 0)
-    return -3;
+  ImgGeom g{N, C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW, mult};
+  g.nhwc = nhwc;
   if ((x1 == nullptr) != (w1 == nullptr)) return -3;  // cross mode takes both second components
-  // every tap coordinate and channel index has to fit an int: the kernels compute them in
-  // 32 bits
-  const int64_t lim = 0x7fffffff;
-  const int64_t dims[] = {N, C, H, W, mult, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW};
-  for (int64_t d : dims)
-    if (d > lim) return -3;
-  if ((OH - 1) * sh + (KH - 1) * dh > lim || (OW - 1) * sw + (KW - 1) * dw > lim ||
-      C * mult > lim || KH * KW > lim)
-    return -3;
+  const int rc = mxr::img_geom_check(g, mxr::kDwconvLeaf, elem_bytes, slots, x_slot_stride,
+                                     w_slot_stride);
+  if (rc <= 0) return rc;
   if (dev)
-    return mxh_dwconv(elem_bytes, x0, x1, w0, w1, out, slots, x_slot_stride, w_slot_stride, N, C,
-                      H, W, mult, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW, nhwc, stream);
-  if (slots * N * OH * OW * C == 0) return 0;
-  switch (elem_bytes) {
-    case 8:
-      dwconv_cpu((const u64*)x0, (const u64*)x1, (const u64*)w0, (const u64*)w1, (u64*)out, slots,
-                 x_slot_stride, w_slot_stride, N, C, H, W, mult, KH, KW, sh, sw, pt, pl, dh, dw,
-                 OH, OW, nhwc);
-      return 0;
-    case 16:
-      dwconv_cpu((const u128*)x0, (const u128*)x1, (const u128*)w0, (const u128*)w1, (u128*)out,
-                 slots, x_slot_stride, w_slot_stride, N, C, H, W, mult, KH, KW, sh, sw, pt, pl,
-                 dh, dw, OH, OW, nhwc);
-      return 0;
-    default: return -2;
-  }
+    return mxh_dwconv(elem_bytes, x0, x1, w0, w1, out, slots, x_slot_stride, w_slot_stride, g,
+                      stream);
+  DISPATCH_ELEM(elem_bytes, T, {
+    dwconv_cpu((const T*)x0, (const T*)x1, (const T*)w0, (const T*)w1, (T*)out, slots,
+               x_slot_stride, w_slot_stride, g);
+    return 0;
+  });
 }
 
 int mx_pwl_cross(int dev, int elem_bytes, const void* s0, const void* s1, const void* x0,
@@ -744,13 +699,11 @@ int mx_pwl_cross(int dev, int elem_bytes, const void* s0, const void* s1, const 
   if (dev)
     return mxh_pwl_cross(elem_bytes, s0, s1, x0, x1, out, slots, s_slot_stride, x_slot_stride, n,
                          k, da, db, ak, stream);
-  if (elem_bytes == 8)
-    pwl_cross_cpu((const u64*)s0, (const u64*)s1, (const u64*)x0, (const u64*)x1, (u64*)out, slots,
+  DISPATCH_ELEM(elem_bytes, T, {
+    pwl_cross_cpu((const T*)s0, (const T*)s1, (const T*)x0, (const T*)x1, (T*)out, slots,
                   s_slot_stride, x_slot_stride, n, k, da, db, ak);
-  else
-    pwl_cross_cpu((const u128*)s0, (const u128*)s1, (const u128*)x0, (const u128*)x1, (u128*)out,
-                  slots, s_slot_stride, x_slot_stride, n, k, da, db, ak);
-  return 0;
+    return 0;
+  });
 }
 
 int mx_ew_unary2(int dev, int op, int words, const void* a0, void* out0, const void* a1,

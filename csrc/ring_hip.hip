@@ -1795,6 +1795,86 @@ __global__ void __launch_bounds__(256) k_prf_expand(T* __restrict__ out, int64_t
   d_prf_expand<T>(out, n, nkeys, keys, nonce);
 }
 
+// ---------------------------------------------------------------------------
+// The image leaves (im2col, dwconv, col2im, resize2d, pwl_cross).  Their kernels are
+// templates over <T, I, V>: the element, the index type (32-bit when every extent fits) and
+// the elements a lane owns (2 only for u64: every access is 16 bytes).  The host side below is
+// shared: the geometry arrives validated in an ImgGeom (img_geom.h), leaf_dispatch picks the
+// form, lane_plan and row_grid shape the launch of a rows x inner output.
+// ---------------------------------------------------------------------------
+using mxr::ImgGeom;
+
+template <class T, int V>
+struct alignas(sizeof(T) * V) LaneVec {
+  T v[V];
+};
+
+template <class T_, class I_, int V_>
+struct LeafForm {
+  using T = T_;
+  using I = I_;
+  static constexpr int V = V_;
+};
+
+// launch(LeafForm<T, I, V>{}) for elem_bytes (1 only where BYTES; else -2, as any other
+// width), 32-bit indices when `small`, two u64 per lane when `two`
+template <class T, int V, class F>
+static int leaf_index(bool small, F& launch) {
+  return small ? launch(LeafForm<T, int32_t, V>{}) : launch(LeafForm<T, int64_t, V>{});
+}
+template <bool BYTES = false, class F>
+static int leaf_dispatch(int elem_bytes, bool small, bool two, F launch) {
+  switch (elem_bytes) {
+    case 1:
+      if constexpr (BYTES) return leaf_index<uint8_t, 1>(small, launch);
+      return -2;
+    case 8: return two ? leaf_index<u64, 2>(small, launch) : leaf_index<u64, 1>(small, launch);
+    case 16: return leaf_index<u128, 1>(small, launch);
+    default: return -2;
+  }
+}
+
+// 32-bit indices serve extents below 2^31 elements less `headroom`, the overshoot of a lane's
+// last loop step
+static bool fits32(int64_t headroom, std::initializer_list<int64_t> extents) {
+  for (int64_t e : extents)
+    if (e >= (1ll << 31) - headroom) return false;
+  return true;
+}
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// A block of 256 lanes over a rows x inner output: bx inner lanes of V elements, no more
+// than the inner extent needs (and at most max_bx), by 256 / bx rows; `tiles` blocks cover
+// the inner extent.
+struct LanePlan {
+  int bx, by;
+  int64_t tiles;
+};
+static LanePlan lane_plan(int64_t inner, int V, int max_bx = 64) {
+  int bx = max_bx;
+  while (bx > 1 && (bx / 2) * V >= inner) bx /= 2;
+  return {bx, 256 / bx, (inner + (int64_t)bx * V - 1) / ((int64_t)bx * V)};
+}
+
+// the row grid is capped at 65,536 rows; a lane strides over the rest
+static int64_t row_grid(int64_t rows, int by) {
+  return std::min<int64_t>((rows + by - 1) / by, 65536 / by);
+}
+
+// the input strides and the window attributes of a kernel's parameter struct
+template <class P>
+static void set_strides(P& p, const ImgGeom& g) {
+  using I = decltype(p.sN);
+  p.sN = (I)g.sN, p.sH = (I)g.sH, p.sW = (I)g.sW, p.sC = (I)g.sC;
+}
+template <class P>
+static void set_window(P& p, const ImgGeom& g) {
+  p.H = (int)g.H, p.W = (int)g.W, p.KH = (int)g.KH, p.KW = (int)g.KW, p.sh = (int)g.sh;
+  p.sw = (int)g.sw, p.pt = (int)g.pt, p.pl = (int)g.pl, p.dh = (int)g.dh, p.dw = (int)g.dw;
+  p.OH = (int)g.OH, p.OW = (int)g.OW, p.nhwc = g.nhwc;
+}
+
 // im2col: the patch gather that turns a 2-D convolution into a GEMM over shares.  Output-
 // stationary: a lane owns V adjacent output columns of one row, so stores are coalesced
 // (V = 2 for u64 with an even row length: one 16-byte store; u128 moves 16 bytes per lane as
@@ -1809,11 +1889,6 @@ struct Im2colP {
   I in_slot_stride, sN, sH, sW, sC;  // input strides in elements (format-dependent)
   I K, rows;
   int C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW, nhwc;
-};
-
-template <class T, int V>
-struct alignas(sizeof(T) * V) Im2colVec {
-  T v[V];
 };
 
 template <class T, class I, int V>
@@ -1854,7 +1929,7 @@ __global__ void __launch_bounds__(256) k_im2col(const T* __restrict__ in, T* __r
     const int oh = (int)(q - n * (U)p.OH);
     const I base = (I)n * p.sN;
     const int y0 = oh * p.sh, x0 = ow * p.sw;
-    Im2colVec<T, V> o;
+    LaneVec<T, V> o;
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       const int iy = y0 + dy[j], ix = x0 + dx[j];
@@ -1863,30 +1938,21 @@ __global__ void __launch_bounds__(256) k_im2col(const T* __restrict__ in, T* __r
         v = src[base + coff[j] + (I)iy * p.sH + (I)ix * p.sW];
       o.v[j] = v;
     }
-    *reinterpret_cast<Im2colVec<T, V>*>(dst + row * p.K + col0) = o;
+    *reinterpret_cast<LaneVec<T, V>*>(dst + row * p.K + col0) = o;
   }
 }
 
 template <class T, class I, int V>
 static int im2col_launch(const void* in, void* out, int64_t slots, int64_t in_slot_stride,
-                         int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH, int64_t KW,
-                         int64_t sh, int64_t sw, int64_t pt, int64_t pl, int64_t dh, int64_t dw,
-                         int64_t OH, int64_t OW, int nhwc, void* stream) {
+                         const ImgGeom& g, void* stream) {
   Im2colP<I> p;
   p.in_slot_stride = (I)in_slot_stride;
-  p.sN = (I)(C * H * W);
-  p.sH = (I)(nhwc ? W * C : W);
-  p.sW = (I)(nhwc ? C : 1);
-  p.sC = (I)(nhwc ? 1 : H * W);
-  p.K = (I)(C * KH * KW);
-  p.rows = (I)(N * OH * OW);
-  p.C = (int)C, p.H = (int)H, p.W = (int)W, p.KH = (int)KH, p.KW = (int)KW;
-  p.sh = (int)sh, p.sw = (int)sw, p.pt = (int)pt, p.pl = (int)pl, p.dh = (int)dh;
-  p.dw = (int)dw, p.OH = (int)OH, p.OW = (int)OW, p.nhwc = nhwc;
-  const int64_t K = C * KH * KW, rows = N * OH * OW;
-  const int64_t gx = (K + 64 * V - 1) / (64 * V);
-  const int64_t gy = std::min<int64_t>((rows + 3) / 4, 16384);
-  hipLaunchKernelGGL((k_im2col<T, I, V>), dim3((unsigned)gx, (unsigned)gy, (unsigned)slots),
+  set_strides(p, g);
+  set_window(p, g);
+  p.K = (I)g.K, p.rows = (I)g.rows, p.C = (int)g.C;
+  const int64_t gx = (g.K + 64 * V - 1) / (64 * V);  // the kernel's block is 64 x 4
+  hipLaunchKernelGGL((k_im2col<T, I, V>),
+                     dim3((unsigned)gx, (unsigned)row_grid(g.rows, 4), (unsigned)slots),
                      dim3(64, 4), 0, S(stream), (const T*)in, (T*)out, p);
   MX_LAUNCH_CHECK();
   return 0;
@@ -1981,7 +2047,7 @@ __global__ void __launch_bounds__(256) k_dwconv(const T* __restrict__ x0,
     }
     const I base = (I)n * p.sN;
     const int y0 = oh * p.sh - p.pt;
-    Im2colVec<T, V> acc;
+    LaneVec<T, V> acc;
 #pragma unroll
     for (int j = 0; j < V; ++j) acc.v[j] = (T)0;
     for (int kh = 0; kh < p.KH; ++kh) {
@@ -2000,48 +2066,39 @@ __global__ void __launch_bounds__(256) k_dwconv(const T* __restrict__ x0,
         }
       }
     }
-    *reinterpret_cast<Im2colVec<T, V>*>(dst + oidx) = acc;
+    *reinterpret_cast<LaneVec<T, V>*>(dst + oidx) = acc;
   }
 }
 
 template <class T, class I, int V, bool CROSS>
 static int dwconv_launch(const void* x0, const void* x1, const void* w0, const void* w1,
                          void* out, int64_t slots, int64_t x_slot_stride, int64_t w_slot_stride,
-                         int64_t N, int64_t C, int64_t H, int64_t W, int64_t mult, int64_t KH,
-                         int64_t KW, int64_t sh, int64_t sw, int64_t pt, int64_t pl, int64_t dh,
-                         int64_t dw, int64_t OH, int64_t OW, int nhwc, void* stream) {
-  const int64_t OC = C * mult, taps = KH * KW;
-  const int64_t inner = nhwc ? OC : OW, rows = nhwc ? N * OH * OW : N * OH;
-  // inner lanes of a block: no more than the inner extent needs, and few enough that the
-  // block's weights fit 64 KB of LDS (NHWC: bx * V channels; NCHW: one channel)
-  const int64_t per = taps * (int64_t)sizeof(T) * (CROSS ? 2 : 1);
-  int bx = 64;
-  while (bx > 1 && (bx / 2) * V >= inner) bx /= 2;
-  while (bx > 1 && nhwc && per * bx * V > 65536) bx /= 2;
-  const int64_t lds = per * (nhwc ? bx * V : 1);
+                         const ImgGeom& g, void* stream) {
+  const bool nhwc = g.nhwc;
+  // NCHW: the channel is part of blockIdx.x, the rows are (n, oh)
+  const int64_t rows = nhwc ? g.rows : g.N * g.OH;
+  // inner lanes of a block: few enough that the block's weights fit 64 KB of LDS (NHWC: bx * V
+  // channels; NCHW: one channel)
+  const int64_t per = g.KH * g.KW * (int64_t)sizeof(T) * (CROSS ? 2 : 1);
+  int max_bx = 64;
+  while (max_bx > 1 && nhwc && per * max_bx * V > 65536) max_bx /= 2;
+  const LanePlan b = lane_plan(g.inner, V, max_bx);
+  const int64_t lds = per * (nhwc ? b.bx * V : 1);
   if (lds > 65536) return -3;
-  const int by = 256 / bx;
-  const int64_t tiles = (inner + (int64_t)bx * V - 1) / ((int64_t)bx * V);
-  const int64_t gx = nhwc ? tiles : OC * tiles;
+  const int64_t gx = nhwc ? b.tiles : g.OC * b.tiles;
   if (gx > 0x7fffffff) return -3;
   // rows per lane: one visit while that leaves the grid small, up to 8 on a large one (the
-  // staged weights serve them all); the row grid is capped at 65,536 rows, as k_im2col's
-  const int64_t gy_full = (rows + by - 1) / by;
+  // staged weights serve them all)
+  const int64_t gy_full = (rows + b.by - 1) / b.by;
   const int64_t visits = std::max<int64_t>(1, std::min<int64_t>(8, gx * slots * gy_full / 4096));
-  const int64_t gy = std::min<int64_t>((gy_full + visits - 1) / visits, 65536 / by);
+  const int64_t gy = std::min<int64_t>((gy_full + visits - 1) / visits, 65536 / b.by);
   DwconvP<I> p;
-  p.x_slot = (I)x_slot_stride, p.w_slot = (I)w_slot_stride;
-  p.o_slot = (I)(N * OH * OW * OC);
-  p.sN = (I)(C * H * W);
-  p.sH = (I)(nhwc ? W * C : W);
-  p.sW = (I)(nhwc ? C : 1);
-  p.sC = (I)(nhwc ? 1 : H * W);
-  p.rows = (I)rows;
-  p.H = (int)H, p.W = (int)W, p.KH = (int)KH, p.KW = (int)KW, p.sh = (int)sh, p.sw = (int)sw;
-  p.pt = (int)pt, p.pl = (int)pl, p.dh = (int)dh, p.dw = (int)dw, p.OH = (int)OH;
-  p.OW = (int)OW, p.OC = (int)OC, p.mult = (int)mult, p.nhwc = nhwc, p.tiles = (int)tiles;
+  p.x_slot = (I)x_slot_stride, p.w_slot = (I)w_slot_stride, p.o_slot = (I)g.n_out;
+  set_strides(p, g);
+  set_window(p, g);
+  p.rows = (I)rows, p.OC = (int)g.OC, p.mult = (int)g.mult, p.tiles = (int)b.tiles;
   hipLaunchKernelGGL((k_dwconv<T, I, V, CROSS>), dim3((unsigned)gx, (unsigned)gy, (unsigned)slots),
-                     dim3(bx, by), (size_t)lds, S(stream), (const T*)x0, (const T*)x1,
+                     dim3(b.bx, b.by), (size_t)lds, S(stream), (const T*)x0, (const T*)x1,
                      (const T*)w0, (const T*)w1, (T*)out, p);
   MX_LAUNCH_CHECK();
   return 0;
@@ -2092,7 +2149,7 @@ __global__ void __launch_bounds__(256) k_col2im(const T* __restrict__ in, T* __r
       x = (int)i0;
     }
     const I nbase = (I)n * (I)p.OH * (I)p.OW;
-    Im2colVec<T, V> acc;
+    LaneVec<T, V> acc;
 #pragma unroll
     for (int j = 0; j < V; ++j) acc.v[j] = (T)0;
     for (int kh = 0; kh < p.KH; ++kh) {
@@ -2108,7 +2165,7 @@ __global__ void __launch_bounds__(256) k_col2im(const T* __restrict__ in, T* __r
           const unsigned ow = (unsigned)tx / (unsigned)p.sw;
           if (ow * (unsigned)p.sw != (unsigned)tx || ow >= (unsigned)p.OW) continue;
           const I si = (rbase + (I)ow) * p.K + (I)(kh * p.KW + kw) * (I)p.C + (I)i0;
-          const Im2colVec<T, V> r = *reinterpret_cast<const Im2colVec<T, V>*>(src + si);
+          const LaneVec<T, V> r = *reinterpret_cast<const LaneVec<T, V>*>(src + si);
 #pragma unroll
           for (int j = 0; j < V; ++j) acc.v[j] += r.v[j];
         }
@@ -2126,33 +2183,21 @@ __global__ void __launch_bounds__(256) k_col2im(const T* __restrict__ in, T* __r
         }
       }
     }
-    *reinterpret_cast<Im2colVec<T, V>*>(dst + row * (I)inner + (I)i0) = acc;
+    *reinterpret_cast<LaneVec<T, V>*>(dst + row * (I)inner + (I)i0) = acc;
   }
 }
 
 template <class T, class I, int V>
 static int col2im_launch(const void* in, void* out, int64_t slots, int64_t in_slot_stride,
-                         int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH, int64_t KW,
-                         int64_t sh, int64_t sw, int64_t pt, int64_t pl, int64_t dh, int64_t dw,
-                         int64_t OH, int64_t OW, int nhwc, void* stream) {
-  const int64_t inner = nhwc ? C : W, rows = nhwc ? N * H * W : N * C * H;
-  // inner lanes of a block: no more than the inner extent needs
-  int bx = 64;
-  while (bx > 1 && (bx / 2) * V >= inner) bx /= 2;
-  const int by = 256 / bx;
-  const int64_t gx = (inner + (int64_t)bx * V - 1) / ((int64_t)bx * V);
-  // the row grid is capped at 65,536 rows, as k_im2col's; a lane strides over the rest
-  const int64_t gy = std::min<int64_t>((rows + by - 1) / by, 65536 / by);
+                         const ImgGeom& g, void* stream) {
+  const LanePlan b = lane_plan(g.inner, V);
   Col2imP<I> p;
-  p.in_slot = (I)in_slot_stride;
-  p.o_slot = (I)(N * C * H * W);
-  p.K = (I)(C * KH * KW);
-  p.rows = (I)rows;
-  p.C = (int)C, p.H = (int)H, p.W = (int)W, p.KH = (int)KH, p.KW = (int)KW;
-  p.sh = (int)sh, p.sw = (int)sw, p.pt = (int)pt, p.pl = (int)pl, p.dh = (int)dh;
-  p.dw = (int)dw, p.OH = (int)OH, p.OW = (int)OW, p.nhwc = nhwc;
-  hipLaunchKernelGGL((k_col2im<T, I, V>), dim3((unsigned)gx, (unsigned)gy, (unsigned)slots),
-                     dim3(bx, by), 0, S(stream), (const T*)in, (T*)out, p);
+  p.in_slot = (I)in_slot_stride, p.o_slot = (I)g.n_out;
+  set_window(p, g);
+  p.K = (I)g.K, p.rows = (I)g.rows, p.C = (int)g.C;
+  hipLaunchKernelGGL((k_col2im<T, I, V>),
+                     dim3((unsigned)b.tiles, (unsigned)row_grid(g.rows, b.by), (unsigned)slots),
+                     dim3(b.bx, b.by), 0, S(stream), (const T*)in, (T*)out, p);
   MX_LAUNCH_CHECK();
   return 0;
 }
@@ -2185,7 +2230,7 @@ __global__ void __launch_bounds__(256) k_resize2d(const T* __restrict__ in, T* _
                                                   const int32_t* __restrict__ tw,
                                                   Resize2dP<I> p) {
   using U = typename std::make_unsigned<I>::type;
-  using Vec = Im2colVec<T, V>;
+  using Vec = LaneVec<T, V>;
   const unsigned bx = blockDim.x, by = blockDim.y;
   const unsigned inner = (unsigned)(p.nhwc ? p.C : p.OW);
   // V == 2 only with an even inner extent: both outputs are inside, or neither
@@ -2242,29 +2287,18 @@ __global__ void __launch_bounds__(256) k_resize2d(const T* __restrict__ in, T* _
 
 template <class T, class I, int V>
 static int resize2d_launch(const void* in, void* out, int64_t slots, int64_t in_slot_stride,
-                           int64_t N, int64_t C, int64_t H, int64_t W, int64_t OH, int64_t OW,
-                           const int32_t* th, const int32_t* tw, int wbh, int wbw, int nhwc,
+                           const ImgGeom& g, const int32_t* th, const int32_t* tw,
                            void* stream) {
-  const int64_t inner = nhwc ? C : OW, rows = nhwc ? N * OH * OW : N * C * OH;
-  // inner lanes of a block: no more than the inner extent needs
-  int bx = 64;
-  while (bx > 1 && (bx / 2) * V >= inner) bx /= 2;
-  const int by = 256 / bx;
-  const int64_t gx = (inner + (int64_t)bx * V - 1) / ((int64_t)bx * V);
-  // the row grid is capped at 65,536 rows, as k_im2col's; a lane strides over the rest
-  const int64_t gy = std::min<int64_t>((rows + by - 1) / by, 65536 / by);
+  const LanePlan b = lane_plan(g.inner, V);
   Resize2dP<I> p;
-  p.in_slot = (I)in_slot_stride;
-  p.o_slot = (I)(N * C * OH * OW);
-  p.sN = (I)(C * H * W);
-  p.sH = (I)(nhwc ? W * C : W);
-  p.sW = (I)(nhwc ? C : 1);
-  p.sC = (I)(nhwc ? 1 : H * W);
-  p.rows = (I)rows;
-  p.C = (int)C, p.H = (int)H, p.W = (int)W, p.OH = (int)OH, p.OW = (int)OW;
-  p.wbh = wbh, p.wbw = wbw, p.nhwc = nhwc;
-  hipLaunchKernelGGL((k_resize2d<T, I, V>), dim3((unsigned)gx, (unsigned)gy, (unsigned)slots),
-                     dim3(bx, by), 0, S(stream), (const T*)in, (T*)out, th, tw, p);
+  p.in_slot = (I)in_slot_stride, p.o_slot = (I)g.n_out;
+  set_strides(p, g);
+  p.rows = (I)g.rows;
+  p.C = (int)g.C, p.H = (int)g.H, p.W = (int)g.W, p.OH = (int)g.OH, p.OW = (int)g.OW;
+  p.wbh = g.wbh, p.wbw = g.wbw, p.nhwc = g.nhwc;
+  hipLaunchKernelGGL((k_resize2d<T, I, V>),
+                     dim3((unsigned)b.tiles, (unsigned)row_grid(g.rows, b.by), (unsigned)slots),
+                     dim3(b.bx, b.by), 0, S(stream), (const T*)in, (T*)out, th, tw, p);
   MX_LAUNCH_CHECK();
   return 0;
 }
@@ -2291,7 +2325,7 @@ __global__ void __launch_bounds__(256) k_pwl_cross(const T* __restrict__ s0,
                                                    const T* __restrict__ x0,
                                                    const T* __restrict__ x1, T* __restrict__ out,
                                                    PwlP<T, I> p) {
-  using Vec = Im2colVec<T, V>;
+  using Vec = LaneVec<T, V>;
   const I sb = (I)blockIdx.z * p.s_slot, xb = (I)blockIdx.z * p.x_slot;
   T* __restrict__ dst = out + (I)blockIdx.z * p.n;
   const I step = (I)(gridDim.x * 256u) * V;
@@ -2624,106 +2658,51 @@ int mxh_transpose2(int words, const void* a0, void* out0, const void* a1, void* 
   });
 }
 
+// The image leaves: g comes validated from mx_* (img_geom_check); what is left here is what
+// only a launch is bound by -- slots are blockIdx.z -- and each leaf's choice of form.
 int mxh_im2col(int elem_bytes, const void* in, void* out, int64_t slots, int64_t in_slot_stride,
-               int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH, int64_t KW, int64_t sh,
-               int64_t sw, int64_t pt, int64_t pl, int64_t dh, int64_t dw, int64_t OH,
-               int64_t OW, int nhwc, void* stream) {
-  const int64_t K = C * KH * KW, rows = N * OH * OW;
-  if (slots <= 0 || rows <= 0 || K <= 0) return 0;
-  const int64_t dims[] = {N, C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW};
-  for (int64_t d : dims)
-    if (d < 0 || d > 0x7fffffff) return -3;
-  if (slots > 65535 || (K + 63) / 64 > 0x7fffffff || in_slot_stride < 0) return -3;
-  const int64_t in_extent = (slots - 1) * in_slot_stride + N * C * H * W;
-  // 32-bit indices below 2^31 elements, less the overshoot of a lane's last loop step
-  const int64_t lim = (1ll << 31) - (1ll << 17);
-  const bool small = in_extent < lim && slots * rows * K < lim;
-#define MX_IM2COL(T, V)                                                                       \
-  return small ? im2col_launch<T, int32_t, V>(in, out, slots, in_slot_stride, N, C, H, W, KH, \
-                                              KW, sh, sw, pt, pl, dh, dw, OH, OW, nhwc,       \
-                                              stream)                                         \
-               : im2col_launch<T, int64_t, V>(in, out, slots, in_slot_stride, N, C, H, W, KH, \
-                                              KW, sh, sw, pt, pl, dh, dw, OH, OW, nhwc, stream)
-  switch (elem_bytes) {
-    case 1: MX_IM2COL(uint8_t, 1);
-    case 8:
-      if (K % 2 == 0 && ((uintptr_t)out & 15) == 0) { MX_IM2COL(u64, 2); }
-      MX_IM2COL(u64, 1);
-    case 16: MX_IM2COL(u128, 1);
-    default: return -2;
-  }
-#undef MX_IM2COL
+               const ImgGeom& g, void* stream) {
+  if (slots > 65535 || (g.K + 63) / 64 > 0x7fffffff) return -3;
+  const int64_t in_extent = (slots - 1) * in_slot_stride + g.n_in;
+  const bool small = fits32(1 << 17, {in_extent, slots * g.n_out});
+  const bool two = g.K % 2 == 0 && aligned16(out);
+  return leaf_dispatch<true>(elem_bytes, small, two, [&](auto f) {
+    using F = decltype(f);
+    return im2col_launch<typename F::T, typename F::I, F::V>(in, out, slots, in_slot_stride, g,
+                                                             stream);
+  });
 }
 
 int mxh_col2im(int elem_bytes, const void* in, void* out, int64_t slots, int64_t in_slot_stride,
-               int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH, int64_t KW, int64_t sh,
-               int64_t sw, int64_t pt, int64_t pl, int64_t dh, int64_t dw, int64_t OH,
-               int64_t OW, int nhwc, void* stream) {
-  const int64_t K = C * KH * KW, n_out = N * C * H * W;
-  if (slots <= 0 || n_out <= 0) return 0;
-  const int64_t dims[] = {N, C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW};
-  for (int64_t d : dims)
-    if (d < 0 || d > 0x7fffffff) return -3;
-  if (OH <= 0 || OW <= 0 || sh <= 0 || sw <= 0 || slots > 65535 || in_slot_stride < 0)
-    return -3;
-  const int64_t in_extent = (slots - 1) * in_slot_stride + N * OH * OW * K;
-  // 32-bit indices below 2^31 elements, less the overshoot of a lane's last loop step
-  const int64_t lim = (1ll << 31) - (1ll << 23);
-  const bool small = in_extent < lim && slots * n_out < lim;
-#define MX_COL2IM(T, V)                                                                       \
-  return small ? col2im_launch<T, int32_t, V>(in, out, slots, in_slot_stride, N, C, H, W, KH, \
-                                              KW, sh, sw, pt, pl, dh, dw, OH, OW, nhwc,       \
-                                              stream)                                         \
-               : col2im_launch<T, int64_t, V>(in, out, slots, in_slot_stride, N, C, H, W, KH, \
-                                              KW, sh, sw, pt, pl, dh, dw, OH, OW, nhwc, stream)
-  switch (elem_bytes) {
-    case 8:
-      // 16-byte stores need an even inner extent; NHWC's 16-byte loads an aligned input too
-      if ((nhwc ? C : W) % 2 == 0 && ((uintptr_t)out & 15) == 0 &&
-          (!nhwc || (((uintptr_t)in & 15) == 0 && in_slot_stride % 2 == 0))) {
-        MX_COL2IM(u64, 2);
-      }
-      MX_COL2IM(u64, 1);
-    case 16: MX_COL2IM(u128, 1);
-    default: return -2;
-  }
-#undef MX_COL2IM
+               const ImgGeom& g, void* stream) {
+  if (slots > 65535) return -3;
+  const int64_t in_extent = (slots - 1) * in_slot_stride + g.N * g.OH * g.OW * g.K;
+  const bool small = fits32(1 << 23, {in_extent, slots * g.n_out});
+  // 16-byte stores need an even inner extent; NHWC's 16-byte loads an aligned input too
+  const bool two = g.inner % 2 == 0 && aligned16(out) &&
+                   (!g.nhwc || (aligned16(in) && in_slot_stride % 2 == 0));
+  return leaf_dispatch(elem_bytes, small, two, [&](auto f) {
+    using F = decltype(f);
+    return col2im_launch<typename F::T, typename F::I, F::V>(in, out, slots, in_slot_stride, g,
+                                                             stream);
+  });
 }
 
 int mxh_resize2d(int elem_bytes, const void* in, void* out, int64_t slots,
-                 int64_t in_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t OH,
-                 int64_t OW, const int32_t* th, const int32_t* tw, int wbh, int wbw, int nhwc,
-                 void* stream) {
-  const int64_t n_in = N * C * H * W, n_out = N * C * OH * OW;
-  if (slots <= 0 || n_out <= 0) return 0;
-  const int64_t dims[] = {N, C, H, W, OH, OW};
-  for (int64_t d : dims)
-    if (d <= 0 || d > 0x7fffffff) return -3;
-  if (slots > 65535 || in_slot_stride < 0 || !th || !tw || wbh < 0 || wbh > 12 || wbw < 0 ||
-      wbw > 12)
-    return -3;
-  const int64_t in_extent = (slots - 1) * in_slot_stride + n_in;
-  // 32-bit indices below 2^31 elements, less the overshoot of a lane's last loop step
-  const int64_t lim = (1ll << 31) - (1ll << 23);
-  const bool small = in_extent < lim && slots * n_out < lim;
-#define MX_RESIZE2D(T, V)                                                                      \
-  return small ? resize2d_launch<T, int32_t, V>(in, out, slots, in_slot_stride, N, C, H, W, OH, \
-                                                OW, th, tw, wbh, wbw, nhwc, stream)             \
-               : resize2d_launch<T, int64_t, V>(in, out, slots, in_slot_stride, N, C, H, W, OH, \
-                                                OW, th, tw, wbh, wbw, nhwc, stream)
-  switch (elem_bytes) {
-    case 8:
-      // two outputs per lane share their taps only in NHWC; 16-byte accesses need an even C
-      // and aligned buffers
-      if (nhwc && C % 2 == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)in & 15) == 0 &&
-          in_slot_stride % 2 == 0) {
-        MX_RESIZE2D(u64, 2);
-      }
-      MX_RESIZE2D(u64, 1);
-    case 16: MX_RESIZE2D(u128, 1);
-    default: return -2;
-  }
-#undef MX_RESIZE2D
+                 int64_t in_slot_stride, const ImgGeom& g, const int32_t* th,
+                 const int32_t* tw, void* stream) {
+  if (slots > 65535) return -3;
+  const int64_t in_extent = (slots - 1) * in_slot_stride + g.n_in;
+  const bool small = fits32(1 << 23, {in_extent, slots * g.n_out});
+  // two outputs per lane share their taps only in NHWC; 16-byte accesses need an even C and
+  // aligned buffers
+  const bool two = g.nhwc && g.C % 2 == 0 && aligned16(out) && aligned16(in) &&
+                   in_slot_stride % 2 == 0;
+  return leaf_dispatch(elem_bytes, small, two, [&](auto f) {
+    using F = decltype(f);
+    return resize2d_launch<typename F::T, typename F::I, F::V>(in, out, slots, in_slot_stride,
+                                                               g, th, tw, stream);
+  });
 }
 
 int mxh_pwl_cross(int elem_bytes, const void* s0, const void* s1, const void* x0, const void* x1,
@@ -2736,65 +2715,36 @@ int mxh_pwl_cross(int elem_bytes, const void* s0, const void* s1, const void* x0
     return -3;
   const int64_t s_extent = (slots - 1) * s_slot_stride + (int64_t)k * n;
   const int64_t x_extent = (slots - 1) * x_slot_stride + n;
-  // 32-bit indices below 2^31 elements, less the overshoot of a lane's last loop step
-  const int64_t lim = (1ll << 31) - (1ll << 23);
-  const bool small = s_extent < lim && x_extent < lim && slots * n < lim;
-#define MX_PWL(T, V)                                                                           \
-  return small ? pwl_cross_launch<T, int32_t, V>(s0, s1, x0, x1, out, slots, s_slot_stride,    \
-                                                 x_slot_stride, n, k, da, db, ak, stream)      \
-               : pwl_cross_launch<T, int64_t, V>(s0, s1, x0, x1, out, slots, s_slot_stride,    \
-                                                 x_slot_stride, n, k, da, db, ak, stream)
-  switch (elem_bytes) {
-    case 8: {
-      // two outputs per lane: every plane, slot and buffer has to start on 16 bytes
-      const uintptr_t al = (uintptr_t)s0 | (uintptr_t)s1 | (uintptr_t)x0 | (uintptr_t)x1 |
-                           (uintptr_t)out;
-      if (n % 2 == 0 && (al & 15) == 0 && s_slot_stride % 2 == 0 && x_slot_stride % 2 == 0) {
-        MX_PWL(u64, 2);
-      }
-      MX_PWL(u64, 1);
-    }
-    case 16: MX_PWL(u128, 1);
-    default: return -2;
-  }
-#undef MX_PWL
+  const bool small = fits32(1 << 23, {s_extent, x_extent, slots * n});
+  // two outputs per lane: every plane, slot and buffer has to start on 16 bytes
+  const bool two = n % 2 == 0 && aligned16(s0) && aligned16(s1) && aligned16(x0) &&
+                   aligned16(x1) && aligned16(out) && s_slot_stride % 2 == 0 &&
+                   x_slot_stride % 2 == 0;
+  return leaf_dispatch(elem_bytes, small, two, [&](auto f) {
+    using F = decltype(f);
+    return pwl_cross_launch<typename F::T, typename F::I, F::V>(
+        s0, s1, x0, x1, out, slots, s_slot_stride, x_slot_stride, n, k, da, db, ak, stream);
+  });
 }
 
 int mxh_dwconv(int elem_bytes, const void* x0, const void* x1, const void* w0, const void* w1,
-               void* out, int64_t slots, int64_t x_slot_stride, int64_t w_slot_stride, int64_t N,
-               int64_t C, int64_t H, int64_t W, int64_t mult, int64_t KH, int64_t KW, int64_t sh,
-               int64_t sw, int64_t pt, int64_t pl, int64_t dh, int64_t dw, int64_t OH,
-               int64_t OW, int nhwc, void* stream) {
-  const int64_t OC = C * mult, taps = KH * KW, n_out = N * OH * OW * OC;
-  if (slots <= 0 || n_out <= 0) return 0;
-  const int64_t dims[] = {N, C, H, W, mult, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW, OC, taps};
-  for (int64_t d : dims)
-    if (d < 0 || d > 0x7fffffff) return -3;
-  if (mult <= 0 || taps <= 0 || slots > 65535 || x_slot_stride < 0 || w_slot_stride < 0)
-    return -3;
-  if ((x1 == nullptr) != (w1 == nullptr)) return -3;
-  const int64_t x_extent = (slots - 1) * x_slot_stride + N * C * H * W;
-  const int64_t w_extent = (slots - 1) * w_slot_stride + OC * taps;
-  // 32-bit indices below 2^31 elements, less the overshoot of a lane's last loop step
-  const int64_t lim = (1ll << 31) - (1ll << 23);
-  const bool small = x_extent < lim && w_extent < lim && slots * n_out < lim &&
-                     (nhwc ? N * OH * OW : N * OH) < lim;
+               void* out, int64_t slots, int64_t x_slot_stride, int64_t w_slot_stride,
+               const ImgGeom& g, void* stream) {
+  if (slots > 65535) return -3;
+  const int64_t x_extent = (slots - 1) * x_slot_stride + g.n_in;
+  const int64_t w_extent = (slots - 1) * w_slot_stride + g.OC * g.KH * g.KW;
+  const bool small = fits32(1 << 23, {x_extent, w_extent, slots * g.n_out});
+  const bool two = g.inner % 2 == 0 && aligned16(out);
   const bool cross = x1 != nullptr;
-#define MX_DWCONV_I(T, I, V, X)                                                                \
-  dwconv_launch<T, I, V, X>(x0, x1, w0, w1, out, slots, x_slot_stride, w_slot_stride, N, C, H, \
-                            W, mult, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW, nhwc, stream)
-#define MX_DWCONV(T, V)                                                              \
-  return small ? (cross ? MX_DWCONV_I(T, int32_t, V, true) : MX_DWCONV_I(T, int32_t, V, false)) \
-               : (cross ? MX_DWCONV_I(T, int64_t, V, true) : MX_DWCONV_I(T, int64_t, V, false))
-  switch (elem_bytes) {
-    case 8:
-      if ((nhwc ? OC : OW) % 2 == 0 && ((uintptr_t)out & 15) == 0) { MX_DWCONV(u64, 2); }
-      MX_DWCONV(u64, 1);
-    case 16: MX_DWCONV(u128, 1);
-    default: return -2;
-  }
-#undef MX_DWCONV
-#undef MX_DWCONV_I
+  return leaf_dispatch(elem_bytes, small, two, [&](auto f) {
+    using F = decltype(f);
+    using T = typename F::T;
+    using I = typename F::I;
+    return cross ? dwconv_launch<T, I, F::V, true>(x0, x1, w0, w1, out, slots, x_slot_stride,
+                                                   w_slot_stride, g, stream)
+                 : dwconv_launch<T, I, F::V, false>(x0, x1, w0, w1, out, slots, x_slot_stride,
+                                                    w_slot_stride, g, stream);
+  });
 }
 
 int mxh_ew_binary_slot2(int op, int words, const void* a0, const void* a1, const void* b,

@@ -726,6 +726,42 @@ def strided_slice(a: RT, slices, nb=0) -> RT:
     return RT(d[tuple(idx)].contiguous(), a.bits)
 
 
+_ELEM_BYTES = {1: 1, 64: 8, 128: 16}
+
+
+def _elem_bytes(bits):
+    """Bytes of one element as the native image leaves count them (a bit is a uint8)."""
+    return _ELEM_BYTES[bits]
+
+
+def _leaf_operand(t: RT, nb, dense, rank4=None, lead=()):
+    """(data, slot stride in elements) of an image leaf's operand after ``nb`` batch dims: a
+    [slots, ...] view with dense slots is read in place (its slot stride non-negative and a
+    multiple of the words per element), anything else as a contiguous copy at the ``dense``
+    stride.  With ``rank4`` (dwconv) a rank-4 operand beside batch dims is public -- one copy
+    for every slot, stride 0 -- and any other operand has to be ``lead + rank4``."""
+    d = t.data
+    if rank4 is not None:
+        if len(t.shape) == 4 and nb:
+            return d.contiguous(), 0
+        if tuple(t.shape[:nb]) != tuple(lead) or tuple(t.shape[nb:]) != tuple(rank4):
+            raise ValueError(f"dwconv: operand of shape {tuple(t.shape)} does not match the batch "
+                             f"dims {lead} and the shape {tuple(rank4)}")
+    if nb == 1 and d.shape[0] and d[0].is_contiguous():
+        st, w = d.stride(0), 2 if t.bits == 128 else 1  # int64 words per element (uint8: bits)
+        if st >= 0 and st % w == 0:
+            return d, st // w
+    return d.contiguous(), dense
+
+
+def _leaf_pair(d0, st0, d1, st1, dense):
+    """Both components of a pair go to the leaf at one slot stride: ``(d0, d1, stride)`` as
+    they are when their strides agree, else both dense."""
+    if st0 == st1:
+        return d0, d1, st0
+    return d0.contiguous(), d1.contiguous(), dense
+
+
 def im2col_geometry(shape, kernel_shape, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1),
                     data_format="NCHW"):
     """Validate the attributes of an im2col over a rank-4 ``shape`` and return
@@ -818,19 +854,12 @@ def im2col(a: RT, kernel_shape, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1,
         tail = 1 if a.bits == 128 else 0
         assert a.data.dim() == nb + 4 + tail
         return RT(im2col_torch(a.data, geom, data_format, nb), a.bits)
-    d = a.data
-    w = 2 if a.bits == 128 else 1  # int64 words per element (uint8 for bits)
+    d, slot_stride = _leaf_operand(a, nb, N * C * H * W)
     slots = math.prod(lead)
-    slot = d[(0,) * nb] if nb and slots else d
-    if nb == 1 and slots and slot.is_contiguous() and d.stride(0) >= 0 and d.stride(0) % w == 0:
-        slot_stride = d.stride(0) // w
-    else:
-        d = d.contiguous()
-        slot_stride = N * C * H * W
     out = empty(out_shape, a.bits, a.device)
     nat.check(
         nat.lib().mx_im2col(
-            nat.dev_of(d), {1: 1, 64: 8, 128: 16}[a.bits], nat.ptr(d), nat.ptr(out.data),
+            nat.dev_of(d), _elem_bytes(a.bits), nat.ptr(d), nat.ptr(out.data),
             slots, slot_stride, N, C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW,
             1 if data_format == "NHWC" else 0, nat.stream_of(d)),
         "im2col",
@@ -905,19 +934,12 @@ def col2im(a: RT, image_chw, kernel_shape, strides=(1, 1), pads=(0, 0, 0, 0), di
     out_shape = lead + ((N, H, W, C) if nhwc else (N, C, H, W))
     if a.device.type == "meta":  # shape inference of the symbolic session
         return empty(out_shape, a.bits, a.device)
-    d = a.data
-    w = 2 if a.bits == 128 else 1  # int64 words per element
+    d, slot_stride = _leaf_operand(a, nb, N * OH * OW * C * KH * KW)
     slots = math.prod(lead)
-    slot = d[(0,) * nb] if nb and slots else d
-    if nb == 1 and slots and slot.is_contiguous() and d.stride(0) >= 0 and d.stride(0) % w == 0:
-        slot_stride = d.stride(0) // w
-    else:
-        d = d.contiguous()
-        slot_stride = N * OH * OW * C * KH * KW
     out = empty(out_shape, a.bits, a.device)
     nat.check(
         nat.lib().mx_col2im(
-            nat.dev_of(d), 16 if a.bits == 128 else 8, nat.ptr(d), nat.ptr(out.data),
+            nat.dev_of(d), _elem_bytes(a.bits), nat.ptr(d), nat.ptr(out.data),
             slots, slot_stride, N, C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW,
             1 if nhwc else 0, nat.stream_of(d)),
         "col2im",
@@ -1187,15 +1209,8 @@ def resize(a: RT, sizes, mode="nearest", coordinate_transformation_mode="half_pi
     if a.bits == 1 or (a.device.type == "cuda" and not RESIZE_KERNEL):
         return RT(resize_torch(a.data, geom, mode, coordinate_transformation_mode,
                                nearest_mode, data_format, nb, a.bits), a.bits)
-    d = a.data
-    w = 2 if a.bits == 128 else 1  # int64 words per element
+    d, slot_stride = _leaf_operand(a, nb, N * C * H * W)
     slots = math.prod(lead)
-    slot = d[(0,) * nb] if nb and slots else d
-    if nb == 1 and slots and slot.is_contiguous() and d.stride(0) >= 0 and d.stride(0) % w == 0:
-        slot_stride = d.stride(0) // w
-    else:
-        d = d.contiguous()
-        slot_stride = N * C * H * W
     out = empty(out_shape, a.bits, a.device)
     if out.data.numel() == 0:
         return out
@@ -1205,7 +1220,7 @@ def resize(a: RT, sizes, mode="nearest", coordinate_transformation_mode="half_pi
         a.device)
     nat.check(
         nat.lib().mx_resize2d(
-            nat.dev_of(d), 16 if a.bits == 128 else 8, nat.ptr(d), nat.ptr(out.data), slots,
+            nat.dev_of(d), _elem_bytes(a.bits), nat.ptr(d), nat.ptr(out.data), slots,
             slot_stride, N, C, H, W, OH, OW, _table_ptr(th), _table_ptr(tw), wbh, wbw,
             1 if nhwc else 0, nat.stream_of(d)),
         "resize2d",
@@ -1236,24 +1251,6 @@ def dwconv_geometry(x_shape, w_shape, strides=(1, 1), pads=(0, 0, 0, 0), dilatio
     return N, C, H, W, w_shape[0] // C, KH, KW, sh, sw, pt, pl, pb, pr, dh, dw, OH, OW
 
 
-def _dwconv_operand(t: RT, nb, rank4, lead, dense):
-    """(data, slot stride in elements) of a dwconv operand: a rank-4 tensor shared by every
-    slot (stride 0), a [slots, ...] view with dense slots read in place, or a dense copy."""
-    w = 2 if t.bits == 128 else 1
-    d = t.data
-    if len(t.shape) == 4 and nb:  # public: one image / weight for every slot
-        return d.contiguous(), 0
-    if tuple(t.shape[:nb]) != lead or tuple(t.shape[nb:]) != tuple(rank4):
-        raise ValueError(f"dwconv: operand of shape {tuple(t.shape)} does not match the batch "
-                         f"dims {lead} and the shape {tuple(rank4)}")
-    if not nb:
-        return d.contiguous(), dense
-    slots = math.prod(lead)
-    if nb == 1 and slots and d[0].is_contiguous() and d.stride(0) >= 0 and d.stride(0) % w == 0:
-        return d, d.stride(0) // w
-    return d.contiguous(), dense
-
-
 def _dwconv(x0, x1, w0, w1, strides, pads, dilations, data_format, nb):
     bits = x0.bits
     ops = [t for t in (x0, x1, w0, w1) if t is not None]
@@ -1272,21 +1269,19 @@ def _dwconv(x0, x1, w0, w1, strides, pads, dilations, data_format, nb):
     out_shape = lead + ((N, OH, OW, C * mult) if nhwc else (N, C * mult, OH, OW))
     if x0.device.type == "meta":  # shape inference of the symbolic session
         return empty(out_shape, bits, x0.device)
-    xd0, xst = _dwconv_operand(x0, nb, xs, lead, N * C * H * W)
-    wd0, wst = _dwconv_operand(w0, nb, ws, lead, C * mult * KH * KW)
+    xn, wn = N * C * H * W, C * mult * KH * KW
+    xd0, xst = _leaf_operand(x0, nb, xn, xs, lead)
+    wd0, wst = _leaf_operand(w0, nb, wn, ws, lead)
     xd1 = wd1 = None
     if x1 is not None:
-        xd1, xst1 = _dwconv_operand(x1, nb, xs, lead, N * C * H * W)
-        wd1, wst1 = _dwconv_operand(w1, nb, ws, lead, C * mult * KH * KW)
-        if xst1 != xst:  # one stride serves both components
-            xd0, xd1, xst = xd0.contiguous(), xd1.contiguous(), (0 if xpub else N * C * H * W)
-        if wst1 != wst:
-            wd0, wd1 = wd0.contiguous(), wd1.contiguous()
-            wst = 0 if wpub else C * mult * KH * KW
+        xd1, xst1 = _leaf_operand(x1, nb, xn, xs, lead)
+        wd1, wst1 = _leaf_operand(w1, nb, wn, ws, lead)
+        xd0, xd1, xst = _leaf_pair(xd0, xst, xd1, xst1, 0 if xpub else xn)
+        wd0, wd1, wst = _leaf_pair(wd0, wst, wd1, wst1, 0 if wpub else wn)
     out = empty(out_shape, bits, x0.device)
     nat.check(
         nat.lib().mx_dwconv(
-            nat.dev_of(out.data), 16 if bits == 128 else 8, nat.ptr(xd0),
+            nat.dev_of(out.data), _elem_bytes(bits), nat.ptr(xd0),
             nat.ptr(xd1) if xd1 is not None else None, nat.ptr(wd0),
             nat.ptr(wd1) if wd1 is not None else None, nat.ptr(out.data), math.prod(lead),
             xst, wst, N, C, H, W, mult, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW,
@@ -1349,16 +1344,6 @@ def _pwl_check(s0, s1, x0, x1, da, db, nb):
     return k, bits, lead, shape
 
 
-def _pwl_operand(t: RT, nb, dense):
-    """(data, slot stride in elements): a [slots, ...] view with dense slots is read in place."""
-    d, w = t.data, 2 if t.bits == 128 else 1
-    if not nb:
-        return d.contiguous(), dense
-    if d.shape[0] and d[0].is_contiguous() and d.stride(0) >= 0 and d.stride(0) % w == 0:
-        return d, d.stride(0) // w
-    return d.contiguous(), dense
-
-
 def pwl_torch(s0: RT, s1, x0: RT, x1, da, db, ak, nb=0) -> RT:
     """:func:`pwl_cross` as a composition of the existing kernels (weighted sums of the flag
     planes, then elementwise products and sums): the fallback and the benchmark's opponent."""
@@ -1389,21 +1374,19 @@ def pwl_cross(s0: RT, s1, x0: RT, x1, da, db, ak, nb=0) -> RT:
     out = empty(lead + shape, bits, x0.device)
     if out.data.numel() == 0:
         return out
-    sd0, sst = _pwl_operand(s0, nb, k * n)
-    xd0, xst = _pwl_operand(x0, nb, n)
+    sd0, sst = _leaf_operand(s0, nb, k * n)
+    xd0, xst = _leaf_operand(x0, nb, n)
     sd1 = xd1 = None
     if s1 is not None:
-        sd1, sst1 = _pwl_operand(s1, nb, k * n)
-        xd1, xst1 = _pwl_operand(x1, nb, n)
-        if sst1 != sst:  # one stride serves both components
-            sd0, sd1, sst = sd0.contiguous(), sd1.contiguous(), k * n
-        if xst1 != xst:
-            xd0, xd1, xst = xd0.contiguous(), xd1.contiguous(), n
+        sd1, sst1 = _leaf_operand(s1, nb, k * n)
+        xd1, xst1 = _leaf_operand(x1, nb, n)
+        sd0, sd1, sst = _leaf_pair(sd0, sst, sd1, sst1, k * n)
+        xd0, xd1, xst = _leaf_pair(xd0, xst, xd1, xst1, n)
     tda, tdb, tak = _pwl_tables(tuple(int(v) for v in da), tuple(int(v) for v in db), int(ak),
                                 bits)
     nat.check(
         nat.lib().mx_pwl_cross(
-            nat.dev_of(out.data), 16 if bits == 128 else 8, nat.ptr(sd0),
+            nat.dev_of(out.data), _elem_bytes(bits), nat.ptr(sd0),
             nat.ptr(sd1) if sd1 is not None else None, nat.ptr(xd0),
             nat.ptr(xd1) if xd1 is not None else None, nat.ptr(out.data), math.prod(lead), sst,
             xst, n, k, tda, tdb, tak, nat.stream_of(out.data)),
