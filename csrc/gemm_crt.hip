@@ -1272,13 +1272,68 @@ __global__ void __launch_bounds__(256)
 // and per (element, R digit) -- 19 dot4 for 4 moduli instead of 4 x (8 multiply-adds + a
 // float convert and fma).  q = round(sum_i c_i R_i / 2^24) (error <= 36 * 128 / 2^25, far
 // inside the 0.05 rounding margin of |Z| <= 0.45 M).  Same output as k_crt_recon16.
+// One thread's share of it: the 4 elements (rows 4 * (lane >> 4) + e of a 16x16 block, one
+// column) whose residue bytes are the dword at ``src`` of every modulus plane, pstride apart.
+template <class T>
+__device__ __forceinline__ void recon16d_lane(const int8_t* __restrict__ src, int64_t pstride,
+                                              int n, const RecTab4& r4, const RecTab& rc,
+                                              T (&z)[4]) {
+  constexpr int ND = (int)sizeof(T);  // W digits
+  constexpr int NK = ND / 2;
+  int acc[4][ND], aq[4][3];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+#pragma unroll
+    for (int d = 0; d < ND; ++d) acc[e][d] = 0;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) aq[e][d] = 0;
+  }
+  for (int g = 0; g < r4.groups; ++g) {
+    uint32_t v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      v[u] = 4 * g + u < n ? *(const uint32_t*)(src + (4 * g + u) * pstride) : 0u;
+    const uint32_t a0 = __builtin_amdgcn_perm(v[1], v[0], 0x05010400u);
+    const uint32_t a1 = __builtin_amdgcn_perm(v[1], v[0], 0x07030602u);
+    const uint32_t c0 = __builtin_amdgcn_perm(v[3], v[2], 0x05010400u);
+    const uint32_t c1 = __builtin_amdgcn_perm(v[3], v[2], 0x07030602u);
+    const int t[4] = {(int)__builtin_amdgcn_perm(c0, a0, 0x05040100u),
+                      (int)__builtin_amdgcn_perm(c0, a0, 0x07060302u),
+                      (int)__builtin_amdgcn_perm(c1, a1, 0x05040100u),
+                      (int)__builtin_amdgcn_perm(c1, a1, 0x07060302u)};
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+      const int w = (int)r4.wd[g][d];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[e][d] = __builtin_amdgcn_sdot4(t[e], w, acc[e][d], false);
+    }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const int w = (int)r4.rd[g][d];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) aq[e][d] = __builtin_amdgcn_sdot4(t[e], w, aq[e][d], false);
+    }
+  }
+  T mw = 0;
+#pragma unroll
+  for (int k = 0; k < NK; ++k) mw |= (T)rc.Mw[k] << (16 * k);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    T s = 0;
+#pragma unroll
+    for (int k = 0; k < NK; ++k)
+      s += (T)(int64_t)(acc[e][2 * k] + acc[e][2 * k + 1] * 256) << (16 * k);
+    const int64_t F = (int64_t)aq[e][0] + (int64_t)aq[e][1] * 256 + (int64_t)aq[e][2] * 65536;
+    const int64_t q = (F + (1 << 23)) >> 24;
+    z[e] = s - (T)q * mw;
+  }
+}
+
 template <class T, int BN>
 __global__ void __launch_bounds__(256)
     k_crt_recon16d(const int8_t* __restrict__ CR, T* __restrict__ C, int64_t M, int64_t N,
                    int64_t tiles_m, int64_t tiles_n, int accumulate, const RecTab4 r4, int n,
                    const RecTab rc) {
-  constexpr int ND = (int)sizeof(T);  // W digits
-  constexpr int NK = ND / 2;
   constexpr int kCrTile = BM * BN, NBJ = BN / 16;
   const int64_t ntiles = tiles_m * tiles_n;
   const int64_t total = ntiles * (kCrTile / 4);
@@ -1290,63 +1345,98 @@ __global__ void __launch_bounds__(256)
     const int blk = (int)(rest % (16 * NBJ));
     const int64_t tile = rest / (16 * NBJ);
     const int64_t off = tile * kCrTile + (blk * 64 + lane) * 4;
-    int acc[4][ND], aq[4][3];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-#pragma unroll
-      for (int d = 0; d < ND; ++d) acc[e][d] = 0;
-#pragma unroll
-      for (int d = 0; d < 3; ++d) aq[e][d] = 0;
-    }
-    const int8_t* src = CR + b * n * ntiles * (int64_t)kCrTile + off;
     const int64_t pstride = ntiles * (int64_t)kCrTile;
-    for (int g = 0; g < r4.groups; ++g) {
-      uint32_t v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        v[u] = 4 * g + u < n ? *(const uint32_t*)(src + (4 * g + u) * pstride) : 0u;
-      const uint32_t a0 = __builtin_amdgcn_perm(v[1], v[0], 0x05010400u);
-      const uint32_t a1 = __builtin_amdgcn_perm(v[1], v[0], 0x07030602u);
-      const uint32_t c0 = __builtin_amdgcn_perm(v[3], v[2], 0x05010400u);
-      const uint32_t c1 = __builtin_amdgcn_perm(v[3], v[2], 0x07030602u);
-      const int t[4] = {(int)__builtin_amdgcn_perm(c0, a0, 0x05040100u),
-                        (int)__builtin_amdgcn_perm(c0, a0, 0x07060302u),
-                        (int)__builtin_amdgcn_perm(c1, a1, 0x05040100u),
-                        (int)__builtin_amdgcn_perm(c1, a1, 0x07060302u)};
-#pragma unroll
-      for (int d = 0; d < ND; ++d) {
-        const int w = (int)r4.wd[g][d];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e][d] = __builtin_amdgcn_sdot4(t[e], w, acc[e][d], false);
-      }
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        const int w = (int)r4.rd[g][d];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) aq[e][d] = __builtin_amdgcn_sdot4(t[e], w, aq[e][d], false);
-      }
-    }
+    T z[4];
+    recon16d_lane<T>(CR + b * n * pstride + off, pstride, n, r4, rc, z);
     const int64_t tm = tile / tiles_n, tn = tile % tiles_n;
     const int bi = blk / NBJ, bj = blk % NBJ;
     const int64_t gcol = tn * BN + bj * 16 + (lane & 15);
-    T mw = 0;
-#pragma unroll
-    for (int k = 0; k < NK; ++k) mw |= (T)rc.Mw[k] << (16 * k);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int64_t grow = tm * BM + bi * 16 + 4 * (lane >> 4) + e;
-      T z = 0;
-#pragma unroll
-      for (int k = 0; k < NK; ++k)
-        z += (T)(int64_t)(acc[e][2 * k] + acc[e][2 * k + 1] * 256) << (16 * k);
-      const int64_t F = (int64_t)aq[e][0] + (int64_t)aq[e][1] * 256 + (int64_t)aq[e][2] * 65536;
-      const int64_t q = (F + (1 << 23)) >> 24;
-      z -= (T)q * mw;
       if (grow < M && gcol < N) {
         T* pc = C + (b * M + grow) * N + gcol;
-        *pc = accumulate ? (T)(*pc + z) : z;
+        *pc = accumulate ? (T)(*pc + z[e]) : z[e];
       }
     }
+  }
+}
+
+// k_crt_recon16d of a three-party product that is only revealed, with the opening on the way
+// (the tail of k_mul_trunc3_open: zero share + reshare + TruncPr by m + reveal + decode): the
+// opened value needs the SUM of the parties' products and r = r0 + r1 of TruncPr's draws
+// only (mxf::trunc_pr_open), so the products never go to memory and seven of the tail's nine
+// keystreams are not drawn.  A workgroup takes strips of 8 rows x one tile's 256 columns:
+//   1. wave w draws r for rows w and w + 4 -- a row's 256 elements are one or two groups of
+//      64 ChaCha blocks (walk_chunks' mapping: block B of group G holds chunks G * 256 +
+//      64 * part + lane), keys k0 / k2 and nonces nr0 / nr1 as the tail -- into LDS;
+//   2. after a barrier, thread t rebuilds 4 rows x 1 column of every party twice (columns
+//      0..127, then 128..255; a wave reads whole 128-byte lines: 32 lanes of a block), adds
+//      the three, takes its r values from LDS and stores 8 B per element.
+// Bitwise k_crt_recon16d<T, 256> followed by k_mul_trunc3_open<T>.
+template <class T>
+__global__ void __launch_bounds__(256)
+    k_crt_recon16d_open(const int8_t* __restrict__ CR, double* __restrict__ out, double scale,
+                        int64_t M, int64_t N, int64_t tiles_n, int64_t pstride,
+                        const RecTab4 r4, int n, const RecTab rc, mxd::KeySrc keys, uint64_t nr0,
+                        uint64_t nr1, int m) {
+  constexpr int BN = 256, kCrTile = BM * BN, P = mxd::Lane<T>::kPer;
+  __shared__ uint32_t rks[3][mxd::kKeyWords];
+  __shared__ T rr[8][BN];
+  mxd::stage_keys(rks, keys, 3);
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int64_t strips = ((M + 7) / 8) * tiles_n;
+  for (int64_t s = blockIdx.x; s < strips; s += gridDim.x) {
+    const int64_t row0 = (s / tiles_n) * 8, tn = s % tiles_n, col0 = tn * BN;
+    const int64_t ncol = N - col0 < BN ? N - col0 : BN;
+    for (int i = wave; i < 8; i += 4) {
+      if (row0 + i >= M) break;
+      const int64_t f0 = (row0 + i) * N + col0, f1 = f0 + ncol;  // the row's flat elements
+      for (int64_t G = (f0 / P) >> 8; G <= ((f1 - 1) / P) >> 8; ++G) {
+        const uint64_t B = ((uint64_t)G << 6) | (uint64_t)lane;
+        uint32_t w0[16], w1[16];
+        mx::chacha_block(rks[0], nr0, B, w0);
+        mx::chacha_block(rks[2], nr1, B, w1);
+#pragma unroll
+        for (int part = 0; part < 4; ++part) {
+          const int64_t c = (int64_t)mx::ks_chunk(B, part);
+          uint64_t lo0, hi0, lo1, hi1;
+          mx::part_u64(w0, part, &lo0, &hi0);
+          mx::part_u64(w1, part, &lo1, &hi1);
+#pragma unroll
+          for (int j = 0; j < P; ++j) {
+            const int64_t e = c * P + j;
+            if (e >= f0 && e < f1)
+              rr[i][e - f0] = mxd::pick<T>(lo0, hi0, j) + mxd::pick<T>(lo1, hi1, j);
+          }
+        }
+      }
+    }
+    __syncthreads();
+    const int q = (tid >> 4) & 1;
+    const int64_t grow0 = row0 + 4 * q;
+    const int64_t tile = (grow0 / BM) * tiles_n + tn;
+    const int bi = (int)(grow0 % BM) / 16, l16 = ((int)(grow0 % 16) / 4) * 16 + (tid & 15);
+#pragma unroll 1
+    for (int h = 0; h < 2; ++h) {
+      const int ct = h * 128 + (tid >> 5) * 16 + (tid & 15);  // column within the tile
+      if (grow0 >= M || ct >= ncol) continue;
+      const int64_t off = tile * kCrTile + ((bi * (BN / 16) + ct / 16) * 64 + l16) * 4;
+      T x[4] = {0, 0, 0, 0};
+#pragma unroll 1
+      for (int b = 0; b < 3; ++b) {
+        T z[4];
+        recon16d_lane<T>(CR + b * n * pstride + off, pstride, n, r4, rc, z);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[e] += z[e];
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (grow0 + e < M)
+          out[(grow0 + e) * N + col0 + ct] =
+              mxr::signed_to_f64<T>(mxf::trunc_pr_open<T>(x[e], rr[4 * q + e][ct], m)) * scale;
+    }
+    __syncthreads();
   }
 }
 
@@ -1591,6 +1681,29 @@ void launch_recon(const CPlan& p, const Tables& tb, int64_t batch, int64_t M, in
                        M, N, p.tiles_m, p.tiles_n, accumulate, tb.rc);
 }
 
+// A product may stop at its residues (run_crt_asym's cr_ext) when they have the layout the
+// opening kernel reads: 16x16 blocks in 256-column tiles, the dot4 reconstruction's tables.
+bool defer_ok(const CPlan& p) { return p.bn == 256 && crt_mfma16() && recon_dot4() && p.n > 0; }
+
+// The plan of run_crt_asym's product, or n < 0 where it declines.
+CPlan asym_plan(int words, int64_t M, int64_t N, int64_t K) {
+  CPlan p;
+  p.n = -1;
+  if ((words != 1 && words != 2) || K % BK || !crt_mfma16() || 2 * K > (1 << 15)) return p;
+  return make_cplan(words, 3, M, N, K, 1, true);
+}
+
+template <class T>
+void launch_recon_open(const CPlan& p, const Tables& tb, int64_t M, int64_t N, const int8_t* cr,
+                       double* out, double scale, const mxd::KeySrc& keys, uint64_t nr0,
+                       uint64_t nr1, int m, hipStream_t st) {
+  const int64_t strips = ((M + 7) / 8) * p.tiles_n;
+  const int64_t pstride = p.tiles_m * p.tiles_n * (int64_t)(BM * 256);
+  hipLaunchKernelGGL((k_crt_recon16d_open<T>), dim3((unsigned)std::min<int64_t>(strips, 1 << 20)),
+                     dim3(256), 0, st, cr, out, scale, M, N, p.tiles_n, pstride, tb.r4, p.n,
+                     tb.rc, keys, nr0, nr1, m);
+}
+
 struct Ws {
   void* ptr = nullptr;
   int64_t bytes = 0;
@@ -1693,10 +1806,13 @@ int run_crt(int64_t batch, int64_t M, int64_t N, int64_t K, const T* A0, const T
 // otherwise, nothing launched.  The residue images are byte for byte those of k_share3
 // followed by k_crt_prep, except that the zero slot's image is held as one zero strip (below);
 // the GEMM reads the same bytes and the reconstruction does not know the difference.
+//
+// cr_ext: the caller's buffer for the GEMM's output residues (defer_bytes) -- the product
+// stops there, C unused: mx_crt_recon or the opening kernel reconstructs it later.
 template <class T>
 int run_crt_asym(int64_t M, int64_t N, int64_t K, const T* S0, const T* S1, const T* T0,
                  const T* T1, int rolled, T* C, hipStream_t st, const ShareSrc* xs = nullptr,
-                 const ShareSrc* ys = nullptr) {
+                 const ShareSrc* ys = nullptr, int8_t* cr_ext = nullptr) {
   constexpr int words = sizeof(T) / 8;
   if (K % BK || !crt_mfma16()) return -7;
   if (2 * K > (1 << 15)) return -6;  // exact epilogue rounding bound
@@ -1776,12 +1892,13 @@ int run_crt_asym(int64_t M, int64_t N, int64_t K, const T* S0, const T* S1, cons
   if (ys) plan_src(true, *ys, bph, bat, nb, bmap, b_strip);
   const int64_t ra_bytes = na * a_entry, rb_bytes = nb * b_entry;
   const int64_t sum_bytes = asum && !duals ? round_up(sa * (int64_t)sizeof(T), 256) : 0;
-  int8_t* ws = (int8_t*)workspace(
-      a_strip + ra_bytes + p.cr_bytes + b_strip + rb_bytes + sum_bytes, st);
+  if (cr_ext && !defer_ok(p)) return -7;
+  const int64_t cr_ws = cr_ext ? 0 : p.cr_bytes;
+  int8_t* ws = (int8_t*)workspace(a_strip + ra_bytes + cr_ws + b_strip + rb_bytes + sum_bytes, st);
   if (!ws) return -4;
   int8_t* ra = ws + a_strip;
-  int8_t* cr = ra + ra_bytes;
-  int8_t* rb = cr + p.cr_bytes + b_strip;
+  int8_t* cr = cr_ext ? cr_ext : ra + ra_bytes;
+  int8_t* rb = ra + ra_bytes + cr_ws + b_strip;
   T* a01 = sum_bytes ? (T*)(rb + rb_bytes) : nullptr;
   if (a01)
     hipLaunchKernelGGL((k_add_pair<T>), dim3((unsigned)std::min<int64_t>((sa + 255) / 256, 65536)),
@@ -1834,7 +1951,7 @@ int run_crt_asym(int64_t M, int64_t N, int64_t K, const T* S0, const T* S1, cons
     launch_prep<T>(p, tb, false, sa_.n, M, K, 0, nullptr, nullptr, 0, ra, st, kn, kn, sa_);
   }
   launch_crt_gemm(p, tb, 3, ra, rb, cr, 0, 0, st, amap, bmap);
-  launch_recon<T>(p, tb, 3, M, N, cr, C, 0, st);
+  if (!cr_ext) launch_recon<T>(p, tb, 3, M, N, cr, C, 0, st);
   const hipError_t e = hipGetLastError();
   return e != hipSuccess ? -100 - (int)e : 0;
 }
@@ -1845,18 +1962,72 @@ extern "C" {
 
 // Asymmetric three-party RSS product (run_crt_asym): C[p] = z_p for p = 0, 1, 2.  -7: not
 // applicable (the caller runs the generic form of the same z_p).
+// residues (or null): a buffer of mx_crt_defer_bytes bytes -- the product stops at the GEMM's
+// output residues there and C is not written (mx_crt_recon, or mx_mul_trunc3_open's crt form,
+// reconstructs it); -7 where that form does not apply.
 int mx_gemm_asym(int words, int64_t M, int64_t N, int64_t K, const void* S0, const void* S1,
-                 const void* T0, const void* T1, int rolled, void* C, void* stream) {
-  if (M == 0 || N == 0) return 0;
+                 const void* T0, const void* T1, int rolled, void* C, void* stream,
+                 void* residues) {
+  if (M == 0 || N == 0) return residues ? -7 : 0;
   if (!rolled && (!S1 || !T1)) return -2;
   hipStream_t st = (hipStream_t)stream;
   if (words == 1)
     return run_crt_asym<u64>(M, N, K, (const u64*)S0, (const u64*)S1, (const u64*)T0,
-                             (const u64*)T1, rolled, (u64*)C, st);
+                             (const u64*)T1, rolled, (u64*)C, st, nullptr, nullptr,
+                             (int8_t*)residues);
   if (words == 2)
     return run_crt_asym<u128>(M, N, K, (const u128*)S0, (const u128*)S1, (const u128*)T0,
-                              (const u128*)T1, rolled, (u128*)C, st);
+                              (const u128*)T1, rolled, (u128*)C, st, nullptr, nullptr,
+                              (int8_t*)residues);
   return -2;
+}
+
+// Bytes of the residue buffer of a deferred M x N x K product (mx_gemm_asym's ``residues``);
+// -7 where the product cannot be deferred (layout or reconstruction switched by environment,
+// sizes run_crt_asym declines).
+int64_t mx_crt_defer_bytes(int words, int64_t M, int64_t N, int64_t K) {
+  if (M <= 0 || N <= 0) return -7;
+  const CPlan p = asym_plan(words, M, N, K);
+  return p.n > 0 && defer_ok(p) ? p.cr_bytes : -7;
+}
+
+// The reconstruction a deferred product skipped: C[p] = z_p from its residues, bitwise the C
+// of the same call without ``residues``.
+int mx_crt_recon(int words, int64_t M, int64_t N, int64_t K, const void* residues, void* C,
+                 void* stream) {
+  const CPlan p = asym_plan(words, M, N, K);
+  if (p.n <= 0 || !defer_ok(p)) return -7;
+  const Tables& tb = tables_for(words, p.n);
+  hipStream_t st = (hipStream_t)stream;
+  if (words == 1)
+    launch_recon<u64>(p, tb, 3, M, N, (const int8_t*)residues, (u64*)C, 0, st);
+  else
+    launch_recon<u128>(p, tb, 3, M, N, (const int8_t*)residues, (u128*)C, 0, st);
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? -100 - (int)e : 0;
+}
+
+// mx_mul_trunc3_open's crt form (moosex.h): crt = {residues, M, N, K} of a deferred product,
+// slots and the six nonces as the tail's (only r0's and r1's are drawn: trunc_pr_open).
+int mxh_crt_recon_open(int words, const int64_t* crt, double* out, int64_t n,
+                       const uint32_t* slots, int m, const uint64_t* nn, int frac, void* stream) {
+  const int64_t M = crt[1], N = crt[2], K = crt[3];
+  if (M <= 0 || N <= 0 || n != M * N || !crt[0]) return -3;
+  const CPlan p = asym_plan(words, M, N, K);
+  if (p.n <= 0 || !defer_ok(p)) return -7;
+  const Tables& tb = tables_for(words, p.n);
+  const uint32_t* ptrs[3];
+  for (int i = 0; i < 3; ++i) ptrs[i] = slots + MX_KEY_SLOT_WORDS * i;
+  const mxd::KeySrc keys = mxd::keysrc_slots(ptrs, 3);
+  const int8_t* cr = (const int8_t*)(intptr_t)crt[0];
+  const double scale = std::ldexp(1.0, -frac);
+  hipStream_t st = (hipStream_t)stream;
+  if (words == 1)
+    launch_recon_open<u64>(p, tb, M, N, cr, out, scale, keys, nn[0], nn[1], m, st);
+  else
+    launch_recon_open<u128>(p, tb, M, N, cr, out, scale, keys, nn[0], nn[1], m, st);
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? -100 - (int)e : 0;
 }
 
 // mx_gemm_asym, rolled, over Z_2^128 with one or both operands given as a share source
@@ -1865,9 +2036,11 @@ int mx_gemm_asym(int words, int64_t M, int64_t N, int64_t K, const void* S0, con
 // owner slot j0, key slot (device memory, as mx_share3_k's slot_next), nonce} -- the
 // arguments of the mx_share3_k launch that would have written the stack.  -7: not
 // applicable, nothing launched (the caller writes the shares and runs mx_gemm_asym).
+// residues: as mx_gemm_asym's.
 int mx_gemm_asym_src(int words, int64_t M, int64_t N, int64_t K, const void* S0, const void* T0,
-                     const int64_t* xsrc, const int64_t* ysrc, void* C, void* stream) {
-  if (M == 0 || N == 0) return 0;
+                     const int64_t* xsrc, const int64_t* ysrc, void* C, void* stream,
+                     void* residues) {
+  if (M == 0 || N == 0) return residues ? -7 : 0;
   if (words != 2) return -7;
   if ((!xsrc && !S0) || (!ysrc && !T0)) return -2;
   ShareSrc sx, sy;
@@ -1885,7 +2058,7 @@ int mx_gemm_asym_src(int words, int64_t M, int64_t N, int64_t K, const void* S0,
   if ((xsrc && !sx.key.slot[0]) || (ysrc && !sy.key.slot[0])) return -2;
   return run_crt_asym<u128>(M, N, K, (const u128*)S0, nullptr, (const u128*)T0, nullptr, 1,
                             (u128*)C, (hipStream_t)stream, xsrc ? &sx : nullptr,
-                            ysrc ? &sy : nullptr);
+                            ysrc ? &sy : nullptr, (int8_t*)residues);
 }
 
 // Moduli count for a K' (= K, or 2K in mode 1) inner dimension; -1 if out of range.

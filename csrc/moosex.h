@@ -148,10 +148,13 @@ int mx_mul_trunc3_kv(int dev, int words, const void* x0, const void* x1, const v
 // + reshare + TruncPr of the parties' local products x ([3] slots, xstride elements apart:
 // a stack, or rows of a larger one), same keys and nonces, and the new shares opened at
 // once -- out[i] = signed(Z0 + Z1 + Z2)[i] / 2^frac, bitwise mx_addn_decode of those shares,
-// which are not written.  Host and device, every size.
+// which are not written.  Host and device, every size.  crt (device only, else null): the
+// product is still the residues of a mx_gemm_asym / mx_gemm_asym_src given a ``residues``
+// buffer -- {residues, M, N, K}, x and xstride unused, n = M * N -- and the opening
+// reconstructs it on the way (k_crt_recon16d_open): bitwise mx_crt_recon, then this entry.
 int mx_mul_trunc3_open(int dev, int words, const void* x, int64_t xstride, double* out,
                        int64_t n, const uint32_t* slots, uint64_t nmul, int m,
-                       const uint64_t* nonces, int frac, void* stream);
+                       const uint64_t* nonces, int frac, void* stream, const int64_t* crt);
 // out = a + b + c elementwise (mod 2^w)
 int mx_ew_add3(int dev, int words, const void* a, const void* b, const void* c, void* out,
                int64_t n, void* stream);

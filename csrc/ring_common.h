@@ -188,6 +188,15 @@ MX_HD inline double i128_to_f64(u128 v) {
   return neg ? -r : r;
 }
 
+// signed value of a ring element (u64 or u128) -> nearest double: the decode of an opening
+template <class T>
+MX_HD inline double signed_to_f64(T v) {
+  if constexpr (sizeof(T) == 8)
+    return (double)(int64_t)v;
+  else
+    return i128_to_f64(v);
+}
+
 }  // namespace mxr
 
 // Device launchers (ring_hip.hip / gemm_mfma.hip)
@@ -257,6 +266,9 @@ int mxh_mul_trunc3_kv(int words, const void* x0, const void* x1, const void* y0,
 int mxh_mul_trunc3_open(int words, const void* x, int64_t xstride, double* out, int64_t n,
                         const uint32_t* slots, uint64_t nmul, int m, const uint64_t* nn, int frac,
                         void* stream);
+// gemm_crt.hip: mxh_mul_trunc3_open of a product still held as the CRT GEMM's residues
+int mxh_crt_recon_open(int words, const int64_t* crt, double* out, int64_t n,
+                       const uint32_t* slots, int m, const uint64_t* nn, int frac, void* stream);
 int mxh_ew_unary2(int op, int words, const void* a0, void* out0, const void* a1, void* out1,
                   int64_t n, int64_t param, void* stream);
 int mxh_transpose2(int words, const void* a0, void* out0, const void* a1, void* out1,

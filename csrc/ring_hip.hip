@@ -1547,11 +1547,7 @@ struct TailOpen {
   double* __restrict__ out;
   double scale;
   __device__ __forceinline__ void operator()(int64_t e, T Z0, T Z1, T Z2) const {
-    const T v = Z0 + Z1 + Z2;
-    if constexpr (sizeof(T) == 8)
-      out[e] = (double)(int64_t)v * scale;
-    else
-      out[e] = mxr::i128_to_f64(v) * scale;
+    out[e] = mxr::signed_to_f64<T>(Z0 + Z1 + Z2) * scale;
   }
 };
 

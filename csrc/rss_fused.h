@@ -47,6 +47,27 @@ MX_HD inline T trunc_pr_z1(T x0, T x1, T x2, T r0, T r1, T rt0, T rm0, T z0, T z
   return (y0 - z0) + (y1 - z2);
 }
 
+// z0 + trunc_pr_z1(x0, x1, x2, r0, r1, rt0, rm0, z0, z2, m) + z2 -- the opened value of the
+// new sharing -- from x = x0 + x1 + x2 and r = r0 + r1 alone.  The sum is y0 + y1 of
+// trunc_pr_z1, and in Z_2^w (shl and the products by c_msb are linear there)
+//   ov0 + ov1 = r_msb - 2 c_msb r_msb + c_msb,      rt0 + rt1 = r_top,
+// so the dealer's split of r_top and r_msb (rt0, rm0) and the output masks z0, z2 cancel
+// bit for bit; c itself reads the slots only through their sum, so a zero share added to
+// them (k_p - k_{p+1} on slot p) cancels as well.  An opening therefore needs two of the
+// tail's nine keystreams and one sum of the three local products.
+template <class T>
+MX_HD inline T trunc_pr_open(T x, T r, int m) {
+  constexpr int W = 8 * sizeof(T);
+  const int k = W - 1;
+  T r_msb = shr<T>(r, W - 1);
+  T r_top = shr<T>(shl<T>(r, 1), m + 1);
+  T c = x + shl<T>((T)1, k - 1) + r;
+  T c_msb = shr<T>(c, W - 1);
+  T c_top = shr<T>(shl<T>(c, 1), m + 1);
+  T ov = r_msb - shl<T>(c_msb * r_msb, 1) + c_msb;
+  return shl<T>(ov, k - m) - r_top + c_top - shl<T>((T)1, k - 1 - m);
+}
+
 // ---------------------------------------------------------------------------------------
 // Input sharing by the member P_j0 (k_share3, its host twin, and the sharing CRT operand prep
 // of gemm_crt.hip): slot j0 = r (one PRF draw), slot j0 + 1 = x - r, slot j0 + 2 = 0;

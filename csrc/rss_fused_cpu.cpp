@@ -262,9 +262,11 @@ int mx_trunc_pr3_kmo(int dev, int words, const void* s0, void* out0, void* out1,
 
 int mx_mul_trunc3_open(int dev, int words, const void* x, int64_t xstride, double* out,
                        int64_t n, const uint32_t* slots, uint64_t nmul, int m,
-                       const uint64_t* nonces, int frac, void* stream) {
+                       const uint64_t* nonces, int frac, void* stream, const int64_t* crt) {
   if (words != 1 && words != 2) return -2;
   if (m < 1 || m > 63) return -3;
+  if (crt)  // the product as the CRT GEMM's residues: device only
+    return dev ? mxh_crt_recon_open(words, crt, out, n, slots, m, nonces, frac, stream) : -2;
   if (dev) return mxh_mul_trunc3_open(words, x, xstride, out, n, slots, nmul, m, nonces, frac,
                                       stream);
   if (xstride < n) return -3;

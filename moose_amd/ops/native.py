@@ -54,9 +54,9 @@ _SIGS = {
                                    c_i64, c_int, c_int, c_int, c_vp]),
     "mx_mul_trunc3_kv": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
                                  c_vp, c_u64, c_int, c_vp, c_vp, c_vp]),
-    # (dev, words, x, xstride, out, n, slots, nmul, m, nonces[6], frac, stream)
+    # (dev, words, x, xstride, out, n, slots, nmul, m, nonces[6], frac, stream, crt[4] | null)
     "mx_mul_trunc3_open": (c_int, [c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_u64, c_int,
-                                   c_vp, c_int, c_vp]),
+                                   c_vp, c_int, c_vp, c_vp]),
     "mx_ew_add3": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "mx_lincomb2": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64,
                             c_int, c_int, c_int, c_vp]),
@@ -283,13 +283,18 @@ _SIGS = {
     "mx_key_refresh_host": (None, [c_vp, c_u64, c_int, c_vp]),
     "mx_copy_many": (c_int, [c_vp, c_int, c_i64, c_vp]),
     "mx_graph_free": (c_int, [c_vp, c_vp]),
+    # (words, M, N, K, S0, S1, T0, T1, rolled, C, stream, residues | null)
     "mx_gemm_asym": (
-        c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp],
+        c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp],
     ),
-    # (words, M, N, K, S0, T0, xsrc[6], ysrc[6], C, stream): operands as share sources
+    # (words, M, N, K, S0, T0, xsrc[6], ysrc[6], C, stream, residues | null): operands as
+    # share sources
     "mx_gemm_asym_src": (
-        c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+        c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     ),
+    "mx_crt_defer_bytes": (c_i64, [c_int, c_i64, c_i64, c_i64]),
+    # (words, M, N, K, residues, C, stream)
+    "mx_crt_recon": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "mx_gemm_roll": (
         c_int,
         [c_int, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int,

@@ -24,6 +24,7 @@ import functools
 import math
 import os
 import threading
+from contextlib import contextmanager
 from fractions import Fraction
 from typing import List
 from typing import Sequence
@@ -1669,6 +1670,32 @@ def _asym_operands(x0: RT, x1: RT, y0: RT, y1: RT):
     return A0, A1, B0, B1
 
 
+_DEFER = threading.local()
+
+
+@contextmanager
+def deferred_products(on: bool = True):
+    """Within the block, dot_cross_asym / dot_cross_asym_src may return their product as a
+    :class:`CrtProduct` (the caller is a tail that waits for its first reader)."""
+    prev = getattr(_DEFER, "on", False)
+    _DEFER.on = bool(on)
+    try:
+        yield
+    finally:
+        _DEFER.on = prev
+
+
+def _defer_residues(bits: int, M: int, N: int, K: int, device):
+    """The residue buffer of a deferred M x N x K product, or None where products are not
+    deferred (outside deferred_products, or the native form declines the layout or sizes)."""
+    if not getattr(_DEFER, "on", False):
+        return None
+    nbytes = nat.lib().mx_crt_defer_bytes(_words(bits), M, N, K)
+    if nbytes < 0:
+        return None
+    return torch.empty(nbytes, dtype=torch.int8, device=device)
+
+
 def dot_cross_asym(x0: RT, x1: RT, y0: RT, y1: RT, rolled: bool = False) -> RT:
     """The three parties' local products of a replicated matrix product, in the asymmetric
     form (x0/x1: [3, M, K] first/second share stacks, y0/y1: [3, K, N]).  With party p
@@ -1693,14 +1720,15 @@ def dot_cross_asym(x0: RT, x1: RT, y0: RT, y1: RT, rolled: bool = False) -> RT:
         if rolled:
             ts[1] = ts[3] = None
         if all(t is None or t.is_contiguous() for t in ts):
-            out = empty((3, M, N), bits, d.device)
+            res = _defer_residues(bits, M, N, K, d.device)
+            out = empty((3, M, N), bits, d.device) if res is None else None
             rc = nat.lib().mx_gemm_asym(
                 _words(bits), M, N, K, nat.ptr(ts[0]), None if ts[1] is None else nat.ptr(ts[1]),
                 nat.ptr(ts[2]), None if ts[3] is None else nat.ptr(ts[3]), 1 if rolled else 0,
-                nat.ptr(out.data), nat.stream_of(d))
+                None if out is None else nat.ptr(out.data), nat.stream_of(d), nat.ptr(res))
             if rc != -7:
                 nat.check(rc, "gemm_asym")
-                return out
+                return out if res is None else CrtProduct(res, M, N, K, bits)
     if x1 is None or y1 is None:
         x1 = RT(torch.roll(x0.data, -1, dims=0), bits)
         y1 = RT(torch.roll(y0.data, -1, dims=0), bits)
@@ -1730,13 +1758,15 @@ def dot_cross_asym_src(x0, y0, xsrc, ysrc, M: int, K: int, N: int):
         words.append((ctypes.c_int64 * 6)(d.data_ptr(), code, int(frac or 0), j0, int(slot),
                                           _i64(nonce)))
     anyt = next(s[1] for s in (xsrc, ysrc) if s is not None)
-    out = empty((3, M, N), 128, anyt.device)
+    res = _defer_residues(128, M, N, K, anyt.device)
+    out = empty((3, M, N), 128, anyt.device) if res is None else None
     rc = nat.lib().mx_gemm_asym_src(2, M, N, K, nat.ptr(ts[0]), nat.ptr(ts[1]), words[0],
-                                    words[1], nat.ptr(out.data), nat.stream_of(anyt))
+                                    words[1], None if out is None else nat.ptr(out.data),
+                                    nat.stream_of(anyt), nat.ptr(res))
     if rc == -7:
         return None
     nat.check(rc, "gemm_asym_src")
-    return out
+    return out if res is None else CrtProduct(res, M, N, K, 128)
 
 
 def _i64(v: int) -> int:
@@ -2228,6 +2258,8 @@ def zs_trunc3_open(z: RT, slot_ptr: int, nmul: int, m: int, nonces, frac: int):
     bits = z.bits
     if bits not in (64, 128):
         return None
+    if isinstance(z, CrtProduct) and z.pending():
+        return z.open(slot_ptr, nmul, m, nonces, frac)
     pv = _party_view(z)
     n = math.prod(z.shape) // 3
     if pv is None or pv[1] != n or pv[0] < n:
@@ -2240,7 +2272,7 @@ def zs_trunc3_open(z: RT, slot_ptr: int, nmul: int, m: int, nonces, frac: int):
     nn = (ctypes.c_uint64 * 6)(*[v & MASK64 for v in nonces])
     nat.check(nat.lib().mx_mul_trunc3_open(
         nat.dev_of(d), _words(bits), nat.ptr(d), xs, nat.ptr(out), n, ctypes.c_void_p(slot_ptr),
-        nmul & MASK64, int(m), nn, int(frac), nat.stream_of(d)), "zs_trunc3_open")
+        nmul & MASK64, int(m), nn, int(frac), nat.stream_of(d), None), "zs_trunc3_open")
     return out
 
 
@@ -2413,6 +2445,72 @@ class OpenedTail(RT):
     @property
     def device(self):
         return self.src.device if self.pending() else self.data.device
+
+
+class CrtProduct(RT):
+    """The three parties' local products [3, M, N] of a stacked dot (dot_cross_asym under
+    :func:`deferred_products`) still held as the CRT GEMM's output residues.  A tail that is
+    opened by its first reader reconstructs them inside the opening kernel (:meth:`open`:
+    mx_mul_trunc3_open's crt form) and the products never go to memory; any read of ``data``
+    runs the reconstruction the product skipped (mx_crt_recon) -- the same values bitwise.
+    The residues are the product's own buffer, not the GEMM workspace, so later products on
+    the stream do not touch them."""
+
+    __slots__ = ("residues", "mnk", "stream")
+
+    def __init__(self, residues: torch.Tensor, M: int, N: int, K: int, bits: int):
+        _RT_DATA.__set__(self, None)
+        self.bits = bits
+        self._shape = (3, M, N)
+        self.residues = residues
+        self.mnk = (M, N, K)
+        self.stream = _stream_of(residues)
+
+    def pending(self) -> bool:
+        return _RT_DATA.__get__(self) is None
+
+    def _residues_here(self) -> torch.Tensor:
+        """The residues, ordered before (and kept alive for) the current stream's use."""
+        _join(self.stream)
+        cur = torch.cuda.current_stream(self.residues.device)
+        if cur != self.stream:
+            self.residues.record_stream(cur)
+        return self.residues
+
+    def open(self, slot_ptr: int, nmul: int, m: int, nonces, frac: int) -> torch.Tensor:
+        """zs_trunc3_open of the product, reconstructed on the way; the residues stay (a
+        later read of the shares rebuilds the product from them)."""
+        res = self._residues_here()
+        M, N, K = self.mnk
+        out = torch.empty((M, N), dtype=torch.float64, device=res.device)
+        nn = (ctypes.c_uint64 * 6)(*[v & MASK64 for v in nonces])
+        crt = (ctypes.c_int64 * 4)(res.data_ptr(), M, N, K)
+        nat.check(nat.lib().mx_mul_trunc3_open(
+            1, _words(self.bits), None, 0, nat.ptr(out), M * N, ctypes.c_void_p(slot_ptr),
+            nmul & MASK64, int(m), nn, int(frac), nat.stream_of(res), crt), "zs_trunc3_open (crt)")
+        return out
+
+    @property
+    def data(self):
+        d = _RT_DATA.__get__(self)
+        if d is None:
+            res = self._residues_here()
+            M, N, K = self.mnk
+            out = empty((3, M, N), self.bits, res.device)
+            nat.check(nat.lib().mx_crt_recon(_words(self.bits), M, N, K, nat.ptr(res),
+                                             nat.ptr(out.data), nat.stream_of(res)), "crt_recon")
+            d = out.data
+            _RT_DATA.__set__(self, d)
+            self.residues = None
+        return d
+
+    @data.setter
+    def data(self, v):
+        _RT_DATA.__set__(self, v)
+
+    @property
+    def device(self):
+        return self.residues.device if self.pending() else self.data.device
 
 
 def opened(a: RT, b: RT, c: RT, d: RT = None) -> RT:

@@ -230,7 +230,8 @@ class StackedTail(RepTensor):
 
     def __init__(self, sess, plc, bits, v, m, nonces):
         self._sess, self.v, self.m, self._nonces = sess, v, m, nonces
-        self._stream = R._stream_of(v.v.data)
+        lazy_v = isinstance(v.v, R.CrtProduct) and v.v.pending()  # its data: not yet
+        self._stream = v.v.stream if lazy_v else R._stream_of(v.v.data)
         self.device = v.v.device
         super().__init__(plc, bits, "arith", None, None)
 
@@ -965,11 +966,16 @@ def dot_trunc(sess, x: RepTensor, y: RepTensor, m: int, nbatch: int = 0) -> RepT
                 and getattr(sess, "device", None) is not None and sess.device.type == "cuda"
                 and os.environ.get("MOOSEX_DOT_TAIL", "1") != "0"):
             with span("rep.dot_trunc_fused"):
-                v = (_zero_slot_cross(sess, x, y) or _dot_cross_src(sess, x, y)
-                     or sess.p_dot_cross(x.plc, x.s0, x.s1, y.s0, y.s1))
                 issue = getattr(sess, "p_zs_trunc_issue", None)
-                if (issue is not None and x.bits in (64, 128)
-                        and os.environ.get("MOOSEX_DOT_OPEN", "1") != "0"):
+                waits = (issue is not None and x.bits in (64, 128)
+                         and os.environ.get("MOOSEX_DOT_OPEN", "1") != "0")
+                # a tail that waits takes the product as its GEMM's residues where that form
+                # applies (R.CrtProduct): an opening reconstructs it on the way
+                with R.deferred_products(
+                        waits and os.environ.get("MOOSEX_DOT_OPEN_FUSED", "1") != "0"):
+                    v = (_zero_slot_cross(sess, x, y) or _dot_cross_src(sess, x, y)
+                         or sess.p_dot_cross(x.plc, x.s0, x.s1, y.s0, y.s1))
+                if waits:
                     # the tail waits for its first reader: a reveal opens it in one kernel
                     return StackedTail(sess, x.plc, x.bits, v, m, issue(x.plc, v))
                 s0, s1 = tail(x.plc, v, m)  # zero share + reshare + TruncPr: one kernel
