@@ -25,12 +25,18 @@
 //   k_crt_prep<T, TRANS>  operand -> n residue planes in a blocked, swizzled int8 image
 //                         [g = batch*n + i][tile][k-step][256 rows][64 bytes] (one 16 KB
 //                         image per (tile, k-step), LDS-DMA ready, ds_read_b128 conflict free)
-//   k_crt_gemm            256x256 block tile, 8 waves (2 per SIMD) of 128x64, K-step 64,
-//                         3-stage LDS-DMA ring, one barrier per step; epilogue reduces the
-//                         i32 accumulators mod p_i and stores one byte per output element in
-//                         MFMA register order (16 B per lane per 32x32 block)
-//   k_crt_recon<T>        n residue bytes per element -> ring element (sum c_i W_i - q Mw),
-//                         optionally accumulated into C
+//   k_crt_prep_src        the same images of an operand that is still the plain input of its
+//                         sharing: the three share slots are formed in registers
+//   k_crt_gemm16          v_mfma_i32_16x16x64_i8 on a 256 x BN block tile (BN = 256 or 128), 8
+//                         or 4 waves, K-step 64, LDS-DMA ring of 3 or 5 stages; the variants
+//                         (kVariants, MOOSEX_CRT_KERNEL) differ in tile, waves and schedule.
+//                         The epilogue reduces the i32 accumulators mod p_i and stores one byte
+//                         per output element in MFMA register order (4 B per lane per 16x16
+//                         block)
+//   k_crt_recon16<T>      n residue bytes per element -> ring element (sum c_i W_i - q Mw),
+//                         optionally accumulated into C; by v_dot4_i32_i8 or multiply-adds
+//   k_crt_recon16d_open   the reconstruction of a product that is only revealed, inside the
+//                         opening of its TruncPr tail
 // Mode 1 (RSS cross GEMM, as in gemm_mfma.hip): A' = [A0 | A1], B' = [B0 + B1 ; B0].
 #include <hip/hip_runtime.h>
 
@@ -40,6 +46,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 
 #include "hip_attr.h"
 #include "moosex.h"
@@ -76,8 +83,7 @@ constexpr int kStages = 3;       // LDS ring depth
 
 // byte offset of 16-byte chunk c (0..3) of image row r: chunks XOR-swizzled by
 // f((r >> 2) & 3), f = [0, 2, 3, 1], so that the 16 lanes of each ds_read_b128 lane group hit
-// 16 distinct 16-byte bank slots both for the 32x32x32 fragments (lane l: row l & 31, one
-// chunk per half-wave) and for the 16x16x64 fragments (lane l: row l & 15, chunk l >> 4).
+// 16 distinct 16-byte bank slots for the 16x16x64 fragments (lane l: row l & 15, chunk l >> 4).
 __device__ __host__ inline int swz(int q) { return (0x78 >> (2 * (q & 3))) & 3; }
 __device__ __host__ inline int img_off(int r, int c) { return r * BK + 16 * (c ^ swz(r >> 2)); }
 
@@ -231,6 +237,12 @@ __device__ __forceinline__ uint32_t pack4(int a, int b, int c, int d) {
   const uint32_t lo = __builtin_amdgcn_perm((uint32_t)b, (uint32_t)a, 0x0c0c0400u);
   const uint32_t hi = __builtin_amdgcn_perm((uint32_t)d, (uint32_t)c, 0x0c0c0400u);
   return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
+}
+__device__ __forceinline__ v4i pack16(const int (&q)[16]) {
+  v4i o;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) o[u] = (int)pack4(q[4 * u], q[4 * u + 1], q[4 * u + 2], q[4 * u + 3]);
+  return o;
 }
 
 template <class T>
@@ -391,10 +403,7 @@ __global__ void __launch_bounds__(256)
       int rr[16];
 #pragma unroll
       for (int j = 0; j < 16; ++j) rr[j] = (int)(v[j][0] * tab.mul0);
-      v4i o;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) o[u] = (int)pack4(rr[4 * u], rr[4 * u + 1], rr[4 * u + 2], rr[4 * u + 3]);
-      *(v4i*)base = o;
+      *(v4i*)base = pack16(rr);
     }
     for (int i = 1; i < n; ++i) {
       const uint32_t w[4] = {tab.w[i][0], tab.w[i][1], tab.w[i][2], tab.w[i][3]};
@@ -409,10 +418,7 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
         for (int j = 0; j < 16; ++j) rr[j] = residue<NW>(v[j], w, neg, p, rcp);
       }
-      v4i o;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) o[u] = (int)pack4(rr[4 * u], rr[4 * u + 1], rr[4 * u + 2], rr[4 * u + 3]);
-      *(v4i*)(base + i * plane) = o;
+      *(v4i*)(base + i * plane) = pack16(rr);
     }
     };
     emit(ob + boff);
@@ -576,12 +582,6 @@ __global__ void __launch_bounds__(256)
       for (int e = 0; e < 4; ++e)
         if (s.ph[e] == ph) *(v4i*)(out + s.off[e] + ioff + boff) = o;
     };
-    auto pack16 = [](const int (&q)[16]) __attribute__((always_inline)) {
-      v4i o;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) o[u] = (int)pack4(q[4 * u], q[4 * u + 1], q[4 * u + 2], q[4 * u + 3]);
-      return o;
-    };
     const v4i zero = {0, 0, 0, 0};
     {  // p = 256: the low byte (times the folded inverse); the sum's is the low bytes' sum
       int q[16];
@@ -686,228 +686,11 @@ __device__ __forceinline__ int centered_mod(int acc, float pf, float rcp, int t1
   return (int)__builtin_fmaf(-qt, pf, fs);
 }
 
-// WR x WC waves per 256x256 block tile; wave tile (256/WR) x (256/WC) = MI x NJ MFMA
-// blocks of 32x32.  <2,2>: 4 waves of 128x128 (256 accumulator registers, one wave per
-// SIMD); <2,4>: 8 waves of 128x64 (128 accumulators, two waves per SIMD, so one wave's
-// LDS reads, address arithmetic and barrier waits hide behind its partner's MFMAs).
-template <int WR, int WC, int BN, int MINW>
-__global__ void __launch_bounds__(64 * WR * WC, MINW)
-    k_crt_gemm(const int8_t* __restrict__ RA, const int8_t* __restrict__ RB,
-               int8_t* __restrict__ CR, int tiles_m, int tiles_n, int nkb, int gM,
-               const EpiTab ep, int dma_mask, int bcast) {
-  constexpr int NW = WR * WC;
-  constexpr int MI = BM / WR / 32, NJ = BN / WC / 32;
-  constexpr int kImgB = BN * BK;                 // one B image per (tile, k-step)
-  constexpr int kStageBytes = kImg + kImgB;
-  constexpr int NPIECE = kStageBytes / 1024;     // 1 KB LDS-DMA pieces per stage
-  constexpr int PPW = NPIECE / NW;               // DMA pieces per wave per stage
-  static_assert(PPW * NW == NPIECE, "stage pieces must split evenly over the waves");
-  extern __shared__ __attribute__((aligned(16))) int8_t smem[];
-  const int ntiles = tiles_m * tiles_n;
-  const int tid_flat = (int)xcd_remap(blockIdx.x, ntiles);
-  const int group = tid_flat / (gM * tiles_n);
-  const int first_m = group * gM;
-  const int gm = tiles_m - first_m < gM ? tiles_m - first_m : gM;
-  const int in_group = tid_flat % (gM * tiles_n);
-  const int tm = first_m + in_group % gm, tn = in_group / gm;
-  const int g = blockIdx.y;  // batch * n + modulus
-  const int mi = g % ep.n;
-  // bcast bit 0 / 1: A / B residues were prepared once for every batch entry
-  const int8_t* ga = RA + ((int64_t)((bcast & 1) ? mi : g) * tiles_m + tm) * nkb * (int64_t)kImg;
-  const int8_t* gb = RB + ((int64_t)((bcast & 2) ? mi : g) * tiles_n + tn) * nkb * (int64_t)kImgB;
-
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wr = wave / WC, wc = wave % WC;
-  const int half = lane >> 5;
-  const int sw = swz(lane >> 2);  // row swizzle of every fragment row this lane reads
-  const int rowa = (wr * (BM / WR) + (lane & 31)) * BK;
-  const int rowb = kImg + (wc * (BN / WC) + (lane & 31)) * BK;
-  const int co0 = 16 * (half ^ sw), co1 = 16 * ((2 + half) ^ sw);
-
-  // wave w issues pieces w, w + NW, .. of the NPIECE 1-KB pieces of a stage (16 A, then
-  // BN / 16 B); the sources advance by one image per k-step
-  const int8_t* srcs[PPW];
-  int dsts[PPW], steps[PPW];
-#pragma unroll
-  for (int t = 0; t < PPW; ++t) {
-    const int pc = wave + NW * t;
-    const bool is_b = pc >= 16;
-    const int pp = is_b ? pc - 16 : pc;
-    srcs[t] = (is_b ? gb : ga) + pp * 1024 + lane * 16;
-    dsts[t] = (is_b ? kImg : 0) + pp * 1024;
-    steps[t] = is_b ? kImgB : kImg;
-  }
-  auto dma = [&](int kb, int t, int8_t* dst_stage) {
-    if (!((dma_mask >> (wave + NW * t >= 16 ? 1 : 0)) & 1)) return;  // timing experiments only
-    __builtin_amdgcn_global_load_lds((const void*)(srcs[t] + (int64_t)kb * steps[t]),
-                                     (__attribute__((address_space(3))) void*)(dst_stage + dsts[t]),
-                                     16, 0, 0);
-  };
-
-  v16i acc[MI][NJ];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[i][j] = v16i{0};
-
-  v4i fa0[MI], fb0[NJ], fa1[MI], fb1[NJ];
-  auto frags = [&](const int8_t* st, int co, v4i(&fa)[MI], v4i(&fb)[NJ]) {
-#pragma unroll
-    for (int i = 0; i < MI; ++i) fa[i] = *(const v4i*)(st + rowa + i * 32 * BK + co);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) fb[j] = *(const v4i*)(st + rowb + j * 32 * BK + co);
-  };
-
-  // prologue: stages 0, 1, 2 in flight; wait for stage 0
-#pragma unroll
-  for (int s = 0; s < kStages; ++s)
-#pragma unroll
-    for (int t = 0; t < PPW; ++t) dma(s < nkb ? s : nkb - 1, t, smem + s * kStageBytes);
-  __builtin_amdgcn_s_waitcnt(waitcnt_vm_lgkm0(2 * PPW));
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-  frags(smem, co0, fa0, fb0);
-  if (dma_mask & 8) frags(smem, co1, fa1, fb1);
-
-  int8_t* cur = smem;                    // stage kb
-  int8_t* nxt = smem + kStageBytes;      // stage kb + 1
-  int8_t* nn = smem + 2 * kStageBytes;   // stage kb + 2
-  for (int kb = 0; kb < nkb; ++kb) {
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa0[i], fb0[j], acc[i][j], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (i == 0 && j == 1 && !(dma_mask & 8)) {  // second-half fragments, behind the
-          frags(cur, co1, fa1, fb1);  // first MFMAs (the compiler waits for all LDS reads
-          __builtin_amdgcn_sched_barrier(0);  // before an MFMA that follows any of them)
-        }
-      }
-    // my DMA of stage kb+1 landed (only stage kb+2's pieces may be outstanding) and my
-    // reads of stage kb are done; after the barrier, everyone's are
-    __builtin_amdgcn_s_waitcnt(waitcnt_vm_lgkm0(PPW));
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    if (!(dma_mask & 8)) frags(nxt, co0, fa0, fb0);  // past the end: stale, never used
-    __builtin_amdgcn_sched_barrier(0);
-    const int kn = kb + kStages < nkb ? kb + kStages : nkb - 1;
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa1[i], fb1[j], acc[i][j], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        // this wave's PPW pieces of stage kb+3 into the freed buffer, spread over the
-        // MI * NJ MFMAs: piece t after MFMA floor((t + 1) MI NJ / PPW) - 1
-        const int m = i * NJ + j;
-#pragma unroll
-        for (int t = 0; t < PPW; ++t)
-          if (m == (t + 1) * MI * NJ / PPW - 1) {
-            dma(kn, t, cur);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-      }
-    int8_t* t = cur;
-    cur = nxt;
-    nxt = nn;
-    nn = t;
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-
-  // epilogue: centered acc mod p, one byte per element, MFMA register order; 32x32 block
-  // (bi, bj) of the tile at byte ((bi * BN / 32 + bj) * 64 + lane) * 16 of the tile's bytes
-  const float pf = ep.pf[mi], rcp = ep.rcp[mi];
-  const int t16 = ep.t16[mi];
-  int8_t* cr = CR + ((int64_t)g * ntiles + tm * tiles_n + tn) * (int64_t)(BM * BN);
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      // (p = 256 takes the same path: t16 = 0, exact power-of-two rounding, r in
-      // [-128, 128] whose low byte is the residue)
-      int rr[16];
-#pragma unroll
-      for (int e = 0; e < 16; ++e)
-        rr[e] = (dma_mask & 4) ? acc[i][j][e] : centered_mod(acc[i][j][e], pf, rcp, t16);
-      v4i o;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) o[u] = (int)pack4(rr[4 * u], rr[4 * u + 1], rr[4 * u + 2], rr[4 * u + 3]);
-      const int bi = wr * MI + i, bj = wc * NJ + j;
-      *(v4i*)(cr + ((bi * (BN / 32) + bj) * 64 + lane) * 16) = o;
-    }
-}
-
-// One thread = 8 residue bytes (8 output elements of one MFMA block) of every modulus.
-template <class T, int BN>
-__global__ void __launch_bounds__(256)
-    k_crt_recon(const int8_t* __restrict__ CR, T* __restrict__ C, int64_t M, int64_t N,
-                int64_t tiles_m, int64_t tiles_n, int accumulate, const RecTab rc) {
-  constexpr int NK = sizeof(T) / 2;  // 16-bit words of a ring element
-  const int64_t ntiles = tiles_m * tiles_n;
-  constexpr int kCrTile = BM * BN, NBJ = BN / 32, LOGB = BN == 256 ? 6 : 5;
-  const int64_t total = ntiles * (kCrTile / 8);
-  const int64_t b = blockIdx.y;
-  const int n = rc.n;
-  for (int64_t gt = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; gt < total;
-       gt += (int64_t)gridDim.x * blockDim.x) {
-    const int hf = (int)(gt & 1);
-    const int lane = (int)((gt >> 1) & 63);
-    const int64_t rest = gt >> 7;
-    const int blk = (int)(rest & ((1 << LOGB) - 1));  // 32x32 block (blk / NBJ, blk % NBJ)
-    const int64_t tile = rest >> LOGB;
-    const int64_t off = tile * kCrTile + (blk * 64 + lane) * 16 + hf * 8;
-    int acc[8][NK];
-    float qs[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      qs[e] = 0.f;
-#pragma unroll
-      for (int k = 0; k < NK; ++k) acc[e][k] = 0;
-    }
-    const int8_t* src = CR + b * n * ntiles * (int64_t)kCrTile + off;
-    for (int i = 0; i < n; ++i) {
-      const uint2 v = *(const uint2*)(src + i * ntiles * (int64_t)kCrTile);
-      const float rcp = rc.rcp[i];
-      int wk[NK];
-#pragma unroll
-      for (int k = 0; k < NK; ++k) wk[k] = rc.W[i][k];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int c = (int)(int8_t)(((e < 4 ? v.x : v.y) >> (8 * (e & 3))) & 0xff);
-        qs[e] = __builtin_fmaf((float)c, rcp, qs[e]);
-#pragma unroll
-        for (int k = 0; k < NK; ++k) acc[e][k] += __mul24(c, wk[k]);
-      }
-    }
-    const int64_t tm = tile / tiles_n, tn = tile % tiles_n;
-    const int bi = blk / NBJ, bj = blk % NBJ;
-    const int64_t gcol = tn * BN + bj * 32 + (lane & 31);
-    T mw = 0;
-#pragma unroll
-    for (int k = 0; k < NK; ++k) mw |= (T)rc.Mw[k] << (16 * k);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int ee = hf * 8 + e;  // accumulator register index in the 32x32 block
-      const int row = (ee & 3) + 8 * (ee >> 2) + 4 * (lane >> 5);
-      const int64_t grow = tm * BM + bi * 32 + row;
-      T z = 0;
-#pragma unroll
-      for (int k = 0; k < NK; ++k) z += (T)(int64_t)acc[e][k] << (16 * k);
-      const int q = (int)__builtin_rintf(qs[e]);
-      z -= (T)(int64_t)q * mw;
-      if (grow < M && gcol < N) {
-        T* pc = C + (b * M + grow) * N + gcol;
-        *pc = accumulate ? (T)(*pc + z) : z;
-      }
-    }
-  }
-}
-
-// 16x16x64 variant: one v_mfma_i32_16x16x64_i8 covers a whole 64-byte k-step, lane l reads
+// The GEMM: one v_mfma_i32_16x16x64_i8 covers a whole 64-byte k-step, lane l reads
 // row l & 15, chunk l >> 4 of the image.  WR x WC waves, wave tile (BM/WR) x (BN/WC) =
-// MI x NJ MFMA blocks of 16x16 (4 accumulator registers each).  Fragments of stage kb+1 are
+// MI x NJ MFMA blocks of 16x16 (4 accumulator registers each): <2,4> is 8 waves of 128x64
+// (two waves per SIMD, so one wave's LDS reads, address arithmetic and barrier waits hide
+// behind its partner's MFMAs), <2,2> 4 waves.  IL == 0: fragments of stage kb+1 are
 // read right after the step's barrier into the second register set (the k-loop is unrolled
 // by two so the sets swap without moves), while the second half of stage kb's MFMAs runs.
 // Output bytes: 16x16 block (bi, bj) at ((bi * BN / 16 + bj) * 64 + lane) * 4 of the tile.
@@ -915,8 +698,7 @@ template <int WR, int WC, int BN, int MINW, int STG = kStages, int IL = 0>
 __global__ void __launch_bounds__(64 * WR * WC, MINW)
     k_crt_gemm16(const int8_t* __restrict__ RA, const int8_t* __restrict__ RB,
                  int8_t* __restrict__ CR, int tiles_m, int tiles_n, int nkb_all, int gM,
-                 const EpiTab ep, int dma_mask, int bcast, int a_nkb, int roll, int amap,
-                 int bmap) {
+                 const EpiTab ep, int bcast, int a_nkb, int roll, int amap, int bmap) {
   constexpr int NW = WR * WC;
   constexpr int MI = BM / WR / 16, NJ = BN / WC / 16;
   constexpr int NM = MI * NJ;                    // MFMAs per wave per k-step
@@ -993,11 +775,7 @@ __global__ void __launch_bounds__(64 * WR * WC, MINW)
     dsts[t] = (is_b ? kImg : 0) + pp * 1024;
     steps[t] = is_b ? kImgB : kImg;
   }
-  bool dma_on[PPW];
-#pragma unroll
-  for (int t = 0; t < PPW; ++t) dma_on[t] = (dma_mask >> ((wave + NW * t) >= 16 ? 1 : 0)) & 1;
   auto dma = [&](int kb, int t, int8_t* dst_stage) {
-    if (!dma_on[t]) return;  // MOOSEX_CRT_DMA_MASK timing experiments only
     const int8_t* src = kb >= khalf ? srcs2[t] : srcs[t];
     __builtin_amdgcn_global_load_lds((const void*)(src + (int64_t)kb * steps[t]),
                                      (__attribute__((address_space(3))) void*)(dst_stage + dsts[t]),
@@ -1011,9 +789,7 @@ __global__ void __launch_bounds__(64 * WR * WC, MINW)
     for (int j = 0; j < NJ; ++j) acc[i][j] = v4i{0, 0, 0, 0};
 
   v4i fa0[MI], fb0[NJ], fa1[MI], fb1[NJ];
-  const bool no_frags = (dma_mask & 8) != 0;  // timing experiments only
   auto frags = [&](const int8_t* st, v4i(&fa)[MI], v4i(&fb)[NJ]) {
-    if (no_frags) return;
 #pragma unroll
     for (int i = 0; i < MI; ++i) fa[i] = *(const v4i*)(st + rowa + i * 16 * BK);
 #pragma unroll
@@ -1068,7 +844,6 @@ __global__ void __launch_bounds__(64 * WR * WC, MINW)
   // every wave bursting its 12 fragment reads into the LDS right after a mid-step barrier
   auto rd_frag = [&](const int8_t* st, int q, v4i(&fa)[MI], v4i(&fb)[NJ])
                      __attribute__((always_inline)) {
-    if (no_frags) return;
     if (q < MI)
       fa[q] = *(const v4i*)(st + rowa + q * 16 * BK);
     else
@@ -1203,35 +978,28 @@ __global__ void __launch_bounds__(64 * WR * WC, MINW)
     }
 }
 
-// reconstruction for the 16x16 output layout: one thread = one lane's 4 bytes of a block
-template <class T, int BN>
-__global__ void __launch_bounds__(256)
-    k_crt_recon16(const int8_t* __restrict__ CR, T* __restrict__ C, int64_t M, int64_t N,
-                  int64_t tiles_m, int64_t tiles_n, int accumulate, const RecTab rc) {
-  constexpr int NK = sizeof(T) / 2;
-  constexpr int kCrTile = BM * BN, NBJ = BN / 16;
-  const int64_t ntiles = tiles_m * tiles_n;
-  const int64_t total = ntiles * (kCrTile / 4);
-  const int64_t b = blockIdx.y;
-  const int n = rc.n;
-  for (int64_t gt = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; gt < total;
-       gt += (int64_t)gridDim.x * blockDim.x) {
-    const int lane = (int)(gt & 63);
-    const int64_t rest = gt >> 6;
-    const int blk = (int)(rest % (16 * NBJ));
-    const int64_t tile = rest / (16 * NBJ);
-    const int64_t off = tile * kCrTile + (blk * 64 + lane) * 4;
-    int acc[4][NK];
-    float qs[4];
+// Reconstruction, one thread's share: the 4 elements (rows 4 * (lane >> 4) + e of a 16x16
+// block, one column) whose residue bytes are the dword at ``src`` of every modulus plane,
+// pstride apart.  The multiply-add form (MOOSEX_CRT_RECON=0): per modulus and element one
+// float fma for the quotient and a 24-bit multiply-add per 16-bit word of W_i.  In two steps,
+// the sums and then one element at a time, so that the caller's index arithmetic (a 64-bit
+// division) sits between them, where only the sums are live (else the u128 form loses a wave
+// of occupancy).
+template <class T>
+struct Recon16m {
+  static constexpr int NK = sizeof(T) / 2;
+  int acc[4][NK];
+  float qs[4];
+  __device__ __forceinline__ void sums(const int8_t* __restrict__ src, int64_t pstride, int n,
+                                       const RecTab& rc) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       qs[e] = 0.f;
 #pragma unroll
       for (int k = 0; k < NK; ++k) acc[e][k] = 0;
     }
-    const int8_t* src = CR + b * n * ntiles * (int64_t)kCrTile + off;
     for (int i = 0; i < n; ++i) {
-      const uint32_t v = *(const uint32_t*)(src + i * ntiles * (int64_t)kCrTile);
+      const uint32_t v = *(const uint32_t*)(src + i * pstride);
       const float rcp = rc.rcp[i];
       int wk[NK];
 #pragma unroll
@@ -1244,36 +1012,29 @@ __global__ void __launch_bounds__(256)
         for (int k = 0; k < NK; ++k) acc[e][k] += __mul24(c, wk[k]);
       }
     }
-    const int64_t tm = tile / tiles_n, tn = tile % tiles_n;
-    const int bi = blk / NBJ, bj = blk % NBJ;
-    const int64_t gcol = tn * BN + bj * 16 + (lane & 15);
+  }
+  static __device__ __forceinline__ T modulus(const RecTab& rc) {  // M mod 2^w
     T mw = 0;
 #pragma unroll
     for (int k = 0; k < NK; ++k) mw |= (T)rc.Mw[k] << (16 * k);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int64_t grow = tm * BM + bi * 16 + 4 * (lane >> 4) + e;
-      T z = 0;
-#pragma unroll
-      for (int k = 0; k < NK; ++k) z += (T)(int64_t)acc[e][k] << (16 * k);
-      const int q = (int)__builtin_rintf(qs[e]);
-      z -= (T)(int64_t)q * mw;
-      if (grow < M && gcol < N) {
-        T* pc = C + (b * M + grow) * N + gcol;
-        *pc = accumulate ? (T)(*pc + z) : z;
-      }
-    }
+    return mw;
   }
-}
+  __device__ __forceinline__ T element(int e, T mw) const {
+    T z = 0;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) z += (T)(int64_t)acc[e][k] << (16 * k);
+    const int q = (int)__builtin_rintf(qs[e]);
+    z -= (T)(int64_t)q * mw;
+    return z;
+  }
+};
 
-// k_crt_recon16 with the per-modulus multiply-adds done as v_dot4_i32_i8: a thread's 4
-// elements x 4 moduli of residues (4 dwords, one per modulus plane) are transposed with 8
+// The same with the per-modulus multiply-adds done as v_dot4_i32_i8 (the default): a thread's
+// 4 elements x 4 moduli of residues (4 dwords, one per modulus plane) are transposed with 8
 // v_perm_b32 into one dword of 4 moduli per element, then one dot4 per (element, W digit)
 // and per (element, R digit) -- 19 dot4 for 4 moduli instead of 4 x (8 multiply-adds + a
 // float convert and fma).  q = round(sum_i c_i R_i / 2^24) (error <= 36 * 128 / 2^25, far
-// inside the 0.05 rounding margin of |Z| <= 0.45 M).  Same output as k_crt_recon16.
-// One thread's share of it: the 4 elements (rows 4 * (lane >> 4) + e of a 16x16 block, one
-// column) whose residue bytes are the dword at ``src`` of every modulus plane, pstride apart.
+// inside the 0.05 rounding margin of |Z| <= 0.45 M).  Same output as Recon16m.
 template <class T>
 __device__ __forceinline__ void recon16d_lane(const int8_t* __restrict__ src, int64_t pstride,
                                               int n, const RecTab4& r4, const RecTab& rc,
@@ -1329,11 +1090,13 @@ __device__ __forceinline__ void recon16d_lane(const int8_t* __restrict__ src, in
   }
 }
 
-template <class T, int BN>
+// Reconstruction of k_crt_gemm16's output: one thread = one lane's 4 bytes of a 16x16 block of
+// every modulus, by the dot4 form (DOT4) or the multiply-add form.
+template <class T, int BN, bool DOT4>
 __global__ void __launch_bounds__(256)
-    k_crt_recon16d(const int8_t* __restrict__ CR, T* __restrict__ C, int64_t M, int64_t N,
-                   int64_t tiles_m, int64_t tiles_n, int accumulate, const RecTab4 r4, int n,
-                   const RecTab rc) {
+    k_crt_recon16(const int8_t* __restrict__ CR, T* __restrict__ C, int64_t M, int64_t N,
+                  int64_t tiles_m, int64_t tiles_n, int accumulate, const RecTab4 r4, int n,
+                  const RecTab rc) {
   constexpr int kCrTile = BM * BN, NBJ = BN / 16;
   const int64_t ntiles = tiles_m * tiles_n;
   const int64_t total = ntiles * (kCrTile / 4);
@@ -1346,24 +1109,35 @@ __global__ void __launch_bounds__(256)
     const int64_t tile = rest / (16 * NBJ);
     const int64_t off = tile * kCrTile + (blk * 64 + lane) * 4;
     const int64_t pstride = ntiles * (int64_t)kCrTile;
-    T z[4];
-    recon16d_lane<T>(CR + b * n * pstride + off, pstride, n, r4, rc, z);
+    T zd[4];
+    Recon16m<T> zm;
+    if constexpr (DOT4)
+      recon16d_lane<T>(CR + b * n * pstride + off, pstride, n, r4, rc, zd);
+    else
+      zm.sums(CR + b * n * pstride + off, pstride, n, rc);
     const int64_t tm = tile / tiles_n, tn = tile % tiles_n;
     const int bi = blk / NBJ, bj = blk % NBJ;
     const int64_t gcol = tn * BN + bj * 16 + (lane & 15);
+    const T mw = Recon16m<T>::modulus(rc);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int64_t grow = tm * BM + bi * 16 + 4 * (lane >> 4) + e;
+      T z;
+      if constexpr (DOT4)
+        z = zd[e];
+      else
+        z = zm.element(e, mw);
       if (grow < M && gcol < N) {
         T* pc = C + (b * M + grow) * N + gcol;
-        *pc = accumulate ? (T)(*pc + z[e]) : z[e];
+        *pc = accumulate ? (T)(*pc + z) : z;
       }
     }
   }
 }
 
-// k_crt_recon16d of a three-party product that is only revealed, with the opening on the way
-// (the tail of k_mul_trunc3_open: zero share + reshare + TruncPr by m + reveal + decode): the
+// The dot4 reconstruction of a three-party product that is only revealed, with the opening on
+// the way (the tail of k_mul_trunc3_open: zero share + reshare + TruncPr by m + reveal +
+// decode): the
 // opened value needs the SUM of the parties' products and r = r0 + r1 of TruncPr's draws
 // only (mxf::trunc_pr_open), so the products never go to memory and seven of the tail's nine
 // keystreams are not drawn.  A workgroup takes strips of 8 rows x one tile's 256 columns:
@@ -1373,7 +1147,7 @@ __global__ void __launch_bounds__(256)
 //   2. after a barrier, thread t rebuilds 4 rows x 1 column of every party twice (columns
 //      0..127, then 128..255; a wave reads whole 128-byte lines: 32 lanes of a block), adds
 //      the three, takes its r values from LDS and stores 8 B per element.
-// Bitwise k_crt_recon16d<T, 256> followed by k_mul_trunc3_open<T>.
+// Bitwise k_crt_recon16<T, 256, true> followed by k_mul_trunc3_open<T>.
 template <class T>
 __global__ void __launch_bounds__(256)
     k_crt_recon16d_open(const int8_t* __restrict__ CR, double* __restrict__ out, double scale,
@@ -1442,47 +1216,94 @@ __global__ void __launch_bounds__(256)
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
-int crt_kernel() {  // MOOSEX_CRT_KERNEL: 1 = 4 waves of 128x128, 2 = 8 waves of 128x64
-  // (256x256 tiles, one block per CU), 3 = 4 waves of 128x64 in 256x128 tiles (two blocks
-  // per CU, so one block's barrier waits, LDS bursts and epilogue overlap the other's MFMAs)
-  // 4 = 16x16x64 MFMAs, 4 waves of 128x128 (256x256 tiles; the compiler spills: 71 ms),
-  // 5 = 16x16x64, 4 waves of 128x64 in 256x128 tiles (72 KB LDS: two blocks per CU; 12 %
-  // faster than 3 -- the chip holds a higher clock on the 16x16 shape), 6 = 16x16x64, 8
-  // waves of 128x64 in 256x256 tiles (96 KB LDS and 242 VGPRs: ONE block per CU, two waves
-  // per SIMD; 11.95 vs 12.12 ms for 5 on the 4096^2 Z_2^128 RSS product,
-  // profiles/r2_crt_variant_ab.md), 7 = 6 with a 4-stage ring (no gain), 8 = 6 with one
-  // barrier at the start of each k-step and the next stage's fragment reads spread over the
-  // step's MFMAs (the default: 4-6 % faster than 6 on the same box, profiles/r3_crt_gemm.md),
-  // 9 = 8 with 4 stages, 10 / 11 = 8 / 9 with the DMAs spread over the step too, 12 = 4
-  // with 8's schedule, 13 = 12 with 4 stages, 14 / 15 = 12 / 13 with the DMAs spread (4 and
-  // 12-15 need the VGPR-form MFMA flag of _native/build.py, else they spill), 16 = 8 with
-  // one barrier per two k-steps over five stage buffers (160 KB LDS).  Tried and removed (profiles/r3_crt_gemm.md): DMAs through
-  // buffer descriptors (16.2 vs 15.5 ms per step), a persistent one-block-per-CU kernel
-  // streaming all its tiles' k-steps (16.2 vs 15.5 ms), B fragments loaded from global
-  // memory straight into registers (hipcc drains every counter before their first use)
-  const char* e = std::getenv("MOOSEX_CRT_KERNEL");
-  const int v = e ? std::atoi(e) : 8;
-  return v >= 1 && v <= 16 ? v : 8;
+// An on/off switch of the environment; every caller caches it at first use (static const).
+// Default on: off with a leading '0'; default off: on with a leading '1'.
+bool env_flag(const char* name, bool dflt) {
+  const char* e = std::getenv(name);
+  return dflt ? !(e && e[0] == '0') : (e && e[0] == '1');
 }
-bool crt_mfma16() { return crt_kernel() >= 4; }
-int recon_dot4() {  // MOOSEX_CRT_RECON=0: the multiply-add reconstruction
-  static const int v = [] {
-    const char* e = std::getenv("MOOSEX_CRT_RECON");
-    return e && e[0] == '0' ? 0 : 1;
-  }();
+bool recon_dot4() {  // MOOSEX_CRT_RECON=0: the multiply-add reconstruction
+  static const bool v = env_flag("MOOSEX_CRT_RECON", true);
   return v;
 }
+int launch_status() {  // the code an entry point returns after its launches
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? -100 - (int)e : 0;
+}
 
+int gemm_group_m() {  // 8: 0.02-0.07 ms per headline step faster than 4 (profiles/r6_asym_products.md)
+  const char* e = std::getenv("MOOSEX_CRT_GROUPM");
+  const int v = e ? std::atoi(e) : 8;
+  return v >= 1 && v <= 64 ? v : 8;
+}
+
+struct Variant;
 struct CPlan {
+  const Variant* var;  // the GEMM variant of the product: tile width, LDS size, kernel
   int n, bn;
   int64_t tiles_m, tiles_n, nkb, a_nkb, ra_bytes, rb_bytes, cr_bytes;
 };
+
+// bcast bit 0 / 1: A / B residues were prepared once for every batch entry; roll, amap, bmap:
+// k_crt_gemm16's
+struct GemmArgs {
+  int64_t batch;
+  const int8_t *ra, *rb;
+  int8_t* cr;
+  int bcast, roll, amap, bmap;
+};
+
+template <int WR, int WC, int BN, int MINW, int STG, int IL>
+void launch_variant(const CPlan& p, const Tables& tb, const GemmArgs& a, hipStream_t st) {
+  constexpr int lds = STG * (kImg + BN * BK);
+  ensure_lds_attr((const void*)k_crt_gemm16<WR, WC, BN, MINW, STG, IL>, lds, st);
+  const dim3 grid((unsigned)(p.tiles_m * p.tiles_n), (unsigned)(a.batch * p.n));
+  hipLaunchKernelGGL((k_crt_gemm16<WR, WC, BN, MINW, STG, IL>), grid, dim3(64 * WR * WC), lds, st,
+                     a.ra, a.rb, a.cr, (int)p.tiles_m, (int)p.tiles_n, (int)p.nkb,
+                     gemm_group_m(), tb.ep, a.bcast, (int)p.a_nkb, a.roll, a.amap, a.bmap);
+}
+
+// One record per GEMM variant, <WR, WC, BN, MINW, STG, IL> of k_crt_gemm16: the plan's B' tile
+// width and the launched instantiation (with its LDS size) come from the same record.  What
+// each was measured at, and the variants that were tried and retired, are in
+// profiles/README.md ("CRT GEMM variants").
+struct Variant {
+  int id, bn;
+  void (*launch)(const CPlan&, const Tables&, const GemmArgs&, hipStream_t);
+};
+template <int WR, int WC, int BN, int MINW, int STG, int IL>
+constexpr Variant variant(int id) {
+  return {id, BN, &launch_variant<WR, WC, BN, MINW, STG, IL>};
+}
+constexpr int kDefaultVariant = 8;
+const Variant kVariants[] = {
+    variant<2, 2, 128, 2, 3, 0>(5),   // 4 waves of 128x64, 256x128 tiles, 72 KB LDS: 2 blocks per CU
+    variant<2, 4, 256, 2, 3, 0>(6),   // 8 waves of 128x64, 256x256 tiles, 96 KB LDS: 1 block per CU
+    variant<2, 4, 256, 2, 3, 1>(8),   // 6 with one barrier at the start of a k-step, reads spread
+    variant<2, 2, 256, 1, 3, 1>(12),  // 4 waves of 128x128 with 8's schedule (VGPR-form MFMA flag)
+    variant<2, 2, 256, 1, 3, 2>(14),  // 12 with the DMAs spread over the step too
+    variant<2, 4, 256, 2, 5, 3>(16),  // 8 with one barrier per two k-steps, five stages (160 KB)
+};
+
+// MOOSEX_CRT_KERNEL, read on every call: the record of that id; every other value (a retired
+// id, text that is no number) selects the default.
+const Variant& crt_variant() {
+  const char* e = std::getenv("MOOSEX_CRT_KERNEL");
+  const int v = e ? std::atoi(e) : kDefaultVariant;
+  const Variant* dflt = nullptr;
+  for (const Variant& r : kVariants) {
+    if (r.id == v) return r;
+    if (r.id == kDefaultVariant) dflt = &r;
+  }
+  return *dflt;
+}
 
 // roll: the A' image holds each batch entry's K residues once (k_crt_gemm16's roll)
 CPlan make_cplan(int words, int64_t batch, int64_t M, int64_t N, int64_t K, int mode,
                  bool roll = false) {
   CPlan p;
-  p.bn = (crt_kernel() == 3 || crt_kernel() == 5) ? 128 : 256;  // B tile columns
+  p.var = &crt_variant();
+  p.bn = p.var->bn;  // B tile columns
   const int64_t kprime = mode ? 2 * K : K;
   p.n = moduli_needed(words, kprime);
   p.tiles_m = (M + BM - 1) / BM;
@@ -1495,18 +1316,23 @@ CPlan make_cplan(int words, int64_t batch, int64_t M, int64_t N, int64_t K, int 
   return p;
 }
 
-int gemm_group_m() {  // 8: 0.02-0.07 ms per headline step faster than 4 (profiles/r6_asym_products.md)
-  const char* e = std::getenv("MOOSEX_CRT_GROUPM");
-  const int v = e ? std::atoi(e) : 8;
-  return v >= 1 && v <= 64 ? v : 8;
+// One dispatch per axis: f gets the plan's B' tile width, a switch, or the ring type of
+// ``words`` (with_ring: -2 for any other) as a constant.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <class F>
+auto with_bn(int bn, F&& f) {
+  return bn == 256 ? f(int_c<256>()) : f(int_c<128>());
 }
-
-bool prep_packed() {
-  static const bool v = [] {
-    const char* e = std::getenv("MOOSEX_CRT_PACKED");
-    return !(e && e[0] == '0');
-  }();
-  return v;
+template <class F>
+auto with_bool(bool b, F&& f) {
+  return b ? f(std::true_type()) : f(std::false_type());
+}
+template <class F>
+int with_ring(int words, F&& f) {
+  if (words == 1) return f(u64());
+  if (words == 2) return f(u128());
+  return -2;
 }
 
 template <class T>
@@ -1522,31 +1348,21 @@ void launch_prep(const CPlan& p, const Tables& tb, bool is_b, int64_t batch, int
   const dim3 grid((unsigned)std::min<int64_t>((work + 255) / 256, 16384), (unsigned)batch);
   // packed residues pay on A' (0.626 -> 0.592 ms at 4096^2) but not on the B' image, which
   // streams 1.5x the bytes and loses more to the extra VGPRs (1.128 -> 1.163 ms)
-  static const bool packed_b = [] {  // MOOSEX_CRT_PACKED_B=1: packed residues on B' too
-    const char* e = std::getenv("MOOSEX_CRT_PACKED_B");
-    return e && e[0] == '1';
-  }();
-  if (!prep_packed() || (is_b && !packed_b)) {  // MOOSEX_CRT_PACKED=0: one at a time everywhere
+  // MOOSEX_CRT_PACKED=0: one at a time everywhere; MOOSEX_CRT_PACKED_B=1: packed on B' too
+  static const bool packed = env_flag("MOOSEX_CRT_PACKED", true);
+  static const bool packed_b = env_flag("MOOSEX_CRT_PACKED_B", false);
+  with_bool(packed && (!is_b || packed_b), [&](auto pk) {
+    auto go = [&](auto trans, auto nrows) {
+      hipLaunchKernelGGL(
+          (k_crt_prep<T, decltype(trans)::value, decltype(nrows)::value, decltype(pk)::value>),
+          grid, dim3(256), 0, st, X0, X1, R, K, xs, mode, out, tiles, nkb, nkb_s,
+          is_b ? tb.pb : tb.pa, src);
+    };
     if (!is_b)
-      hipLaunchKernelGGL((k_crt_prep<T, false, BM, false>), grid, dim3(256), 0, st, X0, X1, R, K,
-                         xs, mode, out, tiles, nkb, nkb_s, tb.pa, src);
-    else if (rows == 256)
-      hipLaunchKernelGGL((k_crt_prep<T, true, 256, false>), grid, dim3(256), 0, st, X0, X1, R, K,
-                         xs, mode, out, tiles, nkb, nkb_s, tb.pb, src);
+      go(std::false_type(), int_c<BM>());
     else
-      hipLaunchKernelGGL((k_crt_prep<T, true, 128, false>), grid, dim3(256), 0, st, X0, X1, R, K,
-                         xs, mode, out, tiles, nkb, nkb_s, tb.pb, src);
-    return;
-  }
-  if (!is_b)
-    hipLaunchKernelGGL((k_crt_prep<T, false, BM>), grid, dim3(256), 0, st, X0, X1, R, K, xs, mode,
-                       out, tiles, nkb, nkb_s, tb.pa, src);
-  else if (rows == 256)
-    hipLaunchKernelGGL((k_crt_prep<T, true, 256>), grid, dim3(256), 0, st, X0, X1, R, K, xs, mode,
-                       out, tiles, nkb, nkb_s, tb.pb, src);
-  else
-    hipLaunchKernelGGL((k_crt_prep<T, true, 128>), grid, dim3(256), 0, st, X0, X1, R, K, xs, mode,
-                       out, tiles, nkb, nkb_s, tb.pb, src);
+      with_bn(rows, [&](auto bn) { go(std::true_type(), bn); });
+  });
 }
 
 bool share_src_ok(const ShareSrc& s) {
@@ -1592,105 +1408,56 @@ void launch_prep_src(const CPlan& p, const Tables& tb, bool is_b, const ShareSrc
   const int rows = is_b ? p.bn : BM;
   const int64_t work = tiles * rows * p.a_nkb * 4;
   const dim3 grid((unsigned)std::min<int64_t>(work / 256, 16384));
+  auto go = [&](auto trans, auto nrows, auto pk) {  // A' packed, B' one at a time (launch_prep)
+    hipLaunchKernelGGL(
+        (k_crt_prep_src<decltype(trans)::value, decltype(nrows)::value, decltype(pk)::value>),
+        grid, dim3(256), 0, st, s, src.key, R, K, out, tiles, p.a_nkb, is_b ? tb.pb : tb.pa);
+  };
   if (!is_b)
-    hipLaunchKernelGGL((k_crt_prep_src<false, BM, true>), grid, dim3(256), 0, st, s, src.key, R, K,
-                       out, tiles, p.a_nkb, tb.pa);
-  else if (rows == 256)
-    hipLaunchKernelGGL((k_crt_prep_src<true, 256, false>), grid, dim3(256), 0, st, s, src.key, R,
-                       K, out, tiles, p.a_nkb, tb.pb);
+    go(std::false_type(), int_c<BM>(), std::true_type());
   else
-    hipLaunchKernelGGL((k_crt_prep_src<true, 128, false>), grid, dim3(256), 0, st, s, src.key, R,
-                       K, out, tiles, p.a_nkb, tb.pb);
-}
-
-// MOOSEX_CRT_DMA_MASK (timing experiments, wrong results): bit 0 = stream A, bit 1 = B,
-// bit 2 = skip the epilogue reduction, bit 3 = no LDS fragment reads in the main loop
-int dma_mask() {
-  const char* e = std::getenv("MOOSEX_CRT_DMA_MASK");
-  return e ? std::atoi(e) : 3;
-}
-
-template <int WR, int WC, int BN, int MINW, bool M16, int STG = kStages, int IL = 0>
-void launch_variant(const CPlan& p, const Tables& tb, int64_t batch, const int8_t* ra,
-                    const int8_t* rb, int8_t* cr, int bcast, int roll, hipStream_t st,
-                    int amap = 0, int bmap = 0) {
-  constexpr int lds = STG * (kImg + BN * BK);
-  const void* fn = M16 ? (const void*)k_crt_gemm16<WR, WC, BN, MINW, STG, IL>
-                       : (const void*)k_crt_gemm<WR, WC, BN, MINW>;
-  ensure_lds_attr(fn, lds, st);
-  const dim3 grid((unsigned)(p.tiles_m * p.tiles_n), (unsigned)(batch * p.n));
-  if constexpr (M16)
-    hipLaunchKernelGGL((k_crt_gemm16<WR, WC, BN, MINW, STG, IL>), grid, dim3(64 * WR * WC), lds, st, ra,
-                       rb, cr, (int)p.tiles_m, (int)p.tiles_n, (int)p.nkb, gemm_group_m(), tb.ep,
-                       dma_mask(), bcast, (int)p.a_nkb, roll, amap, bmap);
-  else
-    hipLaunchKernelGGL((k_crt_gemm<WR, WC, BN, MINW>), grid, dim3(64 * WR * WC), lds, st, ra, rb,
-                       cr, (int)p.tiles_m, (int)p.tiles_n, (int)p.nkb, gemm_group_m(), tb.ep,
-                       dma_mask(), bcast);
-}
-
-void launch_crt_gemm(const CPlan& p, const Tables& tb, int64_t batch, const int8_t* ra,
-                     const int8_t* rb, int8_t* cr, int bcast, int roll, hipStream_t st,
-                     int amap = 0, int bmap = 0) {
-  switch (crt_kernel()) {  // roll, amap: 16x16x64 kernels only (run_crt* check)
-    case 1: launch_variant<2, 2, 256, 1, false>(p, tb, batch, ra, rb, cr, bcast, 0, st); break;
-    case 2: launch_variant<2, 4, 256, 2, false>(p, tb, batch, ra, rb, cr, bcast, 0, st); break;
-    case 4: launch_variant<2, 2, 256, 1, true>(p, tb, batch, ra, rb, cr, bcast, roll, st, amap, bmap); break;
-    case 3: launch_variant<2, 2, 128, 2, false>(p, tb, batch, ra, rb, cr, bcast, 0, st); break;
-    case 6: launch_variant<2, 4, 256, 2, true>(p, tb, batch, ra, rb, cr, bcast, roll, st, amap, bmap); break;
-    case 7: launch_variant<2, 4, 256, 2, true, 4>(p, tb, batch, ra, rb, cr, bcast, roll, st, amap, bmap); break;
-    case 8: launch_variant<2, 4, 256, 2, true, 3, 1>(p, tb, batch, ra, rb, cr, bcast, roll, st, amap, bmap); break;
-    case 9: launch_variant<2, 4, 256, 2, true, 4, 1>(p, tb, batch, ra, rb, cr, bcast, roll, st, amap, bmap); break;
-    case 10: launch_variant<2, 4, 256, 2, true, 3, 2>(p, tb, batch, ra, rb, cr, bcast, roll, st, amap, bmap); break;
-    case 11: launch_variant<2, 4, 256, 2, true, 4, 2>(p, tb, batch, ra, rb, cr, bcast, roll, st, amap, bmap); break;
-    case 12: launch_variant<2, 2, 256, 1, true, 3, 1>(p, tb, batch, ra, rb, cr, bcast, roll, st, amap, bmap); break;
-    case 13: launch_variant<2, 2, 256, 1, true, 4, 1>(p, tb, batch, ra, rb, cr, bcast, roll, st, amap, bmap); break;
-    case 14: launch_variant<2, 2, 256, 1, true, 3, 2>(p, tb, batch, ra, rb, cr, bcast, roll, st, amap, bmap); break;
-    case 15: launch_variant<2, 2, 256, 1, true, 4, 2>(p, tb, batch, ra, rb, cr, bcast, roll, st, amap, bmap); break;
-    case 16: launch_variant<2, 4, 256, 2, true, 5, 3>(p, tb, batch, ra, rb, cr, bcast, roll, st, amap, bmap); break;
-    default: launch_variant<2, 2, 128, 2, true>(p, tb, batch, ra, rb, cr, bcast, roll, st, amap, bmap); break;
-  }
+    with_bn(rows, [&](auto bn) { go(std::true_type(), bn, std::false_type()); });
 }
 
 template <class T>
 void launch_recon(const CPlan& p, const Tables& tb, int64_t batch, int64_t M, int64_t N,
                   const int8_t* cr, T* C, int accumulate, hipStream_t st) {
-  const int64_t work = p.tiles_m * p.tiles_n * (BM * p.bn / 8);
-  const int gx = (int)std::min<int64_t>((work + 255) / 256, 16384);
-  if (crt_mfma16() && recon_dot4()) {
-    const int gx16 = (int)std::min<int64_t>((2 * work + 255) / 256, 16384);
-    if (p.bn == 256)
-      hipLaunchKernelGGL((k_crt_recon16d<T, 256>), dim3(gx16, (unsigned)batch), dim3(256), 0, st,
-                         cr, C, M, N, p.tiles_m, p.tiles_n, accumulate, tb.r4, p.n, tb.rc);
-    else
-      hipLaunchKernelGGL((k_crt_recon16d<T, 128>), dim3(gx16, (unsigned)batch), dim3(256), 0, st,
-                         cr, C, M, N, p.tiles_m, p.tiles_n, accumulate, tb.r4, p.n, tb.rc);
-  } else if (crt_mfma16()) {
-    const int gx16 = (int)std::min<int64_t>((2 * work + 255) / 256, 16384);
-    if (p.bn == 256)
-      hipLaunchKernelGGL((k_crt_recon16<T, 256>), dim3(gx16, (unsigned)batch), dim3(256), 0, st,
-                         cr, C, M, N, p.tiles_m, p.tiles_n, accumulate, tb.rc);
-    else
-      hipLaunchKernelGGL((k_crt_recon16<T, 128>), dim3(gx16, (unsigned)batch), dim3(256), 0, st,
-                         cr, C, M, N, p.tiles_m, p.tiles_n, accumulate, tb.rc);
-  } else if (p.bn == 256)
-    hipLaunchKernelGGL((k_crt_recon<T, 256>), dim3(gx, (unsigned)batch), dim3(256), 0, st, cr, C,
-                       M, N, p.tiles_m, p.tiles_n, accumulate, tb.rc);
-  else
-    hipLaunchKernelGGL((k_crt_recon<T, 128>), dim3(gx, (unsigned)batch), dim3(256), 0, st, cr, C,
-                       M, N, p.tiles_m, p.tiles_n, accumulate, tb.rc);
+  const int64_t work = p.tiles_m * p.tiles_n * (BM * p.bn / 4);
+  const dim3 grid((unsigned)std::min<int64_t>((work + 255) / 256, 16384), (unsigned)batch);
+  with_bn(p.bn, [&](auto bn) {
+    with_bool(recon_dot4(), [&](auto dot4) {
+      hipLaunchKernelGGL((k_crt_recon16<T, decltype(bn)::value, decltype(dot4)::value>), grid,
+                         dim3(256), 0, st, cr, C, M, N, p.tiles_m, p.tiles_n, accumulate, tb.r4,
+                         p.n, tb.rc);
+    });
+  });
 }
 
 // A product may stop at its residues (run_crt_asym's cr_ext) when they have the layout the
 // opening kernel reads: 16x16 blocks in 256-column tiles, the dot4 reconstruction's tables.
-bool defer_ok(const CPlan& p) { return p.bn == 256 && crt_mfma16() && recon_dot4() && p.n > 0; }
+bool defer_ok(const CPlan& p) { return p.bn == 256 && recon_dot4() && p.n > 0; }
 
-// The plan of run_crt_asym's product, or n < 0 where it declines.
-CPlan asym_plan(int words, int64_t M, int64_t N, int64_t K) {
+// run_crt_asym's product: the one place that decides whether it applies.  rc: 0, or the code
+// run_crt_asym returns (-7: not applicable, the caller runs the generic form; -6: past the
+// exact epilogue rounding bound); p: its plan (nkb = 2K/64, a_nkb = K/64); defer: it may stop
+// at its residues.
+struct AsymPlan {
+  int rc;
+  bool defer;
   CPlan p;
-  p.n = -1;
-  if ((words != 1 && words != 2) || K % BK || !crt_mfma16() || 2 * K > (1 << 15)) return p;
-  return make_cplan(words, 3, M, N, K, 1, true);
+};
+AsymPlan asym_plan(int words, int64_t M, int64_t N, int64_t K) {
+  AsymPlan a = {};
+  if ((words != 1 && words != 2) || K % BK)
+    a.rc = -7;
+  else if (2 * K > (1 << 15))
+    a.rc = -6;
+  else {
+    a.p = make_cplan(words, 3, M, N, K, 1, true);
+    a.rc = a.p.n < 0 ? -6 : 0;
+  }
+  a.defer = a.rc == 0 && defer_ok(a.p);
+  return a;
 }
 
 template <class T>
@@ -1758,8 +1525,7 @@ int run_crt(int64_t batch, int64_t M, int64_t N, int64_t K, const T* A0, const T
             const int8_t* rb_pre, int mode, T* C, int accumulate, hipStream_t st,
             int64_t roll = 0) {
   constexpr int words = sizeof(T) / 8;
-  if (roll && (mode != 1 || K % BK || !crt_mfma16() || a_bstride == 0 || batch < 2 ||
-               roll % batch == 0))
+  if (roll && (mode != 1 || K % BK || a_bstride == 0 || batch < 2 || roll % batch == 0))
     return -7;  // not applicable: the caller runs the two-operand form
   const CPlan p = make_cplan(words, batch, M, N, K, mode, roll != 0);
   if (p.n < 0) return -6;
@@ -1784,11 +1550,10 @@ int run_crt(int64_t batch, int64_t M, int64_t N, int64_t K, const T* A0, const T
     launch_prep<T>(p, tb, false, batch, M, K, a_bstride, A0, A0, 0, ra, st, p.a_nkb);
   else
     launch_prep<T>(p, tb, false, a_bc ? 1 : batch, M, K, a_bstride, A0, A1, mode, ra, st);
-  launch_crt_gemm(p, tb, batch, ra, rb, cr, (a_bc ? 1 : 0) | (b_bc ? 2 : 0),
-                  (int)(((roll % batch) + batch) % batch), st);
+  p.var->launch(p, tb, {batch, ra, rb, cr, (a_bc ? 1 : 0) | (b_bc ? 2 : 0),
+                        (int)(((roll % batch) + batch) % batch), 0, 0}, st);
   launch_recon<T>(p, tb, batch, M, N, cr, C, accumulate, st);
-  const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? -100 - (int)e : 0;
+  return launch_status();
 }
 
 // The three parties' local products of a replicated matrix product in the asymmetric
@@ -1814,10 +1579,9 @@ int run_crt_asym(int64_t M, int64_t N, int64_t K, const T* S0, const T* S1, cons
                  const T* T1, int rolled, T* C, hipStream_t st, const ShareSrc* xs = nullptr,
                  const ShareSrc* ys = nullptr, int8_t* cr_ext = nullptr) {
   constexpr int words = sizeof(T) / 8;
-  if (K % BK || !crt_mfma16()) return -7;
-  if (2 * K > (1 << 15)) return -6;  // exact epilogue rounding bound
-  const CPlan p = make_cplan(words, 3, M, N, K, 1, true);  // nkb = 2K/64, a_nkb = K/64
-  if (p.n < 0) return -6;
+  const AsymPlan ap = asym_plan(words, M, N, K);
+  if (ap.rc) return ap.rc;
+  const CPlan& p = ap.p;
   const Tables& tb = tables_for(words, p.n);
   const int64_t sa = M * K, sb = K * N;
   const T* a[3];
@@ -1853,14 +1617,9 @@ int run_crt_asym(int64_t M, int64_t N, int64_t K, const T* S0, const T* S1, cons
     amap = pmap(0, 1, 2, 3, 4);
     bmap = pmap(0, 1, 2, 3, 4);
   }
-  static const bool asum = [] {  // MOOSEX_CRT_ASUM=0: the sum inside the prep (mode 2)
-    const char* e = std::getenv("MOOSEX_CRT_ASUM");
-    return !(e && e[0] == '0');
-  }();
-  static const bool dual = [] {  // MOOSEX_CRT_DUAL=0: separate sum images
-    const char* e = std::getenv("MOOSEX_CRT_DUAL");
-    return !(e && e[0] == '0');
-  }();
+  // MOOSEX_CRT_ASUM=0: the sum inside the prep (mode 2); MOOSEX_CRT_DUAL=0: separate sum images
+  static const bool asum = env_flag("MOOSEX_CRT_ASUM", true);
+  static const bool dual = env_flag("MOOSEX_CRT_DUAL", true);
   // rolled: the sums ride on the share images' threads (dual) -- no separate sum pass
   const bool duals = rolled && dual;
   if (xs || ys) {
@@ -1872,10 +1631,7 @@ int run_crt_asym(int64_t M, int64_t N, int64_t K, const T* S0, const T* S1, cons
   // zero bytes, so the side keeps one strip right below its images instead (k_crt_gemm16's
   // entry kZeroStrip) -- the other images close up, the maps follow, and the GEMM streams
   // the strip from L2 where it fetched a whole image.  All five products still run.
-  static const bool zstrip = [] {  // MOOSEX_ZERO_STRIP=0: the full zero image
-    const char* e = std::getenv("MOOSEX_ZERO_STRIP");
-    return !(e && e[0] == '0');
-  }();
+  static const bool zstrip = env_flag("MOOSEX_ZERO_STRIP", true);  // =0: the full zero image
   int aph[4], bph[4], aat[4] = {0, 1, 2, 3}, bat[4] = {0, 1, 2, 3};
   int64_t a_strip = 0, b_strip = 0;
   auto plan_src = [&](bool is_b, const ShareSrc& s, int (&ph)[4], int (&at)[4], int& n, int& map,
@@ -1892,7 +1648,7 @@ int run_crt_asym(int64_t M, int64_t N, int64_t K, const T* S0, const T* S1, cons
   if (ys) plan_src(true, *ys, bph, bat, nb, bmap, b_strip);
   const int64_t ra_bytes = na * a_entry, rb_bytes = nb * b_entry;
   const int64_t sum_bytes = asum && !duals ? round_up(sa * (int64_t)sizeof(T), 256) : 0;
-  if (cr_ext && !defer_ok(p)) return -7;
+  if (cr_ext && !ap.defer) return -7;
   const int64_t cr_ws = cr_ext ? 0 : p.cr_bytes;
   int8_t* ws = (int8_t*)workspace(a_strip + ra_bytes + cr_ws + b_strip + rb_bytes + sum_bytes, st);
   if (!ws) return -4;
@@ -1950,10 +1706,22 @@ int run_crt_asym(int64_t M, int64_t N, int64_t K, const T* S0, const T* S1, cons
     launch_prep<T>(p, tb, true, sb_.n, N, K, 0, nullptr, nullptr, 0, rb, st, kn, kn, sb_);
     launch_prep<T>(p, tb, false, sa_.n, M, K, 0, nullptr, nullptr, 0, ra, st, kn, kn, sa_);
   }
-  launch_crt_gemm(p, tb, 3, ra, rb, cr, 0, 0, st, amap, bmap);
+  p.var->launch(p, tb, {3, ra, rb, cr, 0, 0, amap, bmap}, st);
   if (!cr_ext) launch_recon<T>(p, tb, 3, M, N, cr, C, 0, st);
-  const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? -100 - (int)e : 0;
+  return launch_status();
+}
+
+// run_crt over the ring of ``words`` on the entry points' untyped operands
+int run_crt_words(int words, int64_t batch, int64_t M, int64_t N, int64_t K, const void* A0,
+                  const void* A1, int64_t a_bstride, const void* B0, const void* B1,
+                  int64_t b_bstride, const void* rb, int mode, void* C, int accumulate,
+                  void* stream, int64_t roll = 0) {
+  return with_ring(words, [&](auto t) {
+    using T = decltype(t);
+    return run_crt<T>(batch, M, N, K, (const T*)A0, (const T*)A1, a_bstride, (const T*)B0,
+                      (const T*)B1, b_bstride, (const int8_t*)rb, mode, (T*)C, accumulate,
+                      (hipStream_t)stream, roll);
+  });
 }
 
 }  // namespace
@@ -1970,16 +1738,12 @@ int mx_gemm_asym(int words, int64_t M, int64_t N, int64_t K, const void* S0, con
                  void* residues) {
   if (M == 0 || N == 0) return residues ? -7 : 0;
   if (!rolled && (!S1 || !T1)) return -2;
-  hipStream_t st = (hipStream_t)stream;
-  if (words == 1)
-    return run_crt_asym<u64>(M, N, K, (const u64*)S0, (const u64*)S1, (const u64*)T0,
-                             (const u64*)T1, rolled, (u64*)C, st, nullptr, nullptr,
-                             (int8_t*)residues);
-  if (words == 2)
-    return run_crt_asym<u128>(M, N, K, (const u128*)S0, (const u128*)S1, (const u128*)T0,
-                              (const u128*)T1, rolled, (u128*)C, st, nullptr, nullptr,
-                              (int8_t*)residues);
-  return -2;
+  return with_ring(words, [&](auto t) {
+    using T = decltype(t);
+    return run_crt_asym<T>(M, N, K, (const T*)S0, (const T*)S1, (const T*)T0, (const T*)T1,
+                           rolled, (T*)C, (hipStream_t)stream, nullptr, nullptr,
+                           (int8_t*)residues);
+  });
 }
 
 // Bytes of the residue buffer of a deferred M x N x K product (mx_gemm_asym's ``residues``);
@@ -1987,24 +1751,21 @@ int mx_gemm_asym(int words, int64_t M, int64_t N, int64_t K, const void* S0, con
 // sizes run_crt_asym declines).
 int64_t mx_crt_defer_bytes(int words, int64_t M, int64_t N, int64_t K) {
   if (M <= 0 || N <= 0) return -7;
-  const CPlan p = asym_plan(words, M, N, K);
-  return p.n > 0 && defer_ok(p) ? p.cr_bytes : -7;
+  const AsymPlan a = asym_plan(words, M, N, K);
+  return a.defer ? a.p.cr_bytes : -7;
 }
 
 // The reconstruction a deferred product skipped: C[p] = z_p from its residues, bitwise the C
 // of the same call without ``residues``.
 int mx_crt_recon(int words, int64_t M, int64_t N, int64_t K, const void* residues, void* C,
                  void* stream) {
-  const CPlan p = asym_plan(words, M, N, K);
-  if (p.n <= 0 || !defer_ok(p)) return -7;
-  const Tables& tb = tables_for(words, p.n);
-  hipStream_t st = (hipStream_t)stream;
-  if (words == 1)
-    launch_recon<u64>(p, tb, 3, M, N, (const int8_t*)residues, (u64*)C, 0, st);
-  else
-    launch_recon<u128>(p, tb, 3, M, N, (const int8_t*)residues, (u128*)C, 0, st);
-  const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? -100 - (int)e : 0;
+  const AsymPlan a = asym_plan(words, M, N, K);
+  if (!a.defer) return -7;
+  return with_ring(words, [&](auto t) {
+    launch_recon<decltype(t)>(a.p, tables_for(words, a.p.n), 3, M, N, (const int8_t*)residues,
+                              (decltype(t)*)C, 0, (hipStream_t)stream);
+    return launch_status();
+  });
 }
 
 // mx_mul_trunc3_open's crt form (moosex.h): crt = {residues, M, N, K} of a deferred product,
@@ -2013,21 +1774,18 @@ int mxh_crt_recon_open(int words, const int64_t* crt, double* out, int64_t n,
                        const uint32_t* slots, int m, const uint64_t* nn, int frac, void* stream) {
   const int64_t M = crt[1], N = crt[2], K = crt[3];
   if (M <= 0 || N <= 0 || n != M * N || !crt[0]) return -3;
-  const CPlan p = asym_plan(words, M, N, K);
-  if (p.n <= 0 || !defer_ok(p)) return -7;
-  const Tables& tb = tables_for(words, p.n);
+  const AsymPlan a = asym_plan(words, M, N, K);
+  if (!a.defer) return -7;
   const uint32_t* ptrs[3];
   for (int i = 0; i < 3; ++i) ptrs[i] = slots + MX_KEY_SLOT_WORDS * i;
   const mxd::KeySrc keys = mxd::keysrc_slots(ptrs, 3);
   const int8_t* cr = (const int8_t*)(intptr_t)crt[0];
   const double scale = std::ldexp(1.0, -frac);
-  hipStream_t st = (hipStream_t)stream;
-  if (words == 1)
-    launch_recon_open<u64>(p, tb, M, N, cr, out, scale, keys, nn[0], nn[1], m, st);
-  else
-    launch_recon_open<u128>(p, tb, M, N, cr, out, scale, keys, nn[0], nn[1], m, st);
-  const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? -100 - (int)e : 0;
+  return with_ring(words, [&](auto t) {
+    launch_recon_open<decltype(t)>(a.p, tables_for(words, a.p.n), M, N, cr, out, scale, keys,
+                                   nn[0], nn[1], m, (hipStream_t)stream);
+    return launch_status();
+  });
 }
 
 // mx_gemm_asym, rolled, over Z_2^128 with one or both operands given as a share source
@@ -2129,15 +1887,8 @@ int mx_crt_combine(int words, int n, int side, int i, int64_t count, const int32
 int mxh_gemm_crt(int words, int64_t batch, int64_t M, int64_t N, int64_t K, const void* A0,
                  const void* A1, const void* B0, const void* B1, int mode, void* C,
                  int accumulate, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (words == 1)
-    return run_crt<u64>(batch, M, N, K, (const u64*)A0, (const u64*)A1, M * K, (const u64*)B0,
-                        (const u64*)B1, K * N, nullptr, mode, (u64*)C, accumulate, st);
-  if (words == 2)
-    return run_crt<u128>(batch, M, N, K, (const u128*)A0, (const u128*)A1, M * K,
-                         (const u128*)B0, (const u128*)B1, K * N, nullptr, mode, (u128*)C,
-                         accumulate, st);
-  return -2;
+  return run_crt_words(words, batch, M, N, K, A0, A1, M * K, B0, B1, K * N, nullptr, mode, C,
+                       accumulate, stream);
 }
 
 // Batch strides given (elements; 0 broadcasts one operand over the batch): the operands of a
@@ -2146,16 +1897,8 @@ int mxh_gemm_crt_strided(int words, int64_t batch, int64_t M, int64_t N, int64_t
                          const void* A0, const void* A1, int64_t a_bstride, const void* B0,
                          const void* B1, int64_t b_bstride, int mode, void* C, int accumulate,
                          void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (words == 1)
-    return run_crt<u64>(batch, M, N, K, (const u64*)A0, (const u64*)A1, a_bstride,
-                        (const u64*)B0, (const u64*)B1, b_bstride, nullptr, mode, (u64*)C,
-                        accumulate, st);
-  if (words == 2)
-    return run_crt<u128>(batch, M, N, K, (const u128*)A0, (const u128*)A1, a_bstride,
-                         (const u128*)B0, (const u128*)B1, b_bstride, nullptr, mode, (u128*)C,
-                         accumulate, st);
-  return -2;
+  return run_crt_words(words, batch, M, N, K, A0, A1, a_bstride, B0, B1, b_bstride, nullptr,
+                       mode, C, accumulate, stream);
 }
 
 // RSS pair form of the mode-1 product: A1 is A0 rolled by ``roll`` batch entries
@@ -2165,16 +1908,8 @@ int mxh_gemm_crt_strided(int words, int64_t batch, int64_t M, int64_t N, int64_t
 int mxh_crt_roll(int words, int64_t batch, int64_t M, int64_t N, int64_t K, const void* A0,
                  int64_t a_bstride, int64_t roll, const void* B0, const void* B1, const void* rb,
                  void* C, int accumulate, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t bs = K * N;
-  if (words == 1)
-    return run_crt<u64>(batch, M, N, K, (const u64*)A0, nullptr, a_bstride, (const u64*)B0,
-                        (const u64*)B1, bs, (const int8_t*)rb, 1, (u64*)C, accumulate, st, roll);
-  if (words == 2)
-    return run_crt<u128>(batch, M, N, K, (const u128*)A0, nullptr, a_bstride, (const u128*)B0,
-                         (const u128*)B1, bs, (const int8_t*)rb, 1, (u128*)C, accumulate, st,
-                         roll);
-  return -2;
+  return run_crt_words(words, batch, M, N, K, A0, nullptr, a_bstride, B0, B1, K * N, rb, 1, C,
+                       accumulate, stream, roll);
 }
 
 // Prepared-B variant (row-chunked dot pipeline): B' residues built once into a caller buffer.
@@ -2188,31 +1923,19 @@ int mxh_crt_prep_b(int words, int64_t batch, int64_t K, int64_t N, const void* B
                    const void* B1, int mode, void* rb, void* stream) {
   const CPlan p = make_cplan(words, batch, BM, N, K, mode);
   if (p.n < 0) return -6;
-  const Tables& tb = tables_for(words, p.n);
-  hipStream_t st = (hipStream_t)stream;
-  if (words == 1)
-    launch_prep<u64>(p, tb, true, batch, N, K, K * N, (const u64*)B0, (const u64*)B1, mode,
-                     (int8_t*)rb, st);
-  else if (words == 2)
-    launch_prep<u128>(p, tb, true, batch, N, K, K * N, (const u128*)B0, (const u128*)B1, mode,
-                      (int8_t*)rb, st);
-  else
-    return -2;
-  const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? -100 - (int)e : 0;
+  return with_ring(words, [&](auto t) {
+    using T = decltype(t);
+    launch_prep<T>(p, tables_for(words, p.n), true, batch, N, K, K * N, (const T*)B0,
+                   (const T*)B1, mode, (int8_t*)rb, (hipStream_t)stream);
+    return launch_status();
+  });
 }
 
 int mxh_crt_with_b(int words, int64_t batch, int64_t M, int64_t N, int64_t K, const void* A0,
                    const void* A1, int64_t a_bstride, int mode, const void* rb, void* C,
                    int accumulate, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (words == 1)
-    return run_crt<u64>(batch, M, N, K, (const u64*)A0, (const u64*)A1, a_bstride, nullptr,
-                        nullptr, 0, (const int8_t*)rb, mode, (u64*)C, accumulate, st);
-  if (words == 2)
-    return run_crt<u128>(batch, M, N, K, (const u128*)A0, (const u128*)A1, a_bstride, nullptr,
-                         nullptr, 0, (const int8_t*)rb, mode, (u128*)C, accumulate, st);
-  return -2;
+  return run_crt_words(words, batch, M, N, K, A0, A1, a_bstride, nullptr, nullptr, 0, rb, mode,
+                       C, accumulate, stream);
 }
 
 }  // extern "C"

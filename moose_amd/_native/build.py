@@ -36,8 +36,9 @@ def _headers_mtime():
 
 # Per-source extra flags.  gemm_crt.hip: let the MFMA accumulators live in VGPRs and the
 # allocator use the AGPR half of the unified register file for the rest, so the 4-wave
-# 128x128 wave-tile variants (256 accumulators per lane, one wave per SIMD) compile without
-# scratch spills (default form: 275 spilled VGPRs).  The 8-wave variants' code is unchanged.
+# 128x128 wave-tile variants (MOOSEX_CRT_KERNEL 12 and 14: 256 accumulators per lane, one wave
+# per SIMD) compile without scratch spills (default form: 275 spilled VGPRs).  The 8-wave
+# variants' code is unchanged.
 _HIP_EXTRA = {"gemm_crt.hip": ("-mllvm", "-amdgpu-mfma-vgpr-form=1")}
 
 
