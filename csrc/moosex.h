@@ -278,6 +278,21 @@ int mx_crt_combine(int words, int n, int side, int i, int64_t count, const int32
 // Fused stacked-session protocols (rss_fused.h).  s0/out0/out1 are [3, n] slot
 // vectors (party p holds out0[p] = z_p and out1[p] = z_{p+1}).
 // trunc_pr3 nonces: r0, r1, r_top, r_msb, z0, z2 (dealer keys k0, k2).
+//
+// What TruncPr computes.  Over Z_2^w (w = 64 * words), for -2^(w-2) <= x < 2^(w-2) and the
+// opening mask r = PRF(k0, r0) + PRF(k2, r1) (mod 2^w), the new sharing reveals to
+//   (x >> m) + [(x mod 2^m) + (r mod 2^m) >= 2^m]   (mod 2^w; >> arithmetic, i.e. floor)
+// with slots z0 = PRF(k0, z0), z2 = PRF(k2, z2) and z1 the rest.  The shift range of the
+// stacked entries -- mx_trunc_pr3, _k, _ko, _kmo, mx_mul_trunc3_kv, mxh_mul_trunc3_kv2 and
+// mxh_wsum_trunc3 -- is 0 <= m <= w - 2 (m = 0: a fresh sharing of x); any other m returns
+// -3 and nothing runs: the offset 2^(w-2) >> m of the protocol is no integer past w - 2.
+// The opening entry (mx_mul_trunc3_open) and the per-party rounds (mx_trunc_party_r*,
+// mx_dot_tail_r*, mx_jobs_r*) take 1 <= m <= 63, -3 otherwise -- the dealer's msb share
+// travels as a u64 -- and the result is the one above only while m <= w - 2 as well.
+// (words other than 1 and 2 are each entry's own -2)
+static inline int mx_trunc_shift_ok(int words, int m) {
+  return (words != 1 && words != 2) || (m >= 0 && m <= 64 * words - 2);
+}
 int mx_trunc_pr3(int dev, int words, const void* s0, void* out0, void* out1, int64_t n, int m,
                  const uint8_t* k0, const uint8_t* k2, const uint64_t* nonces, void* stream);
 // share3: owner party j; slot_j = PRF(k_j, n1) (k_j: held by P_j and P_{j+2}), slot_{j+1} =

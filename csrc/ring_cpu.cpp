@@ -728,6 +728,7 @@ int mx_mul_trunc3_kv(int dev, int words, const void* x0, const void* x1, const v
                      const void* y1, void* out0, void* out1, int64_t n, int64_t ostride,
                      const uint32_t* slots, uint64_t nmul, int m, const uint64_t* nonces,
                      const int64_t* views, void* stream) {
+  if (!mx_trunc_shift_ok(words, m)) return -3;  // moosex.h: 0 <= m <= w - 2
   if (dev)
     return mxh_mul_trunc3_kv(words, x0, x1, y0, y1, out0, out1, n, ostride, slots, nmul, m,
                              nonces, views, stream);

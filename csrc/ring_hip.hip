@@ -3246,6 +3246,7 @@ int mxh_mul_trunc3_kv2(int words, const void* const* x0, const void* const* x1,
     for (int i = 0; i < 2; ++i) {
       const int64_t blocks = (n[i] + P - 1) / P;
       if (n[i] <= 0 || blocks > 8192) return -1;
+      if (!mx_trunc_shift_ok(words, m[i])) return -3;  // moosex.h: 0 <= m <= w - 2
       g = std::max<int64_t>(g, (blocks + EPB - 1) / EPB);
       a.x0[i] = (const T*)x0[i];
       a.x1[i] = (const T*)x1[i];

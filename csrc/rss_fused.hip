@@ -392,6 +392,7 @@ int mxh_wsum_trunc3(int words, const void* S, int64_t ps, int64_t rs, int R,
                                const uint64_t* cadd, void* stream) {
   const int64_t nblk = words == 1 ? (n + 1) / 2 : n;
   if (n <= 0 || R < 1 || nblk > 8192 || (words != 1 && words != 2)) return -1;
+  if (!mx_trunc_shift_ok(words, m)) return -3;  // moosex.h: 0 <= m <= w - 2
   const uint32_t* ptrs[2] = {k0, k2};
   const mxd::KeySrc keys = mxd::keysrc_slots(ptrs, 2);
   const unsigned g = (unsigned)((nblk + 41) / 42);

@@ -176,6 +176,7 @@ extern "C" {
 
 int mx_trunc_pr3(int dev, int words, const void* s0, void* out0, void* out1, int64_t n, int m,
                  const uint8_t* k0, const uint8_t* k2, const uint64_t* nonces, void* stream) {
+  if (!mx_trunc_shift_ok(words, m)) return -3;  // moosex.h: 0 <= m <= w - 2
   if (dev) return mxh_trunc_pr3(words, s0, out0, out1, n, m, k0, k2, nonces, stream);
   if (words == 1)
     return trunc3_host<uint64_t>((const uint64_t*)s0, (uint64_t*)out0, (uint64_t*)out1, n, m, k0,
@@ -209,6 +210,7 @@ int mx_share3(int dev, int kind, int words, const void* x, void* out0, void* out
 int mx_trunc_pr3_k(int dev, int words, const void* s0, void* out0, void* out1, int64_t n, int m,
                    const uint32_t* slot_k0, const uint32_t* slot_k2, const uint64_t* nonces,
                    void* stream) {
+  if (!mx_trunc_shift_ok(words, m)) return -3;  // moosex.h: 0 <= m <= w - 2
   if (dev)
     return mxh_trunc_pr3_k(words, s0, out0, out1, n, m, slot_k0, slot_k2, nonces, stream);
   return mx_trunc_pr3(0, words, s0, out0, out1, n, m, (const uint8_t*)slot_k0,
@@ -220,6 +222,7 @@ int mx_trunc_pr3_k(int dev, int words, const void* s0, void* out0, void* out1, i
 int mx_trunc_pr3_ko(int dev, int words, const void* s0, void* out0, void* out1, int64_t n,
                     int m, const uint32_t* slot_k0, const uint32_t* slot_k2,
                     const uint64_t* nonces, int64_t ostride, void* stream) {
+  if (!mx_trunc_shift_ok(words, m)) return -3;  // moosex.h: 0 <= m <= w - 2
   if (dev)
     return mxh_trunc_pr3_ko(words, s0, out0, out1, n, m, slot_k0, slot_k2, nonces, ostride,
                             stream);
@@ -240,6 +243,7 @@ int mx_trunc_pr3_ko(int dev, int words, const void* s0, void* out0, void* out1, 
 int mx_trunc_pr3_kmo(int dev, int words, const void* s0, void* out0, void* out1, int64_t n,
                      int m, const uint32_t* slot_k0, const uint32_t* slot_k2,
                      const uint64_t* nonces, int64_t ostride, const uint64_t* cm, void* stream) {
+  if (!mx_trunc_shift_ok(words, m)) return -3;  // moosex.h: 0 <= m <= w - 2
   if (dev)
     return mxh_trunc_pr3_kmo(words, s0, out0, out1, n, m, slot_k0, slot_k2, nonces, ostride, cm,
                              stream);

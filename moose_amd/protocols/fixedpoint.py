@@ -956,6 +956,7 @@ def _poly_tail(sess, Pt: RepTensor, coeffs, f: int, shift: int, integ: int) -> R
     weights = [int(round(c * (1 << f))) for c in coeffs[1:]]
     c0 = coeffs[0] / (1 << shift)
     fused = getattr(sess, "p_wsum_trunc_add", None)
+    rep.check_shift(bits, f + shift)
     if fused is not None and getattr(sess, "fused", False):
         r = fused(Pt.plc, Pt.s0, weights, f + shift, int(round(c0 * (1 << f))))
         if r is not None:
@@ -968,6 +969,7 @@ def _poly_tail(sess, Pt: RepTensor, coeffs, f: int, shift: int, integ: int) -> R
 def _tail_trunc(sess, plc, v, bits, m) -> RepTensor:
     """Zero share + reshare + TruncPr(m) of local 3-out-of-3 additive products ``v`` (a
     party vector): the dot's tail (parallel/party.py); 2 rounds."""
+    rep.check_shift(bits, m)
     nonces = tuple(sess.nonce(plc) for _ in range(7))
     s0, s1 = sess.party_dot_trunc(plc, v, m, nonces)
     return RepTensor(plc, bits, "arith", s0, s1)

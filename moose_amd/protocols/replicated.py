@@ -230,6 +230,7 @@ class StackedTail(RepTensor):
 
     def __init__(self, sess, plc, bits, v, m, nonces):
         self._sess, self.v, self.m, self._nonces = sess, v, m, nonces
+        check_shift(bits, m)
         lazy_v = isinstance(v.v, R.CrtProduct) and v.v.pending()  # its data: not yet
         self._stream = v.v.stream if lazy_v else R._stream_of(v.v.data)
         self.device = v.v.device
@@ -682,10 +683,20 @@ def mul(sess, x: RepTensor, y: RepTensor) -> RepTensor:
         return _reshare(sess, x.plc, z, x.bits, kind)
 
 
+def check_shift(bits: int, m: int):
+    """TruncPr by m bits over Z_2^w is defined for 0 <= m <= w - 2 (csrc/moosex.h): past it the
+    protocol's offset 2^(w-2) >> m is no integer.  The stacked kernels refuse such a shift; the
+    opening and per-party ones accept up to 63 over either ring, so every protocol entry that
+    truncates checks it here, before a nonce is drawn."""
+    if not 0 <= m <= bits - 2:
+        raise ValueError(f"TruncPr over Z_2^{bits}: shift {m} outside 0..{bits - 2}")
+
+
 def mul_public_trunc(sess, x: RepTensor, c, m: int, value: int = None) -> RepTensor:
     """trunc_pr(mul_public(x, c), m); for a public scalar ring constant whose integer
     ``value`` the caller knows, on a fused stacked session, the multiplication runs inside the
     TruncPr kernel (same shares); on a per-party session inside the batched tail."""
+    check_shift(x.bits, m)
     if (m and 0 < m <= 63 and value is not None and -(1 << 62) < value < (1 << 62)
             and jobs_ok(sess, x)):
         return mul_public_trunc_jobs(sess, x, value, m)
@@ -702,6 +713,7 @@ def mul_public_trunc(sess, x: RepTensor, c, m: int, value: int = None) -> RepTen
 def mul_trunc(sess, x: RepTensor, y: RepTensor, m: int, out=None) -> RepTensor:
     """trunc_pr(mul(x, y), m): one fused kernel on a stacked device session for small
     operands (same shares as the two steps), the two protocol steps otherwise."""
+    check_shift(x.bits, m)
     f = getattr(sess, "p_mul_trunc", None)
     if f is not None and m and x.kind == "arith" and getattr(sess, "fused", False):
         r = f(x.plc, x.s0, x.s1, y.s0, y.s1, m, out=out)
@@ -779,6 +791,7 @@ def tail_job(sess, plc, bits, m, nonces, like: PV, make, out=None, L=None) -> Re
     """One value through the per-party batched tail (csrc/rss_jobs.hip): ``make(o0, o1)``
     builds its ring.MulJob (one row of ``like``'s size, or rows of length ``L``) writing
     the new shares to o0 / o1.  Non-members get placeholders."""
+    check_shift(bits, m)
     from moose_amd.parallel.spmd import Remote
 
     if sess.party_index(plc) is None:
@@ -819,6 +832,8 @@ def mul_trunc_many(sess, jobs):
     """Independent fixed-point products [(x, y, m, out)] of one placement: two of them in ONE
     launch on a stacked device session (p_mul_trunc2), else one by one -- the same nonces in
     the same order either way, so the same shares."""
+    for x, _, m, _ in jobs:
+        check_shift(x.bits, m)
     f = getattr(sess, "p_mul_trunc2", None)
     if (f is not None and len(jobs) == 2 and getattr(sess, "fused", False)
             and all(x.kind == "arith" and y.kind == "arith" and m for x, y, m, _ in jobs)):
@@ -941,6 +956,7 @@ def dot_trunc(sess, x: RepTensor, y: RepTensor, m: int, nbatch: int = 0) -> RepT
     its own protocol instance (own nonces): a valid sharing of the same product, and two
     sessions that chunk alike produce bitwise-equal shares.  The y operand is limb-split
     once (p_prepare_cross) and x row blocks are read in place."""
+    check_shift(x.bits, m)
     chunks = getattr(sess, "pipeline_chunks", 1)
     nchunk = 1
     if nbatch:
@@ -1057,6 +1073,7 @@ def dwconv_trunc(sess, x: RepTensor, w: RepTensor, m: int, geom: dict) -> RepTen
     :func:`dot_trunc` selects for an unchunked product, on the same nonces in the same order:
     the lazy one-kernel tail of a fused stacked device session, the per-party tail (reshare
     folded into TruncPr) on seven nonces, else zero share + reshare + TruncPr."""
+    check_shift(x.bits, m)
     tail = getattr(sess, "p_zs_trunc", None)
     if (tail is not None and m and x.kind == "arith" and getattr(sess, "fused", False)
             and getattr(sess, "device", None) is not None and sess.device.type == "cuda"
@@ -1096,6 +1113,7 @@ def pwl_trunc(sess, x: RepTensor, T, DA, DB, AK, m: int, width=None) -> RepTenso
     through less_than_zero_arith as one protocol instance; the local products come from one
     kernel (session ``p_pwl_cross``); the tail is :func:`dwconv_trunc`'s selection, on the same
     nonces in the same order.  ``width``: |x - T[j]| < 2^(width - 1) is known."""
+    check_shift(x.bits, m)
     plc, bits = x.plc, x.bits
     with span("rep.pwl_flags"):
         parts = [local(sess, sub_public(sess, x, R.fill((), int(t), bits, sess.device)),
@@ -1169,6 +1187,7 @@ def trunc_pr(sess, x: RepTensor, m: int, out=None) -> RepTensor:
 
     ``out`` (fused stacked sessions only): (s0, s1) party-vector views written in place.
     """
+    check_shift(x.bits, m)
     if m == 0:
         return x
     with span("rep.trunc_pr"):
@@ -1446,6 +1465,7 @@ def mul_add_trunc(sess, a: RepTensor, b: RepTensor, c: RepTensor, m: int) -> Rep
     rounds instead of reshare + TruncPr's 2 after it), and a reveal merges the tail's
     second round with the reveal (parallel/party.py MulAddTail) -- the receiver only sums
     shares of the truncated value."""
+    check_shift(a.bits, m)
     f = getattr(sess, "p_mul_add_deferred", None)
     if f is not None and 0 < m <= 63:
         r = f(a.plc, a, b, c, post_shift=m)

@@ -32,7 +32,9 @@ def _sizes(bits):
 
 
 def _ms(bits):
-    return [1, 23, 63] + ([40] if bits == 128 else [])
+    """Shifts inside TruncPr's range 1 .. bits - 2 (csrc/moosex.h): mx_mul_trunc3_kv and
+    mx_trunc_pr3_k, the other side of the comparison, refuse a larger one."""
+    return [1, 23, 63, 40] if bits == 128 else [1, 23, 62]
 
 
 def _stack(n, bits, seed):
