@@ -1030,6 +1030,18 @@ int crt_mode() {
   return g_crt_mode;
 }
 
+// K = 0: the product is the zero matrix.  The limb kernels stage k-step 0 (and clamp the
+// next one to step -1) before they look at the step count, and the prep grids would be
+// empty, so an empty K never reaches a launch: C is zero-filled, or kept under accumulate.
+int empty_k_product(int words, int64_t batch, int64_t M, int64_t N, void* C, int accumulate,
+                    void* stream) {
+  if (words != 1 && words != 2) return -2;
+  if (accumulate || batch * M * N == 0) return 0;
+  const hipError_t e =
+      hipMemsetAsync(C, 0, (size_t)(batch * M * N) * 8 * words, (hipStream_t)stream);
+  return e != hipSuccess ? -100 - (int)e : 0;
+}
+
 bool use_crt(int64_t M, int64_t N, int64_t K, int mode) {
   const int64_t kp = mode ? 2 * K : K;
   const int m = crt_mode();
@@ -1054,6 +1066,7 @@ int64_t mx_gemm_workspace_bytes(int words, int64_t batch, int64_t M, int64_t N, 
 int mx_gemm_ws(int words, int64_t batch, int64_t M, int64_t N, int64_t K, const void* A0,
                const void* A1, const void* B0, const void* B1, int mode, void* C,
                int accumulate, void* workspace, int64_t ws_bytes, void* stream) {
+  if (K == 0) return empty_k_product(words, batch, M, N, C, accumulate, stream);
   hipStream_t st = (hipStream_t)stream;
   if (words == 1)
     return run<u64>(batch, M, N, K, (const u64*)A0, (const u64*)A1, (const u64*)B0,
@@ -1077,6 +1090,7 @@ int64_t mx_gemm_b_bytes(int words, int64_t batch, int64_t N, int64_t K, int mode
 
 int mx_gemm_prep_b(int words, int64_t batch, int64_t K, int64_t N, const void* B0,
                    const void* B1, int mode, void* lb, void* stream) {
+  if (K == 0) return 0;  // no k-step to prepare; the products answer K = 0 themselves
   if (use_crt(256, N, K, mode)) return mxh_crt_prep_b(words, batch, K, N, B0, B1, mode, lb, stream);
   if (K > max_k_chunk(words, mode)) return -6;
   Plan p = make_plan(words, batch, 64, N, K, mode);
@@ -1095,6 +1109,7 @@ int mx_gemm_prep_b(int words, int64_t batch, int64_t K, int64_t N, const void* B
 int mx_gemm_with_b(int words, int64_t batch, int64_t M, int64_t N, int64_t K, const void* A0,
                    const void* A1, int64_t a_bstride, int mode, const void* lb, void* C,
                    int accumulate, void* stream) {
+  if (K == 0) return empty_k_product(words, batch, M, N, C, accumulate, stream);
   if (use_crt(256, N, K, mode))  // the prepared B' holds residues (same test as prep_b)
     return mxh_crt_with_b(words, batch, M, N, K, A0, A1, a_bstride, mode, lb, C, accumulate,
                           stream);
@@ -1127,6 +1142,7 @@ int mx_gemm_roll(int words, int64_t batch, int64_t M, int64_t N, int64_t K, cons
                  int64_t a_bstride, int64_t roll, const void* B0, const void* B1, const void* lb,
                  void* C, int accumulate, void* stream) {
   if (M == 0 || N == 0 || batch == 0) return 0;
+  if (K == 0) return empty_k_product(words, batch, M, N, C, accumulate, stream);
   if ((words != 1 && words != 2) || !use_crt(lb ? 256 : M, N, K, 1)) return -7;
   return mxh_crt_roll(words, batch, M, N, K, A0, a_bstride, roll, B0, B1, lb, C, accumulate,
                       stream);
@@ -1138,6 +1154,7 @@ int mx_gemm_strided(int words, int64_t batch, int64_t M, int64_t N, int64_t K, c
                     int64_t b_bstride, int mode, void* C, int accumulate, void* stream) {
   if (M == 0 || N == 0 || batch == 0) return 0;
   if (words != 1 && words != 2) return -2;
+  if (K == 0) return empty_k_product(words, batch, M, N, C, accumulate, stream);
   if (use_crt(M, N, K, mode))
     return mxh_gemm_crt_strided(words, batch, M, N, K, A0, A1, a_bstride, B0, B1, b_bstride,
                                 mode, C, accumulate, stream);
@@ -1166,6 +1183,7 @@ int mx_gemm_strided(int words, int64_t batch, int64_t M, int64_t N, int64_t K, c
 int mxh_gemm_mfma(int words, int64_t batch, int64_t M, int64_t N, int64_t K, const void* A0,
                   const void* A1, const void* B0, const void* B1, int mode, void* C,
                   int accumulate, void* stream) {
+  if (K == 0) return empty_k_product(words, batch, M, N, C, accumulate, stream);
   if (use_crt(M, N, K, mode))
     return mxh_gemm_crt(words, batch, M, N, K, A0, A1, B0, B1, mode, C, accumulate, stream);
   if (K > max_k_chunk(words, mode)) return -6;  // caller splits long K
