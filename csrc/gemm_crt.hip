@@ -48,14 +48,11 @@
 #include <mutex>
 #include <type_traits>
 
+#include "gemm_ws.h"
 #include "hip_attr.h"
 #include "moosex.h"
 #include "prf_dev.h"
 #include "rss_fused.h"
-
-void mx_ws_note(int dev, int64_t want, bool ok);  // gemm_mfma.hip: workspace bookkeeping
-bool mx_ws_malloc(void** p, int64_t bytes);       // gemm_mfma.hip: allocation (capture-safe)
-void mx_ws_shared_note(void);
 
 namespace {
 
@@ -1471,53 +1468,7 @@ void launch_recon_open(const CPlan& p, const Tables& tb, int64_t M, int64_t N, c
                      tb.rc, keys, nr0, nr1, m);
 }
 
-struct Ws {
-  void* ptr = nullptr;
-  int64_t bytes = 0;
-  hipStream_t stream = nullptr;
-  bool used = false;
-};
-std::mutex g_mu;
-constexpr int kWsPerDev = 128;
-Ws g_ws[16][kWsPerDev];
-
-// Grow-only scratch per (device, stream): GEMMs issued on different streams (dataflow lanes,
-// pipelined steps, the in-process parties' graphs replayed concurrently) may run at the same
-// time and must not share residue buffers.  kWsPerDev exceeds the streams a process can hold
-// (PyTorch's pools: 32 per priority, plus the null stream); past it streams would share the
-// last slot (ordered only by the caller) -- counted, mx_workspace_shared_count.  Replaced
-// buffers are retired, never freed (a captured graph may hold them).
-void* workspace(int64_t bytes, hipStream_t st) {
-  int dev = 0;
-  hipGetDevice(&dev);
-  if (dev < 0 || dev >= 16) return nullptr;
-  std::lock_guard<std::mutex> lk(g_mu);
-  Ws* slot = nullptr;
-  for (int i = 0; i < kWsPerDev && !slot; ++i)
-    if (g_ws[dev][i].used && g_ws[dev][i].stream == st) slot = &g_ws[dev][i];
-  for (int i = 0; i < kWsPerDev && !slot; ++i)
-    if (!g_ws[dev][i].used) {
-      slot = &g_ws[dev][i];
-      slot->used = true;
-      slot->stream = st;
-    }
-  if (!slot) {
-    slot = &g_ws[dev][kWsPerDev - 1];
-    mx_ws_shared_note();
-  }
-  Ws& w = *slot;
-  if (w.bytes < bytes) {
-    int64_t want = 1 << 20;
-    while (want < bytes) want <<= 1;
-    void* q = nullptr;
-    const bool ok = mx_ws_malloc(&q, want);
-    mx_ws_note(dev, want, ok);
-    if (!ok) return nullptr;
-    w.ptr = q;
-    w.bytes = want;
-  }
-  return w.ptr;
-}
+StreamScratch g_scratch;  // the CRT GEMM's own pool (the limb GEMM keeps another)
 
 template <class T>
 int run_crt(int64_t batch, int64_t M, int64_t N, int64_t K, const T* A0, const T* A1,
@@ -1532,7 +1483,7 @@ int run_crt(int64_t batch, int64_t M, int64_t N, int64_t K, const T* A0, const T
   if ((mode ? 2 * K : K) > (1 << 15)) return -6;  // exact epilogue rounding bound
   const Tables& tb = tables_for(words, p.n);
   const int64_t need = p.ra_bytes + (rb_pre ? 0 : p.rb_bytes) + p.cr_bytes;
-  int8_t* ws = (int8_t*)workspace(need, st);
+  int8_t* ws = (int8_t*)g_scratch.get(need, st);
   if (!ws) return -4;
   int8_t* ra = ws;
   int8_t* cr = ra + p.ra_bytes;
@@ -1650,7 +1601,8 @@ int run_crt_asym(int64_t M, int64_t N, int64_t K, const T* S0, const T* S1, cons
   const int64_t sum_bytes = asum && !duals ? round_up(sa * (int64_t)sizeof(T), 256) : 0;
   if (cr_ext && !ap.defer) return -7;
   const int64_t cr_ws = cr_ext ? 0 : p.cr_bytes;
-  int8_t* ws = (int8_t*)workspace(a_strip + ra_bytes + cr_ws + b_strip + rb_bytes + sum_bytes, st);
+  int8_t* ws = (int8_t*)g_scratch.get(
+      a_strip + ra_bytes + cr_ws + b_strip + rb_bytes + sum_bytes, st);
   if (!ws) return -4;
   int8_t* ra = ws + a_strip;
   int8_t* cr = cr_ext ? cr_ext : ra + ra_bytes;

@@ -9,11 +9,11 @@
 //
 // so the product needs the L(L+1)/2 limb-pair GEMMs on or below the anti-diagonal (36 for
 // Z_2^64, 136 for Z_2^128), each an i8 x i8 -> i32 MFMA (v_mfma_i32_32x32x32_i8).  Pairs on
-// the same anti-diagonal d accumulate into ONE i32 accumulator tile, so a wave holds L
-// accumulator tiles (16 regs each).  Diagonal d contributes S_d * 2^(8d) and only needs S_d
-// mod 2^(8(L-d)); for the low diagonals |S_d| <= (d+1) K' 2^14 < 2^31 whenever K' <= 8192
-// (Z_2^128) / 16384 (Z_2^64), and the high diagonals (8(L-d) <= 32) may wrap freely.
-// Longer K is split into chunks accumulated in the output.
+// the same anti-diagonal d accumulate into ONE i32 accumulator tile, so a 32x32 quarter of
+// the output needs L accumulator tiles (16 regs each).  Diagonal d contributes S_d * 2^(8d)
+// and only needs S_d mod 2^(8(L-d)); for the low diagonals |S_d| <= (d+1) K' 2^14 < 2^31
+// whenever K' <= 8192 (Z_2^128) / 16384 (Z_2^64), and the high diagonals (8(L-d) <= 32) may
+// wrap freely.  Longer K is split into chunks accumulated in the output.
 //
 // The RSS multiplication needs z_i = x_i.(y_i + y_{i+1}) + x_{i+1}.y_i per party.  That is
 // ONE GEMM with a doubled K: A' = [x_i | x_{i+1}], B' = [y_i + y_{i+1} ; y_i]  (mode 1).
@@ -24,16 +24,26 @@
 //      layout [batch][tile][k-step][limb][64 rows][32 bytes] so that each 64x32 tile of a
 //      limb plane is a contiguous 2 KB image whose 16-byte fragment reads are LDS
 //      bank-conflict free (halves of rows r and r+8 are swapped).
-//   2. gemm (MFMA-bound): 256-thread blocks (4 waves as 2x2), 64x64 output tile, each wave
-//      32x32 with L diagonal accumulators; K advances 32 limb-bytes per step, streamed
-//      global->LDS by LDS-DMA (global_load_lds) into a double buffer.
+//   2. gemm (MFMA-bound): 512-thread blocks, 8 waves of one 32x32 quarter each, two waves per
+//      SIMD.  K advances 32 limb-bytes per step, streamed global->LDS by LDS-DMA
+//      (global_load_lds) into two stages; a k-step is a static schedule of rounds split
+//      around one barrier, with the next step's first operands carried in registers
+//      (see "v2 kernels" below).
+//        Z_2^128 (k_gemm128_v2): 64x64 block tile; the quarter's 16 anti-diagonals are split
+//          between a pair of waves (waves 0-3 sum diagonals 0..8, waves 4-7 the rest, handed
+//          over through LDS in the epilogue).
+//        Z_2^64 (k_gemm64_v2): 64x128 block tile, the paired block of two 64-column B tiles
+//          (so N is padded to 128); 2 x 4 quarters, every wave all 8 diagonals.
+//      Blocks take XCD-contiguous ranges of tiles, walked in groups of kGroupM row bands, so
+//      the blocks co-resident on one XCD share A and B k-streams in that XCD's L2
+//      (MOOSEX_GEMM_GROUPM, MOOSEX_GEMM_XCD: gemm_group_m(), gemm_xcd()).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
-#include <mutex>
 
+#include "gemm_ws.h"
 #include "hip_attr.h"
 #include "moosex.h"
 
@@ -44,18 +54,6 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
 namespace {
-
-// MX_SETPRIO=1: raise the wave priority for the MFMA section of each k-step (tuning knob)
-#ifndef MX_SETPRIO
-#define MX_SETPRIO 0
-#endif
-#if MX_SETPRIO
-#define MX_PRIO_HI() __builtin_amdgcn_s_setprio(1)
-#define MX_PRIO_LO() __builtin_amdgcn_s_setprio(0)
-#else
-#define MX_PRIO_HI() ((void)0)
-#define MX_PRIO_LO() ((void)0)
-#endif
 
 constexpr int TM = 64;  // rows of the block tile (A side)
 constexpr int TN = 64;  // cols of the block tile (B side)
@@ -186,264 +184,13 @@ __device__ inline int64_t xcd_remap(int64_t bid, int64_t nwg) {
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
 }
 
-template <class T>
-__global__ void __launch_bounds__(256, Limbs<T>::L == 8 ? 2 : 1)
-    k_gemm_limb(const int8_t* __restrict__ LA, const int8_t* __restrict__ LB,
-                T* __restrict__ C, int64_t M, int64_t N, int64_t Mp, int64_t Np, int64_t Kp,
-                int accumulate, int gM, int xcd) {
-  constexpr int L = Limbs<T>::L;
-  constexpr int STAGE = L * kTileBytes;  // bytes per operand per k-step
-  extern __shared__ __attribute__((aligned(16))) int8_t smem[];
-  // two LDS buffers, each holding the A and B stage of one k-step
-  auto buf = [&](int i) -> int8_t* { return smem + i * 2 * STAGE; };
-
-  const int64_t tiles_n = Np / TN, tiles_m = Mp / TM;
-  const int64_t ntiles = tiles_n * tiles_m;
-  // XCD-contiguous tile ranges, walked in groups of kGroupM row bands so the ~32 blocks
-  // co-resident on one XCD cover a 4 x 8 patch of output tiles: they share 4 A and 8 B
-  // k-streams in that XCD's L2 instead of 1 A and 32 B streams.
-  const int64_t tid_flat = xcd ? xcd_remap(blockIdx.x, ntiles) : (int64_t)blockIdx.x;
-  const int64_t group = tid_flat / (gM * tiles_n);
-  const int64_t first_m = group * gM;
-  const int64_t gm = tiles_m - first_m < gM ? tiles_m - first_m : gM;
-  const int64_t in_group = tid_flat % (gM * tiles_n);
-  const int64_t tm = first_m + in_group % gm, tn = in_group / gm;
-  const int64_t b = blockIdx.y;
-  const int64_t nkb = Kp / TK;
-
-  const int8_t* ga = LA + (b * tiles_m + tm) * nkb * (int64_t)STAGE;
-  const int8_t* gb = LB + (b * tiles_n + tn) * nkb * (int64_t)STAGE;
-
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int wr = wave >> 1, wc = wave & 1;
-  const int arow = wr * 32 + (lane & 31);
-  const int brow = wc * 32 + (lane & 31);
-  const int half = lane >> 5;
-
-  v16i acc[L];
-#pragma unroll
-  for (int d = 0; d < L; ++d) acc[d] = v16i{0};
-
-  // Stage k-step kb of both operands straight into LDS with global_load_lds (16 B per
-  // lane, 1 KiB per wave-instruction): the blocked limb layout makes each stage one
-  // contiguous image, so the lane-linear LDS destination of LDS-DMA matches exactly and no
-  // VGPRs are spent on staging (they hold the 2 x L MFMA fragments instead).
-  constexpr int PIECES = STAGE / 1024;  // 1 KiB pieces per operand per stage
-  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-  auto issue_stage = [&](int64_t kb, int8_t* dst) {
-    const int8_t* sa = ga + kb * STAGE + lane * 16;
-    const int8_t* sb = gb + kb * STAGE + lane * 16;
-#pragma unroll
-    for (int c = wave_u; c < PIECES; c += 4) {
-      __builtin_amdgcn_global_load_lds((const void*)(sa + c * 1024),
-                                       (__attribute__((address_space(3))) void*)(dst + c * 1024),
-                                       16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const void*)(sb + c * 1024),
-                                       (__attribute__((address_space(3))) void*)(dst + STAGE + c * 1024),
-                                       16, 0, 0);
-    }
-  };
-  // Two LDS buffers; the DMA of stage kb+1 is in flight while stage kb is multiplied.  One
-  // barrier per k-step: after it every wave has finished reading buffer kb&1 (so it may be
-  // refilled with stage kb+2) and every wave's DMA of stage kb+1 has landed (vmcnt(0)).
-  // (Commit 221b0c9 moved the barrier before the last A-limb's MFMA run and prefetched
-  // the next step's fragments into a second register set: 4% slower, 43.6 vs 42.0 ms at
-  // 3 x 4096 x 8192 x 4096 -- the extra live VGPRs cost more than the hidden LDS latency.)
-  const int aoff = swz(arow, half), boff = swz(brow, half);
-  issue_stage(0, buf(0));
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (nkb > 1) issue_stage(1, buf(1));
-  for (int64_t kb = 0; kb < nkb; ++kb) {
-    const int cur = (int)(kb & 1);
-    const int8_t* As = buf(cur);
-    const int8_t* Bs = As + STAGE;
-    // B fragments of the step stay resident; A limbs are consumed one per round, so only
-    // two are requested ahead of their round (the rest stream in behind the MFMAs).
-    v4i bf[L], af[L];
-#pragma unroll
-    for (int j = 0; j < L; ++j) bf[j] = *(const v4i*)(Bs + j * kTileBytes + boff);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) af[i] = *(const v4i*)(As + i * kTileBytes + aoff);
-    // Issue order: round i multiplies A limb i into diagonals d = L-1 .. i (j = d - i),
-    // so consecutive MFMAs never share an accumulator and two updates of the same
-    // diagonal are >= 2 MFMAs apart (no back-to-back SrcC dependency); the scheduling
-    // barriers keep the compiler from regrouping them.
-#pragma unroll
-    for (int i = 0; i < L; ++i) {
-      if (i + 2 < L) af[i + 2] = *(const v4i*)(As + (i + 2) * kTileBytes + aoff);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int d = L - 1; d >= i; --d) {
-        acc[d] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[i], bf[d - i], acc[d], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (kb + 2 < nkb) issue_stage(kb + 2, buf(cur));
-  }
-
-  // epilogue: C[row][col] = sum_d sext(acc_d) << 8d
-  const int col = lane & 31;
-  const int64_t gcol = tn * TN + wc * 32 + col;
-  T* cb = C + b * M * N;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    const int64_t grow = tm * TM + wr * 32 + row;
-    T v = 0;
-#pragma unroll
-    for (int d = 0; d < L; ++d) v += ((T)(int64_t)acc[d][r]) << (8 * d);
-    if (grow < M && gcol < N) {
-      T* p = cb + grow * N + gcol;
-      *p = accumulate ? (T)(*p + v) : v;
-    }
-  }
-}
-
-// Z_2^128 variant with TWO waves per SIMD.  The 16 diagonal accumulators of a 32x32 tile
-// (256 registers) pin k_gemm_limb to one wave per SIMD, so every LDS wait and barrier
-// idles the matrix core.  Here each 32x32 tile is owned by a pair of waves that split the
-// anti-diagonals: the "low" wave sums d = 0..kSplit-1 (55 MFMAs, 10 accumulators), the
-// "high" wave d = kSplit..15 (81 MFMAs, 6 accumulators), each within 256 registers, so
-// 8 waves share the CU and one wave's MFMAs cover the other's waits.  B fragments a wave
-// needs stay resident; A fragments stream limb by limb.  The high wave hands its partial
-// sums to the low wave through LDS at the end.
-constexpr int kSplit = 10;
-
-__global__ void __launch_bounds__(512, 1)
-    k_gemm_limb128_split(const int8_t* __restrict__ LA, const int8_t* __restrict__ LB,
-                         u128* __restrict__ C, int64_t M, int64_t N, int64_t Mp, int64_t Np,
-                         int64_t Kp, int accumulate, int gM, int xcd) {
-  constexpr int L = 16;
-  constexpr int STAGE = L * kTileBytes;
-  extern __shared__ __attribute__((aligned(16))) int8_t smem[];
-  auto buf = [&](int i) -> int8_t* { return smem + i * 2 * STAGE; };
-
-  const int64_t tiles_n = Np / TN, tiles_m = Mp / TM;
-  const int64_t ntiles = tiles_n * tiles_m;
-  const int64_t tid_flat = xcd ? xcd_remap(blockIdx.x, ntiles) : (int64_t)blockIdx.x;
-  const int64_t group = tid_flat / (gM * tiles_n);
-  const int64_t first_m = group * gM;
-  const int64_t gm = tiles_m - first_m < gM ? tiles_m - first_m : gM;
-  const int64_t in_group = tid_flat % (gM * tiles_n);
-  const int64_t tm = first_m + in_group % gm, tn = in_group / gm;
-  const int64_t b = blockIdx.y;
-  const int64_t nkb = Kp / TK;
-  const int8_t* ga = LA + (b * tiles_m + tm) * nkb * (int64_t)STAGE;
-  const int8_t* gb = LB + (b * tiles_n + tn) * nkb * (int64_t)STAGE;
-
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;  // 0..7
-  const int tile = wave & 3;          // which 32x32 quarter of the 64x64 block tile
-  const bool high = wave >= 4;        // diagonal half
-  const int wr = tile >> 1, wc = tile & 1;
-  const int half = lane >> 5;
-  const int aoff = swz(wr * 32 + (lane & 31), half);
-  const int boff = swz(wc * 32 + (lane & 31), half);
-
-  constexpr int PIECES = STAGE / 1024;
-  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-  auto issue_stage = [&](int64_t kb, int8_t* dst) {
-    const int8_t* sa = ga + kb * STAGE + lane * 16;
-    const int8_t* sb = gb + kb * STAGE + lane * 16;
-#pragma unroll
-    for (int c = wave_u; c < PIECES; c += 8) {
-      __builtin_amdgcn_global_load_lds((const void*)(sa + c * 1024),
-                                       (__attribute__((address_space(3))) void*)(dst + c * 1024),
-                                       16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const void*)(sb + c * 1024),
-                                       (__attribute__((address_space(3))) void*)(dst + STAGE + c * 1024),
-                                       16, 0, 0);
-    }
-  };
-
-  constexpr int NLO = kSplit, NHI = L - kSplit;
-  v16i acc[NLO > NHI ? NLO : NHI];
-#pragma unroll
-  for (int d = 0; d < (NLO > NHI ? NLO : NHI); ++d) acc[d] = v16i{0};
-
-  issue_stage(0, buf(0));
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (nkb > 1) issue_stage(1, buf(1));
-  for (int64_t kb = 0; kb < nkb; ++kb) {
-    const int cur = (int)(kb & 1);
-    const int8_t* As = buf(cur);
-    const int8_t* Bs = As + STAGE;
-    if (!high) {
-      v4i bf[NLO];
-#pragma unroll
-      for (int j = 0; j < NLO; ++j) bf[j] = *(const v4i*)(Bs + j * kTileBytes + boff);
-      MX_PRIO_HI();
-#pragma unroll
-      for (int i = 0; i < NLO; ++i) {
-        const v4i a = *(const v4i*)(As + i * kTileBytes + aoff);
-#pragma unroll
-        for (int j = 0; j < NLO - i; ++j)
-          acc[i + j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bf[j], acc[i + j], 0, 0, 0);
-      }
-    } else {
-      v4i bf[L];
-#pragma unroll
-      for (int j = 0; j < L; ++j) bf[j] = *(const v4i*)(Bs + j * kTileBytes + boff);
-      MX_PRIO_HI();
-#pragma unroll
-      for (int i = 0; i < L; ++i) {
-        const v4i a = *(const v4i*)(As + i * kTileBytes + aoff);
-#pragma unroll
-        for (int j = (kSplit - i > 0 ? kSplit - i : 0); j < L - i; ++j)
-          acc[i + j - kSplit] =
-              __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bf[j], acc[i + j - kSplit], 0, 0, 0);
-      }
-    }
-    MX_PRIO_LO();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (kb + 2 < nkb) issue_stage(kb + 2, buf(cur));
-  }
-
-  // epilogue: the high wave parks its partial sums in LDS (free now), the low wave adds
-  // its own and writes C.  16 rows x 64 lanes x 16 B = 16 KB per tile.
-  u128* part = (u128*)smem + tile * (16 * 64);
-  if (high) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      u128 v = 0;
-#pragma unroll
-      for (int d = 0; d < NHI; ++d) v += ((u128)(int64_t)acc[d][r]) << (8 * (d + kSplit));
-      part[r * 64 + lane] = v;
-    }
-  }
-  __syncthreads();
-  if (!high) {
-    const int col = lane & 31;
-    const int64_t gcol = tn * TN + wc * 32 + col;
-    u128* cb = C + b * M * N;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-      const int64_t grow = tm * TM + wr * 32 + row;
-      u128 v = part[r * 64 + lane];
-#pragma unroll
-      for (int d = 0; d < NLO; ++d) v += ((u128)(int64_t)acc[d][r]) << (8 * d);
-      if (grow < M && gcol < N) {
-        u128* p = cb + grow * N + gcol;
-        *p = accumulate ? (u128)(*p + v) : v;
-      }
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------
 // v2 kernels: software-pipelined across the k-step boundary.
 //
-// PMC on the kernels above (profiles/r2_v0_gemm_pmc.md): the matrix pipes idle ~26 % of
-// the time.  After each k-step barrier every wave first issues its LDS-DMA pieces, then a
-// burst of fragment reads, and waits for them before its first MFMA -- with both waves of a
-// SIMD doing the same thing at the same moment, the pipe drains at every step.
+// PMC on their predecessors, since removed (profiles/r2_v0_gemm_pmc.md): the matrix pipes
+// idled ~26 % of the time.  After each k-step barrier every wave first issued its LDS-DMA
+// pieces, then a burst of fragment reads, and waited for them before its first MFMA -- with
+// both waves of a SIMD doing the same thing at the same moment, the pipe drained at every step.
 //
 // Here each wave's share of a k-step is a static schedule of "rounds" (round i multiplies
 // A limb i into its diagonals) split in two phases around ONE barrier:
@@ -753,16 +500,6 @@ __global__ void __launch_bounds__(512, 1)
   }
 }
 
-// MOOSEX_GEMM_V=1 selects the round-1 kernels (A/B measurements)
-bool use_v1_kernels() {
-  static const bool on = [] {
-    const char* e = std::getenv("MOOSEX_GEMM_V");
-    return e && e[0] == '1';
-  }();
-  return on;
-}
-
-// MOOSEX_GEMM_SPLIT=0 selects the one-wave-per-SIMD kernel for Z_2^128 (A/B testing)
 // Tile-order knobs (tuning experiments): MOOSEX_GEMM_GROUPM row bands per L2 group
 // (default kGroupM), MOOSEX_GEMM_XCD=0 disables the XCD-contiguous block remap.
 int gemm_group_m() {
@@ -774,14 +511,6 @@ int gemm_group_m() {
 int gemm_xcd() {
   const char* e = std::getenv("MOOSEX_GEMM_XCD");
   return e && e[0] == '0' ? 0 : 1;
-}
-
-bool use_split_kernel() {
-  static const bool on = [] {
-    const char* e = std::getenv("MOOSEX_GEMM_SPLIT");
-    return !(e && e[0] == '0');
-  }();
-  return on;
 }
 
 }  // namespace
@@ -829,50 +558,7 @@ extern "C" int64_t mx_workspace_held_bytes(void) {
 
 namespace {
 
-struct Workspace {
-  void* ptr = nullptr;
-  int64_t bytes = 0;
-  hipStream_t stream = nullptr;
-  bool used = false;
-};
-std::mutex g_ws_mu;
-constexpr int kWsPerDev = 128;
-Workspace g_ws[16][kWsPerDev];
-
-// Grow-only scratch per (device, stream) -- see gemm_crt.hip workspace(): concurrent GEMMs
-// on different streams get different buffers.  A replaced buffer is retired, never freed: a
-// captured hipGraph may still reference it, and freeing would need a device-wide sync.
-void* get_workspace(int64_t bytes, hipStream_t st) {
-  int dev = 0;
-  hipGetDevice(&dev);
-  if (dev < 0 || dev >= 16) return nullptr;
-  std::lock_guard<std::mutex> lk(g_ws_mu);
-  Workspace* slot = nullptr;
-  for (int i = 0; i < kWsPerDev && !slot; ++i)
-    if (g_ws[dev][i].used && g_ws[dev][i].stream == st) slot = &g_ws[dev][i];
-  for (int i = 0; i < kWsPerDev && !slot; ++i)
-    if (!g_ws[dev][i].used) {
-      slot = &g_ws[dev][i];
-      slot->used = true;
-      slot->stream = st;
-    }
-  if (!slot) {
-    slot = &g_ws[dev][kWsPerDev - 1];
-    mx_ws_shared_note();
-  }
-  Workspace& w = *slot;
-  if (w.bytes < bytes) {
-    int64_t want = 1 << 20;
-    while (want < bytes) want <<= 1;
-    void* p = nullptr;
-    const bool ok = mx_ws_malloc(&p, want);
-    mx_ws_note(dev, want, ok);
-    if (!ok) return nullptr;
-    w.ptr = p;  // the previous buffer (if any) stays allocated
-    w.bytes = want;
-  }
-  return w.ptr;
-}
+StreamScratch g_scratch;  // the limb GEMM's own pool (the CRT GEMM keeps another)
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
@@ -921,53 +607,49 @@ void launch_prep_b(const Plan& p, int64_t batch, int64_t K, int64_t N, const T* 
 template <class T>
 void launch_gemm(const Plan& p, int64_t batch, int64_t M, int64_t N, const int8_t* la,
                  const int8_t* lb, T* C, int accumulate, hipStream_t st) {
-  constexpr int L = Limbs<T>::L;
   const int64_t ntiles = (p.Mp / TM) * (p.Np / TN);
-  const size_t lds = 4 * (size_t)L * kTileBytes;  // 2 buffers x (A + B) stages
-  ensure_lds_attr((const void*)k_gemm_limb<T>, (int)lds, st);
-  ensure_lds_attr((const void*)k_gemm_limb128_split, (int)lds, st);
-  ensure_lds_attr((const void*)k_gemm128_v2, 4 * 16 * kTileBytes, st);
-  ensure_lds_attr((const void*)k_gemm64_v2, 2 * 3 * 8 * kTileBytes, st);
-  if (!use_v1_kernels()) {
-    if constexpr (sizeof(T) == 16) {
-      hipLaunchKernelGGL(k_gemm128_v2, dim3((unsigned)ntiles, (unsigned)batch), dim3(512),
-                         4 * 16 * kTileBytes, st, la, lb, (u128*)C, M, N, p.Mp, p.Np, p.Kp,
-                         accumulate, gemm_group_m(), gemm_xcd());
-    } else {
-      hipLaunchKernelGGL(k_gemm64_v2, dim3((unsigned)(ntiles / 2), (unsigned)batch), dim3(512),
-                         2 * 3 * 8 * kTileBytes, st, la, lb, (u64*)C, M, N, p.Mp, p.Np, p.Kp,
-                         accumulate, gemm_group_m(), gemm_xcd());
-    }
-  } else if (sizeof(T) == 16 && use_split_kernel()) {
-    hipLaunchKernelGGL(k_gemm_limb128_split, dim3((unsigned)ntiles, (unsigned)batch), dim3(512),
-                       lds, st, la, lb, (u128*)C, M, N, p.Mp, p.Np, p.Kp, accumulate,
-                       gemm_group_m(), gemm_xcd());
+  if constexpr (sizeof(T) == 16) {
+    ensure_lds_attr((const void*)k_gemm128_v2, 4 * 16 * kTileBytes, st);
+    hipLaunchKernelGGL(k_gemm128_v2, dim3((unsigned)ntiles, (unsigned)batch), dim3(512),
+                       4 * 16 * kTileBytes, st, la, lb, (u128*)C, M, N, p.Mp, p.Np, p.Kp,
+                       accumulate, gemm_group_m(), gemm_xcd());
   } else {
-    hipLaunchKernelGGL(k_gemm_limb<T>, dim3((unsigned)ntiles, (unsigned)batch), dim3(256), lds,
-                       st, la, lb, C, M, N, p.Mp, p.Np, p.Kp, accumulate, gemm_group_m(),
-                       gemm_xcd());
+    ensure_lds_attr((const void*)k_gemm64_v2, 2 * 3 * 8 * kTileBytes, st);
+    hipLaunchKernelGGL(k_gemm64_v2, dim3((unsigned)(ntiles / 2), (unsigned)batch), dim3(512),
+                       2 * 3 * 8 * kTileBytes, st, la, lb, (u64*)C, M, N, p.Mp, p.Np, p.Kp,
+                       accumulate, gemm_group_m(), gemm_xcd());
   }
 }
 
+// One limb product of at most max_k_chunk: A' and, unless the caller prepared it (lb_pre, from
+// mx_gemm_prep_b), B' are limb-split into this stream's scratch, then the GEMM runs.  The
+// batch strides count elements; 0 broadcasts an operand over the batch.
 template <class T>
-int run(int64_t batch, int64_t M, int64_t N, int64_t K, const T* A0, const T* A1, const T* B0,
-        const T* B1, int mode, T* C, int accumulate, void* ws, int64_t ws_bytes,
-        hipStream_t st) {
-  if (K > max_k_chunk(sizeof(T) == 8 ? 1 : 2, mode)) return -6;  // caller splits long K
-  Plan p = make_plan(sizeof(T) == 8 ? 1 : 2, batch, M, N, K, mode);
-  if (p.la_bytes + p.lb_bytes > ws_bytes) return -5;
-  int8_t* la = (int8_t*)ws;
-  int8_t* lb = la + p.la_bytes;
-  launch_prep_a<T>(p, batch, M, K, A0, A1, M * K, mode, la, st);
-  launch_prep_b<T>(p, batch, K, N, B0, B1, mode, lb, st);
-  launch_gemm<T>(p, batch, M, N, la, lb, C, accumulate, st);
-  hipError_t e = hipGetLastError();
+int limb_product(int64_t batch, int64_t M, int64_t N, int64_t K, const void* A0, const void* A1,
+                 int64_t a_bstride, const void* B0, const void* B1, int64_t b_bstride,
+                 const void* lb_pre, int mode, void* C, int accumulate, hipStream_t st) {
+  constexpr int words = sizeof(T) / 8;
+  if (K > max_k_chunk(words, mode)) return -6;  // caller splits long K
+  const Plan p = make_plan(words, batch, M, N, K, mode);
+  int8_t* la = (int8_t*)g_scratch.get(p.la_bytes + (lb_pre ? 0 : p.lb_bytes), st);
+  if (!la) return -4;
+  launch_prep_a<T>(p, batch, M, K, (const T*)A0, (const T*)A1, a_bstride, mode, la, st);
+  if (!lb_pre)
+    launch_prep_b<T>(p, batch, K, N, (const T*)B0, (const T*)B1, mode, la + p.la_bytes, st,
+                     b_bstride);
+  launch_gemm<T>(p, batch, M, N, la, lb_pre ? (const int8_t*)lb_pre : la + p.la_bytes, (T*)C,
+                 accumulate, st);
+  const hipError_t e = hipGetLastError();
   return e != hipSuccess ? -100 - (int)e : 0;
 }
 
-}  // namespace
-
-namespace {
+// words -> ring element: f(u64{}) or f(u128{}), -2 for any other width
+template <class F>
+int by_words(int words, F&& f) {
+  if (words == 1) return f(u64{});
+  if (words == 2) return f(u128{});
+  return -2;
+}
 
 // Register-only MFMA throughput probe: the ceiling the limb GEMM is measured against
 // (same instruction, same clock behaviour, no memory traffic).
@@ -1055,28 +737,6 @@ extern "C" {
 
 void mx_set_gemm_crt(int mode) { g_crt_mode = mode; }
 
-int64_t mx_gemm_workspace_bytes(int words, int64_t batch, int64_t M, int64_t N, int64_t K,
-                                int mode) {
-  if (words != 1 && words != 2) return 0;
-  int64_t kk = std::min(K, max_k_chunk(words, mode));
-  Plan p = make_plan(words, batch, M, N, kk, mode);
-  return p.la_bytes + p.lb_bytes;
-}
-
-int mx_gemm_ws(int words, int64_t batch, int64_t M, int64_t N, int64_t K, const void* A0,
-               const void* A1, const void* B0, const void* B1, int mode, void* C,
-               int accumulate, void* workspace, int64_t ws_bytes, void* stream) {
-  if (K == 0) return empty_k_product(words, batch, M, N, C, accumulate, stream);
-  hipStream_t st = (hipStream_t)stream;
-  if (words == 1)
-    return run<u64>(batch, M, N, K, (const u64*)A0, (const u64*)A1, (const u64*)B0,
-                    (const u64*)B1, mode, (u64*)C, accumulate, workspace, ws_bytes, st);
-  if (words == 2)
-    return run<u128>(batch, M, N, K, (const u128*)A0, (const u128*)A1, (const u128*)B0,
-                     (const u128*)B1, mode, (u128*)C, accumulate, workspace, ws_bytes, st);
-  return -2;
-}
-
 // Prepared-B GEMM: the B' operand's limb planes are built once (mx_gemm_prep_b into a
 // caller buffer of mx_gemm_b_bytes) and reused by several products with different A row
 // blocks (mx_gemm_with_b; A given with a batch stride, so row blocks of a stacked
@@ -1093,17 +753,14 @@ int mx_gemm_prep_b(int words, int64_t batch, int64_t K, int64_t N, const void* B
   if (K == 0) return 0;  // no k-step to prepare; the products answer K = 0 themselves
   if (use_crt(256, N, K, mode)) return mxh_crt_prep_b(words, batch, K, N, B0, B1, mode, lb, stream);
   if (K > max_k_chunk(words, mode)) return -6;
-  Plan p = make_plan(words, batch, 64, N, K, mode);
-  hipStream_t st = (hipStream_t)stream;
-  if (words == 1)
-    launch_prep_b<u64>(p, batch, K, N, (const u64*)B0, (const u64*)B1, mode, (int8_t*)lb, st);
-  else if (words == 2)
-    launch_prep_b<u128>(p, batch, K, N, (const u128*)B0, (const u128*)B1, mode, (int8_t*)lb,
-                        st);
-  else
-    return -2;
-  hipError_t e = hipGetLastError();
-  return e != hipSuccess ? -100 - (int)e : 0;
+  return by_words(words, [&](auto t) {
+    using T = decltype(t);
+    const Plan p = make_plan(words, batch, 64, N, K, mode);
+    launch_prep_b<T>(p, batch, K, N, (const T*)B0, (const T*)B1, mode, (int8_t*)lb,
+                     (hipStream_t)stream);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? -100 - (int)e : 0;
+  });
 }
 
 int mx_gemm_with_b(int words, int64_t batch, int64_t M, int64_t N, int64_t K, const void* A0,
@@ -1113,26 +770,10 @@ int mx_gemm_with_b(int words, int64_t batch, int64_t M, int64_t N, int64_t K, co
   if (use_crt(256, N, K, mode))  // the prepared B' holds residues (same test as prep_b)
     return mxh_crt_with_b(words, batch, M, N, K, A0, A1, a_bstride, mode, lb, C, accumulate,
                           stream);
-  if (K > max_k_chunk(words, mode)) return -6;
-  Plan p = make_plan(words, batch, M, N, K, mode);
-  void* la = get_workspace(p.la_bytes, (hipStream_t)stream);
-  if (!la) return -4;
-  hipStream_t st = (hipStream_t)stream;
-  if (words == 1) {
-    launch_prep_a<u64>(p, batch, M, K, (const u64*)A0, (const u64*)A1, a_bstride, mode,
-                       (int8_t*)la, st);
-    launch_gemm<u64>(p, batch, M, N, (const int8_t*)la, (const int8_t*)lb, (u64*)C, accumulate,
-                     st);
-  } else if (words == 2) {
-    launch_prep_a<u128>(p, batch, M, K, (const u128*)A0, (const u128*)A1, a_bstride, mode,
-                        (int8_t*)la, st);
-    launch_gemm<u128>(p, batch, M, N, (const int8_t*)la, (const int8_t*)lb, (u128*)C,
-                      accumulate, st);
-  } else {
-    return -2;
-  }
-  hipError_t e = hipGetLastError();
-  return e != hipSuccess ? -100 - (int)e : 0;
+  return by_words(words, [&](auto t) {
+    return limb_product<decltype(t)>(batch, M, N, K, A0, A1, a_bstride, nullptr, nullptr, 0, lb,
+                                     mode, C, accumulate, (hipStream_t)stream);
+  });
 }
 
 // Mode-1 product whose second A operand is the first rolled over the batch (a stacked RSS
@@ -1158,26 +799,10 @@ int mx_gemm_strided(int words, int64_t batch, int64_t M, int64_t N, int64_t K, c
   if (use_crt(M, N, K, mode))
     return mxh_gemm_crt_strided(words, batch, M, N, K, A0, A1, a_bstride, B0, B1, b_bstride,
                                 mode, C, accumulate, stream);
-  if (K > max_k_chunk(words, mode)) return -6;
-  Plan p = make_plan(words, batch, M, N, K, mode);
-  void* ws = get_workspace(p.la_bytes + p.lb_bytes, (hipStream_t)stream);
-  if (!ws) return -4;
-  int8_t* la = (int8_t*)ws;
-  int8_t* lb = la + p.la_bytes;
-  hipStream_t st = (hipStream_t)stream;
-  if (words == 1) {
-    launch_prep_a<u64>(p, batch, M, K, (const u64*)A0, (const u64*)A1, a_bstride, mode, la, st);
-    launch_prep_b<u64>(p, batch, K, N, (const u64*)B0, (const u64*)B1, mode, lb, st, b_bstride);
-    launch_gemm<u64>(p, batch, M, N, la, lb, (u64*)C, accumulate, st);
-  } else {
-    launch_prep_a<u128>(p, batch, M, K, (const u128*)A0, (const u128*)A1, a_bstride, mode, la,
-                        st);
-    launch_prep_b<u128>(p, batch, K, N, (const u128*)B0, (const u128*)B1, mode, lb, st,
-                        b_bstride);
-    launch_gemm<u128>(p, batch, M, N, la, lb, (u128*)C, accumulate, st);
-  }
-  hipError_t e = hipGetLastError();
-  return e != hipSuccess ? -100 - (int)e : 0;
+  return by_words(words, [&](auto t) {
+    return limb_product<decltype(t)>(batch, M, N, K, A0, A1, a_bstride, B0, B1, b_bstride,
+                                     nullptr, mode, C, accumulate, (hipStream_t)stream);
+  });
 }
 
 int mxh_gemm_mfma(int words, int64_t batch, int64_t M, int64_t N, int64_t K, const void* A0,
@@ -1186,12 +811,10 @@ int mxh_gemm_mfma(int words, int64_t batch, int64_t M, int64_t N, int64_t K, con
   if (K == 0) return empty_k_product(words, batch, M, N, C, accumulate, stream);
   if (use_crt(M, N, K, mode))
     return mxh_gemm_crt(words, batch, M, N, K, A0, A1, B0, B1, mode, C, accumulate, stream);
-  if (K > max_k_chunk(words, mode)) return -6;  // caller splits long K
-  int64_t bytes = mx_gemm_workspace_bytes(words, batch, M, N, K, mode);
-  void* ws = get_workspace(bytes, (hipStream_t)stream);
-  if (!ws) return -4;
-  return mx_gemm_ws(words, batch, M, N, K, A0, A1, B0, B1, mode, C, accumulate, ws, bytes,
-                    stream);
+  return by_words(words, [&](auto t) {
+    return limb_product<decltype(t)>(batch, M, N, K, A0, A1, M * K, B0, B1, K * N, nullptr, mode,
+                                     C, accumulate, (hipStream_t)stream);
+  });
 }
 
 }  // extern "C"

@@ -87,16 +87,10 @@ _SIGS = {
         c_int,
         [c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp],
     ),
-    "mx_gemm_workspace_bytes": (c_i64, [c_int, c_i64, c_i64, c_i64, c_i64, c_int]),
     "mx_workspace_failed_bytes": (c_i64, []),
     "mx_workspace_held_bytes": (c_i64, []),
     "mx_workspace_shared_count": (c_i64, []),
     "mx_mfma_peak": (c_int, [c_int, c_int, c_vp, c_vp]),
-    "mx_gemm_ws": (
-        c_int,
-        [c_int, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp,
-         c_i64, c_vp],
-    ),
     "mx_set_gemm_impl": (None, [c_int]),
     "mx_set_gemm_crt": (None, [c_int]),
     "mx_gemm_strided": (

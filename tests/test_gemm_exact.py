@@ -1,10 +1,10 @@
 """Every ring GEMM path against exact integer arithmetic, at its edges.
 
-The host GEMM, the VALU and gemv kernels, the limb MFMA kernels (v2, and in child processes the
-v1 and one-wave forms), the tile-order knobs and the CRT GEMM are each forced, run, and compared
-with an oracle that holds no project code: python ``int`` (numpy object arrays), or for Z_2^64
-numpy ``uint64`` arithmetic, which wraps exactly (test_uint64_oracle_is_the_int_oracle).  The
-host kernels are never the oracle.  Everything is exact equality.
+The host GEMM, the VALU and gemv kernels, the limb MFMA kernels, the tile-order knobs and the CRT
+GEMM are each forced, run, and compared with an oracle that holds no project code: python
+``int`` (numpy object arrays), or for Z_2^64 numpy ``uint64`` arithmetic, which wraps exactly
+(test_uint64_oracle_is_the_int_oracle).  The host kernels are never the oracle.  Everything is
+exact equality.
 
 Two kinds of operand keep the oracle cheap:
 
@@ -17,11 +17,8 @@ Two kinds of operand keep the oracle cheap:
   a misplaced, transposed, duplicated or missing tile shows, and a shift of k between the two
   operands changes S.
 """
-import json
-import os
+import ctypes
 import random
-import subprocess
-import sys
 from contextlib import contextmanager
 
 import numpy as np
@@ -599,51 +596,35 @@ def test_gemm_strided_padded_a_broadcast_b(mode, bits):
     same(out, np.stack(want), f"gemm_strided Z_2^{bits} mode {mode}")
 
 
-# ---------------------------------------------------------------------------
-# v1 and one-wave kernels: the switches are read once per process
-# ---------------------------------------------------------------------------
-def child_checks():
-    """What tests/gemm_exact_child.py runs under MOOSEX_GEMM_V=1 (k_gemm_limb<T>,
-    k_gemm_limb128_split; with MOOSEX_GEMM_SPLIT=0 k_gemm_limb<u128>): the tile boundaries at
-    one ragged K, the 7-, 10- and 45-tile cases, and accumulate.  Returns the case count."""
-    n = 0
-    with forced(*LIMB):
-        for bits in WIDTHS:
-            for case in boundary_cases(bits, 33):
-                check_sep(case, n % 2, what="v1 limb")
-                n += 1
-            for tiles in (7, 10, 45):
-                for mode in (0, 1):
-                    check_sep(tile_case(bits, tiles), mode, what=f"v1 limb {tiles} tiles")
-                    n += 1
-            check_sep(SepCase(bits, 3, 129, 130, 70, 820, "cuda"), 1, accumulate=1,
-                      what="v1 limb")
-            check_dense(bits, 1, 65, 63, 33, 1, "cuda", 860, accumulate=1, what="v1 limb")
-            n += 2
-    torch.cuda.synchronize()
-    return n
-
-
-def _child(env):
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gemm_exact_child.py")
-    e = {k: v for k, v in os.environ.items()
-         if k not in ("MOOSEX_GEMM_V", "MOOSEX_GEMM_SPLIT", "MOOSEX_GEMM_GROUPM",
-                      "MOOSEX_GEMM_XCD", "MOOSEX_GEMM_CRT")}
-    e.update(env, PYTHONUNBUFFERED="1")
-    p = subprocess.run([sys.executable, child], env=e, text=True, capture_output=True,
-                       timeout=300)
-    assert p.returncode == 0, (env, p.stdout[-2000:], p.stderr[-4000:])
-    return json.loads(p.stdout.strip().splitlines()[-1])
-
-
 @gpu
-@pytest.mark.parametrize("env", [{"MOOSEX_GEMM_V": "1"},
-                                 {"MOOSEX_GEMM_V": "1", "MOOSEX_GEMM_SPLIT": "0"}],
-                         ids=["v1", "v1-one-wave"])
-def test_v1_kernels_in_a_child(env):
-    got = _child(env)
-    print(env, got)
-    assert got["ok"] and got["cases"] >= 70 and got["env"] == env
+def test_limb_and_crt_scratch_two_pools_keyed_by_stream_grow_only():
+    """The limb GEMM and the CRT GEMM each keep a scratch pool of their own (csrc/gemm_ws.h),
+    one grow-only buffer per stream: on a stream neither has seen, the first limb product
+    allocates one buffer (la + lb = 128 KiB here, so the 1 MiB minimum), the first CRT product
+    another, and repeats of both allocate nothing.  No lookup falls back to the shared slot."""
+    lib = nat.lib()
+    raw = ctypes.c_void_p()  # a new HIP stream: one from torch's pool may have run GEMMs before
+    assert lib.hipStreamCreate(ctypes.byref(raw)) == 0  # resolved in the runtime the library links
+    stream = torch.cuda.ExternalStream(raw.value)  # kept for the process: its slots stay keyed
+    case = SepCase(64, 1, 65, 66, 33, 960, "cuda")
+    ops, want = case.operands(0), case.oracle(0)
+    shared = lib.mx_workspace_shared_count()
+    torch.cuda.synchronize()
+    got, held = [], [lib.mx_workspace_held_bytes()]
+    with torch.cuda.stream(stream):
+        for path in (LIMB, CRT, LIMB, CRT):
+            with forced(*path):
+                got.append(run_gemm(ops, 64, 65, 66, 33))
+            held.append(lib.mx_workspace_held_bytes())
+        stream.synchronize()
+    for g, what in zip(got, ("limb", "crt", "limb again", "crt again")):
+        same(g, want, f"{what} on a new stream")
+    grew = [b - a for a, b in zip(held, held[1:])]
+    print("workspace growth per product:", grew)
+    assert grew[0] == 1 << 20
+    assert grew[1] >= 1 << 20 and grew[1] & (grew[1] - 1) == 0  # one power-of-two buffer
+    assert grew[2:] == [0, 0]
+    assert lib.mx_workspace_shared_count() == shared == 0
 
 
 # ---------------------------------------------------------------------------
