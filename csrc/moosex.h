@@ -131,6 +131,34 @@ int mx_pwl_cross(int dev, int elem_bytes, const void* s0, const void* s1, const 
                  const void* x1, void* out, int64_t slots, int64_t s_slot_stride,
                  int64_t x_slot_stride, int64_t n, int k, const uint64_t* da, const uint64_t* db,
                  const uint64_t* ak, void* stream);
+// One compare-exchange stage (k, j) of a bitonic sorting network in Z_2^64 / Z_2^128
+// (elem_bytes 8 / 16), wrapping, along the middle axis of an [outer, n, inner] array per slot
+// (cswap_geom.h: n, k, j powers of two, j < k <= n; by = -1 sorts every inner index on its own,
+// by >= 0 orders whole rows by column `by`).  Pair t of [0, n/2): i = t with a zero bit
+// inserted at bit log2 j, l = i | j, ascending iff (i & k) == 0 (flipped by `descending`).
+// Input slots are *_slot_stride elements apart (views of a larger buffer are read in place),
+// output slots are dense.
+//   mx_cswap_diff:  out[o, t, c] = ascending ? x[l] - x[i] : x[i] - x[l], [outer, n/2, inner],
+//                   or on the key column only, [outer, n/2, 1], in table mode: negative where
+//                   the pair is out of order
+//   mx_cswap_cross: with D = x[i] - x[l], out[o, t, c] = s0*(D0 + D1) + s1*D0 -- the replicated
+//                   local product of the flag s and the difference (own times the sum plus next
+//                   times own) -- over flags [outer, n/2, inner], or [outer, n/2, 1] broadcast
+//                   over the columns in table mode.  s1 == x1 == null: plain, s0*D0
+//   mx_cswap_apply: out[i] = x[i] - p[t], out[l] = x[l] + p[t] with p [outer, n/2, inner]
+// With s = [diff < 0] and p = s * (x[i] - x[l]) the three make one stage; the direction enters
+// through the sign of diff alone.
+int mx_cswap_diff(int dev, int elem_bytes, const void* x, void* out, int64_t slots,
+                  int64_t x_slot_stride, int64_t outer, int64_t n, int64_t inner, int64_t by,
+                  int64_t k, int64_t j, int descending, void* stream);
+int mx_cswap_cross(int dev, int elem_bytes, const void* s0, const void* s1, const void* x0,
+                   const void* x1, void* out, int64_t slots, int64_t s_slot_stride,
+                   int64_t x_slot_stride, int64_t outer, int64_t n, int64_t inner, int64_t by,
+                   int64_t k, int64_t j, int descending, void* stream);
+int mx_cswap_apply(int dev, int elem_bytes, const void* x, const void* p, void* out,
+                   int64_t slots, int64_t x_slot_stride, int64_t p_slot_stride, int64_t outer,
+                   int64_t n, int64_t inner, int64_t by, int64_t k, int64_t j, int descending,
+                   void* stream);
 // mx_ew_binary_slot on a0 (slot which0) and a1 (slot which1) with one public b
 int mx_ew_binary_slot2(int dev, int op, int words, const void* a0, const void* a1,
                        const void* b, int64_t nb, void* out0, void* out1, int64_t m,

@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include "aes_core.h"
+#include "cswap_geom.h"
 #include "img_geom.h"
 #include "moosex.h"
 
@@ -291,6 +292,15 @@ int mxh_pwl_cross(int elem_bytes, const void* s0, const void* s1, const void* x0
 int mxh_dwconv(int elem_bytes, const void* x0, const void* x1, const void* w0, const void* w1,
                void* out, int64_t slots, int64_t x_slot_stride, int64_t w_slot_stride,
                const mxr::ImgGeom& g, void* stream);
+// the compare-exchange leaves: g is validated and filled by cswap_geom_check (cswap_geom.h)
+int mxh_cswap_diff(int elem_bytes, const void* x, void* out, int64_t slots, int64_t x_slot_stride,
+                   const mxr::CswapGeom& g, void* stream);
+int mxh_cswap_cross(int elem_bytes, const void* s0, const void* s1, const void* x0,
+                    const void* x1, void* out, int64_t slots, int64_t s_slot_stride,
+                    int64_t x_slot_stride, const mxr::CswapGeom& g, void* stream);
+int mxh_cswap_apply(int elem_bytes, const void* x, const void* p, void* out, int64_t slots,
+                    int64_t x_slot_stride, int64_t p_slot_stride, const mxr::CswapGeom& g,
+                    void* stream);
 int mxh_ks_cross1(int words, const void* g0, const void* g1, const void* p0, const void* p1,
                   void* z, int64_t n, int d, int both, const uint8_t* keys16, uint64_t nonce,
                   void* stream);

@@ -509,6 +509,69 @@ void pwl_cross_cpu(const T* s0, const T* s1, const T* x0, const T* x1, T* out, i
   });
 }
 
+using mxr::CswapGeom;
+
+// The compare-exchange leaves (moosex.h mx_cswap_*): one (slot, row, pair) at a time, the
+// pairing as cswap_geom.h words it.  f(s, o, t, i, l): i, l the two positions of pair t.
+template <class F>
+void cswap_pairs(int64_t slots, const CswapGeom& g, F f) {
+  const int64_t per = g.outer * g.half;
+  parallel_for(slots * per, std::max<int64_t>(1, 4096 / g.inner), [&](int64_t b, int64_t e) {
+    for (int64_t q = b; q < e; ++q) {
+      const int64_t s = q / per, r = q - s * per, o = r / g.half, t = r - o * g.half;
+      const int64_t i = mxr::cswap_low(t, g.lj);
+      f(s, o, t, i, i | g.j);
+    }
+  });
+}
+
+template <class T>
+void cswap_diff_cpu(const T* x, T* out, int64_t slots, int64_t x_slot_stride,
+                    const CswapGeom& g) {
+  const int64_t c0 = g.by >= 0 ? g.by : 0;
+  cswap_pairs(slots, g, [&](int64_t s, int64_t o, int64_t t, int64_t i, int64_t l) {
+    const T* xi = x + s * x_slot_stride + (o * g.n + i) * g.inner + c0;
+    const T* xl = x + s * x_slot_stride + (o * g.n + l) * g.inner + c0;
+    T* dst = out + s * g.n_flag + (o * g.half + t) * g.cols;
+    const bool asc = mxr::cswap_ascending(g, i);
+    for (int64_t c = 0; c < g.cols; ++c) dst[c] = asc ? xl[c] - xi[c] : xi[c] - xl[c];
+  });
+}
+
+template <class T>
+void cswap_cross_cpu(const T* s0, const T* s1, const T* x0, const T* x1, T* out, int64_t slots,
+                     int64_t s_slot_stride, int64_t x_slot_stride, const CswapGeom& g) {
+  const bool cross = x1 != nullptr;
+  cswap_pairs(slots, g, [&](int64_t s, int64_t o, int64_t t, int64_t i, int64_t l) {
+    const int64_t xi = s * x_slot_stride + (o * g.n + i) * g.inner;
+    const int64_t xl = s * x_slot_stride + (o * g.n + l) * g.inner;
+    const int64_t f = s * s_slot_stride + (o * g.half + t) * g.cols;
+    T* dst = out + s * g.n_pair + (o * g.half + t) * g.inner;
+    for (int64_t c = 0; c < g.inner; ++c) {
+      const int64_t fc = f + (g.by >= 0 ? 0 : c);
+      const T d0 = x0[xi + c] - x0[xl + c];
+      T v = s0[fc] * (cross ? d0 + (x1[xi + c] - x1[xl + c]) : d0);
+      if (cross) v += s1[fc] * d0;
+      dst[c] = v;
+    }
+  });
+}
+
+template <class T>
+void cswap_apply_cpu(const T* x, const T* p, T* out, int64_t slots, int64_t x_slot_stride,
+                     int64_t p_slot_stride, const CswapGeom& g) {
+  cswap_pairs(slots, g, [&](int64_t s, int64_t o, int64_t t, int64_t i, int64_t l) {
+    const int64_t ri = (o * g.n + i) * g.inner, rl = (o * g.n + l) * g.inner;
+    const T* src = x + s * x_slot_stride;
+    const T* pp = p + s * p_slot_stride + (o * g.half + t) * g.inner;
+    T* dst = out + s * g.n_x;
+    for (int64_t c = 0; c < g.inner; ++c) {
+      dst[ri + c] = src[ri + c] - pp[c];
+      dst[rl + c] = src[rl + c] + pp[c];
+    }
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -702,6 +765,52 @@ int mx_pwl_cross(int dev, int elem_bytes, const void* s0, const void* s1, const 
   DISPATCH_ELEM(elem_bytes, T, {
     pwl_cross_cpu((const T*)s0, (const T*)s1, (const T*)x0, (const T*)x1, (T*)out, slots,
                   s_slot_stride, x_slot_stride, n, k, da, db, ak);
+    return 0;
+  });
+}
+
+int mx_cswap_diff(int dev, int elem_bytes, const void* x, void* out, int64_t slots,
+                  int64_t x_slot_stride, int64_t outer, int64_t n, int64_t inner, int64_t by,
+                  int64_t k, int64_t j, int descending, void* stream) {
+  CswapGeom g{outer, n, inner, by, k, j, descending};
+  const int rc = mxr::cswap_geom_check(g, elem_bytes, slots, x_slot_stride);
+  if (rc <= 0) return rc;
+  if (dev) return mxh_cswap_diff(elem_bytes, x, out, slots, x_slot_stride, g, stream);
+  DISPATCH_ELEM(elem_bytes, T, {
+    cswap_diff_cpu((const T*)x, (T*)out, slots, x_slot_stride, g);
+    return 0;
+  });
+}
+
+int mx_cswap_cross(int dev, int elem_bytes, const void* s0, const void* s1, const void* x0,
+                   const void* x1, void* out, int64_t slots, int64_t s_slot_stride,
+                   int64_t x_slot_stride, int64_t outer, int64_t n, int64_t inner, int64_t by,
+                   int64_t k, int64_t j, int descending, void* stream) {
+  CswapGeom g{outer, n, inner, by, k, j, descending};
+  if ((s1 == nullptr) != (x1 == nullptr)) return -3;  // cross mode takes both next components
+  const int rc = mxr::cswap_geom_check(g, elem_bytes, slots, s_slot_stride, x_slot_stride);
+  if (rc <= 0) return rc;
+  if (dev)
+    return mxh_cswap_cross(elem_bytes, s0, s1, x0, x1, out, slots, s_slot_stride, x_slot_stride,
+                           g, stream);
+  DISPATCH_ELEM(elem_bytes, T, {
+    cswap_cross_cpu((const T*)s0, (const T*)s1, (const T*)x0, (const T*)x1, (T*)out, slots,
+                    s_slot_stride, x_slot_stride, g);
+    return 0;
+  });
+}
+
+int mx_cswap_apply(int dev, int elem_bytes, const void* x, const void* p, void* out,
+                   int64_t slots, int64_t x_slot_stride, int64_t p_slot_stride, int64_t outer,
+                   int64_t n, int64_t inner, int64_t by, int64_t k, int64_t j, int descending,
+                   void* stream) {
+  CswapGeom g{outer, n, inner, by, k, j, descending};
+  const int rc = mxr::cswap_geom_check(g, elem_bytes, slots, x_slot_stride, p_slot_stride);
+  if (rc <= 0) return rc;
+  if (dev)
+    return mxh_cswap_apply(elem_bytes, x, p, out, slots, x_slot_stride, p_slot_stride, g, stream);
+  DISPATCH_ELEM(elem_bytes, T, {
+    cswap_apply_cpu((const T*)x, (const T*)p, (T*)out, slots, x_slot_stride, p_slot_stride, g);
     return 0;
   });
 }

@@ -2381,6 +2381,228 @@ static int pwl_cross_launch(const void* s0, const void* s1, const void* x0, cons
   return 0;
 }
 
+// The compare-exchange leaves (moosex.h mx_cswap_diff / _cross / _apply).  A stage (k, j)
+// pairs position i with i | j, so in memory it is a butterfly over blocks of 2r contiguous
+// elements, r = j * inner: run index e of a block's low half meets run index e of its high
+// half, and the pair-major arrays (differences, flags, products) are dense at b*r + e.  A lane
+// owns a pair and loads both of its elements; adjacent lanes are adjacent in both runs and in
+// the pair-major array, a lane strides over the slot by the grid, slots are blockIdx.z, read at
+// their strides and written densely.  Forms F: 0 one pair per lane (any u128: every access is
+// 16 bytes as it is); 1 two adjacent pairs of a run per lane (u64, r even, 16-byte aligned
+// operands: every access is 16 bytes); 2 r = 1 (j = 1, inner = 1), where the two elements of
+// a pair are adjacent: one 16-byte load takes both (u64).  The table-mode difference reads
+// the key column only: run index q is element q*unit + off with unit = inner, off = by and
+// r = j.  The stage travels in the kernel's arguments: nothing is uploaded.  Ring arithmetic
+// wraps, so the results equal the CPU twins' bit for bit.  Every output element has one
+// writer.  I: the index type, 32-bit when every extent is below 2^31.
+template <class I>
+struct CswapP {
+  I x_slot, a_slot;  // slot strides of x and of the other operand (flags / products)
+  I total;           // pairs (times columns) of a slot
+  I r, unit, off;    // run length; element of run index q: q*unit + off
+  I sdiv;            // cross: the flag of product g is g / sdiv (inner in table mode, else 1)
+  I amask, k;        // block b is ascending iff (((b & amask) << lj1) & k) == 0, ...
+  I n_x;             // apply: elements of an output slot
+  int rs;            // log2 r where r is a power of two, else -1
+  int lj1, desc, cross;
+};
+
+template <class T_, class I_, int F_>
+struct CswapForm {
+  using T = T_;
+  using I = I_;
+  static constexpr int F = F_;
+};
+
+// block b and the low element of pair g
+template <class I>
+__device__ __forceinline__ I cswap_low_of(const CswapP<I>& p, I g, I& b) {
+  using U = typename std::make_unsigned<I>::type;
+  b = p.rs >= 0 ? (I)((U)g >> p.rs) : (I)((U)g / (U)p.r);
+  return (b * p.r + g) * p.unit + p.off;  // (b*2r + e) with e = g - b*r
+}
+
+template <class T, class I, int F>
+__global__ void __launch_bounds__(256) k_cswap_diff(const T* __restrict__ x, T* __restrict__ out,
+                                                    CswapP<I> p) {
+  constexpr int V = F == 1 ? 2 : 1;
+  using Vec = LaneVec<T, 2>;
+  const T* __restrict__ src = x + (I)blockIdx.z * p.x_slot;
+  T* __restrict__ dst = out + (I)blockIdx.z * p.total;
+  const I step = (I)(gridDim.x * 256u) * V;
+  for (I g = (I)(blockIdx.x * 256u + threadIdx.x) * V; g < p.total; g += step) {
+    I b;
+    const I lo = cswap_low_of(p, g, b);
+    const bool asc = ((((b & p.amask) << p.lj1) & p.k) == 0) != (p.desc != 0);
+    if constexpr (F == 0) {
+      const T a = src[lo], c = src[lo + p.r * p.unit];
+      dst[g] = asc ? c - a : a - c;
+    } else if constexpr (F == 1) {  // r even: both pairs are in block b
+      const Vec a = *reinterpret_cast<const Vec*>(src + lo);
+      const Vec c = *reinterpret_cast<const Vec*>(src + lo + p.r);
+      Vec o;
+#pragma unroll
+      for (int v = 0; v < 2; ++v) o.v[v] = asc ? c.v[v] - a.v[v] : a.v[v] - c.v[v];
+      *reinterpret_cast<Vec*>(dst + g) = o;
+    } else {  // r == 1: the pair is one vector
+      const Vec a = *reinterpret_cast<const Vec*>(src + lo);
+      dst[g] = asc ? a.v[1] - a.v[0] : a.v[0] - a.v[1];
+    }
+  }
+}
+
+template <class T, class I, int F>
+__global__ void __launch_bounds__(256) k_cswap_cross(const T* __restrict__ s0,
+                                                     const T* __restrict__ s1,
+                                                     const T* __restrict__ x0,
+                                                     const T* __restrict__ x1,
+                                                     T* __restrict__ out, CswapP<I> p) {
+  constexpr int V = F == 1 ? 2 : 1;
+  using Vec = LaneVec<T, 2>;
+  using U = typename std::make_unsigned<I>::type;
+  const I xb = (I)blockIdx.z * p.x_slot, sb = (I)blockIdx.z * p.a_slot;
+  T* __restrict__ dst = out + (I)blockIdx.z * p.total;
+  const I step = (I)(gridDim.x * 256u) * V;
+  for (I g = (I)(blockIdx.x * 256u + threadIdx.x) * V; g < p.total; g += step) {
+    I b;
+    const I lo = xb + cswap_low_of(p, g, b);
+    T d0[V], d[V], f0[V], f1[V];
+    if constexpr (F == 0) {
+      d0[0] = x0[lo] - x0[lo + p.r];
+      if (p.cross) d[0] = d0[0] + (x1[lo] - x1[lo + p.r]);
+    } else if constexpr (F == 1) {
+      const Vec a = *reinterpret_cast<const Vec*>(x0 + lo);
+      const Vec c = *reinterpret_cast<const Vec*>(x0 + lo + p.r);
+#pragma unroll
+      for (int v = 0; v < 2; ++v) d0[v] = a.v[v] - c.v[v];
+      if (p.cross) {
+        const Vec a1 = *reinterpret_cast<const Vec*>(x1 + lo);
+        const Vec c1 = *reinterpret_cast<const Vec*>(x1 + lo + p.r);
+#pragma unroll
+        for (int v = 0; v < 2; ++v) d[v] = d0[v] + (a1.v[v] - c1.v[v]);
+      }
+    } else {
+      const Vec a = *reinterpret_cast<const Vec*>(x0 + lo);
+      d0[0] = a.v[0] - a.v[1];
+      if (p.cross) {
+        const Vec a1 = *reinterpret_cast<const Vec*>(x1 + lo);
+        d[0] = d0[0] + (a1.v[0] - a1.v[1]);
+      }
+    }
+    bool flag_vec = false;
+    if constexpr (F == 1) {
+      flag_vec = p.sdiv == 1;
+      if (flag_vec) {  // a flag per product: the two are one vector
+        const Vec f = *reinterpret_cast<const Vec*>(s0 + sb + g);
+        f0[0] = f.v[0], f0[1] = f.v[1];
+        if (p.cross) {
+          const Vec h = *reinterpret_cast<const Vec*>(s1 + sb + g);
+          f1[0] = h.v[0], f1[1] = h.v[1];
+        }
+      }
+    }
+    if (!flag_vec) {
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        const I fi = sb + (p.sdiv == 1 ? g + v : (I)((U)(g + v) / (U)p.sdiv));
+        f0[v] = s0[fi];
+        if (p.cross) f1[v] = s1[fi];
+      }
+    }
+    T o[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) o[v] = p.cross ? f0[v] * d[v] + f1[v] * d0[v] : f0[v] * d0[v];
+    if constexpr (F == 1) {
+      Vec w;
+      w.v[0] = o[0], w.v[1] = o[1];
+      *reinterpret_cast<Vec*>(dst + g) = w;
+    } else {
+      dst[g] = o[0];
+    }
+  }
+}
+
+template <class T, class I, int F>
+__global__ void __launch_bounds__(256) k_cswap_apply(const T* __restrict__ x,
+                                                     const T* __restrict__ pr,
+                                                     T* __restrict__ out, CswapP<I> p) {
+  constexpr int V = F == 1 ? 2 : 1;
+  using Vec = LaneVec<T, 2>;
+  const T* __restrict__ src = x + (I)blockIdx.z * p.x_slot;
+  const T* __restrict__ q = pr + (I)blockIdx.z * p.a_slot;
+  T* __restrict__ dst = out + (I)blockIdx.z * p.n_x;
+  const I step = (I)(gridDim.x * 256u) * V;
+  for (I g = (I)(blockIdx.x * 256u + threadIdx.x) * V; g < p.total; g += step) {
+    I b;
+    const I lo = cswap_low_of(p, g, b);
+    if constexpr (F == 0) {
+      const T d = q[g];
+      dst[lo] = src[lo] - d;
+      dst[lo + p.r] = src[lo + p.r] + d;
+    } else if constexpr (F == 1) {
+      const Vec d = *reinterpret_cast<const Vec*>(q + g);
+      Vec a = *reinterpret_cast<const Vec*>(src + lo);
+      Vec c = *reinterpret_cast<const Vec*>(src + lo + p.r);
+#pragma unroll
+      for (int v = 0; v < 2; ++v) a.v[v] -= d.v[v], c.v[v] += d.v[v];
+      *reinterpret_cast<Vec*>(dst + lo) = a;
+      *reinterpret_cast<Vec*>(dst + lo + p.r) = c;
+    } else {
+      const T d = q[g];
+      Vec a = *reinterpret_cast<const Vec*>(src + lo);
+      a.v[0] -= d, a.v[1] += d;
+      *reinterpret_cast<Vec*>(dst + lo) = a;
+    }
+  }
+}
+
+// the parameters of a stage: `key_only` walks the key column's pairs (the table-mode difference)
+template <class I>
+static CswapP<I> cswap_params(const mxr::CswapGeom& g, bool key_only, int64_t x_slot,
+                              int64_t a_slot, bool cross) {
+  CswapP<I> p;
+  std::memset(&p, 0, sizeof(p));
+  const int64_t r = key_only ? g.j : g.j * g.inner;
+  p.x_slot = (I)x_slot, p.a_slot = (I)a_slot;
+  p.total = (I)(key_only ? g.outer * g.half : g.n_pair);
+  p.r = (I)r, p.unit = (I)(key_only ? g.inner : 1), p.off = (I)(key_only ? g.by : 0);
+  p.sdiv = (I)(g.by >= 0 ? g.inner : 1);
+  p.amask = (I)(g.n / (2 * g.j) - 1), p.k = (I)g.k, p.n_x = (I)g.n_x;
+  p.rs = -1;
+  if ((r & (r - 1)) == 0)
+    for (p.rs = 0; ((int64_t)1 << p.rs) < r;) ++p.rs;
+  p.lj1 = g.lj + 1, p.desc = g.descending, p.cross = cross;
+  return p;
+}
+
+// launch(CswapForm<T, I, F>{}): u64 takes form 2 when r == 1 and form 1 when r is even, where
+// `wide` (unit stride, every operand and slot stride on 16 bytes) allows; u128 form 0
+template <class L>
+static int cswap_dispatch(int elem_bytes, bool small, bool wide, int64_t r, L launch) {
+#define MX_CSWAP_FORM(T, F)                                 \
+  return small ? launch(CswapForm<T, int32_t, F>{}) : launch(CswapForm<T, int64_t, F>{})
+  switch (elem_bytes) {
+    case 8:
+      if (wide && r == 1) {
+        MX_CSWAP_FORM(u64, 2);
+      }
+      if (wide && r % 2 == 0) {
+        MX_CSWAP_FORM(u64, 1);
+      }
+      MX_CSWAP_FORM(u64, 0);
+    case 16: MX_CSWAP_FORM(u128, 0);
+    default: return -2;
+  }
+#undef MX_CSWAP_FORM
+}
+
+// the grid is capped at 256 CUs x 8 blocks per slot; a lane strides over the rest
+static dim3 cswap_grid(int64_t total, int F, int64_t slots) {
+  const int64_t lanes = F == 1 ? total / 2 : total;
+  return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((lanes + 255) / 256, 256 * 8)), 1,
+              (unsigned)slots);
+}
+
 // party-batched twins of the per-party sessions' local kernels (party_batch.h)
 MX_X3_GS(k_binary2<u64>, d_binary2<u64>);
 MX_X3_GS(k_binary2<u128>, d_binary2<u128>);
@@ -2720,6 +2942,66 @@ int mxh_pwl_cross(int elem_bytes, const void* s0, const void* s1, const void* x0
     using F = decltype(f);
     return pwl_cross_launch<typename F::T, typename F::I, F::V>(
         s0, s1, x0, x1, out, slots, s_slot_stride, x_slot_stride, n, k, da, db, ak, stream);
+  });
+}
+
+int mxh_cswap_diff(int elem_bytes, const void* x, void* out, int64_t slots, int64_t x_slot_stride,
+                   const mxr::CswapGeom& g, void* stream) {
+  if (slots > 65535) return -3;
+  const bool key_only = g.by >= 0;
+  const int64_t r = key_only ? g.j : g.j * g.inner;
+  const bool small = fits32(1 << 23, {(slots - 1) * x_slot_stride + g.n_x, slots * g.n_flag});
+  const bool wide = (!key_only || g.inner == 1) && aligned16(x) && aligned16(out) &&
+                    x_slot_stride % 2 == 0;
+  return cswap_dispatch(elem_bytes, small, wide, r, [&](auto f) {
+    using F = decltype(f);
+    using T = typename F::T;
+    const auto p = cswap_params<typename F::I>(g, key_only, x_slot_stride, 0, false);
+    hipLaunchKernelGGL((k_cswap_diff<T, typename F::I, F::F>), cswap_grid(g.n_flag, F::F, slots),
+                       dim3(256), 0, S(stream), (const T*)x, (T*)out, p);
+    MX_LAUNCH_CHECK();
+    return 0;
+  });
+}
+
+int mxh_cswap_cross(int elem_bytes, const void* s0, const void* s1, const void* x0,
+                    const void* x1, void* out, int64_t slots, int64_t s_slot_stride,
+                    int64_t x_slot_stride, const mxr::CswapGeom& g, void* stream) {
+  if (slots > 65535 || (s1 == nullptr) != (x1 == nullptr)) return -3;
+  const bool small = fits32(1 << 23, {(slots - 1) * x_slot_stride + g.n_x,
+                                      (slots - 1) * s_slot_stride + g.n_flag, slots * g.n_pair});
+  const bool wide = aligned16(s0) && aligned16(s1) && aligned16(x0) && aligned16(x1) &&
+                    aligned16(out) && s_slot_stride % 2 == 0 && x_slot_stride % 2 == 0;
+  return cswap_dispatch(elem_bytes, small, wide, g.j * g.inner, [&](auto f) {
+    using F = decltype(f);
+    using T = typename F::T;
+    const auto p =
+        cswap_params<typename F::I>(g, false, x_slot_stride, s_slot_stride, x1 != nullptr);
+    hipLaunchKernelGGL((k_cswap_cross<T, typename F::I, F::F>),
+                       cswap_grid(g.n_pair, F::F, slots), dim3(256), 0, S(stream), (const T*)s0,
+                       (const T*)s1, (const T*)x0, (const T*)x1, (T*)out, p);
+    MX_LAUNCH_CHECK();
+    return 0;
+  });
+}
+
+int mxh_cswap_apply(int elem_bytes, const void* x, const void* pr, void* out, int64_t slots,
+                    int64_t x_slot_stride, int64_t p_slot_stride, const mxr::CswapGeom& g,
+                    void* stream) {
+  if (slots > 65535) return -3;
+  const bool small = fits32(1 << 23, {(slots - 1) * x_slot_stride + g.n_x,
+                                      (slots - 1) * p_slot_stride + g.n_pair, slots * g.n_x});
+  const bool wide = aligned16(x) && aligned16(pr) && aligned16(out) && x_slot_stride % 2 == 0 &&
+                    p_slot_stride % 2 == 0;
+  return cswap_dispatch(elem_bytes, small, wide, g.j * g.inner, [&](auto f) {
+    using F = decltype(f);
+    using T = typename F::T;
+    const auto p = cswap_params<typename F::I>(g, false, x_slot_stride, p_slot_stride, false);
+    hipLaunchKernelGGL((k_cswap_apply<T, typename F::I, F::F>),
+                       cswap_grid(g.n_pair, F::F, slots), dim3(256), 0, S(stream), (const T*)x,
+                       (const T*)pr, (T*)out, p);
+    MX_LAUNCH_CHECK();
+    return 0;
   });
 }
 

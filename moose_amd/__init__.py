@@ -99,6 +99,11 @@ from moose_amd.edsl.base import piecewise_linear  # noqa: F401
 from moose_amd.edsl.base import relu6  # noqa: F401
 from moose_amd.edsl.base import tanh  # noqa: F401
 from moose_amd.edsl.base import thresholded_relu  # noqa: F401
+from moose_amd.edsl.base import median  # noqa: F401
+from moose_amd.edsl.base import quantile  # noqa: F401
+from moose_amd.edsl.base import sort  # noqa: F401
+from moose_amd.edsl.base import sort_rows  # noqa: F401
+from moose_amd.edsl.base import top_k  # noqa: F401
 from moose_amd.edsl.base import permute  # noqa: F401
 from moose_amd.edsl.tracer import trace  # noqa: F401
 from moose_amd.edsl.tracer import trace_and_compile  # noqa: F401

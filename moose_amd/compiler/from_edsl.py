@@ -97,6 +97,11 @@ _OPS = {
                    "weight_bits": list(o.weight_bits), "data_format": o.data_format},
     ),
     "PermuteOperation": ("Permute", ["x"], lambda o: {"axes": list(o.axes)}),
+    "SortOperation": (
+        "Sort",
+        ["x"],
+        lambda o: {"axis": int(o.axis), "descending": bool(o.descending), "by": int(o.by)},
+    ),
     "PiecewiseLinearOperation": (
         "PiecewiseLinear",
         ["x"],

@@ -91,6 +91,7 @@ OPERATION_TABLE = [
     ("PermuteOperation", ["axes"]),
     ("DepthwiseConvOperation", ["strides", "pads", "dilations", "data_format"]),
     ("PiecewiseLinearOperation", ["breakpoints", "slopes", "intercepts"]),
+    ("SortOperation", ["axis", "descending", "by"]),
 ]
 
 OPERATION_CLASSES = {}

@@ -769,6 +769,136 @@ def permute(x, axes, placement=None):
     return e
 
 
+# ---------------------------------------------------------------------------
+# sorting and order statistics (one Sort operator each)
+# ---------------------------------------------------------------------------
+QUANTILE_INTERPOLATIONS = ("linear", "lower", "higher", "midpoint")
+
+
+def _sort_shape(fn, x, input_shape, need):
+    """The static shape of ``x`` (``input_shape=`` first), or None where it is unknown and not
+    needed."""
+    shape = tuple(input_shape) if input_shape is not None else x.static_shape
+    if shape is None:
+        if need:
+            raise ValueError(
+                f"`{fn}` needs the static length of the axis it works along: pass "
+                "`input_shape=`, or give the pm.Argument a `shape=`")
+        return None
+    return tuple(None if s is None or s < 0 else int(s) for s in shape)
+
+
+def _sort_axis(fn, axis, shape):
+    if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)):
+        raise ValueError(f"`{fn}`: `axis` must be an int, found {axis!r}")
+    axis = int(axis)
+    if shape is not None:
+        if not -len(shape) <= axis < len(shape):
+            raise ValueError(f"`{fn}`: axis {axis} out of range for a tensor of rank {len(shape)}")
+        axis %= len(shape)
+    return axis
+
+
+def sort(x, axis=-1, descending=False, placement=None):
+    """``x`` sorted along ``axis``, ascending unless ``descending``.  On a secret fixed-point
+    ``x`` a bitonic sorting network: log2 n (log2 n + 1) / 2 compare-exchange stages for an
+    axis of length n (padded to a power of two), each one sign extraction and one
+    multiplication; exact -- the result holds the input's values, reordered."""
+    axis = _sort_axis("sort", axis, x.static_shape)
+    e = _expr("sort", [x], x.vtype, placement, axis=axis, descending=bool(descending), by=-1)
+    e.static_shape = x.static_shape
+    return e
+
+
+def sort_rows(x, by=0, descending=False, placement=None):
+    """The rows of a rank-2 ``x`` reordered so that column ``by`` is sorted; rows with equal
+    keys come out in unspecified order.  On a secret ``x`` the key column has to stay strictly
+    inside the fixed-point type's range (a key equal to the largest encodable value may change
+    places with the network's padding)."""
+    if isinstance(by, bool) or not isinstance(by, (int, np.integer)) or by < 0:
+        raise ValueError(f"`sort_rows`: `by` must be a column index, found {by!r}")
+    shp = x.static_shape
+    if shp is not None and (len(shp) != 2 or (shp[1] is not None and not by < shp[1])):
+        raise ValueError(f"`sort_rows` expects a rank-2 tensor with more than {by} columns, "
+                         f"found shape {shp}")
+    e = _expr("sort", [x], x.vtype, placement, axis=0, descending=bool(descending), by=int(by))
+    e.static_shape = shp
+    return e
+
+
+def top_k(x, k, axis=-1, largest=True, placement=None, input_shape=None):
+    """The ``k`` largest (``largest=False``: smallest) values along ``axis``, sorted from the
+    extreme inwards: a sort and a slice.  A negative ``axis`` needs the rank of ``x`` (a
+    ``shape=`` on the pm.Argument, or ``input_shape=``)."""
+    fn = "top_k"
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError(f"`{fn}`: `k` must be a positive int, found {k!r}")
+    shape = _sort_shape(fn, x, input_shape, need=axis < 0)
+    axis = _sort_axis(fn, axis, shape)
+    if shape is not None and shape[axis] is not None and k > shape[axis]:
+        raise ValueError(f"`{fn}`: k = {k} exceeds the axis length {shape[axis]}")
+    s = sort(x, axis, descending=bool(largest), placement=placement)
+    y = strided_slice(s, [slice(None)] * axis + [slice(0, int(k))], placement)
+    if shape is not None:
+        y.static_shape = shape[:axis] + (int(k),) + shape[axis + 1:]
+    return y
+
+
+def quantile(x, q, axis=-1, interpolation="linear", placement=None, input_shape=None):
+    """The ``q``-quantile (public ``q`` in [0, 1]) along ``axis``, which is dropped, as
+    ``numpy.quantile``: with ``pos = q * (n - 1)`` the order statistics at ``floor(pos)`` and
+    ``ceil(pos)`` are combined by ``interpolation`` -- ``lower``, ``higher``, ``midpoint`` or
+    ``linear``.  ``lower`` and ``higher`` are exact; the other two cost one multiplication by a
+    public weight and its truncation.  Needs the length of the axis: a ``shape=`` on the
+    pm.Argument, a constant, or ``input_shape=``."""
+    fn = "quantile"
+    if interpolation not in QUANTILE_INTERPOLATIONS:
+        raise ValueError(f"`{fn}`: interpolation must be one of {QUANTILE_INTERPOLATIONS}, found "
+                         f"{interpolation!r}")
+    if isinstance(q, bool) or not isinstance(q, (int, float, np.integer, np.floating)) \
+            or not 0.0 <= float(q) <= 1.0:
+        raise ValueError(f"`{fn}`: q must be a real number in [0, 1], found {q!r}")
+    shape = _sort_shape(fn, x, input_shape, need=True)
+    axis = _sort_axis(fn, axis, shape)
+    n = shape[axis]
+    if n is None or n < 1:
+        raise ValueError(f"`{fn}` needs the static length of axis {axis}, found shape {shape}: "
+                         "pass `input_shape=`, or give the pm.Argument a `shape=`")
+    pos = float(q) * (n - 1)
+    lo, hi = int(np.floor(pos)), int(np.ceil(pos))
+    s = sort(x, axis, placement=placement)
+    out_shape = shape[:axis] + shape[axis + 1:]
+
+    def stat(i):
+        e = index_axis(s, axis, i, placement)
+        e.static_shape = out_shape
+        return e
+
+    if interpolation == "lower" or lo == hi:
+        return stat(lo)
+    if interpolation == "higher":
+        return stat(hi)
+    a, b = stat(lo), stat(hi)
+    g = 0.5 if interpolation == "midpoint" else pos - lo
+    d = x.vtype.dtype if isinstance(x.vtype, ty.TensorType) else None
+    if d is not None and d.is_fixedpoint:  # the weight rounded to the nearest encodable one
+        f = d.fractional_precision
+        g = float(Fraction(int(round(Fraction(g) * (1 << f))), 1 << f))
+    w = constant(float(g), vtype=x.vtype, placement=placement)
+    y = add(a, mul(sub(b, a, placement), w, placement), placement)
+    y.static_shape = out_shape
+    return y
+
+
+def median(x, axis=-1, placement=None, input_shape=None):
+    """The median along ``axis`` (dropped): the middle order statistic of an odd length,
+    exact; the mean of the two middle ones of an even length."""
+    try:
+        return quantile(x, 0.5, axis, "linear", placement, input_shape)
+    except ValueError as e:
+        raise ValueError(str(e).replace("`quantile`", "`median`")) from None
+
+
 def _conv_geometry(fn, shape, kernel_shape, strides, pads, dilations, data_format):
     """Validated attributes of a 2-D window op, and (C, H, W, OH, OW) where the static
     ``shape`` (rank 4, batch entry may be None) is known."""

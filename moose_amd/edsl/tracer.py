@@ -67,6 +67,7 @@ _OPS = {
                        ["strides", "pads", "dilations", "data_format"]),
     "piecewise_linear": ("PiecewiseLinearOperation", ["x"], "piecewise_linear",
                          ["breakpoints", "slopes", "intercepts"]),
+    "sort": ("SortOperation", ["x"], "sort", ["axis", "descending", "by"]),
     "shape": ("ShapeOperation", ["x"], "shape", []),
     "mux": ("MuxOperation", ["selector", "x", "y"], "mux", []),
     "load": ("LoadOperation", ["key", "query"], "load", []),

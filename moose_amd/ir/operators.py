@@ -162,6 +162,11 @@ EXTENSION_OPERATORS = {
     # segment i is slopes[i] * x + intercepts[i] on [breakpoints[i-1], breakpoints[i]).  On a
     # secret x: one stacked sign extraction for the k flags, one local kernel, one truncation
     "PiecewiseLinear": [("breakpoints", "ints"), ("slopes", "ints"), ("intercepts", "ints")],
+    # sort along `axis` (ascending unless `descending`); by >= 0: the rows of a rank-2 tensor
+    # reordered so that column `by` is sorted (equal keys in unspecified order).  On a secret
+    # fixed-point x: a bitonic network of compare-exchange stages, each one sign extraction and
+    # one multiplication, exact (nothing truncates)
+    "Sort": [("axis", "int"), ("descending", "bool"), ("by", "int")],
 }
 
 ALL_OPERATORS = {**OPERATORS, **EXTENSION_OPERATORS}

@@ -46,6 +46,17 @@ _SIGS = {
     #  stream)
     "mx_pwl_cross": (c_int, [c_int, c_int] + [c_vp] * 5 + [c_i64] * 4 + [c_int] + [c_vp] * 3
                      + [c_vp]),
+    # (dev, elem_bytes, x out, slots, x_slot_stride, outer n inner by k j, descending, stream)
+    "mx_cswap_diff": (c_int, [c_int, c_int] + [c_vp] * 2 + [c_i64] * 2 + [c_i64] * 6 + [c_int]
+                      + [c_vp]),
+    # (dev, elem_bytes, s0 s1 x0 x1 out, slots, s_slot_stride, x_slot_stride, outer n inner by
+    #  k j, descending, stream)
+    "mx_cswap_cross": (c_int, [c_int, c_int] + [c_vp] * 5 + [c_i64] * 3 + [c_i64] * 6 + [c_int]
+                       + [c_vp]),
+    # (dev, elem_bytes, x p out, slots, x_slot_stride, p_slot_stride, outer n inner by k j,
+    #  descending, stream)
+    "mx_cswap_apply": (c_int, [c_int, c_int] + [c_vp] * 3 + [c_i64] * 3 + [c_i64] * 6 + [c_int]
+                       + [c_vp]),
     # (dev, elem_bytes, x0 x1 w0 w1 out, slots, x_slot_stride, w_slot_stride, N C H W mult,
     #  KH KW, sh sw, pt pl, dh dw, OH OW, nhwc, stream)
     "mx_dwconv": (c_int, [c_int, c_int] + [c_vp] * 5 + [c_i64] * 3 + [c_i64] * 15

@@ -27,6 +27,7 @@ import threading
 from contextlib import contextmanager
 from fractions import Fraction
 from typing import List
+from typing import NamedTuple
 from typing import Sequence
 
 import numpy as np
@@ -1401,6 +1402,230 @@ def pwl(s: RT, x: RT, da, db, ak, nb=0) -> RT:
     s[j]`` over the flag planes ``s`` ([.., k, *shape]) -- a host's ring tensor, or slot-wise
     use."""
     return pwl_cross(s, None, x, None, da, db, ak, nb)
+
+
+# ---------------------------------------------------------------------------
+# compare-exchange stages of a bitonic sorting network
+# ---------------------------------------------------------------------------
+# the device path of cswap_diff / cswap_cross / cswap_apply: the native kernels (True) or the
+# torch compositions cswap_*_torch (False); a CPU tensor always takes the native loops
+CSWAP_KERNEL = True
+
+
+class CswapGeom(NamedTuple):
+    """One stage (k, j) of a bitonic network along the middle axis of an [outer, n, inner]
+    array (csrc/cswap_geom.h): element (o, pos, c) lives at (o*n + pos)*inner + c; n, k, j
+    powers of two with j < k <= n; ``by = -1`` sorts every inner index on its own, ``by >= 0``
+    orders whole rows by column ``by`` (table mode)."""
+
+    outer: int
+    n: int
+    inner: int
+    by: int = -1
+    k: int = 2
+    j: int = 1
+    descending: bool = False
+
+    @property
+    def cols(self):
+        return 1 if self.by >= 0 else self.inner
+
+
+def cswap_stages(n: int):
+    """The (k, j) stages of a bitonic network on n = 2^m elements: m (m + 1) / 2 of them."""
+    out, k = [], 2
+    while k <= n:
+        j = k // 2
+        while j >= 1:
+            out.append((k, j))
+            j //= 2
+        k *= 2
+    return out
+
+
+def cswap_pairs(g: CswapGeom):
+    """(i, l, ascending) of the n/2 pairs of stage ``g``: i is t with a zero bit inserted at
+    bit log2 j, l = i | j, ascending iff (i & k) == 0, flipped by ``descending``."""
+    lj = g.j.bit_length() - 1
+    out = []
+    for t in range(g.n // 2):
+        i = ((t >> lj) << (lj + 1)) | (t & (g.j - 1))
+        out.append((i, i | g.j, ((i & g.k) == 0) != bool(g.descending)))
+    return out
+
+
+def _cswap_check(what, g: CswapGeom, nb, x: RT, others=()):
+    g = CswapGeom(*(int(v) for v in g))
+    n, k, j = g.n, g.k, g.j
+    if (g.outer < 0 or g.inner < 0 or n < 2 or n & (n - 1) or k & (k - 1) or j < 1 or j & (j - 1)
+            or not j < k <= n or not -1 <= g.by < max(g.inner, 1)):
+        raise ValueError(f"{what}: malformed stage {g}")
+    bits = x.bits
+    if bits not in (64, 128) or any(t.bits != bits for t, _ in others if t is not None):
+        raise ValueError(f"{what} is arithmetic only: operands over one of Z_2^64 / Z_2^128")
+    if nb not in (0, 1):
+        raise ValueError(f"{what} takes at most one batch dim")
+    lead = tuple(x.shape[:nb])
+    if math.prod(x.shape[nb:]) != g.outer * n * g.inner:
+        raise ValueError(f"{what}: operand of shape {tuple(x.shape)} does not hold "
+                         f"{g.outer} x {n} x {g.inner} elements after {nb} batch dims")
+    for t, want in others:
+        if t is not None and (tuple(t.shape[:nb]) != lead or math.prod(t.shape[nb:]) != want):
+            raise ValueError(f"{what}: operand of shape {tuple(t.shape)}, expected {want} "
+                             f"elements after the batch dims {lead}")
+    return g, bits, lead
+
+
+def _cswap_args(g: CswapGeom):
+    return (g.outer, g.n, g.inner, g.by, g.k, g.j, int(bool(g.descending)))
+
+
+def _cswap_halves(t: RT, g: CswapGeom, nb, cols):
+    """The low and the high element of every pair as two [.., outer, n/(2j), j, cols] views."""
+    lead = tuple(t.shape[:nb])
+    v = reshape(RT(t.data, t.bits), (g.outer, g.n // (2 * g.j), 2, g.j, cols), nb)
+    return (RT(v.data.select(nb + 2, 0), t.bits), RT(v.data.select(nb + 2, 1), t.bits)), lead
+
+
+def cswap_diff_torch(x: RT, g: CswapGeom, nb=0) -> RT:
+    """:func:`cswap_diff` as a composition of the existing kernels (slices, a subtraction and a
+    product with the public +-1 direction of every block): the benchmark's opponent."""
+    g, bits, lead = _cswap_check("cswap_diff", g, nb, x)
+    cols = g.cols
+    if g.by >= 0:
+        x = slice_axis(reshape(x, (g.outer, g.n, g.inner), nb), 2, g.by, g.by + 1, nb=nb)
+    (lo, hi), _ = _cswap_halves(x, g, nb, cols)
+    c = binary("sub", hi, lo)
+    blocks = g.n // (2 * g.j)
+    dirs = [1 if (((a * 2 * g.j) & g.k) == 0) != bool(g.descending) else -1
+            for a in range(blocks)]
+    if any(d < 0 for d in dirs):
+        c = binary("mul", c, reshape(const_ints(dirs, bits, x.device), (blocks, 1, 1)))
+    return reshape(c, (g.outer, g.n // 2, cols), nb)
+
+
+def cswap_cross_torch(s0: RT, s1, x0: RT, x1, g: CswapGeom, nb=0) -> RT:
+    """:func:`cswap_cross` as a composition of the existing kernels."""
+    g, bits, lead = _cswap_check("cswap_cross", g, nb, x0, _cswap_others(g, s0, s1, x1))
+    blocks = g.n // (2 * g.j)
+
+    def diff(x):
+        (lo, hi), _ = _cswap_halves(x, g, nb, g.inner)
+        return binary("sub", lo, hi)
+
+    def flags(s):
+        return reshape(s, (g.outer, blocks, g.j, g.cols), nb)
+
+    d0 = diff(x0)
+    if x1 is None:
+        v = binary("mul", flags(s0), d0)
+    else:
+        v = binary("add", binary("mul", flags(s0), binary("add", d0, diff(x1))),
+                   binary("mul", flags(s1), d0))
+    return reshape(v, (g.outer, g.n // 2, g.inner), nb)
+
+
+def cswap_apply_torch(x: RT, p: RT, g: CswapGeom, nb=0) -> RT:
+    """:func:`cswap_apply` as a composition of the existing kernels."""
+    g, bits, lead = _cswap_check("cswap_apply", g, nb, x,
+                                 ((p, g.outer * (g.n // 2) * g.inner),))
+    (lo, hi), _ = _cswap_halves(x, g, nb, g.inner)
+    pp = reshape(p, (g.outer, g.n // (2 * g.j), g.j, g.inner), nb)
+    lo, hi = binary("sub", lo, pp), binary("add", hi, pp)
+    out = RT(torch.stack((lo.data, hi.data), dim=nb + 2), bits)
+    return reshape(out, x.shape[nb:], nb)
+
+
+def _cswap_others(g, s0, s1, x1):
+    nf = g.outer * (g.n // 2) * g.cols
+    if (s1 is None) != (x1 is None):
+        raise ValueError("cswap_cross: the cross form takes both next components")
+    return ((s0, nf), (s1, nf), (x1, g.outer * g.n * g.inner))
+
+
+def cswap_diff(x: RT, g: CswapGeom, nb=0) -> RT:
+    """The signed differences of stage ``g``'s pairs, exact in the ring: ``x[l] - x[i]`` for an
+    ascending pair, ``x[i] - x[l]`` for a descending one -- negative where the pair is out of
+    order -- as [.., outer, n/2, inner], or on the key column only, [.., outer, n/2, 1], in
+    table mode.  One native launch over all batch slots (``mx_cswap_diff``); a [slots, ...]
+    view with dense slots is read in place and the stage travels in the launch's arguments."""
+    g, bits, lead = _cswap_check("cswap_diff", g, nb, x)
+    shape = lead + (g.outer, g.n // 2, g.cols)
+    if x.device.type == "meta":  # shape inference of the symbolic session
+        return empty(shape, bits, x.device)
+    if x.device.type == "cuda" and not CSWAP_KERNEL:
+        return cswap_diff_torch(x, g, nb)
+    out = empty(shape, bits, x.device)
+    if out.data.numel() == 0:
+        return out
+    xd, xst = _leaf_operand(x, nb, g.outer * g.n * g.inner)
+    nat.check(
+        nat.lib().mx_cswap_diff(nat.dev_of(out.data), _elem_bytes(bits), nat.ptr(xd),
+                                nat.ptr(out.data), math.prod(lead), xst, *_cswap_args(g),
+                                nat.stream_of(out.data)),
+        "cswap_diff",
+    )
+    return out
+
+
+def cswap_cross(s0: RT, s1, x0: RT, x1, g: CswapGeom, nb=0) -> RT:
+    """One party's local product of the flags and the differences of stage ``g``: with ``D =
+    x[i] - x[l]``, ``s0 * (D0 + D1) + s1 * D0`` (own times the sum plus next times own, as
+    :func:`pwl_cross`) as [.., outer, n/2, inner]; the flags are [.., outer, n/2, inner], or
+    [.., outer, n/2, 1] broadcast over the columns in table mode.  ``s1 = x1 = None``: the
+    plain form ``s0 * D0``.  One native launch over all batch slots (``mx_cswap_cross``)."""
+    g, bits, lead = _cswap_check("cswap_cross", g, nb, x0, _cswap_others(g, s0, s1, x1))
+    shape = lead + (g.outer, g.n // 2, g.inner)
+    if x0.device.type == "meta":
+        return empty(shape, bits, x0.device)
+    if x0.device.type == "cuda" and not CSWAP_KERNEL:
+        return cswap_cross_torch(s0, s1, x0, x1, g, nb)
+    out = empty(shape, bits, x0.device)
+    if out.data.numel() == 0:
+        return out
+    nf, nx = g.outer * (g.n // 2) * g.cols, g.outer * g.n * g.inner
+    sd0, sst = _leaf_operand(s0, nb, nf)
+    xd0, xst = _leaf_operand(x0, nb, nx)
+    sd1 = xd1 = None
+    if s1 is not None:
+        sd1, sst1 = _leaf_operand(s1, nb, nf)
+        xd1, xst1 = _leaf_operand(x1, nb, nx)
+        sd0, sd1, sst = _leaf_pair(sd0, sst, sd1, sst1, nf)
+        xd0, xd1, xst = _leaf_pair(xd0, xst, xd1, xst1, nx)
+    nat.check(
+        nat.lib().mx_cswap_cross(
+            nat.dev_of(out.data), _elem_bytes(bits), nat.ptr(sd0),
+            nat.ptr(sd1) if sd1 is not None else None, nat.ptr(xd0),
+            nat.ptr(xd1) if xd1 is not None else None, nat.ptr(out.data), math.prod(lead), sst,
+            xst, *_cswap_args(g), nat.stream_of(out.data)),
+        "cswap_cross",
+    )
+    return out
+
+
+def cswap_apply(x: RT, p: RT, g: CswapGeom, nb=0) -> RT:
+    """The exchange of stage ``g``: ``out[i] = x[i] - p[t]`` and ``out[l] = x[l] + p[t]`` with
+    the products ``p`` [.., outer, n/2, inner], in ``x``'s shape.  With ``p = s * (x[i] -
+    x[l])`` and ``s`` the 0/1 flag of an out-of-order pair, the pair is swapped where it has to
+    be.  One native launch over all batch slots (``mx_cswap_apply``)."""
+    g, bits, lead = _cswap_check("cswap_apply", g, nb, x, ((p, g.outer * (g.n // 2) * g.inner),))
+    shape = tuple(x.shape)
+    if x.device.type == "meta":
+        return empty(shape, bits, x.device)
+    if x.device.type == "cuda" and not CSWAP_KERNEL:
+        return cswap_apply_torch(x, p, g, nb)
+    out = empty(shape, bits, x.device)
+    if out.data.numel() == 0:
+        return out
+    xd, xst = _leaf_operand(x, nb, g.outer * g.n * g.inner)
+    pd, pst = _leaf_operand(p, nb, g.outer * (g.n // 2) * g.inner)
+    nat.check(
+        nat.lib().mx_cswap_apply(nat.dev_of(out.data), _elem_bytes(bits), nat.ptr(xd),
+                                 nat.ptr(pd), nat.ptr(out.data), math.prod(lead), xst, pst,
+                                 *_cswap_args(g), nat.stream_of(out.data)),
+        "cswap_apply",
+    )
+    return out
 
 
 def select_mask(a: RT, axis: int, mask: torch.Tensor, nb=0) -> RT:

@@ -453,6 +453,58 @@ def maximum(sess, xs):
     return xs[0]
 
 
+def check_sort_width(integ: int, frac: int, bits: int, what="sort") -> int:
+    """A sort compares by the sign of a difference of two fixed(integ, frac) values, which
+    spans integ + frac + 2 bits: the width it needs, or an error where the ring is narrower."""
+    w = integ + frac + 2
+    if w > bits:
+        raise ValueError(
+            f"{what}: comparing fixed({integ}, {frac}) values takes the sign of a difference of "
+            f"{w} bits (integral + fractional + 2), but Z_2^{bits} holds {bits}")
+    return w
+
+
+def sort(sess, x: RepFixed, axis: int = -1, descending: bool = False, by: int = -1) -> RepFixed:
+    """``x`` sorted along ``axis`` by a bitonic network (rep.sort_network), exact: the result
+    holds the ring values of the input, reordered.  ``by >= 0``: the rows of a rank-2 ``x``
+    reordered so that column ``by`` is sorted (``axis`` is 0; rows with equal keys come out in
+    unspecified order).  The axis is padded to the next power of two with public sentinel
+    shares -- the largest encodable value 2^(integ + frac) - 1 for an ascending sort, its
+    negative for a descending one -- which sort to the end and are sliced off.  In table mode a
+    row whose key EQUALS the sentinel may change places with a padding row, so the key column
+    has to stay strictly inside the type's range (|key| < 2^integ - 2^-frac); a plain sort has
+    no such condition, as equal values are interchangeable."""
+    shape = tuple(shape_of(sess, x))
+    nd = len(shape)
+    if by >= 0:
+        if nd != 2 or not by < shape[1]:
+            raise ValueError(f"sort: by={by} takes a rank-2 value with more than {by} columns, "
+                             f"found shape {shape}")
+        axis = 0
+    if nd == 0:
+        return x
+    if not -nd <= axis < nd:
+        raise ValueError(f"sort: axis {axis} out of range for rank {nd}")
+    axis %= nd
+    n = shape[axis]
+    w = check_sort_width(x.integ, x.frac, x.bits)
+    if n <= 1 or math.prod(shape) == 0:
+        return x
+    N = 1 << (n - 1).bit_length()
+    t = x.t
+    if N > n:
+        top = (1 << (x.integ + x.frac)) - 1
+        pshape = shape[:axis] + (N - n,) + shape[axis + 1:]
+        pad = rep.from_public(sess, x.plc, R.fill(pshape, -top if descending else top, x.bits,
+                                                  sess.device), x.bits)
+        t = concat(sess, [t, pad], axis)
+    geom = R.CswapGeom(math.prod(shape[:axis]), N, math.prod(shape[axis + 1:]), by)
+    t = rep.sort_network(sess, t, geom, descending, width=w if 2 < w < x.bits else None)
+    if N > n:
+        t = local(sess, t, "StridedSlice", slices=[slice(None)] * axis + [slice(0, n)])
+    return _with(x, t)
+
+
 # ---------------------------------------------------------------------------
 # normalisation: leading-bit one-hot
 # ---------------------------------------------------------------------------

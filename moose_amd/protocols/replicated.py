@@ -1159,6 +1159,81 @@ def pwl_trunc(sess, x: RepTensor, T, DA, DB, AK, m: int, width=None) -> RepTenso
     return trunc_pr(sess, z, m) if m else z
 
 
+def _cswap_halves(sess, x: RepTensor, g, cols):
+    """The low and the high element of every pair, [outer, n/(2j), j, cols] each."""
+    v = local(sess, x, "Reshape", shape=(g.outer, g.n // (2 * g.j), 2, g.j, cols))
+    return (local(sess, v, "IndexAxis", axis=2, index=0),
+            local(sess, v, "IndexAxis", axis=2, index=1))
+
+
+def _cswap_diff_composed(sess, x: RepTensor, g) -> RepTensor:
+    """R.cswap_diff from Reshape, IndexAxis, Sub and a product with the public +-1 direction
+    of every block -- the operators a lowered graph's executor already has.  The result
+    keeps the pairs as [outer, n/(2j), j, cols]."""
+    if g.by >= 0:
+        x = local(sess, local(sess, x, "Reshape", shape=(g.outer, g.n, g.inner)), "IndexAxis",
+                  axis=2, index=g.by)
+    lo, hi = _cswap_halves(sess, x, g, g.cols)
+    c = sub(sess, hi, lo)
+    blocks = g.n // (2 * g.j)
+    dirs = [1 if (((a * 2 * g.j) & g.k) == 0) != bool(g.descending) else -1
+            for a in range(blocks)]
+    if any(d < 0 for d in dirs):
+        c = mul_public(sess, c, R.reshape(R.const_ints(dirs, x.bits, "cpu"), (blocks, 1, 1)))
+    return c
+
+
+def _cswap_apply_composed(sess, x: RepTensor, p: RepTensor, g, shape) -> RepTensor:
+    """R.cswap_apply from Reshape, IndexAxis, Sub, Add and Concat; ``p`` as
+    :func:`_cswap_diff_composed` keeps the pairs."""
+    lo, hi = _cswap_halves(sess, x, g, g.inner)
+    lo, hi = sub(sess, lo, p), add(sess, hi, p)
+    parts = [local(sess, t, "ExpandDims", axis=[2]) for t in (lo, hi)]
+    out = RepTensor(x.plc, x.bits, "arith",
+                    sess.p("Concat", x.plc, parts[0].s0, parts[1].s0, axis=2),
+                    sess.p("Concat", x.plc, parts[0].s1, parts[1].s1, axis=2))
+    return local(sess, out, "Reshape", shape=tuple(shape))
+
+
+def sort_network(sess, x: RepTensor, geom, descending=False, width=None) -> RepTensor:
+    """Bitonic sorting network over the middle axis of ``x`` seen as [outer, n, inner] (``geom``
+    an R.CswapGeom whose stage fields are ignored; n a power of two): log2 n (log2 n + 1) / 2
+    compare-exchange stages, each one sign extraction and one multiplication.  A stage is
+    R.cswap_diff share-wise (negative where a pair is out of order), less_than_zero_arith of
+    it, the local products of the flag and the pair's difference (session ``p_cswap_cross``),
+    a zero share and a reshare, and R.cswap_apply share-wise.  Nothing truncates: the result
+    holds exactly the input's ring values, reordered.  ``by >= 0`` in ``geom`` orders whole
+    rows by that column.  ``width``: every difference of two compared values is below
+    2^(width - 1) in magnitude.  A symbolic session composes the local steps from Reshape,
+    IndexAxis, Sub, Mul, Add and Concat, so a lowered graph needs no operator of its own."""
+    plc, bits = x.plc, x.bits
+    composed = getattr(sess, "symbolic", False)
+    shape = sess.p_shape(x.s0) if composed else None
+    for k, j in R.cswap_stages(geom.n):
+        g = R.CswapGeom(geom.outer, geom.n, geom.inner, geom.by, k, j, bool(descending))
+        with span("rep.sort_stage"):
+            if composed:
+                c = _cswap_diff_composed(sess, x, g)
+            else:
+                c0, c1 = _sharewise(sess, "CswapDiff", plc, (x.s0, x.s1), geom=tuple(g))
+                c = RepTensor(plc, bits, "arith", c0, c1)
+            s = less_than_zero_arith(sess, c, width=width)
+            v = sess.p_cswap_cross(plc, s.s0, s.s1, x.s0, x.s1, g)
+            fused = getattr(sess, "p_zero_share_reshare", None)
+            if fused is not None and getattr(sess, "fused", False):
+                p0, p1 = fused(plc, v, "arith")
+                p = RepTensor(plc, bits, "arith", p0, p1)
+            else:
+                p = _reshare(sess, plc, sess.p_add_zero_share(plc, v, "arith"), bits, "arith")
+            if composed:
+                x = _cswap_apply_composed(sess, x, p, g, shape)
+            else:
+                o0, o1 = _sharewise(sess, "CswapApply", plc, (x.s0, x.s1), (p.s0, p.s1),
+                                    geom=tuple(g))
+                x = RepTensor(plc, bits, "arith", o0, o1)
+    return x
+
+
 def dwconv_public(sess, x: RepTensor, c, geom: dict, public_image=False) -> RepTensor:
     """Depthwise convolution of a secret image with the public weight ``c`` (or, with
     ``public_image``, of the public image ``c`` with a secret weight): the plain kernel

@@ -151,6 +151,20 @@ def _pwl_ring(c, x):
 
 
 kernel("PiecewiseLinear", "rep", "rep_ring")(_pwl_ring)
+
+
+def _sort_ring(c, x):
+    """Sort on a raw ring sharing: the elements are signed ring integers below 2^(bits - 2) in
+    magnitude (a difference of two keeps its sign in the ring's top bit); the padding is the
+    largest such value."""
+    from moose_amd.protocols import fixedpoint as fxp
+
+    r = fxp.sort(c.sess, fxp.RepFixed(x, 0, x.bits - 2), int(c.attr("axis", default=-1)),
+                 bool(c.attr("descending", default=False)), int(c.attr("by", default=-1)))
+    return r.t
+
+
+kernel("Sort", "rep", "rep_ring")(_sort_ring)
 kernel("Neg", "rep", "rep_ring")(lambda c, x: rep.neg(c.sess, x))
 kernel("Sum", "rep", "rep_ring")(lambda c, x: rep.sum(c.sess, x, c.attr("axis")))
 kernel("AddN", "rep", "rep_ring", variadic=True)(lambda c, *xs: _add_n(c, xs))

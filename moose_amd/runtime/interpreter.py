@@ -1546,6 +1546,30 @@ class Interpreter:
             return LV(y.plc, "tensor", y.dtype, MV(y.plc, z.v))
         return LV(y.plc, "tensor", y.dtype, fxp._with(y.v, rep.trunc_pr(self.sess, y.v.t, m)))
 
+    def op_Sort(self, op, ins):
+        """Sort along an axis, or of a table's rows by a key column: a host's (or a public)
+        tensor through the plaintext primitive on floats or on the ring values of a fixed-point
+        tensor; a replicated fixed-point tensor through fixedpoint.sort (a bitonic network,
+        exact)."""
+        a = op.attrs
+        attrs = dict(axis=int(a.get("axis", -1)), descending=bool(a.get("descending", False)),
+                     by=int(a.get("by", -1)))
+        x = self.at(op, ins[0])
+        if x.kind != "tensor":
+            raise MooseRuntimeError(f"{op.name}: Sort expects a tensor, got a {x.kind}")
+        if x.is_host:
+            return LV(x.plc, "tensor", x.dtype, self.sess.h("Sort", x.host, x.v, **attrs))
+        if x.is_mir or (x.is_rep and isinstance(x.v, MV)):
+            return self._public_prim(x, "Sort", **attrs)
+        if x.dtype is None or not x.dtype.is_fixed:
+            raise MooseRuntimeError(
+                f"{op.name}: Sort on a replicated placement expects a fixed-point tensor, got "
+                f"{x.dtype}; cast a float tensor to fixed point first")
+        try:
+            return LV(x.plc, "tensor", x.dtype, fxp.sort(self.sess, x.v, **attrs))
+        except ValueError as e:
+            raise MooseRuntimeError(f"{op.name}: {e}") from None
+
     def op_PiecewiseLinear(self, op, ins):
         """Piecewise-linear activation of a fixed-point tensor: replicated values through
         fixedpoint.piecewise_linear (one sign extraction, one local kernel, one truncation);

@@ -293,6 +293,8 @@ def _index_axis(nb, a, axis, index):
 
 @prim("Slice")
 def _slice(nb, a, slice):
+    if isinstance(slice, list):  # one (start, end, step) per leading axis
+        return _strided_slice(nb, a, [builtins_slice(*s) for s in slice])
     start, end, step = slice
     if isinstance(a, tuple):  # a shape (HostShape slice, reference host/ops.rs Slice)
         return a[start:end:step]
@@ -400,6 +402,60 @@ def _pwl_plain(nb, s, x, da, db, ak):
     """The plain piecewise-linear leaf on ring tensors (R.pwl): (ak + sum_j da[j] * s[j]) * x +
     sum_j db[j] * s[j] over the flag planes s stacked on the leading logical axis."""
     return R.pwl(s, x, tuple(da), tuple(db), int(ak), nb)
+
+
+@prim("CswapDiff")
+def _cswap_diff(nb, x, geom):
+    """The signed differences of one compare-exchange stage (R.cswap_diff): negative where a
+    pair is out of order."""
+    return R.cswap_diff(x, R.CswapGeom(*geom), nb)
+
+
+@prim("CswapApply")
+def _cswap_apply(nb, x, p, geom):
+    """The exchange of one compare-exchange stage (R.cswap_apply): x[i] - p, x[l] + p."""
+    return R.cswap_apply(x, p, R.CswapGeom(*geom), nb)
+
+
+@prim("Sort")
+def _sort(nb, x, axis=-1, descending=False, by=-1):
+    """Plaintext sort of a host's tensor along ``axis`` -- floats, or fixed-point ring values by
+    their signed value; ``by >= 0``: the rows of a rank-2 tensor ordered by column ``by``."""
+    rt = _is_rt(x)
+    d = x.data if rt else x
+    if rt and x.bits == 128:  # (lo, hi) words: one signed key per element, ordered by rank
+        key = _rank128(d)
+    else:
+        key = d
+    nd = key.dim() - nb
+    ax = (axis + nd if axis < 0 else axis) + nb
+    if by >= 0:
+        order = torch.argsort(key.select(nb + 1, by), dim=nb, descending=bool(descending))
+        idx = order.reshape(order.shape + (1,) * (d.dim() - order.dim()))
+        out = torch.take_along_dim(d, idx.expand(d.shape), dim=nb)
+    elif rt and x.bits == 128:
+        order = torch.argsort(key, dim=ax, descending=bool(descending))
+        out = torch.take_along_dim(d, order.unsqueeze(-1).expand(d.shape), dim=ax)
+    else:
+        out = torch.sort(d, dim=ax, descending=bool(descending)).values
+    return R.RT(out.contiguous(), x.bits) if rt else out
+
+
+def _rank128(d):
+    """The rank of every signed 128-bit element ([..., 2] int64 words, low word first) among
+    all of them, as an int64 tensor of the elements' shape: equal elements share a rank."""
+    flat = d.reshape(-1, 2)
+    lo = flat[:, 0] ^ torch.iinfo(torch.int64).min  # the low word compares unsigned
+    o1 = torch.argsort(lo, stable=True)
+    o2 = torch.argsort(flat[o1, 1], stable=True)
+    order = o1[o2]
+    s = flat[order]
+    new = torch.ones(len(s), dtype=torch.int64, device=d.device)
+    if len(s) > 1:
+        new[1:] = ((s[1:] != s[:-1]).any(dim=1)).to(torch.int64)
+    rank = torch.empty(len(s), dtype=torch.int64, device=d.device)
+    rank[order] = torch.cumsum(new, 0)
+    return rank.reshape(d.shape[:-1])
 
 
 @prim("StridedSlice")
