@@ -1,6 +1,6 @@
 // Geometry of the compare-exchange leaves (cswap_diff, cswap_cross, cswap_apply): one stage
 // (k, j) of a bitonic sorting network along the middle axis of an [outer, n, inner] array.
-// Plain data and host code only, shared by ring_cpu.cpp (the CPU twins) and ring_hip.hip (the
+// Plain data and host code only, shared by leaf_cpu.cpp (the CPU twins) and leaf_hip.hip (the
 // launchers), in the style of img_geom.h; the kernels keep their own parameter struct.
 #pragma once
 #include <stdint.h>

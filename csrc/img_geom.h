@@ -1,6 +1,6 @@
 // Geometry of the image leaf kernels (im2col, col2im, resize2d, dwconv): the attributes the
 // mx_* entry points take, what is derived from them once, and their range checks.  Plain
-// data and host code only, shared by ring_cpu.cpp (the CPU twins) and ring_hip.hip (the
+// data and host code only, shared by leaf_cpu.cpp (the CPU twins) and leaf_hip.hip (the
 // launchers); the kernels keep their own parameter structs, filled from this record.
 #pragma once
 #include <stdint.h>

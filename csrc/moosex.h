@@ -1,5 +1,5 @@
-// moosex native core: C ABI shared by the CPU (ring_cpu.cpp) and the gfx950 HIP
-// (ring_hip.hip, gemm_mfma.hip) implementations.
+// moosex native core: C ABI shared by the CPU (*_cpu.cpp) and the gfx950 HIP (*.hip)
+// implementations; a family's host twins X_cpu.cpp sit next to its kernels X.hip.
 //
 // Ring tensors: Z_2^64 elements are uint64 words; Z_2^128 elements are two little-endian
 // uint64 words (lo, hi) == the in-memory layout of unsigned __int128 on x86-64 and

@@ -200,7 +200,7 @@ MX_HD inline double signed_to_f64(T v) {
 
 }  // namespace mxr
 
-// Device launchers (ring_hip.hip / gemm_mfma.hip)
+// Device launchers (ring_hip.hip, leaf_hip.hip, gemm_valu.hip, gemm_mfma.hip)
 extern "C" {
 int mxh_ew_binary(int op, int words, const void* a, int64_t na, const void* b, int64_t nb,
                   void* out, int64_t n, void* stream);

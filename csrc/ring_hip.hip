@@ -1,6 +1,14 @@
-// gfx950 kernels for the moosex ring dialect: elementwise Z_2^64 / Z_2^128 / Z_2 ops,
-// the ChaCha12 correlated-randomness generator (prf_core.h), the fused RSS local step
-// (cross terms + zero share in one pass), fixed-point encode/decode, reductions.
+// gfx950 kernels for the moosex ring dialect: the elementwise family (binary / unary / compare
+// on Z_2^64 / Z_2^128 / Z_2 in plain, slot and share-pair forms, linear combinations, bit planes,
+// fixed-point encode / decode, weighted and axis sums, the raw keystream k_prg) and the kernels
+// for three stacked parties of a replicated sharing: the fused RSS local step (cross terms +
+// zero share in one pass), the fixed-point product with its TruncPr tail, b2a, mux, bit
+// decomposition, the Kogge-Stone adder and the PRF expansion.  The leaves live in leaf_hip.hip,
+// the VALU GEMM in gemm_valu.hip; ring_launch.h holds what the launches of all three share.
+//
+// The keystream kernels stay in ONE translation unit on purpose: the compiler's code for those
+// that draw single chunks (mx::prf_chunk) depends on which other keystream kernels it sees
+// (profiles/ring_split.md).
 //
 // Design notes (MI355X):
 //  * every elementwise kernel is a grid-stride loop over 16-byte elements (one u128, two
@@ -11,37 +19,19 @@
 //  * the fused RSS kernel (mxh_rss_cross) reads the four share streams once and writes
 //    z_i + alpha_i once: the whole local half of an RSS multiplication is one launch, for
 //    all three parties at once when they are stacked on one device.
+
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
-#include <type_traits>
+#include <cstdlib>
 
-#include "prf_dev.h"
 #include "moosex.h"
 #include "party_batch.h"
-#include "ring_common.h"
+#include "ring_launch.h"
 #include "rss_fused.h"
 
-using mxr::u128;
-using u64 = uint64_t;
-
 namespace {
-
-constexpr int kBlock = 256;
-
-inline int grid_for(int64_t n, int per_thread = 1) {
-  int64_t blocks = (n + (int64_t)kBlock * per_thread - 1) / ((int64_t)kBlock * per_thread);
-  return (int)std::max<int64_t>(1, std::min<int64_t>(blocks, 256 * 8));
-}
-
-inline hipStream_t S(void* s) { return (hipStream_t)s; }
-
-#define MX_LAUNCH_CHECK()                               \
-  do {                                                  \
-    hipError_t _e = hipGetLastError();                  \
-    if (_e != hipSuccess) return -100 - (int)_e;        \
-  } while (0)
 
 template <class T>
 __device__ __forceinline__ void d_binary(int op, const T* __restrict__ a, int64_t na,
@@ -79,16 +69,6 @@ __global__ void __launch_bounds__(256) k_binary_slot(int op, const T* __restrict
                                                      int which) {
   d_binary_slot<T>(op, a, b, nb, out, m, np, which);
 }
-
-// Share-pair forms: both replicated share vectors (s0, s1) of a share-wise op in ONE launch,
-// blockIdx.y picks the pair member.
-template <class T>
-struct Pair {
-  const T* a[2];
-  const T* b[2];
-  T* o[2];
-  int which[2];
-};
 
 template <class T>
 __device__ __forceinline__ void d_binary2(int op, const Pair<T>& p, int64_t na, int64_t nb,
@@ -648,12 +628,6 @@ __global__ void __launch_bounds__(256) k_sum_axis_wide(const T* __restrict__ a, 
 // ---------------------------------------------------------------------------
 // PRF (ChaCha12 keystream, prf_core.h / prf_dev.h)
 // ---------------------------------------------------------------------------
-using mxd::KeySrc;
-using mxd::Lane;
-using mxd::pick;
-using mxd::stage_keys;
-using mxd::prf_chunk;
-using mxd::kKeyWords;
 
 struct RawKey {
   uint32_t k[kKeyWords];
@@ -1791,818 +1765,6 @@ __global__ void __launch_bounds__(256) k_prf_expand(T* __restrict__ out, int64_t
   d_prf_expand<T>(out, n, nkeys, keys, nonce);
 }
 
-// ---------------------------------------------------------------------------
-// The image leaves (im2col, dwconv, col2im, resize2d, pwl_cross).  Their kernels are
-// templates over <T, I, V>: the element, the index type (32-bit when every extent fits) and
-// the elements a lane owns (2 only for u64: every access is 16 bytes).  The host side below is
-// shared: the geometry arrives validated in an ImgGeom (img_geom.h), leaf_dispatch picks the
-// form, lane_plan and row_grid shape the launch of a rows x inner output.
-// ---------------------------------------------------------------------------
-using mxr::ImgGeom;
-
-template <class T, int V>
-struct alignas(sizeof(T) * V) LaneVec {
-  T v[V];
-};
-
-template <class T_, class I_, int V_>
-struct LeafForm {
-  using T = T_;
-  using I = I_;
-  static constexpr int V = V_;
-};
-
-// launch(LeafForm<T, I, V>{}) for elem_bytes (1 only where BYTES; else -2, as any other
-// width), 32-bit indices when `small`, two u64 per lane when `two`
-template <class T, int V, class F>
-static int leaf_index(bool small, F& launch) {
-  return small ? launch(LeafForm<T, int32_t, V>{}) : launch(LeafForm<T, int64_t, V>{});
-}
-template <bool BYTES = false, class F>
-static int leaf_dispatch(int elem_bytes, bool small, bool two, F launch) {
-  switch (elem_bytes) {
-    case 1:
-      if constexpr (BYTES) return leaf_index<uint8_t, 1>(small, launch);
-      return -2;
-    case 8: return two ? leaf_index<u64, 2>(small, launch) : leaf_index<u64, 1>(small, launch);
-    case 16: return leaf_index<u128, 1>(small, launch);
-    default: return -2;
-  }
-}
-
-// 32-bit indices serve extents below 2^31 elements less `headroom`, the overshoot of a lane's
-// last loop step
-static bool fits32(int64_t headroom, std::initializer_list<int64_t> extents) {
-  for (int64_t e : extents)
-    if (e >= (1ll << 31) - headroom) return false;
-  return true;
-}
-
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// A block of 256 lanes over a rows x inner output: bx inner lanes of V elements, no more
-// than the inner extent needs (and at most max_bx), by 256 / bx rows; `tiles` blocks cover
-// the inner extent.
-struct LanePlan {
-  int bx, by;
-  int64_t tiles;
-};
-static LanePlan lane_plan(int64_t inner, int V, int max_bx = 64) {
-  int bx = max_bx;
-  while (bx > 1 && (bx / 2) * V >= inner) bx /= 2;
-  return {bx, 256 / bx, (inner + (int64_t)bx * V - 1) / ((int64_t)bx * V)};
-}
-
-// the row grid is capped at 65,536 rows; a lane strides over the rest
-static int64_t row_grid(int64_t rows, int by) {
-  return std::min<int64_t>((rows + by - 1) / by, 65536 / by);
-}
-
-// the input strides and the window attributes of a kernel's parameter struct
-template <class P>
-static void set_strides(P& p, const ImgGeom& g) {
-  using I = decltype(p.sN);
-  p.sN = (I)g.sN, p.sH = (I)g.sH, p.sW = (I)g.sW, p.sC = (I)g.sC;
-}
-template <class P>
-static void set_window(P& p, const ImgGeom& g) {
-  p.H = (int)g.H, p.W = (int)g.W, p.KH = (int)g.KH, p.KW = (int)g.KW, p.sh = (int)g.sh;
-  p.sw = (int)g.sw, p.pt = (int)g.pt, p.pl = (int)g.pl, p.dh = (int)g.dh, p.dw = (int)g.dw;
-  p.OH = (int)g.OH, p.OW = (int)g.OW, p.nhwc = g.nhwc;
-}
-
-// im2col: the patch gather that turns a 2-D convolution into a GEMM over shares.  Output-
-// stationary: a lane owns V adjacent output columns of one row, so stores are coalesced
-// (V = 2 for u64 with an even row length: one 16-byte store; u128 moves 16 bytes per lane as
-// is).  Block = 64 columns x 4 rows: a wave walks one output row, reading contiguous c runs
-// (NHWC) or kw runs (NCHW, dw == 1).  The column (c, kh, kw) is decomposed once per lane and
-// kept while the lane strides over rows; a row (n, oh, ow) once per visit.  A tap in the
-// padding stores zero without a load.  Slots (share slots of a stacked buffer) are
-// blockIdx.z, read at in_slot_stride and written densely.  I is the index type: 32-bit when
-// both extents are below 2^31.
-template <class I>
-struct Im2colP {
-  I in_slot_stride, sN, sH, sW, sC;  // input strides in elements (format-dependent)
-  I K, rows;
-  int C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW, nhwc;
-};
-
-template <class T, class I, int V>
-__global__ void __launch_bounds__(256) k_im2col(const T* __restrict__ in, T* __restrict__ out,
-                                                Im2colP<I> p) {
-  using U = typename std::make_unsigned<I>::type;
-  const I col0 = (I)((blockIdx.x * (I)64 + threadIdx.x) * V);
-  if (col0 >= p.K) return;
-  I coff[V];
-  int dy[V], dx[V];
-#pragma unroll
-  for (int j = 0; j < V; ++j) {
-    const U col = (U)(col0 + j);
-    U c, kh, kw;
-    if (p.nhwc) {
-      const U t = col / (U)p.C;
-      c = col - t * (U)p.C;
-      kh = t / (U)p.KW;
-      kw = t - kh * (U)p.KW;
-    } else {
-      const U kk = (U)(p.KH * p.KW);
-      c = col / kk;
-      const U r = col - c * kk;
-      kh = r / (U)p.KW;
-      kw = r - kh * (U)p.KW;
-    }
-    coff[j] = (I)c * p.sC;
-    dy[j] = (int)kh * p.dh - p.pt;
-    dx[j] = (int)kw * p.dw - p.pl;
-  }
-  const T* __restrict__ src = in + (I)blockIdx.z * p.in_slot_stride;
-  T* __restrict__ dst = out + (I)blockIdx.z * p.rows * p.K;
-  for (I row = (I)(blockIdx.y * blockDim.y + threadIdx.y); row < p.rows;
-       row += (I)(gridDim.y * blockDim.y)) {
-    const U q = (U)row / (U)p.OW;
-    const int ow = (int)((U)row - q * (U)p.OW);
-    const U n = q / (U)p.OH;
-    const int oh = (int)(q - n * (U)p.OH);
-    const I base = (I)n * p.sN;
-    const int y0 = oh * p.sh, x0 = ow * p.sw;
-    LaneVec<T, V> o;
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-      const int iy = y0 + dy[j], ix = x0 + dx[j];
-      T v = (T)0;
-      if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W)
-        v = src[base + coff[j] + (I)iy * p.sH + (I)ix * p.sW];
-      o.v[j] = v;
-    }
-    *reinterpret_cast<LaneVec<T, V>*>(dst + row * p.K + col0) = o;
-  }
-}
-
-template <class T, class I, int V>
-static int im2col_launch(const void* in, void* out, int64_t slots, int64_t in_slot_stride,
-                         const ImgGeom& g, void* stream) {
-  Im2colP<I> p;
-  p.in_slot_stride = (I)in_slot_stride;
-  set_strides(p, g);
-  set_window(p, g);
-  p.K = (I)g.K, p.rows = (I)g.rows, p.C = (int)g.C;
-  const int64_t gx = (g.K + 64 * V - 1) / (64 * V);  // the kernel's block is 64 x 4
-  hipLaunchKernelGGL((k_im2col<T, I, V>),
-                     dim3((unsigned)gx, (unsigned)row_grid(g.rows, 4), (unsigned)slots),
-                     dim3(64, 4), 0, S(stream), (const T*)in, (T*)out, p);
-  MX_LAUNCH_CHECK();
-  return 0;
-}
-
-// Depthwise convolution over shares (moosex.h mx_dwconv): a memory-bound stencil, output-
-// stationary like k_im2col.  The output is rows x inner: inner = the C*mult channels (NHWC,
-// rows (n, oh, ow)) or the OW columns of one channel (NCHW, rows (n, oh)); a lane owns V
-// adjacent inner outputs of a row (V = 2 for u64 with an even inner extent: every store is 16
-// bytes), adjacent lanes are adjacent in c (NHWC) or ow (NCHW), and the lane strides over
-// rows.  A block is blockDim.x inner lanes x 256 / blockDim.x rows; blockIdx.x picks its
-// inner tile: a run of blockDim.x * V channels (NHWC), or one channel and a run of OW (NCHW).
-// The weights of the block's channels -- all KH*KW taps, in cross mode w0 + w1 (formed here,
-// once per element) and w0 -- are staged in LDS once, laid out [tap][channel] so a lane's
-// read is its own 16 bytes (NHWC) or a broadcast (NCHW).  Per output: KH*KW wrapping
-// multiply-adds (two in cross mode, x0.(w0 + w1) + x1.w0) on inputs read once; a tap in the
-// padding is skipped without a load.  Slots are blockIdx.z.  I: the index type, 32-bit when
-// every extent is below 2^31.
-template <class I>
-struct DwconvP {
-  I x_slot, w_slot, o_slot;  // slot strides in elements
-  I sN, sH, sW, sC;          // input strides in elements (format-dependent)
-  I rows;
-  int H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW, OC, mult, nhwc;
-  int tiles;  // NCHW: inner tiles per channel
-};
-
-template <class T, class I, int V, bool CROSS>
-__global__ void __launch_bounds__(256) k_dwconv(const T* __restrict__ x0,
-                                                const T* __restrict__ x1,
-                                                const T* __restrict__ w0,
-                                                const T* __restrict__ w1, T* __restrict__ out,
-                                                DwconvP<I> p) {
-  using U = typename std::make_unsigned<I>::type;
-  extern __shared__ __align__(16) unsigned char dwconv_lds[];
-  T* __restrict__ wl = reinterpret_cast<T*>(dwconv_lds);
-  const int taps = p.KH * p.KW;
-  const int bx = (int)blockDim.x, by = (int)blockDim.y;
-  const int cw = p.nhwc ? bx * V : 1;  // channels of this block
-  int oc_base, ow_base = 0;
-  if (p.nhwc) {
-    oc_base = (int)blockIdx.x * cw;
-  } else {
-    oc_base = (int)(blockIdx.x / (unsigned)p.tiles);
-    ow_base = (int)(blockIdx.x - (unsigned)oc_base * (unsigned)p.tiles) * bx * V;
-  }
-  {
-    const int nch = min(cw, p.OC - oc_base);
-    const I woff = (I)blockIdx.z * p.w_slot + (I)oc_base * (I)taps;
-    const int nw = nch * taps;
-    for (int i = (int)(threadIdx.y * bx + threadIdx.x); i < nw; i += bx * by) {
-      const int cl = i / taps, tap = i - cl * taps;
-      const T a = w0[woff + i];
-      if (CROSS) {
-        wl[tap * cw + cl] = a + w1[woff + i];
-        wl[(taps + tap) * cw + cl] = a;
-      } else {
-        wl[tap * cw + cl] = a;
-      }
-    }
-  }
-  __syncthreads();
-  const int l0 = (int)threadIdx.x * V;
-  // V == 2 only with an even inner extent: both outputs are inside, or neither
-  if ((p.nhwc ? oc_base + l0 >= p.OC : ow_base + l0 >= p.OW)) return;
-  I coff[V];  // the input channel's offset
-  int wcol[V];
-#pragma unroll
-  for (int j = 0; j < V; ++j) {
-    const int oc = p.nhwc ? oc_base + l0 + j : oc_base;
-    coff[j] = (I)(oc / p.mult) * p.sC;
-    wcol[j] = p.nhwc ? l0 + j : 0;
-  }
-  const T* __restrict__ xs0 = x0 + (I)blockIdx.z * p.x_slot;
-  const T* __restrict__ xs1 = CROSS ? x1 + (I)blockIdx.z * p.x_slot : nullptr;
-  T* __restrict__ dst = out + (I)blockIdx.z * p.o_slot;
-  for (I row = (I)(blockIdx.y * by + threadIdx.y); row < p.rows; row += (I)(gridDim.y * by)) {
-    U n;
-    int oh, ow;
-    I oidx;
-    if (p.nhwc) {
-      const U q = (U)row / (U)p.OW;
-      ow = (int)((U)row - q * (U)p.OW);
-      n = q / (U)p.OH;
-      oh = (int)(q - n * (U)p.OH);
-      oidx = row * (I)p.OC + (I)(oc_base + l0);
-    } else {
-      n = (U)row / (U)p.OH;
-      oh = (int)((U)row - n * (U)p.OH);
-      ow = ow_base + l0;
-      oidx = (((I)n * (I)p.OC + (I)oc_base) * (I)p.OH + (I)oh) * (I)p.OW + (I)ow;
-    }
-    const I base = (I)n * p.sN;
-    const int y0 = oh * p.sh - p.pt;
-    LaneVec<T, V> acc;
-#pragma unroll
-    for (int j = 0; j < V; ++j) acc.v[j] = (T)0;
-    for (int kh = 0; kh < p.KH; ++kh) {
-      const int iy = y0 + kh * p.dh;
-      if (iy < 0 || iy >= p.H) continue;
-      const I rbase = base + (I)iy * p.sH;
-      for (int kw = 0; kw < p.KW; ++kw) {
-        const int tap = kh * p.KW + kw;
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-          const int ix = (p.nhwc ? ow : ow + j) * p.sw - p.pl + kw * p.dw;
-          if (ix < 0 || ix >= p.W) continue;
-          const I xi = rbase + coff[j] + (I)ix * p.sW;
-          acc.v[j] += xs0[xi] * wl[tap * cw + wcol[j]];
-          if (CROSS) acc.v[j] += xs1[xi] * wl[(taps + tap) * cw + wcol[j]];
-        }
-      }
-    }
-    *reinterpret_cast<LaneVec<T, V>*>(dst + oidx) = acc;
-  }
-}
-
-template <class T, class I, int V, bool CROSS>
-static int dwconv_launch(const void* x0, const void* x1, const void* w0, const void* w1,
-                         void* out, int64_t slots, int64_t x_slot_stride, int64_t w_slot_stride,
-                         const ImgGeom& g, void* stream) {
-  const bool nhwc = g.nhwc;
-  // NCHW: the channel is part of blockIdx.x, the rows are (n, oh)
-  const int64_t rows = nhwc ? g.rows : g.N * g.OH;
-  // inner lanes of a block: few enough that the block's weights fit 64 KB of LDS (NHWC: bx * V
-  // channels; NCHW: one channel)
-  const int64_t per = g.KH * g.KW * (int64_t)sizeof(T) * (CROSS ? 2 : 1);
-  int max_bx = 64;
-  while (max_bx > 1 && nhwc && per * max_bx * V > 65536) max_bx /= 2;
-  const LanePlan b = lane_plan(g.inner, V, max_bx);
-  const int64_t lds = per * (nhwc ? b.bx * V : 1);
-  if (lds > 65536) return -3;
-  const int64_t gx = nhwc ? b.tiles : g.OC * b.tiles;
-  if (gx > 0x7fffffff) return -3;
-  // rows per lane: one visit while that leaves the grid small, up to 8 on a large one (the
-  // staged weights serve them all)
-  const int64_t gy_full = (rows + b.by - 1) / b.by;
-  const int64_t visits = std::max<int64_t>(1, std::min<int64_t>(8, gx * slots * gy_full / 4096));
-  const int64_t gy = std::min<int64_t>((gy_full + visits - 1) / visits, 65536 / b.by);
-  DwconvP<I> p;
-  p.x_slot = (I)x_slot_stride, p.w_slot = (I)w_slot_stride, p.o_slot = (I)g.n_out;
-  set_strides(p, g);
-  set_window(p, g);
-  p.rows = (I)rows, p.OC = (int)g.OC, p.mult = (int)g.mult, p.tiles = (int)b.tiles;
-  hipLaunchKernelGGL((k_dwconv<T, I, V, CROSS>), dim3((unsigned)gx, (unsigned)gy, (unsigned)slots),
-                     dim3(b.bx, b.by), (size_t)lds, S(stream), (const T*)x0, (const T*)x1,
-                     (const T*)w0, (const T*)w1, (T*)out, p);
-  MX_LAUNCH_CHECK();
-  return 0;
-}
-
-// col2im (moosex.h mx_col2im): the adjoint of k_im2col, as an output-stationary gather -- no
-// atomics and no scatter, so the wrapping sums equal the CPU twin's bit for bit.  The output
-// image is rows x inner: inner = the C channels (NHWC, rows (n, y, x)) or the W columns of one
-// channel (NCHW, rows (n, c, y)); a lane owns V adjacent inner outputs of a row (V = 2 for u64
-// with an even inner extent: every store is 16 bytes), adjacent lanes are adjacent in c (NHWC)
-// or x (NCHW), and the lane strides over rows.  Per output the lane walks the KH*KW taps: a
-// tap contributes when y + pt - kh*dh is a non-negative multiple of sh whose quotient oh is
-// below OH (and its w twin).  NHWC: a wave reads contiguous channel runs of one patch-matrix
-// row, 16 bytes per lane; NCHW lanes read K elements apart (correct, uncoalesced).  A block is
-// blockDim.x inner lanes x 256 / blockDim.x rows.  Slots are blockIdx.z, read at in_slot and
-// written densely.  I: the index type, 32-bit when every extent is below 2^31.
-template <class I>
-struct Col2imP {
-  I in_slot, o_slot;  // slot strides in elements
-  I K, rows;          // patch-matrix row length; output rows
-  int C, H, W, KH, KW, sh, sw, pt, pl, dh, dw, OH, OW, nhwc;
-};
-
-template <class T, class I, int V>
-__global__ void __launch_bounds__(256) k_col2im(const T* __restrict__ in, T* __restrict__ out,
-                                                Col2imP<I> p) {
-  using U = typename std::make_unsigned<I>::type;
-  const unsigned bx = blockDim.x, by = blockDim.y;
-  const unsigned inner = (unsigned)(p.nhwc ? p.C : p.W);
-  // V == 2 only with an even inner extent: both outputs are inside, or neither
-  const unsigned i0 = (blockIdx.x * bx + threadIdx.x) * V;
-  if (i0 >= inner) return;
-  const T* __restrict__ src = in + (I)blockIdx.z * p.in_slot;
-  T* __restrict__ dst = out + (I)blockIdx.z * p.o_slot;
-  for (I row = (I)(blockIdx.y * by + threadIdx.y); row < p.rows; row += (I)(gridDim.y * by)) {
-    U n;
-    int y, x, c = 0;
-    if (p.nhwc) {
-      const U q = (U)row / (U)p.W;
-      x = (int)((U)row - q * (U)p.W);
-      n = q / (U)p.H;
-      y = (int)(q - n * (U)p.H);
-    } else {
-      const U q = (U)row / (U)p.H;
-      y = (int)((U)row - q * (U)p.H);
-      n = q / (U)p.C;
-      c = (int)(q - n * (U)p.C);
-      x = (int)i0;
-    }
-    const I nbase = (I)n * (I)p.OH * (I)p.OW;
-    LaneVec<T, V> acc;
-#pragma unroll
-    for (int j = 0; j < V; ++j) acc.v[j] = (T)0;
-    for (int kh = 0; kh < p.KH; ++kh) {
-      const int ty = y + p.pt - kh * p.dh;
-      if (ty < 0) break;  // ty only falls with kh
-      const unsigned oh = (unsigned)ty / (unsigned)p.sh;
-      if (oh * (unsigned)p.sh != (unsigned)ty || oh >= (unsigned)p.OH) continue;
-      const I rbase = nbase + (I)oh * (I)p.OW;
-      if (p.nhwc) {
-        for (int kw = 0; kw < p.KW; ++kw) {
-          const int tx = x + p.pl - kw * p.dw;
-          if (tx < 0) break;
-          const unsigned ow = (unsigned)tx / (unsigned)p.sw;
-          if (ow * (unsigned)p.sw != (unsigned)tx || ow >= (unsigned)p.OW) continue;
-          const I si = (rbase + (I)ow) * p.K + (I)(kh * p.KW + kw) * (I)p.C + (I)i0;
-          const LaneVec<T, V> r = *reinterpret_cast<const LaneVec<T, V>*>(src + si);
-#pragma unroll
-          for (int j = 0; j < V; ++j) acc.v[j] += r.v[j];
-        }
-      } else {
-        const I cbase = ((I)c * (I)p.KH + (I)kh) * (I)p.KW;
-        for (int kw = 0; kw < p.KW; ++kw) {
-#pragma unroll
-          for (int j = 0; j < V; ++j) {
-            const int tx = x + j + p.pl - kw * p.dw;
-            if (tx < 0) continue;
-            const unsigned ow = (unsigned)tx / (unsigned)p.sw;
-            if (ow * (unsigned)p.sw != (unsigned)tx || ow >= (unsigned)p.OW) continue;
-            acc.v[j] += src[(rbase + (I)ow) * p.K + cbase + (I)kw];
-          }
-        }
-      }
-    }
-    *reinterpret_cast<LaneVec<T, V>*>(dst + row * (I)inner + (I)i0) = acc;
-  }
-}
-
-template <class T, class I, int V>
-static int col2im_launch(const void* in, void* out, int64_t slots, int64_t in_slot_stride,
-                         const ImgGeom& g, void* stream) {
-  const LanePlan b = lane_plan(g.inner, V);
-  Col2imP<I> p;
-  p.in_slot = (I)in_slot_stride, p.o_slot = (I)g.n_out;
-  set_window(p, g);
-  p.K = (I)g.K, p.rows = (I)g.rows, p.C = (int)g.C;
-  hipLaunchKernelGGL((k_col2im<T, I, V>),
-                     dim3((unsigned)b.tiles, (unsigned)row_grid(g.rows, b.by), (unsigned)slots),
-                     dim3(b.bx, b.by), 0, S(stream), (const T*)in, (T*)out, p);
-  MX_LAUNCH_CHECK();
-  return 0;
-}
-
-// image resize (moosex.h mx_resize2d), on k_col2im's plan: output-stationary, no atomics, so
-// the wrapping sums equal the CPU twin's bit for bit.  The output image is rows x inner: inner
-// = the C channels (NHWC, rows (n, oy, ox)) or the OW columns of one channel (NCHW, rows (n, c,
-// oy)); a lane owns V adjacent inner outputs of a row (V = 2 only for u64 in NHWC with an even
-// C: both outputs share their taps, every load and store is 16 bytes), adjacent lanes are
-// adjacent in c (NHWC: a wave reads contiguous channel runs of four input pixels) or in ox
-// (NCHW: a wave reads two input rows at the columns its width taps name -- neighbouring when
-// upsampling, strided when downsampling), and the lane strides over rows.  The tables th / tw
-// are int32 [3, O] (i0, i1, w1): NHWC reads both once per row, the same entries for all lanes
-// of the row; NCHW reads the width entries of its column once and the height entries per row.
-// The four weights wh_a * ww_b < 2^24 are 32-bit; with both weight widths 0 the lane copies its
-// one tap.  Indices are clamped to the image: a bad table reads a wrong pixel, never outside.
-// Slots are blockIdx.z, read at in_slot and written densely.  I: the index type, 32-bit when
-// every extent is below 2^31.
-template <class I>
-struct Resize2dP {
-  I in_slot, o_slot;  // slot strides in elements
-  I sN, sH, sW, sC;   // input strides in elements (format-dependent)
-  I rows;             // output rows
-  int C, H, W, OH, OW, wbh, wbw, nhwc;
-};
-
-template <class T, class I, int V>
-__global__ void __launch_bounds__(256) k_resize2d(const T* __restrict__ in, T* __restrict__ out,
-                                                  const int32_t* __restrict__ th,
-                                                  const int32_t* __restrict__ tw,
-                                                  Resize2dP<I> p) {
-  using U = typename std::make_unsigned<I>::type;
-  using Vec = LaneVec<T, V>;
-  const unsigned bx = blockDim.x, by = blockDim.y;
-  const unsigned inner = (unsigned)(p.nhwc ? p.C : p.OW);
-  // V == 2 only with an even inner extent: both outputs are inside, or neither
-  const unsigned i0 = (blockIdx.x * bx + threadIdx.x) * V;
-  if (i0 >= inner) return;
-  const bool nearest = (p.wbh | p.wbw) == 0;
-  const unsigned hmax = (unsigned)p.H - 1u, wmax = (unsigned)p.W - 1u;
-  const T* __restrict__ src = in + (I)blockIdx.z * p.in_slot;
-  T* __restrict__ dst = out + (I)blockIdx.z * p.o_slot;
-  unsigned xa = 0, xb = 0, w1 = 0;
-  if (!p.nhwc) {  // the lane's column, and so its width taps, are fixed
-    xa = min((unsigned)tw[i0], wmax);
-    xb = min((unsigned)tw[(unsigned)p.OW + i0], wmax);
-    w1 = (unsigned)tw[2u * (unsigned)p.OW + i0];
-  }
-  for (I row = (I)(blockIdx.y * by + threadIdx.y); row < p.rows; row += (I)(gridDim.y * by)) {
-    unsigned oy;
-    I base;
-    if (p.nhwc) {
-      const U q = (U)row / (U)p.OW;
-      const unsigned ox = (unsigned)((U)row - q * (U)p.OW);
-      const U n = q / (U)p.OH;
-      oy = (unsigned)(q - n * (U)p.OH);
-      xa = min((unsigned)tw[ox], wmax);
-      xb = min((unsigned)tw[(unsigned)p.OW + ox], wmax);
-      w1 = (unsigned)tw[2u * (unsigned)p.OW + ox];
-      base = (I)n * p.sN + (I)i0;
-    } else {
-      const U q = (U)row / (U)p.OH;
-      oy = (unsigned)((U)row - q * (U)p.OH);
-      const U n = q / (U)p.C;
-      base = (I)n * p.sN + (I)(q - n * (U)p.C) * p.sC;
-    }
-    const unsigned ya = min((unsigned)th[oy], hmax);
-    const I ra = base + (I)ya * p.sH;
-    Vec acc = *reinterpret_cast<const Vec*>(src + ra + (I)xa * p.sW);
-    if (!nearest) {
-      const unsigned yb = min((unsigned)th[(unsigned)p.OH + oy], hmax);
-      const unsigned h1 = (unsigned)th[2u * (unsigned)p.OH + oy];
-      const unsigned h0 = (1u << p.wbh) - h1, w0 = (1u << p.wbw) - w1;
-      const I rb = base + (I)yb * p.sH;
-      const Vec r01 = *reinterpret_cast<const Vec*>(src + ra + (I)xb * p.sW);
-      const Vec r10 = *reinterpret_cast<const Vec*>(src + rb + (I)xa * p.sW);
-      const Vec r11 = *reinterpret_cast<const Vec*>(src + rb + (I)xb * p.sW);
-      const uint32_t c00 = h0 * w0, c01 = h0 * w1, c10 = h1 * w0, c11 = h1 * w1;
-#pragma unroll
-      for (int j = 0; j < V; ++j)
-        acc.v[j] = acc.v[j] * (T)c00 + r01.v[j] * (T)c01 + r10.v[j] * (T)c10 +
-                   r11.v[j] * (T)c11;
-    }
-    *reinterpret_cast<Vec*>(dst + row * (I)inner + (I)i0) = acc;
-  }
-}
-
-template <class T, class I, int V>
-static int resize2d_launch(const void* in, void* out, int64_t slots, int64_t in_slot_stride,
-                           const ImgGeom& g, const int32_t* th, const int32_t* tw,
-                           void* stream) {
-  const LanePlan b = lane_plan(g.inner, V);
-  Resize2dP<I> p;
-  p.in_slot = (I)in_slot_stride, p.o_slot = (I)g.n_out;
-  set_strides(p, g);
-  p.rows = (I)g.rows;
-  p.C = (int)g.C, p.H = (int)g.H, p.W = (int)g.W, p.OH = (int)g.OH, p.OW = (int)g.OW;
-  p.wbh = g.wbh, p.wbw = g.wbw, p.nhwc = g.nhwc;
-  hipLaunchKernelGGL((k_resize2d<T, I, V>),
-                     dim3((unsigned)b.tiles, (unsigned)row_grid(g.rows, b.by), (unsigned)slots),
-                     dim3(b.bx, b.by), 0, S(stream), (const T*)in, (T*)out, th, tw, p);
-  MX_LAUNCH_CHECK();
-  return 0;
-}
-
-// piecewise-linear local step (moosex.h mx_pwl_cross), on k_col2im's plan with one row per
-// slot: a lane owns V adjacent outputs (one u128, or two u64 when n is even and every buffer
-// is 16-byte aligned, so every load and store is 16 bytes), adjacent lanes are adjacent in
-// memory, the lane strides over the slot by the grid, and slots are blockIdx.z, read at their
-// strides and written densely.  Per output: 2k + 2 reads (k + 1 in plain mode) and one write;
-// the flag planes of a slot are n elements apart.  The public tables arrive in the kernel's
-// arguments (scalar registers, no table in memory); the loop over the k planes is unrolled to
-// MX_PWL_MAX with a uniform exit.  Wrapping sums in the CPU twin's order, so the results
-// are equal bit for bit.  I: the index type, 32-bit when every extent is below 2^31.
-template <class T, class I>
-struct PwlP {
-  T da[MX_PWL_MAX], db[MX_PWL_MAX], ak;
-  I s_slot, x_slot, n;  // slot strides and slot length in elements
-  int k, cross;
-};
-
-template <class T, class I, int V>
-__global__ void __launch_bounds__(256) k_pwl_cross(const T* __restrict__ s0,
-                                                   const T* __restrict__ s1,
-                                                   const T* __restrict__ x0,
-                                                   const T* __restrict__ x1, T* __restrict__ out,
-                                                   PwlP<T, I> p) {
-  using Vec = LaneVec<T, V>;
-  const I sb = (I)blockIdx.z * p.s_slot, xb = (I)blockIdx.z * p.x_slot;
-  T* __restrict__ dst = out + (I)blockIdx.z * p.n;
-  const I step = (I)(gridDim.x * 256u) * V;
-  // V == 2 only with an even n: both outputs are inside, or neither
-  for (I i = (I)(blockIdx.x * 256u + threadIdx.x) * V; i < p.n; i += step) {
-    const Vec a0 = *reinterpret_cast<const Vec*>(x0 + xb + i);
-    Vec g0, g1, h, a;
-#pragma unroll
-    for (int v = 0; v < V; ++v) g0.v[v] = g1.v[v] = h.v[v] = (T)0, a.v[v] = a0.v[v];
-    if (p.cross) {
-      const Vec a1 = *reinterpret_cast<const Vec*>(x1 + xb + i);
-#pragma unroll
-      for (int v = 0; v < V; ++v) a.v[v] += a1.v[v];
-    }
-#pragma unroll
-    for (int j = 0; j < MX_PWL_MAX; ++j) {
-      if (j >= p.k) break;
-      const I fi = sb + (I)j * p.n + i;
-      const Vec f0 = *reinterpret_cast<const Vec*>(s0 + fi);
-#pragma unroll
-      for (int v = 0; v < V; ++v) g0.v[v] += p.da[j] * f0.v[v], h.v[v] += p.db[j] * f0.v[v];
-      if (p.cross) {
-        const Vec f1 = *reinterpret_cast<const Vec*>(s1 + fi);
-#pragma unroll
-        for (int v = 0; v < V; ++v) g1.v[v] += p.da[j] * f1.v[v];
-      }
-    }
-    Vec o;
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-      o.v[v] = g0.v[v] * a.v[v] + p.ak * a0.v[v] + h.v[v];
-      if (p.cross) o.v[v] += g1.v[v] * a0.v[v];
-    }
-    *reinterpret_cast<Vec*>(dst + i) = o;
-  }
-}
-
-template <class T, class I, int V>
-static int pwl_cross_launch(const void* s0, const void* s1, const void* x0, const void* x1,
-                            void* out, int64_t slots, int64_t s_slot_stride,
-                            int64_t x_slot_stride, int64_t n, int k, const uint64_t* da,
-                            const uint64_t* db, const uint64_t* ak, void* stream) {
-  PwlP<T, I> p;
-  std::memset(&p, 0, sizeof(p));
-  std::memcpy(p.da, da, sizeof(T) * k);
-  std::memcpy(p.db, db, sizeof(T) * k);
-  std::memcpy(&p.ak, ak, sizeof(T));
-  p.s_slot = (I)s_slot_stride, p.x_slot = (I)x_slot_stride, p.n = (I)n;
-  p.k = k, p.cross = x1 != nullptr;
-  const int64_t lanes = (n + V - 1) / V;
-  // the grid is capped at 256 CUs x 8 blocks per slot; a lane strides over the rest
-  const int64_t gx = std::min<int64_t>((lanes + 255) / 256, 256 * 8);
-  hipLaunchKernelGGL((k_pwl_cross<T, I, V>), dim3((unsigned)gx, 1, (unsigned)slots), dim3(256), 0,
-                     S(stream), (const T*)s0, (const T*)s1, (const T*)x0, (const T*)x1, (T*)out,
-                     p);
-  MX_LAUNCH_CHECK();
-  return 0;
-}
-
-// The compare-exchange leaves (moosex.h mx_cswap_diff / _cross / _apply).  A stage (k, j)
-// pairs position i with i | j, so in memory it is a butterfly over blocks of 2r contiguous
-// elements, r = j * inner: run index e of a block's low half meets run index e of its high
-// half, and the pair-major arrays (differences, flags, products) are dense at b*r + e.  A lane
-// owns a pair and loads both of its elements; adjacent lanes are adjacent in both runs and in
-// the pair-major array, a lane strides over the slot by the grid, slots are blockIdx.z, read at
-// their strides and written densely.  Forms F: 0 one pair per lane (any u128: every access is
-// 16 bytes as it is); 1 two adjacent pairs of a run per lane (u64, r even, 16-byte aligned
-// operands: every access is 16 bytes); 2 r = 1 (j = 1, inner = 1), where the two elements of
-// a pair are adjacent: one 16-byte load takes both (u64).  The table-mode difference reads
-// the key column only: run index q is element q*unit + off with unit = inner, off = by and
-// r = j.  The stage travels in the kernel's arguments: nothing is uploaded.  Ring arithmetic
-// wraps, so the results equal the CPU twins' bit for bit.  Every output element has one
-// writer.  I: the index type, 32-bit when every extent is below 2^31.
-template <class I>
-struct CswapP {
-  I x_slot, a_slot;  // slot strides of x and of the other operand (flags / products)
-  I total;           // pairs (times columns) of a slot
-  I r, unit, off;    // run length; element of run index q: q*unit + off
-  I sdiv;            // cross: the flag of product g is g / sdiv (inner in table mode, else 1)
-  I amask, k;        // block b is ascending iff (((b & amask) << lj1) & k) == 0, ...
-  I n_x;             // apply: elements of an output slot
-  int rs;            // log2 r where r is a power of two, else -1
-  int lj1, desc, cross;
-};
-
-template <class T_, class I_, int F_>
-struct CswapForm {
-  using T = T_;
-  using I = I_;
-  static constexpr int F = F_;
-};
-
-// block b and the low element of pair g
-template <class I>
-__device__ __forceinline__ I cswap_low_of(const CswapP<I>& p, I g, I& b) {
-  using U = typename std::make_unsigned<I>::type;
-  b = p.rs >= 0 ? (I)((U)g >> p.rs) : (I)((U)g / (U)p.r);
-  return (b * p.r + g) * p.unit + p.off;  // (b*2r + e) with e = g - b*r
-}
-
-template <class T, class I, int F>
-__global__ void __launch_bounds__(256) k_cswap_diff(const T* __restrict__ x, T* __restrict__ out,
-                                                    CswapP<I> p) {
-  constexpr int V = F == 1 ? 2 : 1;
-  using Vec = LaneVec<T, 2>;
-  const T* __restrict__ src = x + (I)blockIdx.z * p.x_slot;
-  T* __restrict__ dst = out + (I)blockIdx.z * p.total;
-  const I step = (I)(gridDim.x * 256u) * V;
-  for (I g = (I)(blockIdx.x * 256u + threadIdx.x) * V; g < p.total; g += step) {
-    I b;
-    const I lo = cswap_low_of(p, g, b);
-    const bool asc = ((((b & p.amask) << p.lj1) & p.k) == 0) != (p.desc != 0);
-    if constexpr (F == 0) {
-      const T a = src[lo], c = src[lo + p.r * p.unit];
-      dst[g] = asc ? c - a : a - c;
-    } else if constexpr (F == 1) {  // r even: both pairs are in block b
-      const Vec a = *reinterpret_cast<const Vec*>(src + lo);
-      const Vec c = *reinterpret_cast<const Vec*>(src + lo + p.r);
-      Vec o;
-#pragma unroll
-      for (int v = 0; v < 2; ++v) o.v[v] = asc ? c.v[v] - a.v[v] : a.v[v] - c.v[v];
-      *reinterpret_cast<Vec*>(dst + g) = o;
-    } else {  // r == 1: the pair is one vector
-      const Vec a = *reinterpret_cast<const Vec*>(src + lo);
-      dst[g] = asc ? a.v[1] - a.v[0] : a.v[0] - a.v[1];
-    }
-  }
-}
-
-template <class T, class I, int F>
-__global__ void __launch_bounds__(256) k_cswap_cross(const T* __restrict__ s0,
-                                                     const T* __restrict__ s1,
-                                                     const T* __restrict__ x0,
-                                                     const T* __restrict__ x1,
-                                                     T* __restrict__ out, CswapP<I> p) {
-  constexpr int V = F == 1 ? 2 : 1;
-  using Vec = LaneVec<T, 2>;
-  using U = typename std::make_unsigned<I>::type;
-  const I xb = (I)blockIdx.z * p.x_slot, sb = (I)blockIdx.z * p.a_slot;
-  T* __restrict__ dst = out + (I)blockIdx.z * p.total;
-  const I step = (I)(gridDim.x * 256u) * V;
-  for (I g = (I)(blockIdx.x * 256u + threadIdx.x) * V; g < p.total; g += step) {
-    I b;
-    const I lo = xb + cswap_low_of(p, g, b);
-    T d0[V], d[V], f0[V], f1[V];
-    if constexpr (F == 0) {
-      d0[0] = x0[lo] - x0[lo + p.r];
-      if (p.cross) d[0] = d0[0] + (x1[lo] - x1[lo + p.r]);
-    } else if constexpr (F == 1) {
-      const Vec a = *reinterpret_cast<const Vec*>(x0 + lo);
-      const Vec c = *reinterpret_cast<const Vec*>(x0 + lo + p.r);
-#pragma unroll
-      for (int v = 0; v < 2; ++v) d0[v] = a.v[v] - c.v[v];
-      if (p.cross) {
-        const Vec a1 = *reinterpret_cast<const Vec*>(x1 + lo);
-        const Vec c1 = *reinterpret_cast<const Vec*>(x1 + lo + p.r);
-#pragma unroll
-        for (int v = 0; v < 2; ++v) d[v] = d0[v] + (a1.v[v] - c1.v[v]);
-      }
-    } else {
-      const Vec a = *reinterpret_cast<const Vec*>(x0 + lo);
-      d0[0] = a.v[0] - a.v[1];
-      if (p.cross) {
-        const Vec a1 = *reinterpret_cast<const Vec*>(x1 + lo);
-        d[0] = d0[0] + (a1.v[0] - a1.v[1]);
-      }
-    }
-    bool flag_vec = false;
-    if constexpr (F == 1) {
-      flag_vec = p.sdiv == 1;
-      if (flag_vec) {  // a flag per product: the two are one vector
-        const Vec f = *reinterpret_cast<const Vec*>(s0 + sb + g);
-        f0[0] = f.v[0], f0[1] = f.v[1];
-        if (p.cross) {
-          const Vec h = *reinterpret_cast<const Vec*>(s1 + sb + g);
-          f1[0] = h.v[0], f1[1] = h.v[1];
-        }
-      }
-    }
-    if (!flag_vec) {
-#pragma unroll
-      for (int v = 0; v < V; ++v) {
-        const I fi = sb + (p.sdiv == 1 ? g + v : (I)((U)(g + v) / (U)p.sdiv));
-        f0[v] = s0[fi];
-        if (p.cross) f1[v] = s1[fi];
-      }
-    }
-    T o[V];
-#pragma unroll
-    for (int v = 0; v < V; ++v) o[v] = p.cross ? f0[v] * d[v] + f1[v] * d0[v] : f0[v] * d0[v];
-    if constexpr (F == 1) {
-      Vec w;
-      w.v[0] = o[0], w.v[1] = o[1];
-      *reinterpret_cast<Vec*>(dst + g) = w;
-    } else {
-      dst[g] = o[0];
-    }
-  }
-}
-
-template <class T, class I, int F>
-__global__ void __launch_bounds__(256) k_cswap_apply(const T* __restrict__ x,
-                                                     const T* __restrict__ pr,
-                                                     T* __restrict__ out, CswapP<I> p) {
-  constexpr int V = F == 1 ? 2 : 1;
-  using Vec = LaneVec<T, 2>;
-  const T* __restrict__ src = x + (I)blockIdx.z * p.x_slot;
-  const T* __restrict__ q = pr + (I)blockIdx.z * p.a_slot;
-  T* __restrict__ dst = out + (I)blockIdx.z * p.n_x;
-  const I step = (I)(gridDim.x * 256u) * V;
-  for (I g = (I)(blockIdx.x * 256u + threadIdx.x) * V; g < p.total; g += step) {
-    I b;
-    const I lo = cswap_low_of(p, g, b);
-    if constexpr (F == 0) {
-      const T d = q[g];
-      dst[lo] = src[lo] - d;
-      dst[lo + p.r] = src[lo + p.r] + d;
-    } else if constexpr (F == 1) {
-      const Vec d = *reinterpret_cast<const Vec*>(q + g);
-      Vec a = *reinterpret_cast<const Vec*>(src + lo);
-      Vec c = *reinterpret_cast<const Vec*>(src + lo + p.r);
-#pragma unroll
-      for (int v = 0; v < 2; ++v) a.v[v] -= d.v[v], c.v[v] += d.v[v];
-      *reinterpret_cast<Vec*>(dst + lo) = a;
-      *reinterpret_cast<Vec*>(dst + lo + p.r) = c;
-    } else {
-      const T d = q[g];
-      Vec a = *reinterpret_cast<const Vec*>(src + lo);
-      a.v[0] -= d, a.v[1] += d;
-      *reinterpret_cast<Vec*>(dst + lo) = a;
-    }
-  }
-}
-
-// the parameters of a stage: `key_only` walks the key column's pairs (the table-mode difference)
-template <class I>
-static CswapP<I> cswap_params(const mxr::CswapGeom& g, bool key_only, int64_t x_slot,
-                              int64_t a_slot, bool cross) {
-  CswapP<I> p;
-  std::memset(&p, 0, sizeof(p));
-  const int64_t r = key_only ? g.j : g.j * g.inner;
-  p.x_slot = (I)x_slot, p.a_slot = (I)a_slot;
-  p.total = (I)(key_only ? g.outer * g.half : g.n_pair);
-  p.r = (I)r, p.unit = (I)(key_only ? g.inner : 1), p.off = (I)(key_only ? g.by : 0);
-  p.sdiv = (I)(g.by >= 0 ? g.inner : 1);
-  p.amask = (I)(g.n / (2 * g.j) - 1), p.k = (I)g.k, p.n_x = (I)g.n_x;
-  p.rs = -1;
-  if ((r & (r - 1)) == 0)
-    for (p.rs = 0; ((int64_t)1 << p.rs) < r;) ++p.rs;
-  p.lj1 = g.lj + 1, p.desc = g.descending, p.cross = cross;
-  return p;
-}
-
-// launch(CswapForm<T, I, F>{}): u64 takes form 2 when r == 1 and form 1 when r is even, where
-// `wide` (unit stride, every operand and slot stride on 16 bytes) allows; u128 form 0
-template <class L>
-static int cswap_dispatch(int elem_bytes, bool small, bool wide, int64_t r, L launch) {
-#define MX_CSWAP_FORM(T, F)                                 \
-  return small ? launch(CswapForm<T, int32_t, F>{}) : launch(CswapForm<T, int64_t, F>{})
-  switch (elem_bytes) {
-    case 8:
-      if (wide && r == 1) {
-        MX_CSWAP_FORM(u64, 2);
-      }
-      if (wide && r % 2 == 0) {
-        MX_CSWAP_FORM(u64, 1);
-      }
-      MX_CSWAP_FORM(u64, 0);
-    case 16: MX_CSWAP_FORM(u128, 0);
-    default: return -2;
-  }
-#undef MX_CSWAP_FORM
-}
-
-// the grid is capped at 256 CUs x 8 blocks per slot; a lane strides over the rest
-static dim3 cswap_grid(int64_t total, int F, int64_t slots) {
-  const int64_t lanes = F == 1 ? total / 2 : total;
-  return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((lanes + 255) / 256, 256 * 8)), 1,
-              (unsigned)slots);
-}
-
 // party-batched twins of the per-party sessions' local kernels (party_batch.h)
 MX_X3_GS(k_binary2<u64>, d_binary2<u64>);
 MX_X3_GS(k_binary2<u128>, d_binary2<u128>);
@@ -2643,181 +1805,9 @@ MX_X3(k_prf_expand<u128>, d_prf_expand<u128>);
 MX_X3(k_ring_inject<u64>, d_ring_inject<u64>);
 MX_X3(k_ring_inject<u128>, d_ring_inject<u128>);
 
-// Reference (VALU) ring GEMM: 16x16 output tile per block, K staged through LDS.
-// a_bs / b_bs: batch strides in elements (0: one operand broadcast over the batch).
-template <class T, int TS>
-__device__ __forceinline__ void d_gemm_valu(int64_t M, int64_t N, int64_t K,
-                                            const T* __restrict__ A0, const T* __restrict__ A1,
-                                            const T* __restrict__ B0, const T* __restrict__ B1,
-                                            int mode, T* __restrict__ C, int accumulate,
-                                            int64_t a_bs, int64_t b_bs, int zb) {
-  __shared__ T As[TS][TS + 1];
-  __shared__ T Bs[TS][TS + 1];
-  const int64_t b = zb >= 0 ? zb : blockIdx.z;  // zb >= 0: an unbatched launch's only product
-  const int64_t row = blockIdx.y * TS + threadIdx.y;
-  const int64_t col = blockIdx.x * TS + threadIdx.x;
-  const T* a0 = A0 + b * a_bs;
-  const T* b0 = B0 + b * b_bs;
-  const T* a1 = mode ? A1 + b * a_bs : nullptr;
-  const T* b1 = mode ? B1 + b * b_bs : nullptr;
-  T acc = 0;
-  const int passes = mode ? 2 : 1;
-  for (int pass = 0; pass < passes; ++pass) {
-    for (int64_t k0 = 0; k0 < K; k0 += TS) {
-      int64_t ka = k0 + threadIdx.x, kb = k0 + threadIdx.y;
-      T av = 0, bv = 0;
-      if (row < M && ka < K) av = (pass == 0 ? a0 : a1)[row * K + ka];
-      if (col < N && kb < K) {
-        bv = b0[kb * N + col];
-        if (mode && pass == 0) bv += b1[kb * N + col];
-      }
-      As[threadIdx.y][threadIdx.x] = av;
-      Bs[threadIdx.y][threadIdx.x] = bv;
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < TS; ++k) acc += As[threadIdx.y][k] * Bs[k][threadIdx.x];
-      __syncthreads();
-    }
-  }
-  if (row < M && col < N) {
-    T* c = C + b * M * N + row * N + col;
-    *c = accumulate ? (T)(*c + acc) : acc;
-  }
-}
-
-template <class T, int TS>
-__global__ void __launch_bounds__(256) k_gemm_valu(int64_t M, int64_t N, int64_t K,
-                                                   const T* __restrict__ A0,
-                                                   const T* __restrict__ A1,
-                                                   const T* __restrict__ B0,
-                                                   const T* __restrict__ B1, int mode,
-                                                   T* __restrict__ C, int accumulate,
-                                                   int64_t a_bs, int64_t b_bs, int zb) {
-  d_gemm_valu<T, TS>(M, N, K, A0, A1, B0, B1, mode, C, accumulate, a_bs, b_bs, zb);
-}
-
-// an unbatched product (grid z = 1, zb = 0) of several parties: one party-batched launch
-MX_X3((k_gemm_valu<u64, 16>), (d_gemm_valu<u64, 16>));
-MX_X3((k_gemm_valu<u128, 16>), (d_gemm_valu<u128, 16>));
-
-// Skinny products (N <= 4: a matrix times a vector or a few columns -- the per-party
-// LogReg and LR dots): one wave per output row, its lanes splitting K, then a butterfly over
-// whole ring elements.  One pass of coalesced loads instead of the tiled kernel's serial
-// k-tiles with two barriers each (a 100 x 128 by 128 x 1 product: ~25 us there).  The same
-// ring sums (addition mod 2^w is associative), so the same products.
-template <class T>
-__device__ __forceinline__ T shfl_xor_wave(T v, int m) {
-  constexpr int W = (int)(sizeof(T) / 4);
-  uint32_t w[W];
-#pragma unroll
-  for (int q = 0; q < W; ++q) w[q] = (uint32_t)(v >> (32 * q));
-#pragma unroll
-  for (int q = 0; q < W; ++q) w[q] = (uint32_t)__shfl_xor((int)w[q], m, 64);
-  T r = 0;
-#pragma unroll
-  for (int q = 0; q < W; ++q) r |= (T)w[q] << (32 * q);
-  return r;
-}
-
-template <class T>
-__device__ __forceinline__ void d_gemv_valu(int64_t M, int64_t N, int64_t K,
-                                            const T* __restrict__ A0, const T* __restrict__ A1,
-                                            const T* __restrict__ B0, const T* __restrict__ B1,
-                                            int mode, T* __restrict__ C, int accumulate,
-                                            int64_t a_bs, int64_t b_bs, int zb) {
-  const int64_t b = zb >= 0 ? zb : blockIdx.z;
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (row >= M) return;  // uniform per wave: the butterfly below sees whole waves
-  const T* a0 = A0 + b * a_bs + row * K;
-  const T* a1 = mode ? A1 + b * a_bs + row * K : nullptr;
-  const T* b0 = B0 + b * b_bs;
-  const T* b1 = mode ? B1 + b * b_bs : nullptr;
-  for (int64_t n = 0; n < N; ++n) {
-    T acc = 0;
-    for (int64_t k = lane; k < K; k += 64) {
-      const T y0 = b0[k * N + n];
-      if (mode) {
-        acc += a0[k] * (y0 + b1[k * N + n]) + a1[k] * y0;
-      } else {
-        acc += a0[k] * y0;
-      }
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) acc += shfl_xor_wave(acc, m);
-    if (lane == 0) {
-      T* c = C + b * M * N + row * N + n;
-      *c = accumulate ? (T)(*c + acc) : acc;
-    }
-  }
-}
-
-template <class T>
-__global__ void __launch_bounds__(256) k_gemv_valu(int64_t M, int64_t N, int64_t K,
-                                                   const T* __restrict__ A0,
-                                                   const T* __restrict__ A1,
-                                                   const T* __restrict__ B0,
-                                                   const T* __restrict__ B1, int mode,
-                                                   T* __restrict__ C, int accumulate,
-                                                   int64_t a_bs, int64_t b_bs, int zb) {
-  d_gemv_valu<T>(M, N, K, A0, A1, B0, B1, mode, C, accumulate, a_bs, b_bs, zb);
-}
-
-MX_X3(k_gemv_valu<u64>, d_gemv_valu<u64>);
-MX_X3(k_gemv_valu<u128>, d_gemv_valu<u128>);
-
-// MOOSEX_GEMV=0: skinny products on the tiled kernel too
-bool gemv_on() {
-  static const bool on = [] {
-    const char* e = std::getenv("MOOSEX_GEMV");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-template <class T>
-int launch_gemm_valu(int64_t batch, int64_t M, int64_t N, int64_t K, const void* A0,
-                     const void* A1, const void* B0, const void* B1, int mode, void* C,
-                     int accumulate, hipStream_t st, int64_t a_bs = -1, int64_t b_bs = -1) {
-  if (N <= 4 && gemv_on()) {
-    const dim3 grid((unsigned)((M + 3) / 4), 1, (unsigned)batch);
-    hipLaunchKernelGGL((k_gemv_valu<T>), grid, dim3(256), 0, st, M, N, K, (const T*)A0,
-                       (const T*)A1, (const T*)B0, (const T*)B1, mode, (T*)C, accumulate,
-                       a_bs < 0 ? M * K : a_bs, b_bs < 0 ? K * N : b_bs, batch == 1 ? 0 : -1);
-    MX_LAUNCH_CHECK();
-    return 0;
-  }
-  constexpr int TS = 16;
-  dim3 grid((unsigned)((N + TS - 1) / TS), (unsigned)((M + TS - 1) / TS), (unsigned)batch);
-  dim3 block(TS, TS);
-  hipLaunchKernelGGL((k_gemm_valu<T, TS>), grid, block, 0, st, M, N, K, (const T*)A0,
-                     (const T*)A1, (const T*)B0, (const T*)B1, mode, (T*)C, accumulate,
-                     a_bs < 0 ? M * K : a_bs, b_bs < 0 ? K * N : b_bs, batch == 1 ? 0 : -1);
-  MX_LAUNCH_CHECK();
-  return 0;
-}
-
-
 }  // namespace
 
-// from gemm_mfma.hip
-extern "C" int mxh_gemm_mfma(int words, int64_t batch, int64_t M, int64_t N, int64_t K,
-                             const void* A0, const void* A1, const void* B0, const void* B1,
-                             int mode, void* C, int accumulate, void* stream);
-
-static int g_gemm_impl = 0;
-
-#define DEV_DISPATCH(words, T, ...)            \
-  switch (words) {                             \
-    case 0: { using T = uint8_t; __VA_ARGS__; } \
-    case 1: { using T = u64; __VA_ARGS__; }     \
-    case 2: { using T = u128; __VA_ARGS__; }    \
-    default: return -2;                        \
-  }
-
 extern "C" {
-
-void mx_set_gemm_impl(int impl) { g_gemm_impl = impl; }
 
 int mx_device_count(void) {
   int n = 0;
@@ -2873,155 +1863,6 @@ int mxh_transpose2(int words, const void* a0, void* out0, const void* a1, void* 
                        rows, cols);
     MX_LAUNCH_CHECK();
     return 0;
-  });
-}
-
-// The image leaves: g comes validated from mx_* (img_geom_check); what is left here is what
-// only a launch is bound by -- slots are blockIdx.z -- and each leaf's choice of form.
-int mxh_im2col(int elem_bytes, const void* in, void* out, int64_t slots, int64_t in_slot_stride,
-               const ImgGeom& g, void* stream) {
-  if (slots > 65535 || (g.K + 63) / 64 > 0x7fffffff) return -3;
-  const int64_t in_extent = (slots - 1) * in_slot_stride + g.n_in;
-  const bool small = fits32(1 << 17, {in_extent, slots * g.n_out});
-  const bool two = g.K % 2 == 0 && aligned16(out);
-  return leaf_dispatch<true>(elem_bytes, small, two, [&](auto f) {
-    using F = decltype(f);
-    return im2col_launch<typename F::T, typename F::I, F::V>(in, out, slots, in_slot_stride, g,
-                                                             stream);
-  });
-}
-
-int mxh_col2im(int elem_bytes, const void* in, void* out, int64_t slots, int64_t in_slot_stride,
-               const ImgGeom& g, void* stream) {
-  if (slots > 65535) return -3;
-  const int64_t in_extent = (slots - 1) * in_slot_stride + g.N * g.OH * g.OW * g.K;
-  const bool small = fits32(1 << 23, {in_extent, slots * g.n_out});
-  // 16-byte stores need an even inner extent; NHWC's 16-byte loads an aligned input too
-  const bool two = g.inner % 2 == 0 && aligned16(out) &&
-                   (!g.nhwc || (aligned16(in) && in_slot_stride % 2 == 0));
-  return leaf_dispatch(elem_bytes, small, two, [&](auto f) {
-    using F = decltype(f);
-    return col2im_launch<typename F::T, typename F::I, F::V>(in, out, slots, in_slot_stride, g,
-                                                             stream);
-  });
-}
-
-int mxh_resize2d(int elem_bytes, const void* in, void* out, int64_t slots,
-                 int64_t in_slot_stride, const ImgGeom& g, const int32_t* th,
-                 const int32_t* tw, void* stream) {
-  if (slots > 65535) return -3;
-  const int64_t in_extent = (slots - 1) * in_slot_stride + g.n_in;
-  const bool small = fits32(1 << 23, {in_extent, slots * g.n_out});
-  // two outputs per lane share their taps only in NHWC; 16-byte accesses need an even C and
-  // aligned buffers
-  const bool two = g.nhwc && g.C % 2 == 0 && aligned16(out) && aligned16(in) &&
-                   in_slot_stride % 2 == 0;
-  return leaf_dispatch(elem_bytes, small, two, [&](auto f) {
-    using F = decltype(f);
-    return resize2d_launch<typename F::T, typename F::I, F::V>(in, out, slots, in_slot_stride,
-                                                               g, th, tw, stream);
-  });
-}
-
-int mxh_pwl_cross(int elem_bytes, const void* s0, const void* s1, const void* x0, const void* x1,
-                  void* out, int64_t slots, int64_t s_slot_stride, int64_t x_slot_stride,
-                  int64_t n, int k, const uint64_t* da, const uint64_t* db, const uint64_t* ak,
-                  void* stream) {
-  if (slots <= 0 || n <= 0) return 0;
-  if (k < 0 || k > MX_PWL_MAX || slots > 65535 || s_slot_stride < 0 || x_slot_stride < 0 || !ak ||
-      (k && (!da || !db)) || (s1 == nullptr) != (x1 == nullptr))
-    return -3;
-  const int64_t s_extent = (slots - 1) * s_slot_stride + (int64_t)k * n;
-  const int64_t x_extent = (slots - 1) * x_slot_stride + n;
-  const bool small = fits32(1 << 23, {s_extent, x_extent, slots * n});
-  // two outputs per lane: every plane, slot and buffer has to start on 16 bytes
-  const bool two = n % 2 == 0 && aligned16(s0) && aligned16(s1) && aligned16(x0) &&
-                   aligned16(x1) && aligned16(out) && s_slot_stride % 2 == 0 &&
-                   x_slot_stride % 2 == 0;
-  return leaf_dispatch(elem_bytes, small, two, [&](auto f) {
-    using F = decltype(f);
-    return pwl_cross_launch<typename F::T, typename F::I, F::V>(
-        s0, s1, x0, x1, out, slots, s_slot_stride, x_slot_stride, n, k, da, db, ak, stream);
-  });
-}
-
-int mxh_cswap_diff(int elem_bytes, const void* x, void* out, int64_t slots, int64_t x_slot_stride,
-                   const mxr::CswapGeom& g, void* stream) {
-  if (slots > 65535) return -3;
-  const bool key_only = g.by >= 0;
-  const int64_t r = key_only ? g.j : g.j * g.inner;
-  const bool small = fits32(1 << 23, {(slots - 1) * x_slot_stride + g.n_x, slots * g.n_flag});
-  const bool wide = (!key_only || g.inner == 1) && aligned16(x) && aligned16(out) &&
-                    x_slot_stride % 2 == 0;
-  return cswap_dispatch(elem_bytes, small, wide, r, [&](auto f) {
-    using F = decltype(f);
-    using T = typename F::T;
-    const auto p = cswap_params<typename F::I>(g, key_only, x_slot_stride, 0, false);
-    hipLaunchKernelGGL((k_cswap_diff<T, typename F::I, F::F>), cswap_grid(g.n_flag, F::F, slots),
-                       dim3(256), 0, S(stream), (const T*)x, (T*)out, p);
-    MX_LAUNCH_CHECK();
-    return 0;
-  });
-}
-
-int mxh_cswap_cross(int elem_bytes, const void* s0, const void* s1, const void* x0,
-                    const void* x1, void* out, int64_t slots, int64_t s_slot_stride,
-                    int64_t x_slot_stride, const mxr::CswapGeom& g, void* stream) {
-  if (slots > 65535 || (s1 == nullptr) != (x1 == nullptr)) return -3;
-  const bool small = fits32(1 << 23, {(slots - 1) * x_slot_stride + g.n_x,
-                                      (slots - 1) * s_slot_stride + g.n_flag, slots * g.n_pair});
-  const bool wide = aligned16(s0) && aligned16(s1) && aligned16(x0) && aligned16(x1) &&
-                    aligned16(out) && s_slot_stride % 2 == 0 && x_slot_stride % 2 == 0;
-  return cswap_dispatch(elem_bytes, small, wide, g.j * g.inner, [&](auto f) {
-    using F = decltype(f);
-    using T = typename F::T;
-    const auto p =
-        cswap_params<typename F::I>(g, false, x_slot_stride, s_slot_stride, x1 != nullptr);
-    hipLaunchKernelGGL((k_cswap_cross<T, typename F::I, F::F>),
-                       cswap_grid(g.n_pair, F::F, slots), dim3(256), 0, S(stream), (const T*)s0,
-                       (const T*)s1, (const T*)x0, (const T*)x1, (T*)out, p);
-    MX_LAUNCH_CHECK();
-    return 0;
-  });
-}
-
-int mxh_cswap_apply(int elem_bytes, const void* x, const void* pr, void* out, int64_t slots,
-                    int64_t x_slot_stride, int64_t p_slot_stride, const mxr::CswapGeom& g,
-                    void* stream) {
-  if (slots > 65535) return -3;
-  const bool small = fits32(1 << 23, {(slots - 1) * x_slot_stride + g.n_x,
-                                      (slots - 1) * p_slot_stride + g.n_pair, slots * g.n_x});
-  const bool wide = aligned16(x) && aligned16(pr) && aligned16(out) && x_slot_stride % 2 == 0 &&
-                    p_slot_stride % 2 == 0;
-  return cswap_dispatch(elem_bytes, small, wide, g.j * g.inner, [&](auto f) {
-    using F = decltype(f);
-    using T = typename F::T;
-    const auto p = cswap_params<typename F::I>(g, false, x_slot_stride, p_slot_stride, false);
-    hipLaunchKernelGGL((k_cswap_apply<T, typename F::I, F::F>),
-                       cswap_grid(g.n_pair, F::F, slots), dim3(256), 0, S(stream), (const T*)x,
-                       (const T*)pr, (T*)out, p);
-    MX_LAUNCH_CHECK();
-    return 0;
-  });
-}
-
-int mxh_dwconv(int elem_bytes, const void* x0, const void* x1, const void* w0, const void* w1,
-               void* out, int64_t slots, int64_t x_slot_stride, int64_t w_slot_stride,
-               const ImgGeom& g, void* stream) {
-  if (slots > 65535) return -3;
-  const int64_t x_extent = (slots - 1) * x_slot_stride + g.n_in;
-  const int64_t w_extent = (slots - 1) * w_slot_stride + g.OC * g.KH * g.KW;
-  const bool small = fits32(1 << 23, {x_extent, w_extent, slots * g.n_out});
-  const bool two = g.inner % 2 == 0 && aligned16(out);
-  const bool cross = x1 != nullptr;
-  return leaf_dispatch(elem_bytes, small, two, [&](auto f) {
-    using F = decltype(f);
-    using T = typename F::T;
-    using I = typename F::I;
-    return cross ? dwconv_launch<T, I, F::V, true>(x0, x1, w0, w1, out, slots, x_slot_stride,
-                                                   w_slot_stride, g, stream)
-                 : dwconv_launch<T, I, F::V, false>(x0, x1, w0, w1, out, slots, x_slot_stride,
-                                                    w_slot_stride, g, stream);
   });
 }
 
@@ -3822,45 +2663,6 @@ int mxh_prf_expand_k(int words, void* out, int64_t n, int nkeys, const uint32_t*
   const uint32_t* ptrs[4];
   for (int i = 0; i < nkeys; ++i) ptrs[i] = slots + MX_KEY_SLOT_WORDS * i;
   return launch_prf_expand(words, out, n, nkeys, mxd::keysrc_slots(ptrs, nkeys), nonce, stream);
-}
-
-int mxh_gemm(int words, int64_t batch, int64_t M, int64_t N, int64_t K, const void* A0,
-             const void* A1, const void* B0, const void* B1, int mode, void* C, int accumulate,
-             void* stream) {
-  if (M == 0 || N == 0 || batch == 0) return 0;
-  bool big = M >= 64 && N >= 64 && K >= 32;
-  if ((g_gemm_impl == 2 || (g_gemm_impl == 0 && big)) && (words == 1 || words == 2))
-    return mxh_gemm_mfma(words, batch, M, N, K, A0, A1, B0, B1, mode, C, accumulate, stream);
-  if (words == 1)
-    return launch_gemm_valu<u64>(batch, M, N, K, A0, A1, B0, B1, mode, C, accumulate,
-                                 S(stream));
-  if (words == 2)
-    return launch_gemm_valu<u128>(batch, M, N, K, A0, A1, B0, B1, mode, C, accumulate,
-                                  S(stream));
-  return -2;
-}
-
-// Plain batched product with explicit batch strides (elements; 0 broadcasts an operand):
-// the small-product (VALU) kernel, or the strided MFMA/CRT GEMM for large ones.
-extern "C" int mx_gemm_strided(int words, int64_t batch, int64_t M, int64_t N, int64_t K,
-                               const void* A0, const void* A1, int64_t a_bstride, const void* B0,
-                               const void* B1, int64_t b_bstride, int mode, void* C,
-                               int accumulate, void* stream);
-
-int mxh_gemm_bs(int words, int64_t batch, int64_t M, int64_t N, int64_t K, const void* A0,
-                int64_t a_bs, const void* B0, int64_t b_bs, void* C, void* stream) {
-  if (M == 0 || N == 0 || batch == 0) return 0;
-  const bool big = M >= 64 && N >= 64 && K >= 32;
-  if (big && g_gemm_impl != 1)
-    return mx_gemm_strided(words, batch, M, N, K, A0, nullptr, a_bs, B0, nullptr, b_bs, 0, C, 0,
-                           stream);
-  if (words == 1)
-    return launch_gemm_valu<u64>(batch, M, N, K, A0, nullptr, B0, nullptr, 0, C, 0, S(stream),
-                                 a_bs, b_bs);
-  if (words == 2)
-    return launch_gemm_valu<u128>(batch, M, N, K, A0, nullptr, B0, nullptr, 0, C, 0, S(stream),
-                                  a_bs, b_bs);
-  return -2;
 }
 
 }  // extern "C"

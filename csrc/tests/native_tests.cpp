@@ -68,7 +68,7 @@ struct Reg {
   static void name()
 
 // ---------------------------------------------------------------------------------
-// ring kernels (host path of libmoosex: csrc/ring_cpu.cpp, rss_fused_cpu.cpp)
+// ring kernels (host path of libmoosex: csrc/ring_cpu.cpp and the other *_cpu.cpp)
 // ---------------------------------------------------------------------------------
 static std::mt19937_64 rng(7);
 
