@@ -1328,7 +1328,7 @@ __global__ void __launch_bounds__(256) k_ks_cross1(const T* __restrict__ g0,
                                                    const T* __restrict__ t1 = nullptr,
                                                    T* __restrict__ go0 = nullptr,
                                                    T* __restrict__ go1 = nullptr) {
-  d_ks_cross1<T>(g0, g1, p0, p1, z, n, d, both, keys, nonce, nullptr, nullptr, nullptr, nullptr);
+  d_ks_cross1<T>(g0, g1, p0, p1, z, n, d, both, keys, nonce, t0, t1, go0, go1);
 }
 
 // Latency form of k_ks_cross1 (a per-party level of the LR inference's adders: a few

@@ -241,7 +241,8 @@ def test_ks_cross1_matches_host(bits, both):
 def test_ks_cross1_slots_latency_form_matches_host(bits, both, n):
     """The key-slot Kogge-Stone level kernels of the per-party adders (ks_cross1_s and the
     xor-folding ks_cross1x_s; small launches take the latency form k_ks_cross1_lat):
-    GPU == CPU bitwise, keys read from device / host key slots."""
+    GPU == CPU bitwise, keys read from device / host key slots.  Both sizes stay in the
+    latency form; tests/test_size_switches.py runs both sides of its 16,384-chunk limit."""
     from moose_amd.runtime.keys import KeyTable
 
     xs = [rand_rt((n,), bits, 80 + i) for i in range(6)]
