@@ -188,6 +188,39 @@ void pwl_cross_cpu(const T* s0, const T* s1, const T* x0, const T* x1, T* out, i
   });
 }
 
+// piecewise-polynomial local step (moosex.h mx_pwp_cross): the arithmetic of k_pwp_cross in
+// plain loops, one output element at a time.  G[0] is the constant's sum H.
+template <class T>
+void pwp_cross_cpu(const T* s0, const T* s1, const void* const* p0, const void* const* p1, T* out,
+                   int64_t slots, int64_t s_slot_stride, const int64_t* p_slot_stride, int64_t n,
+                   int k, int d, const uint64_t* dt, const uint64_t* ck) {
+  T D[MX_PWP_DEG + 1][MX_PWP_MAX], CK[MX_PWP_DEG + 1];
+  for (int i = 0; i <= d; ++i) std::memcpy(D[i], (const T*)dt + (int64_t)i * k, sizeof(T) * k);
+  std::memcpy(CK + 1, ck, sizeof(T) * d);
+  const bool cross = p1 != nullptr;
+  parallel_for(slots * n, 1 << 12, [&](int64_t b, int64_t e) {
+    for (int64_t g = b; g < e; ++g) {
+      const int64_t s = g / n, i = g - s * n;
+      const T* f0 = s0 + s * s_slot_stride + i;
+      const T* f1 = cross ? s1 + s * s_slot_stride + i : nullptr;
+      T g0[MX_PWP_DEG + 1] = {0, 0, 0, 0}, g1[MX_PWP_DEG + 1] = {0, 0, 0, 0};
+      for (int j = 0; j < k; ++j) {
+        for (int q = 0; q <= d; ++q) g0[q] += D[q][j] * f0[j * n];
+        if (cross)
+          for (int q = 1; q <= d; ++q) g1[q] += D[q][j] * f1[j * n];
+      }
+      T v = 0;
+      for (int q = 1; q <= d; ++q) {
+        const int64_t pi = s * p_slot_stride[q - 1] + i;
+        const T a0 = ((const T*)p0[q - 1])[pi];
+        v += g0[q] * (cross ? a0 + ((const T*)p1[q - 1])[pi] : a0) + CK[q] * a0;
+        if (cross) v += g1[q] * a0;
+      }
+      out[g] = v + g0[0];
+    }
+  });
+}
+
 using mxr::CswapGeom;
 
 // The compare-exchange leaves (moosex.h mx_cswap_*): one (slot, row, pair) at a time, the
@@ -351,6 +384,31 @@ int mx_pwl_cross(int dev, int elem_bytes, const void* s0, const void* s1, const 
   DISPATCH_ELEM(elem_bytes, T, {
     pwl_cross_cpu((const T*)s0, (const T*)s1, (const T*)x0, (const T*)x1, (T*)out, slots,
                   s_slot_stride, x_slot_stride, n, k, da, db, ak);
+    return 0;
+  });
+}
+
+int mx_pwp_cross(int dev, int elem_bytes, const void* s0, const void* s1, const void* const* p0,
+                 const void* const* p1, void* out, int64_t slots, int64_t s_slot_stride,
+                 const int64_t* p_slot_stride, int64_t n, int k, int d, const uint64_t* dt,
+                 const uint64_t* ck, void* stream) {
+  if (slots < 0 || n < 0 || k < 1 || k > MX_PWP_MAX || d < 1 || d > MX_PWP_DEG ||
+      s_slot_stride < 0 || !p0 || !p_slot_stride || !dt || !ck)
+    return -3;
+  if ((s1 == nullptr) != (p1 == nullptr)) return -3;  // cross mode takes both next components
+  if (elem_bytes != 8 && elem_bytes != 16) return -2;
+  for (int i = 0; i < d; ++i)
+    if (p_slot_stride[i] < 0) return -3;
+  if (slots * n == 0) return 0;
+  for (int i = 0; i < d; ++i)
+    if (!p0[i] || (p1 && !p1[i])) return -3;
+  if (!s0 || !out) return -3;
+  if (dev)
+    return mxh_pwp_cross(elem_bytes, s0, s1, p0, p1, out, slots, s_slot_stride, p_slot_stride, n,
+                         k, d, dt, ck, stream);
+  DISPATCH_ELEM(elem_bytes, T, {
+    pwp_cross_cpu((const T*)s0, (const T*)s1, p0, p1, (T*)out, slots, s_slot_stride,
+                  p_slot_stride, n, k, d, dt, ck);
     return 0;
   });
 }

@@ -1,5 +1,6 @@
 // gfx950 leaf kernels of the moosex ring dialect: the image leaves (im2col, dwconv, col2im,
-// resize2d), the piecewise-linear local step (pwl_cross) and the compare-exchange leaves
+// resize2d), the piecewise-linear and piecewise-polynomial local steps (pwl_cross, pwp_cross)
+// and the compare-exchange leaves
 // (cswap_diff / _cross / _apply), each a share-wise kernel over slots with its geometry checked
 // on the host (img_geom.h, cswap_geom.h) before it gets here.
 
@@ -605,6 +606,104 @@ static int pwl_cross_launch(const void* s0, const void* s1, const void* x0, cons
   return 0;
 }
 
+// piecewise-polynomial local step (moosex.h mx_pwp_cross), on k_pwl_cross's plan: a lane owns V
+// adjacent outputs (one u128, or two u64 when n is even and every buffer is 16-byte aligned),
+// strides over the slot by the grid, slots are blockIdx.z.  Per output: 2k + 2D reads of 16
+// bytes per lane (k + D in plain mode) and one write; each power is read through its own
+// pointer pair at its own slot stride, where its multiplication wrote it.  The (D + 1) x k
+// difference tables, the D last-piece coefficients and the power pointers arrive in the
+// kernel's arguments and every index into them is a compile-time constant once the loops are
+// unrolled, so they are scalar operands and nothing is a table in memory.  The loop over the
+// planes is unrolled to MX_PWP_MAX with a uniform exit.  g0[0] is the constant's sum H.
+// Wrapping sums, so the results equal the CPU twin's bit for bit.
+template <class T, class I, int D>
+struct PwpP {
+  T dt[D + 1][MX_PWP_MAX], ck[D];
+  const T* p0[D];
+  const T* p1[D];
+  I p_slot[D];  // slot strides of the powers in elements
+  I s_slot, n;  // the flags' slot stride and the slot length
+  int k, cross;
+};
+
+template <class T, class I, int V, int D>
+__global__ void __launch_bounds__(256) k_pwp_cross(const T* __restrict__ s0,
+                                                   const T* __restrict__ s1, T* __restrict__ out,
+                                                   PwpP<T, I, D> p) {
+  using Vec = LaneVec<T, V>;
+  const I sb = (I)blockIdx.z * p.s_slot;
+  T* __restrict__ dst = out + (I)blockIdx.z * p.n;
+  const I step = (I)(gridDim.x * 256u) * V;
+  // V == 2 only with an even n: both outputs are inside, or neither
+  for (I i = (I)(blockIdx.x * 256u + threadIdx.x) * V; i < p.n; i += step) {
+    Vec g0[D + 1], g1[D + 1];
+#pragma unroll
+    for (int q = 0; q <= D; ++q)
+#pragma unroll
+      for (int v = 0; v < V; ++v) g0[q].v[v] = g1[q].v[v] = (T)0;
+#pragma unroll
+    for (int j = 0; j < MX_PWP_MAX; ++j) {
+      if (j >= p.k) break;
+      const I fi = sb + (I)j * p.n + i;
+      const Vec f0 = *reinterpret_cast<const Vec*>(s0 + fi);
+#pragma unroll
+      for (int q = 0; q <= D; ++q)
+#pragma unroll
+        for (int v = 0; v < V; ++v) g0[q].v[v] += p.dt[q][j] * f0.v[v];
+      if (p.cross) {
+        const Vec f1 = *reinterpret_cast<const Vec*>(s1 + fi);
+#pragma unroll
+        for (int q = 1; q <= D; ++q)
+#pragma unroll
+          for (int v = 0; v < V; ++v) g1[q].v[v] += p.dt[q][j] * f1.v[v];
+      }
+    }
+    Vec o = g0[0];
+#pragma unroll
+    for (int q = 1; q <= D; ++q) {
+      const I pi = (I)blockIdx.z * p.p_slot[q - 1] + i;
+      const Vec a0 = *reinterpret_cast<const Vec*>(p.p0[q - 1] + pi);
+      Vec a = a0;
+      if (p.cross) {
+        const Vec a1 = *reinterpret_cast<const Vec*>(p.p1[q - 1] + pi);
+#pragma unroll
+        for (int v = 0; v < V; ++v) a.v[v] += a1.v[v];
+      }
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        o.v[v] += g0[q].v[v] * a.v[v] + p.ck[q - 1] * a0.v[v];
+        if (p.cross) o.v[v] += g1[q].v[v] * a0.v[v];
+      }
+    }
+    *reinterpret_cast<Vec*>(dst + i) = o;
+  }
+}
+
+template <class T, class I, int V, int D>
+static int pwp_cross_launch(const void* s0, const void* s1, const void* const* p0,
+                            const void* const* p1, void* out, int64_t slots,
+                            int64_t s_slot_stride, const int64_t* p_slot_stride, int64_t n, int k,
+                            const uint64_t* dt, const uint64_t* ck, void* stream) {
+  PwpP<T, I, D> p;
+  std::memset(&p, 0, sizeof(p));
+  for (int q = 0; q <= D; ++q) std::memcpy(p.dt[q], (const T*)dt + (int64_t)q * k, sizeof(T) * k);
+  std::memcpy(p.ck, ck, sizeof(T) * D);
+  for (int q = 0; q < D; ++q) {
+    p.p0[q] = (const T*)p0[q];
+    p.p1[q] = p1 ? (const T*)p1[q] : nullptr;
+    p.p_slot[q] = (I)p_slot_stride[q];
+  }
+  p.s_slot = (I)s_slot_stride, p.n = (I)n;
+  p.k = k, p.cross = p1 != nullptr;
+  const int64_t lanes = (n + V - 1) / V;
+  // the grid is capped at 256 CUs x 8 blocks per slot; a lane strides over the rest
+  const int64_t gx = std::min<int64_t>((lanes + 255) / 256, 256 * 8);
+  hipLaunchKernelGGL((k_pwp_cross<T, I, V, D>), dim3((unsigned)gx, 1, (unsigned)slots), dim3(256),
+                     0, S(stream), (const T*)s0, (const T*)s1, (T*)out, p);
+  MX_LAUNCH_CHECK();
+  return 0;
+}
+
 // The compare-exchange leaves (moosex.h mx_cswap_diff / _cross / _apply).  A stage (k, j)
 // pairs position i with i | j, so in memory it is a butterfly over blocks of 2r contiguous
 // elements, r = j * inner: run index e of a block's low half meets run index e of its high
@@ -897,6 +996,41 @@ int mxh_pwl_cross(int elem_bytes, const void* s0, const void* s1, const void* x0
     using F = decltype(f);
     return pwl_cross_launch<typename F::T, typename F::I, F::V>(
         s0, s1, x0, x1, out, slots, s_slot_stride, x_slot_stride, n, k, da, db, ak, stream);
+  });
+}
+
+int mxh_pwp_cross(int elem_bytes, const void* s0, const void* s1, const void* const* p0,
+                  const void* const* p1, void* out, int64_t slots, int64_t s_slot_stride,
+                  const int64_t* p_slot_stride, int64_t n, int k, int d, const uint64_t* dt,
+                  const uint64_t* ck, void* stream) {
+  if (slots <= 0 || n <= 0) return 0;
+  if (k < 1 || k > MX_PWP_MAX || d < 1 || d > MX_PWP_DEG || slots > 65535 || s_slot_stride < 0 ||
+      !s0 || !out || !p0 || !p_slot_stride || !dt || !ck || (s1 == nullptr) != (p1 == nullptr))
+    return -3;
+  bool small = fits32(1 << 23, {(slots - 1) * s_slot_stride + (int64_t)k * n, slots * n});
+  // two outputs per lane: every plane, slot and buffer has to start on 16 bytes
+  bool two = n % 2 == 0 && aligned16(s0) && aligned16(s1) && aligned16(out) &&
+             s_slot_stride % 2 == 0;
+  for (int q = 0; q < d; ++q) {
+    if (p_slot_stride[q] < 0 || !p0[q] || (p1 && !p1[q])) return -3;
+    small = small && fits32(1 << 23, {(slots - 1) * p_slot_stride[q] + n});
+    two = two && aligned16(p0[q]) && (!p1 || aligned16(p1[q])) && p_slot_stride[q] % 2 == 0;
+  }
+  return leaf_dispatch(elem_bytes, small, two, [&](auto f) {
+    using F = decltype(f);
+    using T = typename F::T;
+    using I = typename F::I;
+#define MX_PWP(D)                                                                              \
+  case D:                                                                                      \
+    return pwp_cross_launch<T, I, F::V, D>(s0, s1, p0, p1, out, slots, s_slot_stride,          \
+                                           p_slot_stride, n, k, dt, ck, stream)
+    switch (d) {
+      MX_PWP(1);
+      MX_PWP(2);
+      MX_PWP(3);
+      default: return -3;
+    }
+#undef MX_PWP
   });
 }
 

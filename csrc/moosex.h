@@ -131,6 +131,26 @@ int mx_pwl_cross(int dev, int elem_bytes, const void* s0, const void* s1, const 
                  const void* x1, void* out, int64_t slots, int64_t s_slot_stride,
                  int64_t x_slot_stride, int64_t n, int k, const uint64_t* da, const uint64_t* db,
                  const uint64_t* ak, void* stream);
+// The local step of a secret piecewise polynomial of degree d in {1, 2, 3} in Z_2^64 / Z_2^128
+// (elem_bytes 8 / 16), wrapping.  s0 / s1: one party's components of the k stacked flags
+// [slots, k, n], as mx_pwl_cross takes them.  p0 / p1: host arrays of d device pointers each,
+// the components of the powers P_1 = x, .., P_d, [slots, n] each, slots p_slot_stride[i-1]
+// elements apart: a power is read where its multiplication wrote it.  dt: (d + 1) * k public
+// ring elements, row i the differences D_i[j] of the degree-i coefficients (row 0: the
+// constants, at the scale of the products); ck: d elements, the last piece's coefficients of
+// degrees 1..d; both on the host, elem_bytes wide, little-endian words -- they travel in the
+// kernel's arguments.  With G_i^c = sum_j D_i[j]*sc[j,e],
+//   out[s][e] = sum_{i=1..d} [ G_i^0*(P_i^0[e] + P_i^1[e]) + G_i^1*P_i^0[e] + ck_i*P_i^0[e] ]
+//               + sum_j D_0[j]*s0[j,e]
+// (mx_pwl_cross's cross convention; over the three parties a 3-out-of-3 sharing of
+// sum_i (ck_i + G_i)*P_i + H).  s1 == p1 == null: plain, sum_i (ck_i + G_i^0)*P_i^0 + H.  d = 1
+// is mx_pwl_cross bit for bit.  1 <= k <= MX_PWP_MAX.  Output slots are dense.
+#define MX_PWP_MAX 8
+#define MX_PWP_DEG 3
+int mx_pwp_cross(int dev, int elem_bytes, const void* s0, const void* s1, const void* const* p0,
+                 const void* const* p1, void* out, int64_t slots, int64_t s_slot_stride,
+                 const int64_t* p_slot_stride, int64_t n, int k, int d, const uint64_t* dt,
+                 const uint64_t* ck, void* stream);
 // One compare-exchange stage (k, j) of a bitonic sorting network in Z_2^64 / Z_2^128
 // (elem_bytes 8 / 16), wrapping, along the middle axis of an [outer, n, inner] array per slot
 // (cswap_geom.h: n, k, j powers of two, j < k <= n; by = -1 sorts every inner index on its own,

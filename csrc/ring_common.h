@@ -289,6 +289,10 @@ int mxh_pwl_cross(int elem_bytes, const void* s0, const void* s1, const void* x0
                   void* out, int64_t slots, int64_t s_slot_stride, int64_t x_slot_stride,
                   int64_t n, int k, const uint64_t* da, const uint64_t* db, const uint64_t* ak,
                   void* stream);
+int mxh_pwp_cross(int elem_bytes, const void* s0, const void* s1, const void* const* p0,
+                  const void* const* p1, void* out, int64_t slots, int64_t s_slot_stride,
+                  const int64_t* p_slot_stride, int64_t n, int k, int d, const uint64_t* dt,
+                  const uint64_t* ck, void* stream);
 int mxh_dwconv(int elem_bytes, const void* x0, const void* x1, const void* w0, const void* w1,
                void* out, int64_t slots, int64_t x_slot_stride, int64_t w_slot_stride,
                const mxr::ImgGeom& g, void* stream);

@@ -96,6 +96,16 @@ from moose_amd.edsl.base import hard_swish  # noqa: F401
 from moose_amd.edsl.base import hard_tanh  # noqa: F401
 from moose_amd.edsl.base import leaky_relu  # noqa: F401
 from moose_amd.edsl.base import piecewise_linear  # noqa: F401
+from moose_amd.edsl.base import piecewise_polynomial  # noqa: F401
+from moose_amd.edsl.base import celu  # noqa: F401
+from moose_amd.edsl.base import elu  # noqa: F401
+from moose_amd.edsl.base import erf  # noqa: F401
+from moose_amd.edsl.base import gelu  # noqa: F401
+from moose_amd.edsl.base import mish  # noqa: F401
+from moose_amd.edsl.base import selu  # noqa: F401
+from moose_amd.edsl.base import silu  # noqa: F401
+from moose_amd.edsl.base import softplus  # noqa: F401
+from moose_amd.edsl.base import swish  # noqa: F401
 from moose_amd.edsl.base import relu6  # noqa: F401
 from moose_amd.edsl.base import tanh  # noqa: F401
 from moose_amd.edsl.base import thresholded_relu  # noqa: F401

@@ -108,6 +108,12 @@ _OPS = {
         lambda o: {"breakpoints": list(o.breakpoints), "slopes": list(o.slopes),
                    "intercepts": list(o.intercepts)},
     ),
+    "PiecewisePolynomialOperation": (
+        "PiecewisePolynomial",
+        ["x"],
+        lambda o: {"breakpoints": list(o.breakpoints), "coefficients": list(o.coefficients),
+                   "degree": int(o.degree)},
+    ),
     "DepthwiseConvOperation": (
         "DepthwiseConv",
         ["x", "w"],

@@ -72,7 +72,8 @@ def typing_pass(comp: Computation, **_) -> Computation:
 
 
 _SAME_SHAPE_OPS = {"Cast", "Identity", "Relu", "Sigmoid", "Abs", "Neg", "Exp", "Sqrt", "Log",
-                   "Log2", "Softmax", "Share", "Reveal", "PiecewiseLinear", "Sort"}
+                   "Log2", "Softmax", "Share", "Reveal", "PiecewiseLinear", "Sort",
+                   "PiecewisePolynomial"}
 
 
 def _static_shape(op, shapes):

@@ -91,6 +91,7 @@ OPERATION_TABLE = [
     ("PermuteOperation", ["axes"]),
     ("DepthwiseConvOperation", ["strides", "pads", "dilations", "data_format"]),
     ("PiecewiseLinearOperation", ["breakpoints", "slopes", "intercepts"]),
+    ("PiecewisePolynomialOperation", ["breakpoints", "coefficients", "degree"]),
     ("SortOperation", ["axis", "descending", "by"]),
 ]
 

@@ -270,7 +270,7 @@ def _check_arithmetickable(expr, fn_name):
 
 # builders whose result has the shape of their (first) operand
 _SAME_SHAPE = {"identity", "cast", "exp", "sqrt", "sigmoid", "relu", "log", "log2", "abs",
-               "softmax", "piecewise_linear"}
+               "softmax", "piecewise_linear", "piecewise_polynomial"}
 
 
 def _expr(kind, inputs, vtype, placement, **attrs):
@@ -705,6 +705,123 @@ def tanh(x, placement=None):
     y = sub(add(s, s, placement), one, placement)
     y.static_shape = x.static_shape
     return y
+
+
+# ---------------------------------------------------------------------------
+# smooth activations (one PiecewisePolynomial operator each)
+# ---------------------------------------------------------------------------
+PWP_MAX = 8  # breakpoints of one PiecewisePolynomial operator (MX_PWP_MAX of the native leaf)
+PWP_DEG = 3  # its largest degree
+
+
+def _pwp_op(fn, x, breakpoints, rows, placement=None):
+    """The PiecewisePolynomial operator from integer tables at the input's fractional
+    precision: ``rows[j] = (c_0, .., c_d)`` of piece j."""
+    _pwl_dtype(fn, x)
+    k = len(breakpoints)
+    if not 1 <= k <= PWP_MAX:
+        raise ValueError(f"`{fn}`: between 1 and {PWP_MAX} breakpoints, found {k}")
+    widths = sorted({len(r) for r in rows})
+    if len(rows) != k + 1 or len(widths) != 1 or not 2 <= widths[0] <= PWP_DEG + 1:
+        raise ValueError(f"`{fn}`: {k} breakpoints take {k + 1} coefficient rows of one length "
+                         f"between 2 and {PWP_DEG + 1} (degree 1 to {PWP_DEG}), found "
+                         f"{len(rows)} rows of lengths {widths}")
+    flat = [v for r in rows for v in r]
+    for what, vals in (("breakpoints", breakpoints), ("coefficients", flat)):
+        for v in vals:
+            if not -(1 << 63) <= v < (1 << 63):
+                raise ValueError(f"`{fn}`: {what} entry {v} (at the input's fractional "
+                                 "precision) does not fit a signed 64-bit integer")
+    if any(b <= a for a, b in zip(breakpoints, breakpoints[1:])):
+        raise ValueError(f"`{fn}`: breakpoints must be strictly increasing at the input's "
+                         f"fractional precision, found {list(breakpoints)}")
+    return _expr("piecewise_polynomial", [x], x.vtype, placement, breakpoints=list(breakpoints),
+                 coefficients=flat, degree=widths[0] - 1)
+
+
+def piecewise_polynomial(x, breakpoints, coefficients, placement=None):
+    """Elementwise piecewise polynomial of a fixed-point ``x`` with public pieces: ``k``
+    increasing real ``breakpoints`` (at most ``PWP_MAX``) and ``k + 1`` rows ``coefficients[j]
+    = (c_0, .., c_d)`` of one degree ``d`` in 1..3; the result is ``sum_i c_i * x^i`` of row j
+    for ``breakpoints[j-1] <= x < breakpoints[j]``.  The numbers are rounded to the input's
+    fractional precision.  On a secret ``x`` all ``k`` comparisons are ONE sign extraction;
+    the powers cost ``d - 1`` multiplications that do not wait for it, and one local kernel
+    with one truncation combines them -- whatever ``k``."""
+    fn = "piecewise_polynomial"
+    f = _pwl_dtype(fn, x).fractional_precision
+    rows = [list(r) for r in coefficients]
+    return _pwp_op(fn, x, _pwl_encode(fn, "breakpoints", breakpoints, f),
+                   [_pwl_encode(fn, "coefficients", r, f) for r in rows], placement)
+
+
+def _smooth(fn, name, x, alpha, degree, pieces, placement):
+    from moose_amd.protocols import fixedpoint as fxp
+
+    f = _pwl_dtype(fn, x).fractional_precision
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(alpha):
+        raise ValueError(f"`{fn}`: alpha must be a finite real number, found {alpha!r}")
+    if name == "celu" and alpha == 0:
+        raise ValueError(f"`{fn}`: alpha must not be zero")
+    if degree not in (1, 2, 3):
+        raise ValueError(f"`{fn}`: a degree of 1, 2 or 3, found {degree!r}")
+    lo = 3 if name in ("elu", "selu", "celu") else 2
+    if isinstance(pieces, bool) or not isinstance(pieces, int) or not lo <= pieces <= PWP_MAX:
+        raise ValueError(f"`{fn}`: between {lo} and {PWP_MAX} breakpoints, found {pieces!r}")
+    T, C, _err = fxp.smooth_tables(name, float(alpha), int(degree), pieces, f)
+    return _pwp_op(fn, x, _pwl_encode(fn, "breakpoints", T, f),
+                   [_pwl_encode(fn, "coefficients", r, f) for r in C], placement)
+
+
+def gelu(x, approximate="none", degree=3, pieces=8, placement=None):
+    """``x * Phi(x)`` (``approximate="none"``) or its tanh form (``"tanh"``) as one piecewise
+    polynomial of ``degree`` with ``pieces`` breakpoints (fixedpoint.pwp_fit; the fit errors
+    are listed in docs/API.md)."""
+    if approximate not in ("none", "tanh"):
+        raise ValueError(f"`gelu`: approximate is 'none' or 'tanh', found {approximate!r}")
+    return _smooth("gelu", "gelu" if approximate == "none" else "gelu_tanh", x, 1.0, degree,
+                   pieces, placement)
+
+
+def silu(x, degree=3, pieces=8, placement=None):
+    """``x * sigmoid(x)`` as one piecewise polynomial."""
+    return _smooth("silu", "silu", x, 1.0, degree, pieces, placement)
+
+
+swish = silu
+
+
+def mish(x, degree=3, pieces=8, placement=None):
+    """``x * tanh(softplus(x))`` as one piecewise polynomial."""
+    return _smooth("mish", "mish", x, 1.0, degree, pieces, placement)
+
+
+def softplus(x, degree=3, pieces=8, placement=None):
+    """``log(1 + exp(x))`` as one piecewise polynomial."""
+    return _smooth("softplus", "softplus", x, 1.0, degree, pieces, placement)
+
+
+def elu(x, alpha=1.0, degree=3, pieces=8, placement=None):
+    """``x`` where ``x > 0``, else ``alpha * (exp(x) - 1)``, as one piecewise polynomial with
+    a knot at 0."""
+    return _smooth("elu", "elu", x, alpha, degree, pieces, placement)
+
+
+def selu(x, degree=3, pieces=8, placement=None):
+    """``scale * elu(x, alpha)`` with the self-normalising constants (ONNX ``Selu``'s
+    defaults)."""
+    return _smooth("selu", "selu", x, 1.0, degree, pieces, placement)
+
+
+def celu(x, alpha=1.0, degree=3, pieces=8, placement=None):
+    """``max(0, x) + min(0, alpha * (exp(x / alpha) - 1))`` as one piecewise polynomial with
+    a knot at 0."""
+    return _smooth("celu", "celu", x, alpha, degree, pieces, placement)
+
+
+def erf(x, degree=3, pieces=8, placement=None):
+    """The error function as one piecewise polynomial (its tails are -1 and 1)."""
+    return _smooth("erf", "erf", x, 1.0, degree, pieces, placement)
 
 
 def softmax(x, axis, upmost_index, placement=None):

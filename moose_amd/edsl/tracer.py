@@ -67,6 +67,8 @@ _OPS = {
                        ["strides", "pads", "dilations", "data_format"]),
     "piecewise_linear": ("PiecewiseLinearOperation", ["x"], "piecewise_linear",
                          ["breakpoints", "slopes", "intercepts"]),
+    "piecewise_polynomial": ("PiecewisePolynomialOperation", ["x"], "piecewise_polynomial",
+                             ["breakpoints", "coefficients", "degree"]),
     "sort": ("SortOperation", ["x"], "sort", ["axis", "descending", "by"]),
     "shape": ("ShapeOperation", ["x"], "shape", []),
     "mux": ("MuxOperation", ["selector", "x", "y"], "mux", []),

@@ -162,6 +162,13 @@ EXTENSION_OPERATORS = {
     # segment i is slopes[i] * x + intercepts[i] on [breakpoints[i-1], breakpoints[i]).  On a
     # secret x: one stacked sign extraction for the k flags, one local kernel, one truncation
     "PiecewiseLinear": [("breakpoints", "ints"), ("slopes", "ints"), ("intercepts", "ints")],
+    # elementwise piecewise polynomial of degree 1..3 with public pieces: k sorted breakpoints
+    # and (k + 1) x (degree + 1) coefficients, row-major, row j = (c_0, .., c_degree) of piece
+    # j on [breakpoints[j-1], breakpoints[j]); signed integers at the input dtype's fractional
+    # precision.  On a secret x: degree - 1 multiplications for the powers, one stacked sign
+    # extraction for the k flags, one local kernel, one truncation
+    "PiecewisePolynomial": [("breakpoints", "ints"), ("coefficients", "ints"),
+                            ("degree", "int")],
     # sort along `axis` (ascending unless `descending`); by >= 0: the rows of a rank-2 tensor
     # reordered so that column `by` is sorted (equal keys in unspecified order).  On a secret
     # fixed-point x: a bitonic network of compare-exchange stages, each one sign extraction and

@@ -7,7 +7,10 @@ pixels followed by the ``col2im`` sum), ``Resize`` (opset 11+) / ``Upsample`` (o
 ``nearest`` or ``linear`` mode with constant ``scales`` / ``sizes`` (``pm.resize2d`` in the
 activation's layout), ``Relu`` / ``Sigmoid`` / ``Tanh``, the piecewise-linear activations ``Clip``
 (attribute or initializer bounds, one-sided included), ``LeakyRelu``, ``PRelu`` (one slope),
-``HardSigmoid``, ``HardSwish`` and ``ThresholdedRelu``, ``MaxPool`` / ``AveragePool``,
+``HardSigmoid``, ``HardSwish`` and ``ThresholdedRelu``, the smooth activations ``Gelu`` (both
+``approximate`` values), ``Mish``, ``Softplus``, ``Elu``, ``Selu`` (default constants), ``Celu``,
+``Erf`` and ``Swish`` (``alpha = 1``) as one piecewise polynomial each, in a model whose opset has
+the operator, ``MaxPool`` / ``AveragePool``,
 ``Flatten`` (or ``Reshape`` to ``[N, -1]``), ``Gemm`` / ``MatMul`` + ``Add``, a ``Reshape`` of a
 dense layer's output back to an image ``[N, C, H, W]`` (a decoder's first step) and a final
 ``Softmax``.  The model input is rank 4, NCHW.  Inside the MPC the activations are NHWC from
@@ -118,6 +121,48 @@ def _activation_layer(node, init):
     return {"op": op.lower()}  # HardSwish, Tanh
 
 
+# the smooth activations (one PiecewisePolynomial operator each): the opset of the default
+# domain that introduced the operator, and the attributes it may carry
+_SMOOTH = {"Gelu": (20, ("approximate",)), "Mish": (18, ()), "Softplus": (1, ()),
+           "Elu": (1, ("alpha",)), "Selu": (1, ("alpha", "gamma")), "Celu": (12, ("alpha",)),
+           "Erf": (9, ()), "Swish": (24, ("alpha",))}
+_SELU = (1.6732632423543772, 1.0507009873554805)  # ONNX Selu's default alpha and gamma
+
+
+def _smooth_layer(node, opset):
+    """The layer of a smooth activation node."""
+    op = node.op_type
+    since, allowed = _SMOOTH[op]
+    if 0 < opset < since:
+        raise _unsupported(node, f"not an operator of opset {opset}: {op} enters the default "
+                                 f"domain with opset {since}")
+    extra = sorted(a.name for a in node.attribute if a.name not in allowed)
+    if extra:
+        raise _unsupported(node, f"unsupported attribute(s) {', '.join(extra)}")
+    if op == "Gelu":
+        approximate = _str(node, "approximate", "none")
+        if approximate not in ("none", "tanh"):
+            raise _unsupported(node, f"approximate={approximate!r} is neither 'none' nor 'tanh'")
+        return {"op": "gelu", "approximate": approximate}
+    if op in ("Elu", "Celu"):
+        alpha = _float(node, "alpha", 1.0)
+        if op == "Celu" and alpha == 0:
+            raise _unsupported(node, "alpha=0")
+        return {"op": op.lower(), "alpha": alpha}
+    if op == "Selu":
+        got = (_float(node, "alpha", _SELU[0]), _float(node, "gamma", _SELU[1]))
+        if any(abs(g - w) > 1e-6 for g, w in zip(got, _SELU)):
+            raise _unsupported(node, f"alpha={got[0]}, gamma={got[1]}: only the default "
+                                     "self-normalising constants are supported")
+        return {"op": "selu"}
+    if op == "Swish":
+        alpha = _float(node, "alpha", 1.0)
+        if alpha != 1.0:
+            raise _unsupported(node, f"alpha={alpha}: only x * sigmoid(x) is supported")
+        return {"op": "silu"}
+    return {"op": op.lower()}  # Mish, Softplus, Erf
+
+
 def _opset(model):
     """Version of the default ONNX operator set the model imports (0: not stated)."""
     return max((int(o.version) for o in model.opset_import if o.domain in ("", "ai.onnx")),
@@ -196,8 +241,8 @@ def hwc_rows(w, c, h, w_):
 def conv_layers_from_onnx(model):
     """-> (input (C, H, W), layers): each layer a dict with ``op`` in conv / convtranspose /
     resize / relu / sigmoid / tanh / clip / leakyrelu / hardsigmoid / hardswish /
-    thresholdedrelu / maxpool / avgpool / flatten / dense / unflatten / softmax and its
-    parameters (ONNX layouts)."""
+    thresholdedrelu / gelu / silu / mish / softplus / elu / selu / celu / erf / maxpool /
+    avgpool / flatten / dense / unflatten / softmax and its parameters (ONNX layouts)."""
     dims = model.graph.input[0].type.tensor_type.shape.dim
     if len(dims) != 4:
         raise ValueError("a convolutional predictor expects a rank-4 [batch, C, H, W] model input")
@@ -277,6 +322,8 @@ def conv_layers_from_onnx(model):
         elif op in ("Clip", "LeakyRelu", "PRelu", "HardSigmoid", "HardSwish",
                     "ThresholdedRelu", "Tanh"):
             layers.append(_activation_layer(node, init))
+        elif op in _SMOOTH:
+            layers.append(_smooth_layer(node, _opset(model)))
         elif op == "MaxPool":
             kernel, strides, pads = _window_attrs(node)
             if any(pads):
@@ -486,6 +533,12 @@ class ConvNetwork(Predictor):
                 x = pm.hard_swish(x)
             elif op == "thresholdedrelu":
                 x = pm.thresholded_relu(x, l["alpha"])
+            elif op == "gelu":
+                x = pm.gelu(x, approximate=l["approximate"])
+            elif op in ("elu", "celu"):
+                x = getattr(pm, op)(x, l["alpha"])
+            elif op in ("silu", "mish", "softplus", "selu", "erf"):
+                x = getattr(pm, op)(x)
             elif op == "unflatten":
                 x = pm.reshape(x, [-1, *l["out_chw"]])
             elif op == "flatten":

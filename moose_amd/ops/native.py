@@ -46,6 +46,10 @@ _SIGS = {
     #  stream)
     "mx_pwl_cross": (c_int, [c_int, c_int] + [c_vp] * 5 + [c_i64] * 4 + [c_int] + [c_vp] * 3
                      + [c_vp]),
+    # (dev, elem_bytes, s0 s1 p0[d] p1[d] out, slots, s_slot_stride, p_slot_stride[d], n, k, d,
+    #  dt ck, stream)
+    "mx_pwp_cross": (c_int, [c_int, c_int] + [c_vp] * 5 + [c_i64, c_i64, c_vp, c_i64, c_int,
+                                                           c_int] + [c_vp] * 3),
     # (dev, elem_bytes, x out, slots, x_slot_stride, outer n inner by k j, descending, stream)
     "mx_cswap_diff": (c_int, [c_int, c_int] + [c_vp] * 2 + [c_i64] * 2 + [c_i64] * 6 + [c_int]
                       + [c_vp]),

@@ -1405,6 +1405,129 @@ def pwl(s: RT, x: RT, da, db, ak, nb=0) -> RT:
 
 
 # ---------------------------------------------------------------------------
+# piecewise-polynomial local step
+# ---------------------------------------------------------------------------
+PWP_MAX = 8  # MX_PWP_MAX (moosex.h): the flag planes one launch takes
+PWP_DEG = 3  # MX_PWP_DEG: the largest degree
+
+# the device path of pwp / pwp_cross: the native kernel (True) or the torch composition
+# pwp_torch (False); a CPU tensor always takes the native loops
+PWP_KERNEL = True
+
+
+@functools.lru_cache(maxsize=1024)
+def _pwp_tables(D, CK, bits):
+    return _ring_words([v for row in D for v in row], bits), _ring_words(CK, bits)
+
+
+def _pwp_check(s0, s1, p0, p1, D, CK, nb):
+    """-> (k, d, bits, lead, shape).  ``D``: d + 1 rows of k ring integers, row i the
+    differences of the degree-i coefficients (row 0 the constants); ``CK``: the last piece's d
+    coefficients of degrees 1..d; ``p0`` / ``p1``: the d powers' components."""
+    d = len(D) - 1
+    if not 1 <= d <= PWP_DEG:
+        raise ValueError(f"pwp: a degree between 1 and {PWP_DEG} (one table row per degree and "
+                         f"one for the constants), found {len(D)} rows")
+    k = len(D[0])
+    if not 1 <= k <= PWP_MAX or any(len(row) != k for row in D):
+        raise ValueError(f"pwp: between 1 and {PWP_MAX} flag planes with one entry per plane in "
+                         f"every table row, found rows of {[len(row) for row in D]}")
+    if len(CK) != d:
+        raise ValueError(f"pwp: degree {d} takes {d} last-piece coefficients (degrees 1..{d}), "
+                         f"found {len(CK)}")
+    if isinstance(p0, RT) or len(p0) != d or (p1 is not None and (isinstance(p1, RT)
+                                                                  or len(p1) != d)):
+        raise ValueError(f"pwp: degree {d} takes {d} powers per component")
+    if (s1 is None) != (p1 is None):
+        raise ValueError("pwp: the cross form takes both next components")
+    ops = [s0, *p0] + ([s1, *p1] if s1 is not None else [])
+    bits = p0[0].bits
+    if bits not in (64, 128) or any(t.bits != bits for t in ops):
+        raise ValueError("pwp is arithmetic only: operands over one of Z_2^64 / Z_2^128, found "
+                         f"{[t.bits for t in ops]} bits")
+    if nb not in (0, 1):
+        raise ValueError("pwp takes at most one batch dim")
+    lead, shape = tuple(p0[0].shape[:nb]), tuple(p0[0].shape[nb:])
+    wants = [(s0, lead + (k,) + shape), (s1, lead + (k,) + shape)]
+    wants += [(t, lead + shape) for t in (*p0, *(p1 or ()))]
+    for t, want in wants:
+        if t is not None and tuple(t.shape) != want:
+            raise ValueError(f"pwp: operand of shape {tuple(t.shape)}, expected {want}")
+    return k, d, bits, lead, shape
+
+
+def pwp_torch(s0: RT, s1, p0, p1, D, CK, nb=0) -> RT:
+    """:func:`pwp_cross` as a composition of the existing kernels (weighted sums of the flag
+    planes, then elementwise products and sums): the fallback and the benchmark's opponent."""
+    _k, d, _bits, _lead, _shape = _pwp_check(s0, s1, p0, p1, D, CK, nb)
+    v = weighted_sum(s0, D[0], nb)
+    for i in range(1, d + 1):
+        g0 = weighted_sum(s0, D[i], nb)
+        v = binary("add", v, binary("mul", binary("add", g0, int(CK[i - 1])), p0[i - 1]))
+        if s1 is not None:
+            g1 = weighted_sum(s1, D[i], nb)
+            v = binary("add", v, binary("add", binary("mul", g0, p1[i - 1]),
+                                        binary("mul", g1, p0[i - 1])))
+    return v
+
+
+def pwp_cross(s0: RT, s1, p0, p1, D, CK, nb=0) -> RT:
+    """One party's local step of a secret piecewise polynomial of degree ``d = len(D) - 1`` in
+    {1, 2, 3}, exact in the ring: with the flag planes ``s0`` / ``s1`` ([.., k, *shape]), the
+    components ``p0[i-1]`` / ``p1[i-1]`` of the powers P_1 = x, .., P_d ([.., *shape] each) and
+    public python ints ``D[i][j]`` (row 0: the constants) and ``CK[i-1]``,
+    ``sum_{i=1..d} [G_i^0 * (P_i^0 + P_i^1) + G_i^1 * P_i^0 + CK_i * P_i^0] + sum_j D[0][j] *
+    s0[j]`` where ``G_i^c = sum_j D[i][j] * sc[j]`` (own times the sum plus next times own, as
+    :func:`pwl_cross`, which it equals bit for bit at d = 1).  ``s1 = p1 = None``: the plain
+    form.  One native launch over all batch slots (``mx_pwp_cross``); every power is read in
+    place through its own pointer, [slots, ...] views with dense slots included, and the
+    tables travel in the launch's arguments."""
+    k, d, bits, lead, shape = _pwp_check(s0, s1, p0, p1, D, CK, nb)
+    dev = p0[0].device
+    if dev.type == "meta":  # shape inference of the symbolic session
+        return empty(lead + shape, bits, dev)
+    if dev.type == "cuda" and not PWP_KERNEL:
+        return pwp_torch(s0, s1, p0, p1, D, CK, nb)
+    n = math.prod(shape)
+    out = empty(lead + shape, bits, dev)
+    if out.data.numel() == 0:
+        return out
+    sd0, sst = _leaf_operand(s0, nb, k * n)
+    sd1 = None
+    if s1 is not None:
+        sd1, sst1 = _leaf_operand(s1, nb, k * n)
+        sd0, sd1, sst = _leaf_pair(sd0, sst, sd1, sst1, k * n)
+    pd0, pd1, pst = [], [], []
+    for i in range(d):
+        a0, st = _leaf_operand(p0[i], nb, n)
+        a1 = None
+        if p1 is not None:
+            a1, st1 = _leaf_operand(p1[i], nb, n)
+            a0, a1, st = _leaf_pair(a0, st, a1, st1, n)
+        pd0.append(a0), pd1.append(a1), pst.append(st)
+    tdt, tck = _pwp_tables(tuple(tuple(int(v) for v in row) for row in D),
+                           tuple(int(v) for v in CK), bits)
+    ptrs = ctypes.c_void_p * d
+    nat.check(
+        nat.lib().mx_pwp_cross(
+            nat.dev_of(out.data), _elem_bytes(bits), nat.ptr(sd0),
+            nat.ptr(sd1) if sd1 is not None else None, ptrs(*[nat.ptr(t) for t in pd0]),
+            ptrs(*[nat.ptr(t) for t in pd1]) if p1 is not None else None, nat.ptr(out.data),
+            math.prod(lead), sst, (ctypes.c_int64 * d)(*pst), n, k, d, tdt, tck,
+            nat.stream_of(out.data)),
+        "pwp_cross",
+    )
+    return out
+
+
+def pwp(s: RT, p, D, CK, nb=0) -> RT:
+    """The plain form of :func:`pwp_cross`: ``sum_i (CK_i + sum_j D[i][j] * s[j]) * p[i-1] +
+    sum_j D[0][j] * s[j]`` over the flag planes ``s`` ([.., k, *shape]) and the powers ``p`` --
+    a host's ring tensors, or slot-wise use."""
+    return pwp_cross(s, None, p, None, D, CK, nb)
+
+
+# ---------------------------------------------------------------------------
 # compare-exchange stages of a bitonic sorting network
 # ---------------------------------------------------------------------------
 # the device path of cswap_diff / cswap_cross / cswap_apply: the native kernels (True) or the

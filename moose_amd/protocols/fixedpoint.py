@@ -419,6 +419,235 @@ def piecewise_linear(sess, x: RepFixed, breakpoints, slopes, intercepts) -> RepF
     return _with(x, z)
 
 
+def pwp_tables(breakpoints, coeffs, f: int, integ: int, bits: int, what="pwp"):
+    """The integer tables of a piecewise polynomial at ``f`` fractional bits: ``(T, D, CK,
+    C0K)`` from ``k`` increasing breakpoints and ``k + 1`` coefficient rows ``coeffs[j] =
+    (c_0, .., c_d)`` of piece j (signed integers at scale 2^f; piece j is ``breakpoints[j-1] <=
+    x < breakpoints[j]``).  D[i][j] = c_{i,j} - c_{i,j+1}, row 0 shifted by f (the constants
+    meet the products at scale 2f); CK = the last piece's c_1..c_d; C0K its constant, added
+    after the truncation so it is counted once.
+
+    Checked, with L_i the largest |x| of a piece whose degree-i coefficient is nonzero (an outer
+    piece reaches the type's 2^integ) and |c_i| the largest degree-i coefficient or difference:
+    (1) the combination fits before the truncation, max_i(bitlength(L_i^i * 2^f) +
+    bitlength(|c_i|)) + 1 <= bits - 2, the bits counted as :func:`pwl_tables` counts them;
+    (2) each power fits before its own truncation, bitlength(L_i^i * 2^f) + f + 1 <= bits - 2.
+    Outside those pieces a power may wrap; that is harmless, because there its selected
+    coefficient CK_i + G_i is an exact sharing of zero, whatever the power's shares hold."""
+    T = [int(t) for t in breakpoints]
+    C = [[int(v) for v in row] for row in coeffs]
+    k = len(T)
+    d = len(C[0]) - 1 if C else 0
+    if not 1 <= k <= R.PWP_MAX or len(C) != k + 1:
+        raise ValueError(f"{what}: between 1 and {R.PWP_MAX} breakpoints with one more "
+                         f"coefficient row, found {k} and {len(C)}")
+    if not 1 <= d <= R.PWP_DEG or any(len(row) != d + 1 for row in C):
+        raise ValueError(f"{what}: rows of d + 1 coefficients for a degree d between 1 and "
+                         f"{R.PWP_DEG}, found rows of {sorted({len(row) for row in C})}")
+    if any(t1 <= t0 for t0, t1 in zip(T, T[1:])):
+        raise ValueError(f"{what}: breakpoints must be strictly increasing, found {T}")
+    top = 1 << (integ + f)
+    reach = [top] + [max(abs(T[j - 1]), abs(T[j])) for j in range(1, k)] + [top]
+    need, worst = f + max(abs(v) for v in [C[j][0] for j in range(k + 1)]
+                          + [C[j][0] - C[j + 1][0] for j in range(k)]).bit_length() + 1, 0
+    for i in range(1, d + 1):
+        used = [reach[j] for j in range(k + 1) if C[j][i]]
+        if not used:
+            continue
+        L = max(used)
+        power = -((-L ** i) >> (f * (i - 1)))  # ceil(L^i * 2^f) at scale 2^f
+        cmax = max(abs(v) for v in [C[j][i] for j in range(k + 1)]
+                   + [C[j][i] - C[j + 1][i] for j in range(k)])
+        if power.bit_length() + cmax.bit_length() + 1 > need:
+            need, worst = power.bit_length() + cmax.bit_length() + 1, i
+        if i > 1 and power.bit_length() + f + 1 > bits - 2:
+            raise ValueError(
+                f"{what}: the power x^{i} of a fixed({integ}, {f}) value up to {L} / 2^{f} "
+                f"needs {power.bit_length() + f + 1} bits before its truncation, but "
+                f"Z_2^{bits} leaves {bits - 2}")
+    if need > bits - 2:
+        raise ValueError(
+            f"{what}: the degree-{worst} term on a fixed({integ}, {f}) value needs {need} bits "
+            f"before the truncation (the power's bits and the coefficient's), but Z_2^{bits} "
+            f"leaves {bits - 2}")
+    D = [[(C[j][0] - C[j + 1][0]) << f for j in range(k)]]
+    D += [[C[j][i] - C[j + 1][i] for j in range(k)] for i in range(1, d + 1)]
+    return T, D, [C[k][i] for i in range(1, d + 1)], C[k][0]
+
+
+def piecewise_polynomial(sess, x: RepFixed, breakpoints, coeffs) -> RepFixed:
+    """Piecewise polynomial (degree 1..3) of a secret fixed-point ``x`` with public integer
+    tables at x's fractional precision (:func:`pwp_tables`): rep.pwp_trunc -- d - 1
+    multiplications for the powers, one stacked sign extraction, one local kernel, one
+    truncation by f -- then the last piece's constant with add_public."""
+    f = x.frac
+    T, D, CK, C0K = pwp_tables(breakpoints, coeffs, f, x.integ, x.bits, "piecewise_polynomial")
+    w = x.integ + f + 2  # x - t spans one bit more than x
+    width = w if SIGN_WIDTH and 2 < w < x.bits and all(abs(t) < (1 << (x.integ + f)) for t in T) \
+        else None
+    z = rep.pwp_trunc(sess, x.t, T, D, CK, f, width=width)
+    if C0K:
+        z = rep.add_public(sess, z, R.fill((), C0K, x.bits, sess.device))
+    return _with(x, z)
+
+
+_ERF = np.vectorize(math.erf, otypes=[np.float64])
+_FIT_SPAN = 24.0  # the dense grid of pwp_fit covers [-_FIT_SPAN, _FIT_SPAN]
+_FIT_STEP = 1.0 / 256
+
+
+def _fit_monitor(fn, degree, grid, kinks):
+    """|fn^(degree + 1)|^(1 / (degree + 1)) on ``grid`` by repeated central differences, each
+    smooth stretch between two kinks on its own (a difference across a kink is no derivative)."""
+    mon = np.zeros_like(grid)
+    cuts = [grid[0]] + sorted(kinks) + [grid[-1]]
+    for a, b in zip(cuts, cuts[1:]):
+        sel = (grid >= a) & (grid <= b)
+        if sel.sum() < 2 * (degree + 2):
+            continue
+        g = fn(grid[sel])
+        for _ in range(degree + 1):
+            g = np.gradient(g, grid[sel])
+        mon[sel] = np.abs(g) ** (1.0 / (degree + 1))
+    return mon + 1e-6  # a flat stretch still takes its share of a piece
+
+
+def _fit_knots(grid, mon, lo, hi, kinks, k):
+    """k breakpoints: lo, hi, the kinks strictly between and, in each smooth stretch, the
+    points that split the integral of the monitor evenly."""
+    inner = [t for t in sorted(kinks) if lo < t < hi]
+    cuts = [lo] + inner + [hi]
+    spare = k - len(cuts)
+    if spare < 0:
+        return None
+    mass = []
+    for a, b in zip(cuts, cuts[1:]):
+        sel = (grid >= a) & (grid <= b)
+        mass.append(float((0.5 * (mon[sel][1:] + mon[sel][:-1]) * np.diff(grid[sel])).sum()))
+    # extra knots go, one at a time, to the stretch with the most monitor mass per piece
+    extra = [0] * len(mass)
+    for _ in range(spare):
+        j = int(np.argmax([m / (e + 1) for m, e in zip(mass, extra)]))
+        extra[j] += 1
+    knots = list(cuts)
+    for (a, b), e in zip(zip(cuts, cuts[1:]), extra):
+        if not e:
+            continue
+        sel = (grid >= a) & (grid <= b)
+        cum = np.concatenate([[0.0], np.cumsum(0.5 * (mon[sel][1:] + mon[sel][:-1])
+                                               * np.diff(grid[sel]))])
+        knots += list(np.interp(np.arange(1, e + 1) * cum[-1] / (e + 1), cum, grid[sel]))
+    return sorted(knots)
+
+
+def _fit_eval(T, C, x):
+    """The piecewise polynomial with breakpoints T and rows C at the float64 points x."""
+    seg = np.searchsorted(np.asarray(T), x, side="right")
+    C = np.asarray(C, dtype=np.float64)
+    y = np.zeros_like(x)
+    for i in range(C.shape[1] - 1, -1, -1):
+        y = y * x + C[seg, i]
+    return y
+
+
+def pwp_fit(fn, degree: int, pieces: int = 8, tails=((0.0, 0.0), (1.0, 0.0)), kinks=(),
+            frac: int = None):
+    """Deterministic float64 fit of ``fn`` (a vectorised float64 function) by a piecewise
+    polynomial of ``degree`` with ``pieces`` breakpoints: ``(breakpoints, coeffs, err)``, the
+    coefficient rows ``(c_0, .., c_degree)`` of the ``pieces + 1`` pieces in powers of x
+    itself.  The outer pieces are the exact linear asymptotes ``tails = ((slope, intercept) for
+    x -> -inf, (slope, intercept) for x -> +inf)``.  Between them the knots equidistribute
+    ``|fn^(degree + 1)|^(1 / (degree + 1))``; every point of ``kinks`` (where a derivative of
+    ``fn`` jumps) is a knot; each inner piece interpolates ``fn`` at its Chebyshev nodes.  The
+    clip range is the best of a small search over half-integer ends (and the kinks).  ``err``
+    is the largest ``|fit - fn|`` on a grid of step 2^-8 over [-24, 24] and at both sides of
+    every knot.  With ``frac``, breakpoints and coefficients are rounded to multiples of
+    2^-frac before ``err`` is measured, so it is the error of exactly the tables a
+    fixed-point type of that precision holds."""
+    if degree not in (1, 2, 3):
+        raise ValueError(f"pwp_fit: a degree of 1, 2 or 3, found {degree}")
+    kinks = tuple(float(t) for t in kinks)
+    if not 2 + len(kinks) <= pieces <= R.PWP_MAX:
+        raise ValueError(f"pwp_fit: between {2 + len(kinks)} and {R.PWP_MAX} breakpoints, found "
+                         f"{pieces}")
+    grid = np.arange(-_FIT_SPAN, _FIT_SPAN + _FIT_STEP / 2, _FIT_STEP)
+    want = fn(grid)
+    mon = _fit_monitor(fn, degree, grid, kinks)
+    (al, bl), (ah, bh) = tails
+    ends = [float(v) for v in np.arange(1.0, 12.25, 0.5)]
+    nodes = np.cos((2 * np.arange(degree + 1) + 1) * np.pi / (2 * (degree + 1)))
+    quant = (lambda v: np.round(np.asarray(v) * 2.0 ** frac) / 2.0 ** frac) if frac is not None \
+        else (lambda v: np.asarray(v, dtype=np.float64))
+    best = None
+    for lo in sorted({-e for e in ends} | {t for t in kinks if t <= 0}):
+        for hi in sorted({e for e in ends} | {t for t in kinks if t >= 0}):
+            if not lo < hi:
+                continue
+            T = _fit_knots(grid, mon, lo, hi, kinks, pieces)
+            if T is None:
+                continue
+            T = quant(T)
+            if np.any(np.diff(T) <= 0):
+                continue
+            rows = [[bl, al] + [0.0] * (degree - 1)]
+            for a, b in zip(T, T[1:]):
+                xs = 0.5 * (a + b) + 0.5 * (b - a) * nodes
+                rows.append(list(np.linalg.solve(np.vander(xs, degree + 1, increasing=True),
+                                                 fn(xs))))
+            rows.append([bh, ah] + [0.0] * (degree - 1))
+            C = quant(rows)
+            edge = np.concatenate([T, np.nextafter(T, -np.inf)])
+            err = max(float(np.abs(_fit_eval(T, C, grid) - want).max()),
+                      float(np.abs(_fit_eval(T, C, edge) - fn(edge)).max()))
+            if best is None or err < best[2]:
+                best = ([float(t) for t in T], [[float(c) for c in row] for row in C], err)
+    if best is None:
+        raise ValueError("pwp_fit: no admissible knot placement")
+    return best
+
+
+SELU_ALPHA, SELU_SCALE = 1.6732632423543772, 1.0507009873554805
+
+
+def smooth_function(name: str, alpha: float = 1.0):
+    """``(fn, tails, kinks)`` of a smooth activation for :func:`pwp_fit`: the float64
+    function, its linear asymptotes and the points where one of its derivatives jumps."""
+    a = float(alpha)
+    std = ((0.0, 0.0), (1.0, 0.0))
+    if name == "gelu":
+        return (lambda x: 0.5 * x * (1.0 + _ERF(x / math.sqrt(2.0)))), std, ()
+    if name == "gelu_tanh":
+        c = math.sqrt(2.0 / math.pi)
+        return (lambda x: 0.5 * x * (1.0 + np.tanh(c * (x + 0.044715 * x ** 3)))), std, ()
+    if name == "silu":
+        return (lambda x: x / (1.0 + np.exp(-x))), std, ()
+    if name == "mish":
+        return (lambda x: x * np.tanh(np.logaddexp(0.0, x))), std, ()
+    if name == "softplus":
+        return (lambda x: np.logaddexp(0.0, x)), std, ()
+    if name == "erf":
+        return (lambda x: _ERF(x)), ((0.0, -1.0), (0.0, 1.0)), ()
+    if name == "elu":
+        return ((lambda x: np.where(x > 0, x, a * np.expm1(np.minimum(x, 0.0)))),
+                ((0.0, -a), (1.0, 0.0)), (0.0,))
+    if name == "selu":
+        s, sa = SELU_SCALE, SELU_SCALE * SELU_ALPHA
+        return ((lambda x: np.where(x > 0, s * x, sa * np.expm1(np.minimum(x, 0.0)))),
+                ((0.0, -sa), (s, 0.0)), (0.0,))
+    if name == "celu":
+        return ((lambda x: np.maximum(x, 0.0) + a * np.expm1(np.minimum(x, 0.0) / a)),
+                ((0.0, -a), (1.0, 0.0)), (0.0,))
+    raise ValueError(f"no smooth activation named {name!r}")
+
+
+@lru_cache(maxsize=256)
+def smooth_tables(name: str, alpha: float = 1.0, degree: int = 3, pieces: int = 8,
+                  frac: int = None):
+    """:func:`pwp_fit` of :func:`smooth_function` ``name``: ``(breakpoints, coeffs, err)``."""
+    fn, tails, kinks = smooth_function(name, alpha)
+    return pwp_fit(fn, degree, pieces, tails, kinks, frac)
+
+
 def abs_(sess, x: RepFixed) -> RepFixed:
     s = sign_bit(sess, x)
     return _with(x, rep.negate_where(sess, s, x.t))

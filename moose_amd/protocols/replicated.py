@@ -1159,6 +1159,69 @@ def pwl_trunc(sess, x: RepTensor, T, DA, DB, AK, m: int, width=None) -> RepTenso
     return trunc_pr(sess, z, m) if m else z
 
 
+def pwp_trunc(sess, x: RepTensor, T, D, CK, m: int, width=None) -> RepTensor:
+    """trunc_pr(sum_{i=1..d} (CK_i + G_i) * P_i + H, m) with G_i = sum_j D[i][j] * s_j, H =
+    sum_j D[0][j] * s_j, the secret flags s_j = [x < T[j]] and the powers P_1 = x, P_i =
+    trunc_pr(P_{i-1} * x, m) -- a piecewise polynomial of degree d = len(D) - 1 in {1, 2, 3} of
+    a secret ``x`` with public breakpoints ``T`` (python ints, ring values); ``CK``: the last
+    piece's d coefficients of degrees 1..d.  The powers do not depend on the flags and are
+    issued first (d - 1 multiplications); the flags are :func:`pwl_trunc`'s one stacked sign
+    extraction; the selected coefficients meet the powers in one kernel (session
+    ``p_pwp_cross``), each power read where its multiplication wrote it; the tail is
+    :func:`pwl_trunc`'s selection, on the same nonces in the same order.  ``width``:
+    |x - T[j]| < 2^(width - 1) is known."""
+    check_shift(x.bits, m)
+    plc, bits = x.plc, x.bits
+    d = len(D) - 1
+    powers = [x]
+    with span("rep.pwp_powers"):
+        for _ in range(d - 1):
+            powers.append(mul_trunc(sess, powers[-1], x, m) if m else mul(sess, powers[-1], x))
+    with span("rep.pwp_flags"):
+        parts = [local(sess, sub_public(sess, x, R.fill((), int(t), bits, sess.device)),
+                       "ExpandDims", axis=[0]) for t in T]
+        if len(parts) == 1:
+            stack = parts[0]
+        else:
+            stack = RepTensor(plc, bits, "arith",
+                              sess.p("Concat", plc, *[p.s0 for p in parts], axis=0),
+                              sess.p("Concat", plc, *[p.s1 for p in parts], axis=0))
+        s = less_than_zero_arith(sess, stack, width=width)
+
+    def cross():
+        return sess.p_pwp_cross(plc, s.s0, s.s1, [p.s0 for p in powers],
+                                [p.s1 for p in powers], D, CK)
+
+    tail = getattr(sess, "p_zs_trunc", None)
+    if (tail is not None and m and getattr(sess, "fused", False)
+            and getattr(sess, "device", None) is not None and sess.device.type == "cuda"
+            and os.environ.get("MOOSEX_DOT_TAIL", "1") != "0"):
+        with span("rep.pwp_trunc_fused"):
+            v = cross()
+            issue = getattr(sess, "p_zs_trunc_issue", None)
+            if (issue is not None and bits in (64, 128)
+                    and os.environ.get("MOOSEX_DOT_OPEN", "1") != "0"):
+                return StackedTail(sess, plc, bits, v, m, issue(plc, v))
+            s0, s1 = tail(plc, v, m)
+            return RepTensor(plc, bits, "arith", s0, s1)
+    party = getattr(sess, "party_dot_trunc", None)
+    if (party is not None and m and 0 < m <= 63 and bits in (64, 128)
+            and os.environ.get("MOOSEX_DOT_TAIL", "1") != "0"):
+        with span("rep.pwp_trunc_party"):
+            nonces = tuple(sess.nonce(plc) for _ in range(7))  # as dot + trunc_pr
+            s0, s1 = party(plc, cross(), m, nonces)
+            return RepTensor(plc, bits, "arith", s0, s1)
+    with span("rep.pwp"):
+        v = cross()
+        fused = getattr(sess, "p_zero_share_reshare", None)
+        if fused is not None and getattr(sess, "fused", False):
+            s0, s1 = fused(plc, v, "arith")
+            z = RepTensor(plc, bits, "arith", s0, s1)
+        else:
+            z = _reshare(sess, plc, sess.p_add_zero_share(plc, v, "arith"), bits, "arith")
+    return trunc_pr(sess, z, m) if m else z
+
+
 def _cswap_halves(sess, x: RepTensor, g, cols):
     """The low and the high element of every pair, [outer, n/(2j), j, cols] each."""
     v = local(sess, x, "Reshape", shape=(g.outer, g.n // (2 * g.j), 2, g.j, cols))

@@ -153,6 +153,20 @@ def _pwl_ring(c, x):
 kernel("PiecewiseLinear", "rep", "rep_ring")(_pwl_ring)
 
 
+def _pwp_ring(c, x):
+    """PiecewisePolynomial on a raw ring sharing: the tables are ring integers (no fractional
+    bits), so the powers and the pieces are exact and nothing is truncated."""
+    T, flat, d = list(c.attr("breakpoints")), list(c.attr("coefficients")), int(c.attr("degree"))
+    k = len(T)
+    C = [flat[j * (d + 1):(j + 1) * (d + 1)] for j in range(k + 1)]
+    D = [[C[j][i] - C[j + 1][i] for j in range(k)] for i in range(d + 1)]
+    z = rep.pwp_trunc(c.sess, x, T, D, C[k][1:], 0)
+    return rep.add_public(c.sess, z, R.fill((), C[k][0], x.bits, c.sess.device)) if C[k][0] else z
+
+
+kernel("PiecewisePolynomial", "rep", "rep_ring")(_pwp_ring)
+
+
 def _sort_ring(c, x):
     """Sort on a raw ring sharing: the elements are signed ring integers below 2^(bits - 2) in
     magnitude (a difference of two keeps its sign in the ring's top bit); the padding is the

@@ -1615,6 +1615,61 @@ class Interpreter:
         z = sess.h("Sar", host, v, amount=f)
         return sess.h("Add", host, z, R.fill((), BK, bits, dev)) if BK else z
 
+    def op_PiecewisePolynomial(self, op, ins):
+        """Piecewise-polynomial activation of a fixed-point tensor: replicated values through
+        fixedpoint.piecewise_polynomial (degree - 1 multiplications, one sign extraction, one
+        local kernel, one truncation); a host's or a mirrored value through the plain leaf on
+        the ring tensor, its flags the sign bits of x - t_j and its powers Mul + Sar, then Sar
+        by the fractional precision."""
+        a = op.attrs
+        T_, flat, deg = list(a["breakpoints"]), list(a["coefficients"]), int(a["degree"])
+        if deg < 1 or len(flat) != (len(T_) + 1) * (deg + 1):
+            raise MooseRuntimeError(
+                f"{op.name}: PiecewisePolynomial of degree {deg} with {len(T_)} breakpoints takes "
+                f"{(len(T_) + 1) * (deg + 1)} coefficients, got {len(flat)}")
+        tabs = (T_, [flat[j * (deg + 1):(j + 1) * (deg + 1)] for j in range(len(T_) + 1)])
+        x = self.at(op, ins[0])
+        d = x.dtype
+        if x.kind != "tensor" or d is None or not d.is_fixed:
+            raise MooseRuntimeError(
+                f"{op.name}: PiecewisePolynomial expects a fixed-point tensor, got {d}; cast a "
+                "float tensor to fixed point first")
+        if x.is_host:
+            return LV(x.plc, "tensor", d, self._host_pwp(x.host, x.v, d, tabs))
+        if x.is_mir or (x.is_rep and isinstance(x.v, MV)):
+            host = x.plc.owners[0]
+            z = self._host_pwp(host, HV(host, x.v.v), d, tabs)
+            return LV(x.plc, "tensor", d, MV(x.plc, z.v))
+        return LV(x.plc, "tensor", d, fxp.piecewise_polynomial(self.sess, x.v, *tabs))
+
+    def _host_pwp(self, host, xv, d, tabs):
+        sess = self.sess
+        f = d.fractional_precision
+        bits = getattr(xv.v, "bits", None) or d.ring_bits
+        T_, D, CK, C0K = fxp.pwp_tables(*tabs, f, d.integral_precision, bits,
+                                        "PiecewisePolynomial")
+        dev = sess.device
+        powers = [xv]
+        for _ in range(len(D) - 2):
+            powers.append(sess.h("Sar", host, sess.h("Mul", host, powers[-1], xv), amount=f))
+        flags = [sess.h("ExpandDims", host,
+                        sess.h("Shr", host, sess.h("Sub", host, xv, R.fill((), t, bits, dev)),
+                               amount=bits - 1), axis=[0]) for t in T_]
+        s = flags[0] if len(flags) == 1 else sess.h("Concat", host, *flags, axis=0)
+        if self.symbolic:  # a lowered graph takes no operator of its own
+            sh, d0 = fxp.pwl_shift(D[0])
+            v = sess.h("WeightedSum", host, s, weights=d0, bits=bits)
+            if sh:
+                v = sess.h("Shl", host, v, amount=sh)
+            for i in range(1, len(D)):
+                g = sess.h("Add", host, sess.h("WeightedSum", host, s, weights=D[i], bits=bits),
+                           R.fill((), CK[i - 1], bits, dev))
+                v = sess.h("Add", host, v, sess.h("Mul", host, g, powers[i - 1]))
+        else:
+            v = sess.h("PwpPlain", host, s, *powers, dt=D, ck=CK)
+        z = sess.h("Sar", host, v, amount=f)
+        return sess.h("Add", host, z, R.fill((), C0K, bits, dev)) if C0K else z
+
     def op_DepthwiseConv(self, op, ins):
         """Depthwise convolution: host tensors (float, or fixed point with the truncation
         that Dot takes) through the primitive, replicated fixed point through

@@ -458,6 +458,14 @@ def _rank128(d):
     return rank.reshape(d.shape[:-1])
 
 
+@prim("PwpPlain")
+def _pwp_plain(nb, s, *powers, dt, ck):
+    """The plain piecewise-polynomial leaf on ring tensors (R.pwp): sum_i (ck[i-1] + sum_j
+    dt[i][j] * s[j]) * powers[i-1] + sum_j dt[0][j] * s[j] over the flag planes s stacked on the
+    leading logical axis."""
+    return R.pwp(s, list(powers), tuple(tuple(r) for r in dt), tuple(int(c) for c in ck), nb)
+
+
 @prim("StridedSlice")
 def _strided_slice(nb, a, slices):
     if _is_rt(a):

@@ -947,6 +947,13 @@ class StackedSession(Session):
         -- are read in place."""
         return PV(plc, R.pwl_cross(s0.v, s1.v, x0.v, x1.v, da, db, ak, nb=1))
 
+    def p_pwp_cross(self, plc, s0, s1, p0, p1, D, CK):
+        """The three parties' local steps of a piecewise polynomial (R.pwp_cross) in one
+        launch: the flag share vectors and every power's -- the views of a share-pair buffer
+        included -- are read in place."""
+        return PV(plc, R.pwp_cross(s0.v, s1.v, [p.v for p in p0], [p.v for p in p1], D, CK,
+                                   nb=1))
+
     def p_cswap_cross(self, plc, s0, s1, x0, x1, geom):
         """The three parties' local products of the flags and the differences of one
         compare-exchange stage (R.cswap_cross) in one launch: the share vectors -- the views of
