@@ -1,6 +1,7 @@
 // Host (CPU) twins of the leaf kernels of leaf_hip.hip -- the image leaves, the piecewise-
-// linear local step and the compare-exchange leaves -- and their mx_* entry points, which
-// check the geometry (img_geom.h, cswap_geom.h) for both sides.  Plain loops: the oracle.
+// linear local step, the compare-exchange leaves and the permuted row gather -- and their
+// mx_* entry points, which check the geometry (img_geom.h, cswap_geom.h) and the sizes for
+// both sides.  Plain loops: the oracle.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -284,9 +285,63 @@ void cswap_apply_cpu(const T* x, const T* p, T* out, int64_t slots, int64_t x_sl
   });
 }
 
+// The permuted row gather (moosex.h mx_perm_gather): one (slot, row) at a time.
+template <class T>
+void perm_gather_cpu(const T* a, const T* b, const T* p, const T* m, const int64_t* perm, T* out,
+                     int64_t slots, int64_t a_slot, int64_t b_slot, int64_t p_slot,
+                     int64_t m_slot, int64_t outer, int64_t n, int64_t inner) {
+  const int64_t rows = outer * n;
+  parallel_for(slots * rows, std::max<int64_t>(1, 4096 / inner), [=](int64_t q0, int64_t q1) {
+    for (int64_t q = q0; q < q1; ++q) {
+      const int64_t s = q / rows, row = q - s * rows, o = row / n, r = row - o * n;
+      const int64_t si = (o * n + perm[r]) * inner, di = row * inner;
+      T* dst = out + q * inner;
+      for (int64_t c = 0; c < inner; ++c) {
+        T v = a[s * a_slot + si + c];
+        if (b) v += b[s * b_slot + si + c];
+        if (p) v += p[s * p_slot + di + c];
+        if (m) v -= m[s * m_slot + di + c];
+        dst[c] = v;
+      }
+    }
+  });
+}
+
 }  // namespace
 
 extern "C" {
+
+int mx_perm_gather(int dev, int elem_bytes, const void* a, const void* b, const void* p,
+                   const void* m, const int64_t* perm, void* out, int64_t slots,
+                   int64_t a_slot_stride, int64_t b_slot_stride, int64_t p_slot_stride,
+                   int64_t m_slot_stride, int64_t outer, int64_t n, int64_t inner, void* stream) {
+  const int64_t lim = 0x7fffffff;
+  if (slots < 0 || outer < 0 || n < 0 || inner < 0 || outer > lim || n > lim || inner > lim ||
+      a_slot_stride < 0 || b_slot_stride < 0 || p_slot_stride < 0 || m_slot_stride < 0)
+    return -3;
+  if (elem_bytes != 8 && elem_bytes != 16) return -2;
+  if (slots == 0 || outer == 0 || n == 0 || inner == 0) return 0;
+  if (n > ((int64_t)1 << 60) / outer / inner) return -3;
+  // every extent a side forms -- (slots - 1) * stride + n_x and slots * n_x -- stays below 2^62
+  const int64_t n_x = outer * n * inner, cap = ((int64_t)1 << 61) / slots;
+  if (n_x > cap || a_slot_stride > cap || b_slot_stride > cap || p_slot_stride > cap ||
+      m_slot_stride > cap)
+    return -3;
+  if (!a || !perm || !out) return -3;
+  if (dev)
+    return mxh_perm_gather(elem_bytes, a, b, p, m, perm, out, slots, a_slot_stride,
+                           b_slot_stride, p_slot_stride, m_slot_stride, outer, n, inner, stream);
+  std::vector<bool> seen(n, false);  // a permutation: every index once
+  for (int64_t r = 0; r < n; ++r) {
+    if (perm[r] < 0 || perm[r] >= n || seen[perm[r]]) return -3;
+    seen[perm[r]] = true;
+  }
+  DISPATCH_ELEM(elem_bytes, T, {
+    perm_gather_cpu((const T*)a, (const T*)b, (const T*)p, (const T*)m, perm, (T*)out, slots,
+                    a_slot_stride, b_slot_stride, p_slot_stride, m_slot_stride, outer, n, inner);
+    return 0;
+  });
+}
 
 int mx_im2col(int dev, int elem_bytes, const void* in, void* out, int64_t slots,
               int64_t in_slot_stride, int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH,

@@ -1,8 +1,8 @@
 // gfx950 leaf kernels of the moosex ring dialect: the image leaves (im2col, dwconv, col2im,
-// resize2d), the piecewise-linear and piecewise-polynomial local steps (pwl_cross, pwp_cross)
-// and the compare-exchange leaves
-// (cswap_diff / _cross / _apply), each a share-wise kernel over slots with its geometry checked
-// on the host (img_geom.h, cswap_geom.h) before it gets here.
+// resize2d), the piecewise-linear and piecewise-polynomial local steps (pwl_cross, pwp_cross),
+// the compare-exchange leaves (cswap_diff / _cross / _apply) and the permuted row gather of a
+// shuffle step (perm_gather).  Each is a share-wise kernel over slots whose geometry and sizes
+// are checked on the host (img_geom.h, cswap_geom.h, mx_perm_gather) before it gets here.
 
 #include <hip/hip_runtime.h>
 
@@ -926,9 +926,114 @@ static dim3 cswap_grid(int64_t total, int F, int64_t slots) {
               (unsigned)slots);
 }
 
+// permuted row gather (moosex.h mx_perm_gather), on k_resize2d's plan: the output is rows x
+// inner with rows = outer * n; a lane owns V adjacent inner outputs of a row (V = 2 only for
+// u64 with an even inner extent and aligned buffers: every load and store is 16 bytes; u128
+// moves 16 bytes per lane as is), adjacent lanes are adjacent in the row -- a gathered row is
+// read as one contiguous run, the masks and the output are read and written in order -- and
+// the lane strides over rows.  perm[r] is read once per row, the same entry for all lanes of
+// the row, and clamped to [0, n): a bad perm gathers a wrong row, never outside.  The optional
+// operands are uniform null tests.  Slots are blockIdx.z, read at their strides and written
+// densely.  I: the index type, 32-bit when every extent is below 2^31.
+template <class I>
+struct PermGatherP {
+  I a_slot, b_slot, p_slot, m_slot, o_slot;  // slot strides in elements
+  I rows, n, inner;
+};
+
+template <class T, class I, int V>
+__global__ void __launch_bounds__(256) k_perm_gather(const T* __restrict__ a,
+                                                     const T* __restrict__ b,
+                                                     const T* __restrict__ pl,
+                                                     const T* __restrict__ mi,
+                                                     const int64_t* __restrict__ perm,
+                                                     T* __restrict__ out, PermGatherP<I> p) {
+  using U = typename std::make_unsigned<I>::type;
+  using Vec = LaneVec<T, V>;
+  const unsigned by = blockDim.y;
+  // V == 2 only with an even inner extent: both outputs are inside, or neither
+  const I c0 = ((I)blockIdx.x * (I)blockDim.x + (I)threadIdx.x) * V;
+  if (c0 >= p.inner) return;
+  const I z = (I)blockIdx.z;
+  const T* __restrict__ sa = a + z * p.a_slot;
+  const T* __restrict__ sb = b ? b + z * p.b_slot : nullptr;
+  const T* __restrict__ sp = pl ? pl + z * p.p_slot : nullptr;
+  const T* __restrict__ sm = mi ? mi + z * p.m_slot : nullptr;
+  T* __restrict__ dst = out + z * p.o_slot;
+  const uint64_t last = (uint64_t)p.n - 1u;
+  for (I row = (I)(blockIdx.y * by + threadIdx.y); row < p.rows; row += (I)(gridDim.y * by)) {
+    const U o = (U)row / (U)p.n;
+    const I r = row - (I)o * p.n;
+    const uint64_t want = (uint64_t)perm[r];  // a negative entry wraps above `last`
+    const I src = (I)(want < last ? want : last);
+    const I si = ((I)o * p.n + src) * p.inner + c0, di = row * p.inner + c0;
+    Vec v = *reinterpret_cast<const Vec*>(sa + si);
+    if (sb) {
+      const Vec w = *reinterpret_cast<const Vec*>(sb + si);
+#pragma unroll
+      for (int j = 0; j < V; ++j) v.v[j] += w.v[j];
+    }
+    if (sp) {
+      const Vec w = *reinterpret_cast<const Vec*>(sp + di);
+#pragma unroll
+      for (int j = 0; j < V; ++j) v.v[j] += w.v[j];
+    }
+    if (sm) {
+      const Vec w = *reinterpret_cast<const Vec*>(sm + di);
+#pragma unroll
+      for (int j = 0; j < V; ++j) v.v[j] -= w.v[j];
+    }
+    *reinterpret_cast<Vec*>(dst + di) = v;
+  }
+}
+
+template <class T, class I, int V>
+static int perm_gather_launch(const void* a, const void* b, const void* pl, const void* mi,
+                              const int64_t* perm, void* out, int64_t slots, int64_t a_slot,
+                              int64_t b_slot, int64_t p_slot, int64_t m_slot, int64_t outer,
+                              int64_t n, int64_t inner, void* stream) {
+  const LanePlan lp = lane_plan(inner, V);
+  const int64_t rows = outer * n;
+  PermGatherP<I> p;
+  p.a_slot = (I)a_slot, p.b_slot = (I)b_slot, p.p_slot = (I)p_slot, p.m_slot = (I)m_slot;
+  p.o_slot = (I)(rows * inner), p.rows = (I)rows, p.n = (I)n, p.inner = (I)inner;
+  hipLaunchKernelGGL((k_perm_gather<T, I, V>),
+                     dim3((unsigned)lp.tiles, (unsigned)row_grid(rows, lp.by), (unsigned)slots),
+                     dim3(lp.bx, lp.by), 0, S(stream), (const T*)a, (const T*)b, (const T*)pl,
+                     (const T*)mi, perm, (T*)out, p);
+  MX_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mxh_perm_gather(int elem_bytes, const void* a, const void* b, const void* p, const void* m,
+                    const int64_t* perm, void* out, int64_t slots, int64_t a_slot_stride,
+                    int64_t b_slot_stride, int64_t p_slot_stride, int64_t m_slot_stride,
+                    int64_t outer, int64_t n, int64_t inner, void* stream) {
+  if (slots <= 0 || outer <= 0 || n <= 0 || inner <= 0) return 0;
+  if (slots > 65535 || !a || !perm || !out || a_slot_stride < 0 || b_slot_stride < 0 ||
+      p_slot_stride < 0 || m_slot_stride < 0)
+    return -3;
+  // mx_perm_gather bounded n_x, the strides and their products with `slots` below 2^62
+  const int64_t n_x = outer * n * inner;
+  const bool small = fits32(1 << 17, {(slots - 1) * a_slot_stride + n_x,
+                                      b ? (slots - 1) * b_slot_stride + n_x : 0,
+                                      p ? (slots - 1) * p_slot_stride + n_x : 0,
+                                      m ? (slots - 1) * m_slot_stride + n_x : 0, slots * n_x});
+  // two outputs per lane: every row, slot and buffer has to start on 16 bytes
+  const bool two = inner % 2 == 0 && aligned16(a) && aligned16(b) && aligned16(p) &&
+                   aligned16(m) && aligned16(out) && a_slot_stride % 2 == 0 &&
+                   b_slot_stride % 2 == 0 && p_slot_stride % 2 == 0 && m_slot_stride % 2 == 0;
+  return leaf_dispatch(elem_bytes, small, two, [&](auto f) {
+    using F = decltype(f);
+    return perm_gather_launch<typename F::T, typename F::I, F::V>(
+        a, b, p, m, perm, out, slots, a_slot_stride, b_slot_stride, p_slot_stride, m_slot_stride,
+        outer, n, inner, stream);
+  });
+}
 
 // The image leaves: g comes validated from mx_* (img_geom_check); what is left here is what
 // only a launch is bound by -- slots are blockIdx.z -- and each leaf's choice of form.

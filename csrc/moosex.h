@@ -179,6 +179,19 @@ int mx_cswap_apply(int dev, int elem_bytes, const void* x, const void* p, void* 
                    int64_t slots, int64_t x_slot_stride, int64_t p_slot_stride, int64_t outer,
                    int64_t n, int64_t inner, int64_t by, int64_t k, int64_t j, int descending,
                    void* stream);
+// Permuted row gather in Z_2^64 / Z_2^128 (elem_bytes 8 / 16), wrapping, along the middle axis
+// of an [outer, n, inner] array per slot -- the local step of an oblivious shuffle:
+//   out[o, r, c] = a[o, perm[r], c] (+ b[o, perm[r], c]) (+ p[o, r, c]) (- m[o, r, c])
+// b, p and m are each optional (null); with all three null it is a plain row gather.  perm is
+// int64 [n] on the operands' device and has to be a permutation of 0..n-1: the CPU twin checks
+// it (-3), the kernel clamps what it reads (a bad perm gathers a wrong row, never outside).
+// Input slots are *_slot_stride elements apart (views of a larger buffer are read in place),
+// output slots are dense.  out must not overlap an input: a gather is not in-place safe.
+// -3 also where slots times the elements of a slot, or times a slot stride, exceeds 2^61.
+int mx_perm_gather(int dev, int elem_bytes, const void* a, const void* b, const void* p,
+                   const void* m, const int64_t* perm, void* out, int64_t slots,
+                   int64_t a_slot_stride, int64_t b_slot_stride, int64_t p_slot_stride,
+                   int64_t m_slot_stride, int64_t outer, int64_t n, int64_t inner, void* stream);
 // mx_ew_binary_slot on a0 (slot which0) and a1 (slot which1) with one public b
 int mx_ew_binary_slot2(int dev, int op, int words, const void* a0, const void* a1,
                        const void* b, int64_t nb, void* out0, void* out1, int64_t m,

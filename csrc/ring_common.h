@@ -305,6 +305,11 @@ int mxh_cswap_cross(int elem_bytes, const void* s0, const void* s1, const void* 
 int mxh_cswap_apply(int elem_bytes, const void* x, const void* p, void* out, int64_t slots,
                     int64_t x_slot_stride, int64_t p_slot_stride, const mxr::CswapGeom& g,
                     void* stream);
+// the permuted row gather: sizes and strides checked by mx_perm_gather, rows = outer * n
+int mxh_perm_gather(int elem_bytes, const void* a, const void* b, const void* p, const void* m,
+                    const int64_t* perm, void* out, int64_t slots, int64_t a_slot_stride,
+                    int64_t b_slot_stride, int64_t p_slot_stride, int64_t m_slot_stride,
+                    int64_t outer, int64_t n, int64_t inner, void* stream);
 int mxh_ks_cross1(int words, const void* g0, const void* g1, const void* p0, const void* p1,
                   void* z, int64_t n, int d, int both, const uint8_t* keys16, uint64_t nonce,
                   void* stream);

@@ -111,6 +111,9 @@ from moose_amd.edsl.base import tanh  # noqa: F401
 from moose_amd.edsl.base import thresholded_relu  # noqa: F401
 from moose_amd.edsl.base import median  # noqa: F401
 from moose_amd.edsl.base import quantile  # noqa: F401
+from moose_amd.edsl.base import sample_rows  # noqa: F401
+from moose_amd.edsl.base import shuffle  # noqa: F401
+from moose_amd.edsl.base import shuffle_together  # noqa: F401
 from moose_amd.edsl.base import sort  # noqa: F401
 from moose_amd.edsl.base import sort_rows  # noqa: F401
 from moose_amd.edsl.base import top_k  # noqa: F401

@@ -102,6 +102,7 @@ _OPS = {
         ["x"],
         lambda o: {"axis": int(o.axis), "descending": bool(o.descending), "by": int(o.by)},
     ),
+    "ShuffleOperation": ("Shuffle", ["x"], lambda o: {"axis": int(o.axis)}),
     "PiecewiseLinearOperation": (
         "PiecewiseLinear",
         ["x"],

@@ -73,7 +73,7 @@ def typing_pass(comp: Computation, **_) -> Computation:
 
 _SAME_SHAPE_OPS = {"Cast", "Identity", "Relu", "Sigmoid", "Abs", "Neg", "Exp", "Sqrt", "Log",
                    "Log2", "Softmax", "Share", "Reveal", "PiecewiseLinear", "Sort",
-                   "PiecewisePolynomial"}
+                   "PiecewisePolynomial", "Shuffle", "PermGather", "PermFromKeys"}
 
 
 def _static_shape(op, shapes):

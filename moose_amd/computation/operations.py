@@ -93,6 +93,7 @@ OPERATION_TABLE = [
     ("PiecewiseLinearOperation", ["breakpoints", "slopes", "intercepts"]),
     ("PiecewisePolynomialOperation", ["breakpoints", "coefficients", "degree"]),
     ("SortOperation", ["axis", "descending", "by"]),
+    ("ShuffleOperation", ["axis"]),
 ]
 
 OPERATION_CLASSES = {}

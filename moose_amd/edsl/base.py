@@ -887,6 +887,92 @@ def permute(x, axes, placement=None):
 
 
 # ---------------------------------------------------------------------------
+# oblivious shuffle (one Shuffle operator each)
+# ---------------------------------------------------------------------------
+def _shuffle_operand(fn, x, placement):
+    plc = _materialize_placement_arg(placement)
+    if not isinstance(plc, ReplicatedPlacementExpression):
+        raise ValueError(
+            f"`{fn}` runs on a replicated placement, found {type(plc).__name__} "
+            f"`{plc.name}`: a permutation drawn by one host is known to that host, so the "
+            "shuffle would not be oblivious")
+    d = x.vtype.dtype if isinstance(x, Expression) and isinstance(x.vtype, ty.TensorType) \
+        else None
+    if d is None or not d.is_fixedpoint:
+        raise ValueError(f"`{fn}` expects a fixed-point tensor (cast the input first; bit "
+                         f"tensors are not supported), found {getattr(x, 'vtype', type(x))}")
+    return plc
+
+
+def shuffle(x, axis=0, placement=None):
+    """``x`` reordered along ``axis`` by a uniformly random permutation that no single party
+    knows: three rounds and six messages of the tensor's size, exact -- the result holds the
+    input's values in a new order, freshly re-shared.  Replicated placements and fixed-point
+    tensors only.  Every evaluation draws a fresh permutation."""
+    plc = _shuffle_operand("shuffle", x, placement)
+    axis = _sort_axis("shuffle", axis, x.static_shape)
+    e = _expr("shuffle", [x], x.vtype, plc, axis=axis)
+    e.static_shape = x.static_shape
+    return e
+
+
+def shuffle_together(arrays, axis=0, placement=None, input_shape=None):
+    """The rank-2 tensors ``arrays`` (one dtype, e.g. features and labels) shuffled by ONE
+    permutation along ``axis`` 0: concatenated along axis 1, shuffled, sliced back.  The column
+    widths come from each pm.Argument's ``shape=`` or from ``input_shape=``, a list with one
+    shape per array."""
+    fn = "shuffle_together"
+    arrays = list(arrays)
+    if not arrays:
+        raise ValueError(f"`{fn}` takes at least one tensor")
+    if axis != 0:
+        raise ValueError(f"`{fn}` shuffles rows: `axis` must be 0, found {axis!r}")
+    if input_shape is not None and len(input_shape) != len(arrays):
+        raise ValueError(f"`{fn}`: `input_shape` must list one shape per array")
+    plc = None
+    widths = []
+    for k, x in enumerate(arrays):
+        plc = _shuffle_operand(fn, x, placement)
+        shape = _sort_shape(fn, x, None if input_shape is None else input_shape[k], need=False)
+        if shape is None or len(shape) != 2 or shape[1] is None:
+            raise ValueError(
+                f"`{fn}` needs the static column width of every rank-2 array (array {k} has "
+                f"shape {shape}): pass `input_shape=`, or give the pm.Argument a `shape=`")
+        widths.append(shape)
+    rows = {s[0] for s in widths if s[0] is not None}
+    if len(rows) > 1:
+        raise ValueError(f"`{fn}`: the arrays have different numbers of rows, {sorted(rows)}")
+    if len(arrays) == 1:
+        return [shuffle(arrays[0], 0, plc)]
+    cat = concatenate(arrays, axis=1, placement=plc)
+    n = next(iter(rows), None)
+    cat.static_shape = (n, builtins.sum(s[1] for s in widths))
+    mixed = shuffle(cat, 0, plc)
+    outs, c0 = [], 0
+    for s in widths:
+        y = strided_slice(mixed, [slice(None), slice(c0, c0 + s[1])], plc)
+        y.static_shape = (n, s[1])
+        outs.append(y)
+        c0 += s[1]
+    return outs
+
+
+def sample_rows(x, k, placement=None):
+    """``k`` rows of ``x`` drawn uniformly without replacement, in random order: a shuffle
+    along axis 0 and a slice."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 0:
+        raise ValueError(f"`sample_rows`: `k` must be a non-negative int, found {k!r}")
+    shp = x.static_shape if isinstance(x, Expression) else None
+    if shp and shp[0] is not None and shp[0] >= 0 and k > shp[0]:
+        raise ValueError(f"`sample_rows`: k = {k} exceeds the {shp[0]} rows")
+    s = shuffle(x, 0, placement)
+    y = sliced(s, 0, int(k), s.placement)
+    if shp:
+        y.static_shape = (int(k),) + tuple(shp[1:])
+    return y
+
+
+# ---------------------------------------------------------------------------
 # sorting and order statistics (one Sort operator each)
 # ---------------------------------------------------------------------------
 QUANTILE_INTERPOLATIONS = ("linear", "lower", "higher", "midpoint")

@@ -70,6 +70,7 @@ _OPS = {
     "piecewise_polynomial": ("PiecewisePolynomialOperation", ["x"], "piecewise_polynomial",
                              ["breakpoints", "coefficients", "degree"]),
     "sort": ("SortOperation", ["x"], "sort", ["axis", "descending", "by"]),
+    "shuffle": ("ShuffleOperation", ["x"], "shuffle", ["axis"]),
     "shape": ("ShapeOperation", ["x"], "shape", []),
     "mux": ("MuxOperation", ["selector", "x", "y"], "mux", []),
     "load": ("LoadOperation", ["key", "query"], "load", []),

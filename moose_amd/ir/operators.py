@@ -174,6 +174,17 @@ EXTENSION_OPERATORS = {
     # fixed-point x: a bitonic network of compare-exchange stages, each one sign extraction and
     # one multiplication, exact (nothing truncates)
     "Sort": [("axis", "int"), ("descending", "bool"), ("by", "int")],
+    # oblivious shuffle along `axis` by a uniformly random permutation no single party knows.
+    # On a secret x: three steps, one per PRF key; the key's two holders derive a permutation
+    # and two masks from it, gather their share components through it and send one masked
+    # tensor each to the third party.  Exact: the result is the input's values, reordered
+    "Shuffle": [("axis", "int")],
+    # the two host operators a lowered Shuffle step is made of: the permutation that stably
+    # sorts a vector of 64-bit PRF output as unsigned integers, and the row gather through it
+    # fused with the step's sums -- inputs (a, perm, then the optional operands `form` names:
+    # b gathered and added, p added in place, m subtracted in place)
+    "PermFromKeys": [],
+    "PermGather": [("axis", "int"), ("form", "str")],
 }
 
 ALL_OPERATORS = {**OPERATORS, **EXTENSION_OPERATORS}

@@ -61,6 +61,8 @@ _SIGS = {
     #  descending, stream)
     "mx_cswap_apply": (c_int, [c_int, c_int] + [c_vp] * 3 + [c_i64] * 3 + [c_i64] * 6 + [c_int]
                        + [c_vp]),
+    # (dev, elem_bytes, a b p m perm out, slots, a b p m slot strides, outer n inner, stream)
+    "mx_perm_gather": (c_int, [c_int, c_int] + [c_vp] * 6 + [c_i64] * 5 + [c_i64] * 3 + [c_vp]),
     # (dev, elem_bytes, x0 x1 w0 w1 out, slots, x_slot_stride, w_slot_stride, N C H W mult,
     #  KH KW, sh sw, pt pl, dh dw, OH OW, nhwc, stream)
     "mx_dwconv": (c_int, [c_int, c_int] + [c_vp] * 5 + [c_i64] * 3 + [c_i64] * 15

@@ -1751,6 +1751,123 @@ def cswap_apply(x: RT, p: RT, g: CswapGeom, nb=0) -> RT:
     return out
 
 
+# ---------------------------------------------------------------------------
+# the local step of an oblivious shuffle: a permutation from PRF output, and a row gather
+# ---------------------------------------------------------------------------
+# the device path of perm_gather: the native kernel (True) or the torch composition
+# perm_gather_torch (False); a CPU tensor always takes the native loops
+SHUFFLE_KERNEL = True
+
+_I64_MIN = torch.iinfo(torch.int64).min
+
+
+def perm_from_keys(keys: RT) -> torch.Tensor:
+    """The permutation of 0..n-1 that sorts the n 64-bit ``keys`` (a Z_2^64 vector of PRF
+    output) as unsigned integers, ascending and STABLE: equal keys keep their order, so both
+    holders of a PRF key derive the same permutation on any device.  An int64 tensor on the
+    keys' device -- the only producer of the index vectors :func:`perm_gather` takes.  torch
+    has no unsigned 64-bit sort: the top bit is flipped and the values sort as int64."""
+    if not isinstance(keys, RT) or keys.bits != 64 or keys.ndim != 1:
+        raise ValueError("perm_from_keys takes a Z_2^64 vector of sort keys")
+    if keys.device.type == "meta":  # shape inference of the symbolic session
+        return torch.empty(keys.shape, dtype=torch.int64, device="meta")
+    return torch.argsort(keys.data ^ _I64_MIN, dim=0, stable=True)
+
+
+def _perm_gather_check(a: RT, perm, others, axis, nb):
+    if not isinstance(a, RT) or a.bits not in (64, 128):
+        raise ValueError("perm_gather is arithmetic only: operands over one of Z_2^64 / Z_2^128")
+    if nb not in (0, 1):
+        raise ValueError("perm_gather takes at most one batch dim")
+    nd = a.ndim - nb
+    if nd < 1 or isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) \
+            or not -nd <= axis < nd:
+        raise ValueError(f"perm_gather: axis {axis!r} out of range for a tensor of rank {nd}")
+    ax = int(axis) % nd + nb
+    shape = tuple(a.shape)
+    n = shape[ax]
+    if not isinstance(perm, torch.Tensor) or perm.dtype != torch.int64:
+        raise ValueError("perm_gather: `perm` must be an int64 tensor (R.perm_from_keys), found "
+                         f"{getattr(perm, 'dtype', type(perm).__name__)}")
+    if perm.dim() != 1 or perm.shape[0] != n:
+        raise ValueError(f"perm_gather: `perm` of shape {tuple(perm.shape)} does not match the "
+                         f"axis length {n}")
+    if perm.device != a.device:
+        raise ValueError(f"perm_gather: `perm` lives on {perm.device}, the operands on "
+                         f"{a.device}")
+    for name, t in others:
+        if t is not None and (not isinstance(t, RT) or t.bits != a.bits
+                              or tuple(t.shape) != shape or t.device != a.device):
+            raise ValueError(f"perm_gather: `{name}` must be a Z_2^{a.bits} tensor of shape "
+                             f"{shape} on {a.device}, found {t!r}")
+    return ax, math.prod(shape[nb:ax]), n, math.prod(shape[ax + 1:])
+
+
+def _add128(x, y):
+    lo = x[..., 0] + y[..., 0]
+    carry = ((lo ^ _I64_MIN) < (x[..., 0] ^ _I64_MIN)).to(torch.int64)
+    return torch.stack((lo, x[..., 1] + y[..., 1] + carry), dim=-1)
+
+
+def _sub128(x, y):
+    borrow = ((x[..., 0] ^ _I64_MIN) < (y[..., 0] ^ _I64_MIN)).to(torch.int64)
+    return torch.stack((x[..., 0] - y[..., 0], x[..., 1] - y[..., 1] - borrow), dim=-1)
+
+
+def perm_gather_torch(a: RT, perm, b=None, plus=None, minus=None, axis=0, nb=0) -> RT:
+    """:func:`perm_gather` as a torch composition on the int64 views (index_select, add and
+    sub, with the carry between the two words for Z_2^128): the benchmark's opponent."""
+    ax, _, _, _ = _perm_gather_check(a, perm, (("b", b), ("plus", plus), ("minus", minus)),
+                                     axis, nb)
+    add, sub = (_add128, _sub128) if a.bits == 128 else (torch.add, torch.sub)
+    v = a.data.index_select(ax, perm)
+    if b is not None:
+        v = add(v, b.data.index_select(ax, perm))
+    if plus is not None:
+        v = add(v, plus.data)
+    if minus is not None:
+        v = sub(v, minus.data)
+    return RT(v, a.bits)
+
+
+def perm_gather(a: RT, perm, b=None, plus=None, minus=None, axis=0, nb=0) -> RT:
+    """Rows of ``a`` gathered along ``axis`` through ``perm``, fused with the sums of a shuffle
+    step, wrapping in the ring: over ``a`` seen as [.., outer, n, inner],
+
+        out[o, r, c] = a[o, perm[r], c] (+ b[o, perm[r], c]) (+ plus[o, r, c]) (- minus[o, r, c])
+
+    ``b``, ``plus`` and ``minus`` are optional tensors of ``a``'s shape; without them it is a
+    plain row gather.  ``perm`` is an int64 [n] tensor on the operands' device and MUST be a
+    permutation of 0..n-1 (:func:`perm_from_keys` is the one producer): the CPU twin refuses
+    anything else, but nothing reads a device ``perm`` back to check it -- there the kernel
+    only clamps what it reads, so a bad ``perm`` gathers wrong rows, never outside the tensor.
+    One native launch over all batch slots (``mx_perm_gather``); [slots, ...] views with dense
+    slots are read in place.  The result is a new tensor: a gather is not in-place safe."""
+    others = (("b", b), ("plus", plus), ("minus", minus))
+    ax, outer, n, inner = _perm_gather_check(a, perm, others, axis, nb)
+    bits, shape, lead = a.bits, tuple(a.shape), tuple(a.shape[:nb])
+    if a.device.type == "meta":
+        return empty(shape, bits, a.device)
+    if a.device.type == "cuda" and not SHUFFLE_KERNEL:
+        return perm_gather_torch(a, perm, b, plus, minus, axis, nb)
+    out = empty(shape, bits, a.device)
+    if out.data.numel() == 0:
+        return out
+    dense = outer * n * inner
+    ops = [_leaf_operand(t, nb, dense) if t is not None else (None, 0)
+           for t in (a, b, plus, minus)]
+    pd = perm.contiguous()
+    nat.check(
+        nat.lib().mx_perm_gather(
+            nat.dev_of(out.data), _elem_bytes(bits),
+            *[nat.ptr(d) if d is not None else None for d, _ in ops], nat.ptr(pd),
+            nat.ptr(out.data), math.prod(lead), *[st for _, st in ops], outer, n, inner,
+            nat.stream_of(out.data)),
+        "perm_gather",
+    )
+    return out
+
+
 def select_mask(a: RT, axis: int, mask: torch.Tensor, nb=0) -> RT:
     ax = _ax(a, axis, nb)
     keep = torch.nonzero(mask.reshape(-1).to(torch.bool)).reshape(-1).to(a.device)

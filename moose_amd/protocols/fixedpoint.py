@@ -734,6 +734,13 @@ def sort(sess, x: RepFixed, axis: int = -1, descending: bool = False, by: int = 
     return _with(x, t)
 
 
+def shuffle(sess, x: RepFixed, axis: int = 0) -> RepFixed:
+    """``x`` reordered along ``axis`` by a uniformly random permutation no single party knows
+    (rep.shuffle: three rounds, six messages of the tensor's size).  Exact: the result holds
+    the ring values of the input, reordered and re-shared; the precision is unchanged."""
+    return _with(x, rep.shuffle(sess, x.t, axis))
+
+
 # ---------------------------------------------------------------------------
 # normalisation: leading-bit one-hot
 # ---------------------------------------------------------------------------

@@ -34,6 +34,7 @@ instead of k bit tensors (reference bits.rs stacks a [k, ...] bit array).
 """
 from __future__ import annotations
 
+import math
 import os
 from dataclasses import dataclass
 from typing import Optional
@@ -1294,6 +1295,76 @@ def sort_network(sess, x: RepTensor, geom, descending=False, width=None) -> RepT
                 o0, o1 = _sharewise(sess, "CswapApply", plc, (x.s0, x.s1), (p.s0, p.s1),
                                     geom=tuple(g))
                 x = RepTensor(plc, bits, "arith", o0, o1)
+    return x
+
+
+def _shuffle_step(sess, x: RepTensor, i: int, axis: int, n: int) -> RepTensor:
+    """One step of :func:`shuffle`: the holders of PRF key ``k_i`` -- H0 = P_{i-1} and H1 = P_i
+    -- permute ``x`` by a permutation pi_i that the outsider C = P_{i+1} cannot derive.  Both
+    holders draw pi_i (the stable argsort of n 64-bit PRF values) and two masks r, s of x's
+    shape from k_i.  H0 holds x_{i-1} + x_i, H1 holds x_{i+1}; the new slots are
+
+        y_i     = r                                   (both holders, no message)
+        y_{i-1} = pi_i(x_{i-1} + x_i) - s             (H0, sent to C)
+        y_{i+1} = pi_i(x_{i+1}) + s - r               (H1, sent to C)
+
+    which sum to pi_i(x).  One round, two messages, both to C."""
+    plc, bits, o = x.plc, x.bits, x.plc.owners
+    h0, h1, c = (i - 1) % 3, i, (i + 1) % 3
+    n_perm, n_r, n_s = sess.nonce(plc), sess.nonce(plc), sess.nonce(plc)
+    perm, r, s = {}, {}, {}
+    for h in (h0, h1):
+        own = sess.take(x.s0, h)
+        shape = sess.h("Shape", o[h], own)
+        keys = sess.h_prf(plc, o[h], i, HV(o[h], (int(n),)), 64, n_perm)
+        perm[h] = sess.h("PermFromKeys", o[h], keys)
+        r[h] = sess.h_prf(plc, o[h], i, shape, bits, n_r)
+        s[h] = sess.h_prf(plc, o[h], i, shape, bits, n_s)
+    # H0 = P_{i-1} holds (x_{i-1}, x_i); H1 = P_i holds (x_i, x_{i+1})
+    y_prev = sess.h("PermGather", o[h0], sess.take(x.s0, h0), perm[h0], sess.take(x.s1, h0),
+                    s[h0], axis=axis, form="bm")
+    y_next = sess.h("PermGather", o[h1], sess.take(x.s1, h1), perm[h1], s[h1], r[h1],
+                    axis=axis, form="pm")
+    # P_j holds (y_j, y_{j+1}): H0 (y_{i-1}, r), H1 (r, y_{i+1}), C (y_{i+1}, y_{i-1})
+    comp0 = {h0: y_prev, h1: r[h1], c: sess.move(y_next, o[c])}
+    comp1 = {h0: r[h0], h1: y_next, c: sess.move(y_prev, o[c])}
+    s0 = sess.gather(plc, [comp0[j] for j in range(3)])
+    s1 = sess.gather(plc, [comp1[j] for j in range(3)])
+    stats = getattr(sess, "stats", None)
+    if stats is not None:
+        v = getattr(y_prev, "v", None)
+        stats.record_round(2 * payload_bytes_of(v) if isinstance(v, R.RT) else 0)
+    return RepTensor(plc, bits, "arith", s0, s1)
+
+
+def shuffle(sess, x: RepTensor, axis: int = 0) -> RepTensor:
+    """Oblivious shuffle: ``x`` reordered along ``axis`` by a uniformly random permutation that
+    no single party knows (semi-honest, one corruption).  Three steps (:func:`_shuffle_step`),
+    one per PRF key k_0, k_1, k_2; every party is the outsider of exactly one step, so the
+    composition pi_2 . pi_1 . pi_0 is unknown to each.  Three rounds and six messages of the
+    tensor's size; no comparison, multiplication or truncation, so the result holds exactly
+    the input's ring values, reordered and freshly re-shared.  Arithmetic sharings over
+    Z_2^64 / Z_2^128 of rank >= 1; an axis of length <= 1 returns ``x`` unchanged.  Written
+    from the session primitives of the generic :func:`share` path, so it runs in the stacked,
+    per-party, SPMD and symbolic sessions alike (a lowered graph: the PRF operators of a
+    share plus PermFromKeys and PermGather)."""
+    if x.kind != "arith" or x.bits not in (64, 128):
+        raise ValueError("shuffle takes an arithmetic sharing over Z_2^64 or Z_2^128; a bit "
+                         "sharing is not supported (inject the bits into a ring first)")
+    shape = tuple(sess.p_shape(x.s0))
+    nd = len(shape)
+    if nd < 1:
+        raise ValueError("shuffle takes a tensor of rank >= 1, found a scalar")
+    if isinstance(axis, bool) or not isinstance(axis, int) or not -nd <= axis < nd:
+        raise ValueError(f"shuffle: axis {axis!r} out of range for a tensor of rank {nd}")
+    axis %= nd
+    n = shape[axis]
+    if n <= 1 or math.prod(shape) == 0:
+        return x
+    with span("rep.shuffle"):
+        sess.setup(x.plc)
+        for i in range(3):
+            x = _shuffle_step(sess, x, i, axis, n)
     return x
 
 

@@ -179,6 +179,10 @@ def _sort_ring(c, x):
 
 
 kernel("Sort", "rep", "rep_ring")(_sort_ring)
+# Shuffle on a raw ring sharing (the host operators PermFromKeys and PermGather of its steps
+# are primitives of runtime/prims.py, run by name like every host operator)
+kernel("Shuffle", "rep", "rep_ring")(
+    lambda c, x: rep.shuffle(c.sess, x, int(c.attr("axis", default=0))))
 kernel("Neg", "rep", "rep_ring")(lambda c, x: rep.neg(c.sess, x))
 kernel("Sum", "rep", "rep_ring")(lambda c, x: rep.sum(c.sess, x, c.attr("axis")))
 kernel("AddN", "rep", "rep_ring", variadic=True)(lambda c, *xs: _add_n(c, xs))

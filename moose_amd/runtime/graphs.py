@@ -107,9 +107,13 @@ def signature(arguments: dict):
 
 def capturable(comp) -> bool:
     """Can an evaluation of ``comp`` be replayed?  Host Load / Save go through a StorageTap;
-    share checkpoints and computed keys keep the computation eager."""
+    share checkpoints and computed keys keep the computation eager, and so does a Shuffle: its
+    permutation is a device argsort of fresh PRF output, which is not captured -- run eagerly,
+    every evaluation draws fresh keys and with them a fresh permutation."""
     from moose_amd.runtime import storage_tap
 
+    if any(op.kind == "Shuffle" for op in comp.operations):
+        return False
     return storage_tap.capturable(comp)
 
 

@@ -1570,6 +1570,28 @@ class Interpreter:
         except ValueError as e:
             raise MooseRuntimeError(f"{op.name}: {e}") from None
 
+    def op_Shuffle(self, op, ins):
+        """Oblivious shuffle of a replicated fixed-point tensor along an axis
+        (fixedpoint.shuffle: three rounds, exact).  A host's or a public value is refused: a
+        permutation one host draws is not hidden from it."""
+        axis = int(op.attrs.get("axis", 0))
+        x = self.at(op, ins[0])
+        if x.kind != "tensor":
+            raise MooseRuntimeError(f"{op.name}: Shuffle expects a tensor, got a {x.kind}")
+        if not x.is_rep or isinstance(x.v, MV):
+            where = getattr(x.plc, "name", None) or getattr(x.plc, "owner", None) or x.plc
+            raise MooseRuntimeError(
+                f"{op.name}: Shuffle runs on a replicated placement with a secret-shared "
+                f"tensor; the value lives on {where}, where one host would know the order")
+        if x.dtype is None or not x.dtype.is_fixed:
+            raise MooseRuntimeError(
+                f"{op.name}: Shuffle expects a fixed-point tensor, got {x.dtype}; cast a float "
+                "tensor to fixed point first (bit tensors are not supported)")
+        try:
+            return LV(x.plc, "tensor", x.dtype, fxp.shuffle(self.sess, x.v, axis))
+        except ValueError as e:
+            raise MooseRuntimeError(f"{op.name}: {e}") from None
+
     def op_PiecewiseLinear(self, op, ins):
         """Piecewise-linear activation of a fixed-point tensor: replicated values through
         fixedpoint.piecewise_linear (one sign extraction, one local kernel, one truncation);

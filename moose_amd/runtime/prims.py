@@ -417,6 +417,30 @@ def _cswap_apply(nb, x, p, geom):
     return R.cswap_apply(x, p, R.CswapGeom(*geom), nb)
 
 
+@prim("PermFromKeys", ty=lambda tys, **a: T.Ty("HostUint64Tensor"))
+def _perm_from_keys(nb, keys):
+    """The permutation that stably sorts a Z_2^64 vector of PRF output as unsigned integers
+    (R.perm_from_keys): what both holders of a PRF key derive alike in a shuffle step."""
+    return R.perm_from_keys(keys)
+
+
+PERM_GATHER_FORMS = {"": (), "b": ("b",), "p": ("plus",), "m": ("minus",), "bp": ("b", "plus"),
+                     "bm": ("b", "minus"), "pm": ("plus", "minus"),
+                     "bpm": ("b", "plus", "minus")}
+
+
+@prim("PermGather")
+def _perm_gather(nb, a, perm, *rest, axis=0, form=""):
+    """Rows of ``a`` gathered along ``axis`` through ``perm`` with the sums of a shuffle step
+    (R.perm_gather).  ``form`` names the optional operands that follow ``perm``, in order:
+    ``b`` (gathered and added), ``p`` (added in place), ``m`` (subtracted in place)."""
+    names = PERM_GATHER_FORMS.get(form)
+    if names is None or len(names) != len(rest):
+        raise ValueError(f"PermGather: form {form!r} does not name its {len(rest)} optional "
+                         "operand(s)")
+    return R.perm_gather(a, perm, axis=int(axis), nb=nb, **dict(zip(names, rest)))
+
+
 @prim("Sort")
 def _sort(nb, x, axis=-1, descending=False, by=-1):
     """Plaintext sort of a host's tensor along ``axis`` -- floats, or fixed-point ring values by
