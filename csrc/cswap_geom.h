@@ -5,6 +5,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "img_geom.h"  // slot_cap
+
 namespace mxr {
 
 struct CswapGeom {
@@ -53,6 +55,9 @@ inline int cswap_geom_check(CswapGeom& g, int elem_bytes, int64_t slots, int64_t
   g.n_pair = g.outer * g.half * g.inner;
   g.n_flag = g.outer * g.half * g.cols;
   if (slots == 0 || g.n_x == 0) return 0;
+  // n_x (the largest count of a slot) and the strides within slot_cap: no extent wraps
+  const int64_t cap = slot_cap(slots);
+  if (g.n_x > cap || stride_a > cap || stride_b > cap) return -3;
   return 1;
 }
 

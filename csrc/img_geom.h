@@ -5,7 +5,28 @@
 #pragma once
 #include <stdint.h>
 
+#include <initializer_list>
+
 namespace mxr {
+
+// What a slot's element count and a slot stride may be at most, for `slots` > 0 slots: with
+// both within it, (slots - 1) * stride + count and slots * count stay below 2^62, so no entry
+// point forms an extent that wraps int64_t (and comes out looking small to the index-width
+// choice of a launcher).  mx_perm_gather's rule, shared by every leaf.
+inline int64_t slot_cap(int64_t slots) { return ((int64_t)1 << 61) / slots; }
+
+// whether the product of non-negative factors is at most cap, without forming a product
+// that wraps
+inline bool product_within(int64_t cap, std::initializer_list<int64_t> factors) {
+  for (int64_t f : factors)
+    if (f == 0) return true;
+  int64_t p = 1;
+  for (int64_t f : factors) {
+    if (p > cap / f) return false;
+    p *= f;
+  }
+  return true;
+}
 
 struct ImgGeom {
   // attributes (resize2d: OH x OW is the output size and the window is 1 x 1)
@@ -78,6 +99,13 @@ inline int img_geom_check(ImgGeom& g, ImgLeaf leaf, int elem_bytes, int64_t slot
   if ((ck & IMG_CHANNELS) && g.C * g.mult > lim) return -3;
   if (slots == 0 || g.N == 0 || g.C == 0) return 0;
   if (leaf.out == IMG_INPUT && (g.H == 0 || g.W == 0)) return 0;
+  // Every extent a side forms -- (slots - 1) * stride + a slot's elements, slots * n_out --
+  // stays below 2^62: the strides, the input image and the taps of all outputs (which bound
+  // the patch matrix, the output image and the weights) are each at most 2^61 / slots.
+  const int64_t cap = slot_cap(slots);
+  if (stride_a > cap || stride_b > cap || !product_within(cap, {g.N, g.C, g.H, g.W}) ||
+      !product_within(cap, {g.N, g.C, g.mult, g.OH, g.OW, g.KH, g.KW}))
+    return -3;
   const bool nhwc = g.nhwc != 0;
   g.sN = g.C * g.H * g.W;
   g.sH = nhwc ? g.W * g.C : g.W;

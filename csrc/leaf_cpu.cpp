@@ -323,7 +323,7 @@ int mx_perm_gather(int dev, int elem_bytes, const void* a, const void* b, const 
   if (slots == 0 || outer == 0 || n == 0 || inner == 0) return 0;
   if (n > ((int64_t)1 << 60) / outer / inner) return -3;
   // every extent a side forms -- (slots - 1) * stride + n_x and slots * n_x -- stays below 2^62
-  const int64_t n_x = outer * n * inner, cap = ((int64_t)1 << 61) / slots;
+  const int64_t n_x = outer * n * inner, cap = mxr::slot_cap(slots);
   if (n_x > cap || a_slot_stride > cap || b_slot_stride > cap || p_slot_stride > cap ||
       m_slot_stride > cap)
     return -3;
@@ -431,7 +431,10 @@ int mx_pwl_cross(int dev, int elem_bytes, const void* s0, const void* s1, const 
     return -3;
   if ((s1 == nullptr) != (x1 == nullptr)) return -3;  // cross mode takes both next components
   if (elem_bytes != 8 && elem_bytes != 16) return -2;
-  if (slots * n == 0) return 0;
+  if (slots == 0 || n == 0) return 0;
+  // the flags' k * n elements of a slot (the largest count) and the strides within slot_cap
+  const int64_t cap = mxr::slot_cap(slots);
+  if (n > cap / std::max(k, 1) || s_slot_stride > cap || x_slot_stride > cap) return -3;
   if (!ak || (k && (!da || !db))) return -3;
   if (dev)
     return mxh_pwl_cross(elem_bytes, s0, s1, x0, x1, out, slots, s_slot_stride, x_slot_stride, n,
@@ -454,9 +457,12 @@ int mx_pwp_cross(int dev, int elem_bytes, const void* s0, const void* s1, const 
   if (elem_bytes != 8 && elem_bytes != 16) return -2;
   for (int i = 0; i < d; ++i)
     if (p_slot_stride[i] < 0) return -3;
-  if (slots * n == 0) return 0;
+  if (slots == 0 || n == 0) return 0;
+  // the flags' k * n elements of a slot (the largest count) and the strides within slot_cap
+  const int64_t cap = mxr::slot_cap(slots);
+  if (n > cap / k || s_slot_stride > cap) return -3;
   for (int i = 0; i < d; ++i)
-    if (!p0[i] || (p1 && !p1[i])) return -3;
+    if (p_slot_stride[i] > cap || !p0[i] || (p1 && !p1[i])) return -3;
   if (!s0 || !out) return -3;
   if (dev)
     return mxh_pwp_cross(elem_bytes, s0, s1, p0, p1, out, slots, s_slot_stride, p_slot_stride, n,

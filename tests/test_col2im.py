@@ -340,7 +340,7 @@ def test_kernel_reads_slot_views_in_place(fmt):
 @pytest.mark.parametrize("bits", BITS)
 def test_kernel_row_loop(bits, fmt):
     """The row grid-stride loop takes a second trip (TALL).  Only the 32-bit index forms run
-    here: the 64-bit ones need 2^31 elements."""
+    here: the 64-bit ones run in test_leaf_index_forms.py, on slots 2^31 elements apart."""
     cols, want = _cpu_result(TALL, fmt, bits)
     rows = want.data.numel() // (2 if bits == 128 else 1) // (2 if fmt == "NHWC" else 1)
     assert rows > 65536

@@ -255,7 +255,8 @@ def test_kernel_reads_slot_views_in_place(fmt):
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_kernel_row_loop_and_column_blocks(fmt):
     """The row grid-stride loop (TALL) and a second column block at two u64 per lane (WIDE).
-    Only the 32-bit index forms run here: the 64-bit ones need 2^31 elements."""
+    Only the 32-bit index forms run here: the 64-bit ones run in test_leaf_index_forms.py, on
+    slots 2^31 elements apart."""
     x, want = _cpu_result(TALL, fmt, 1)
     assert want.shape[0] > 65536
     # K = 1, 1x1, no padding: the patch matrix is the image

@@ -157,6 +157,19 @@ CODES = [
     (_pwl, dict(eb=4, k=9), -3),
 ]
 
+# A slot stride above 2^61 / slots: (slots - 1) * stride would wrap int64_t (3 * 2^61 and
+# 2 * (2^62 + 1) both do) and come out looking like a small or a negative extent.  Refused
+# before any extent is formed and before anything is read.
+_FAR = (dict(slots=4, stride=1 << 61), dict(slots=3, stride=(1 << 62) + 1))
+for _call, _names in ((_i2c, ("stride",)), (_c2i, ("stride",)), (_resize, ("stride",)),
+                      (_dwconv, ("xst", "wst")), (_pwl, ("sst", "xst"))):
+    for _name in _names:
+        CODES += [(_call, {"slots": f["slots"], _name: f["stride"]}, -3) for f in _FAR]
+# a slot's element count above 2^61 / slots: N * C * H * W = 2^60 with four slots
+CODES += [(_i2c, dict(slots=4, N=1 << 30, C=1 << 30), -3),
+          (_pwl, dict(slots=4, n=1 << 59), -3),
+          (_pwl, dict(slots=1, n=1 << 59, k=8), -3)]
+
 
 def _rt(words, bits):
     """A ring tensor over ``words`` ([.., 2] int64 for 128 bits)."""

@@ -242,3 +242,28 @@ def test_bad_operands_are_rejected():
         R.pwp(s, [z(4, bits=128)], [[1, 2]] * 2, [0])
     with pytest.raises(ValueError, match="arithmetic only"):  # bit tensors
         R.pwp(z(2, 4, bits=1), [z(4, bits=1)], [[1, 0]] * 2, [1])
+
+
+def test_a_slot_stride_whose_extent_would_wrap_is_refused():
+    """mx_pwp_cross bounds n * k and every slot stride -- the flags' and each power's -- by
+    2^61 / slots before any (slots - 1) * stride is formed: -3, nothing read."""
+    import ctypes
+
+    from moose_amd.ops import native as nat
+
+    bufs = [torch.zeros(64, dtype=torch.int64) for _ in range(4)]
+    tab = torch.zeros(32, dtype=torch.int64)
+
+    def call(slots, sst, pst, n=4, k=2, d=2):
+        ptrs = (ctypes.c_void_p * d)(*[nat.ptr(bufs[1])] * d)
+        return nat.lib().mx_pwp_cross(0, 8, nat.ptr(bufs[0]), None, ptrs, None, nat.ptr(bufs[3]),
+                                      slots, sst, (ctypes.c_int64 * d)(*pst), n, k, d,
+                                      nat.ptr(tab), nat.ptr(tab), None)
+
+    assert call(1, 8, (4, 4)) == 0
+    for slots, far in ((4, 1 << 61), (3, (1 << 62) + 1)):
+        assert call(slots, far, (4, 4)) == -3
+        assert call(slots, 8, (far, 4)) == -3
+        assert call(slots, 8, (4, far)) == -3
+    assert call(4, 8, (4, 4), n=1 << 59) == -3  # k * n of a slot
+    assert call(1 << 40, 8, (4, 4), n=1 << 22) == -3  # slots * n

@@ -658,7 +658,8 @@ def test_kernel_equals_cpu_twin(case, mode, bits, fmt):
 @pytest.mark.parametrize("mode", GPU_MODES + [MODES[2]], ids=["nearest", "linear", "aligned"])
 def test_kernel_row_loop(mode, bits):
     """NHWC [1, 136, 136, 1] -> 272 x 272: 73,984 rows, so the row grid-stride loop takes a
-    second trip.  Only the 32-bit index forms run here: the 64-bit ones need 2^31 elements."""
+    second trip.  Only the 32-bit index forms run here: the 64-bit ones run in
+    test_leaf_index_forms.py, on slots 2^31 elements apart."""
     x, want = _cpu_result(ROWS, "NHWC", bits, mode)
     assert want.shape[1] * want.shape[2] > 65536
     got = R.resize(R.RT(x.data.cuda(), bits), **_attrs(ROWS, mode), data_format="NHWC")

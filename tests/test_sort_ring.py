@@ -238,3 +238,30 @@ def test_malformed_stage_is_refused():
                 R.CswapGeom(2, 8, 1, -1, 2, 1)):
         with pytest.raises(ValueError):
             R.cswap_diff(x, bad)
+
+
+def test_a_slot_stride_whose_extent_would_wrap_is_refused():
+    """The three mx_cswap_* entries bound n_x and every slot stride by 2^61 / slots before any
+    (slots - 1) * stride is formed: -3, nothing read."""
+    from moose_amd.ops import native as nat
+
+    bufs = [torch.zeros(64, dtype=torch.int64) for _ in range(4)]
+    p = [nat.ptr(b) for b in bufs]
+    geom = (1, 8, 1, -1, 2, 1, 0)  # outer, n, inner, by, k, j, descending
+    L = nat.lib()
+
+    def diff(slots, xst, g=geom):
+        return L.mx_cswap_diff(0, 8, p[0], p[3], slots, xst, *g, None)
+
+    def cross(slots, sst, xst):
+        return L.mx_cswap_cross(0, 8, p[1], None, p[0], None, p[3], slots, sst, xst, *geom, None)
+
+    def apply(slots, xst, pst):
+        return L.mx_cswap_apply(0, 8, p[0], p[1], p[3], slots, xst, pst, *geom, None)
+
+    assert diff(1, 8) == 0 and cross(1, 4, 8) == 0 and apply(1, 8, 4) == 0
+    for slots, far in ((4, 1 << 61), (3, (1 << 62) + 1)):
+        assert diff(slots, far) == -3
+        assert cross(slots, far, 8) == -3 and cross(slots, 4, far) == -3
+        assert apply(slots, far, 4) == -3 and apply(slots, 8, far) == -3
+    assert diff(4, 8, (1 << 30, 1 << 30, 1, -1, 2, 1, 0)) == -3  # slots * n_x = 2^62
