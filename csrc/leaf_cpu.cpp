@@ -1,7 +1,7 @@
 // Host (CPU) twins of the leaf kernels of leaf_hip.hip -- the image leaves, the piecewise-
-// linear local step, the compare-exchange leaves and the permuted row gather -- and their
-// mx_* entry points, which check the geometry (img_geom.h, cswap_geom.h) and the sizes for
-// both sides.  Plain loops: the oracle.
+// linear local step, the compare-exchange leaves, the permuted row gather and the prefix-sum
+// leaves -- and their mx_* entry points, which check the geometry (img_geom.h, cswap_geom.h,
+// segscan_geom.h) and the sizes for both sides.  Plain loops: the oracle.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -307,9 +307,131 @@ void perm_gather_cpu(const T* a, const T* b, const T* p, const T* m, const int64
   });
 }
 
+using mxr::ScanGeom;
+using mxr::SegscanGeom;
+
+// The prefix sum (moosex.h mx_scan): one (slot, row, column) line at a time, front to back or
+// back to front.  The plain walk is the oracle of the kernel's three phases: sums in the ring
+// are the same in any grouping.
+template <class T>
+void scan_cpu(const T* x, T* out, int64_t slots, int64_t x_slot_stride, const ScanGeom& g) {
+  const int64_t lines = g.outer * g.inner;
+  parallel_for(slots * lines, std::max<int64_t>(1, 4096 / g.n), [&](int64_t b, int64_t e) {
+    for (int64_t q = b; q < e; ++q) {
+      const int64_t s = q / lines, r = q - s * lines, o = r / g.inner, c = r - o * g.inner;
+      const T* src = x + s * x_slot_stride + o * g.n * g.inner + c;
+      T* dst = out + s * g.n_x + o * g.n * g.inner + c;
+      T acc = 0;
+      for (int64_t t = 0; t < g.n; ++t) {
+        const int64_t i = (g.reverse ? g.n - 1 - t : t) * g.inner;
+        const T v = src[i];
+        if (g.exclusive) {
+          dst[i] = acc;
+          acc += v;
+        } else {
+          acc += v;
+          dst[i] = acc;
+        }
+      }
+    }
+  });
+}
+
+// The segmented-scan stage (moosex.h mx_segscan_cross / _apply): one (slot, row, position) at
+// a time.
+template <class T>
+void segscan_cross_cpu(const T* a, const T* b, T* out, int64_t slots, int64_t slot_stride,
+                       const SegscanGeom& g) {
+  const int64_t nj = g.n - g.j, rows = g.outer * nj;
+  parallel_for(slots * rows, std::max<int64_t>(1, 4096 / g.inner), [&](int64_t q0, int64_t q1) {
+    for (int64_t q = q0; q < q1; ++q) {
+      const int64_t s = q / rows, row = q - s * rows, o = row / nj, t = row - o * nj;
+      const int64_t ti = s * slot_stride + (o * g.n + t) * g.inner;
+      const int64_t fi = s * slot_stride + (o * g.n + t + g.j) * g.inner + g.inner - 1;
+      T* dst = out + q * g.inner;
+      for (int64_t c = 0; c < g.inner; ++c)
+        dst[c] = b ? a[fi] * (a[ti + c] + b[ti + c]) + b[fi] * a[ti + c] : a[fi] * a[ti + c];
+    }
+  });
+}
+
+template <class T>
+void segscan_apply_cpu(const T* x, const T* p, T* out, int64_t slots, int64_t x_slot_stride,
+                       int64_t p_slot_stride, const SegscanGeom& g) {
+  const int64_t nj = g.n - g.j, rows = g.outer * g.n;
+  parallel_for(slots * rows, std::max<int64_t>(1, 4096 / g.inner), [&](int64_t q0, int64_t q1) {
+    for (int64_t q = q0; q < q1; ++q) {
+      const int64_t s = q / rows, row = q - s * rows, o = row / g.n, pos = row - o * g.n;
+      const T* src = x + s * x_slot_stride + row * g.inner;
+      T* dst = out + q * g.inner;
+      if (pos < g.j) {
+        for (int64_t c = 0; c < g.inner; ++c) dst[c] = src[c];
+        continue;
+      }
+      const T* pp = p + s * p_slot_stride + (o * nj + pos - g.j) * g.inner;
+      for (int64_t c = 0; c + 1 < g.inner; ++c) dst[c] = src[c] + pp[c];
+      dst[g.inner - 1] = pp[g.inner - 1];
+    }
+  });
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t mx_scan_chunk(void) { return mxr::kScanChunk; }
+
+int64_t mx_scan_ws_elems(int64_t slots, int64_t outer, int64_t n, int64_t inner) {
+  ScanGeom g{outer, n, inner};
+  const int rc = mxr::scan_geom_check(g, 8, slots, 0);
+  return rc < 0 ? rc : slots * g.ws;
+}
+
+int mx_scan(int dev, int elem_bytes, const void* x, void* out, void* ws, int64_t ws_elems,
+            int64_t slots, int64_t x_slot_stride, int64_t outer, int64_t n, int64_t inner,
+            int exclusive, int reverse, void* stream) {
+  ScanGeom g{outer, n, inner, exclusive != 0, reverse != 0};
+  const int rc = mxr::scan_geom_check(g, elem_bytes, slots, x_slot_stride);
+  if (rc <= 0) return rc;
+  // both sides take the same workspace, so both refuse the same calls
+  if (g.ws && (!ws || ws_elems < slots * g.ws)) return -3;
+  if (!x || !out) return -3;
+  if (dev) return mxh_scan(elem_bytes, x, out, ws, slots, x_slot_stride, g, stream);
+  DISPATCH_ELEM(elem_bytes, T, {
+    scan_cpu((const T*)x, (T*)out, slots, x_slot_stride, g);
+    return 0;
+  });
+}
+
+int mx_segscan_cross(int dev, int elem_bytes, const void* a, const void* b, void* out,
+                     int64_t slots, int64_t slot_stride, int64_t outer, int64_t n,
+                     int64_t inner, int64_t j, void* stream) {
+  SegscanGeom g{outer, n, inner, j};
+  const int rc = mxr::segscan_geom_check(g, elem_bytes, slots, slot_stride);
+  if (rc <= 0) return rc;
+  if (!a || !out) return -3;
+  if (dev) return mxh_segscan_cross(elem_bytes, a, b, out, slots, slot_stride, g, stream);
+  DISPATCH_ELEM(elem_bytes, T, {
+    segscan_cross_cpu((const T*)a, (const T*)b, (T*)out, slots, slot_stride, g);
+    return 0;
+  });
+}
+
+int mx_segscan_apply(int dev, int elem_bytes, const void* x, const void* p, void* out,
+                     int64_t slots, int64_t x_slot_stride, int64_t p_slot_stride, int64_t outer,
+                     int64_t n, int64_t inner, int64_t j, void* stream) {
+  SegscanGeom g{outer, n, inner, j};
+  const int rc = mxr::segscan_geom_check(g, elem_bytes, slots, x_slot_stride, p_slot_stride);
+  if (rc <= 0) return rc;
+  if (!x || !p || !out) return -3;
+  if (dev)
+    return mxh_segscan_apply(elem_bytes, x, p, out, slots, x_slot_stride, p_slot_stride, g,
+                             stream);
+  DISPATCH_ELEM(elem_bytes, T, {
+    segscan_apply_cpu((const T*)x, (const T*)p, (T*)out, slots, x_slot_stride, p_slot_stride, g);
+    return 0;
+  });
+}
 
 int mx_perm_gather(int dev, int elem_bytes, const void* a, const void* b, const void* p,
                    const void* m, const int64_t* perm, void* out, int64_t slots,

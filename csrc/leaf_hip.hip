@@ -1,8 +1,9 @@
 // gfx950 leaf kernels of the moosex ring dialect: the image leaves (im2col, dwconv, col2im,
 // resize2d), the piecewise-linear and piecewise-polynomial local steps (pwl_cross, pwp_cross),
-// the compare-exchange leaves (cswap_diff / _cross / _apply) and the permuted row gather of a
-// shuffle step (perm_gather).  Each is a share-wise kernel over slots whose geometry and sizes
-// are checked on the host (img_geom.h, cswap_geom.h, mx_perm_gather) before it gets here.
+// the compare-exchange leaves (cswap_diff / _cross / _apply), the permuted row gather of a
+// shuffle step (perm_gather) and the prefix-sum leaves (scan, segscan_cross / _apply).  Each is
+// a share-wise kernel over slots whose geometry and sizes are checked on the host (img_geom.h,
+// cswap_geom.h, segscan_geom.h, mx_perm_gather) before it gets here.
 
 #include <hip/hip_runtime.h>
 
@@ -1005,9 +1006,262 @@ static int perm_gather_launch(const void* a, const void* b, const void* pl, cons
   return 0;
 }
 
+// The prefix-sum leaves (moosex.h mx_scan, mx_segscan_cross / _apply), on k_perm_gather's plan:
+// a rows x inner index space, a lane owns V adjacent inner elements of a row (V = 2 only for
+// u64 with an even inner extent and aligned buffers: every access is 16 bytes; u128 moves 16
+// bytes per lane as is, its carry between the limbs is the compiler's 128-bit add), adjacent
+// lanes are adjacent in memory, a lane strides over rows, slots are blockIdx.z, read at their
+// strides and written densely.  I: the index type, 32-bit when every extent is below 2^31.
+//
+// k_scan: a row is (o, chunk k) -- positions [k * kScanChunk, ...) of line o -- and the lane
+// walks them with the running sum in registers.  SUMS: the chunk's sum goes to sums[o, k, c].
+// Else the scan proper: the sum starts at off[o, k, c] (null: 0; the exclusive scan of the
+// chunk sums, in the same direction) and every position is written once.  The three phases
+// are three launches on one stream: no workgroup waits for another.
+template <class I>
+struct ScanP {
+  I x_slot, o_slot, s_slot;  // slot strides of x, out and the sums / offsets
+  I rows, chunks, n, inner;  // rows = outer * chunks
+  int excl, rev;
+};
+
+template <class T, class I, int V, bool SUMS>
+__global__ void __launch_bounds__(256) k_scan(const T* __restrict__ x, const T* __restrict__ off,
+                                              T* __restrict__ out, ScanP<I> p) {
+  using U = typename std::make_unsigned<I>::type;
+  using Vec = LaneVec<T, V>;
+  const unsigned by = blockDim.y;
+  const I c0 = ((I)blockIdx.x * (I)blockDim.x + (I)threadIdx.x) * V;
+  if (c0 >= p.inner) return;
+  const I z = (I)blockIdx.z;
+  const T* __restrict__ src = x + z * p.x_slot;
+  const T* __restrict__ so = off ? off + z * p.s_slot : nullptr;
+  T* __restrict__ dst = out + z * (SUMS ? p.s_slot : p.o_slot);
+  constexpr I chunk = (I)mxr::kScanChunk;
+  for (I row = (I)(blockIdx.y * by + threadIdx.y); row < p.rows; row += (I)(gridDim.y * by)) {
+    const I o = (I)((U)row / (U)p.chunks), k = row - o * p.chunks;
+    const I p0 = k * chunk, len = p.n - p0 < chunk ? p.n - p0 : chunk;
+    const I base = (o * p.n + p0) * p.inner + c0;
+    Vec acc;
+#pragma unroll
+    for (int e = 0; e < V; ++e) acc.v[e] = 0;
+    if constexpr (SUMS) {
+#pragma unroll 4
+      for (I t = 0; t < len; ++t) {
+        const Vec v = *reinterpret_cast<const Vec*>(src + base + t * p.inner);
+#pragma unroll
+        for (int e = 0; e < V; ++e) acc.v[e] += v.v[e];
+      }
+      *reinterpret_cast<Vec*>(dst + row * p.inner + c0) = acc;
+    } else {
+      if (so) acc = *reinterpret_cast<const Vec*>(so + row * p.inner + c0);
+      const I step = p.rev ? -p.inner : p.inner;
+      const I first = p.rev ? base + (len - 1) * p.inner : base;
+#pragma unroll 4
+      for (I t = 0; t < len; ++t) {
+        const I i = first + t * step;
+        const Vec v = *reinterpret_cast<const Vec*>(src + i);
+        Vec w = acc;
+#pragma unroll
+        for (int e = 0; e < V; ++e) acc.v[e] += v.v[e];
+        if (!p.excl) w = acc;
+        *reinterpret_cast<Vec*>(dst + i) = w;
+      }
+    }
+  }
+}
+
+// a block of bx x by lanes for a rows x inner space: lane_plan's, its rows halved down to one
+// wavefront while the grid would stay below 512 blocks (a long axis of few lines has few rows)
+static dim3 scan_block(const LanePlan& lp, int64_t rows, int64_t slots, int* by_out) {
+  int by = lp.by;
+  while (by > 1 && lp.bx * by > 64 && lp.tiles * ((rows + by - 1) / by) * slots < 512) by /= 2;
+  *by_out = by;
+  return dim3(lp.bx, by);
+}
+
+template <class T, class I, int V, bool SUMS>
+static int scan_launch(const void* x, const void* off, void* out, int64_t slots, int64_t x_slot,
+                       int64_t outer, int64_t n, int64_t inner, int excl, int rev,
+                       void* stream) {
+  const LanePlan lp = lane_plan(inner, V);
+  const int64_t chunks = (n + mxr::kScanChunk - 1) / mxr::kScanChunk, rows = outer * chunks;
+  ScanP<I> p;
+  p.x_slot = (I)x_slot, p.o_slot = (I)(outer * n * inner), p.s_slot = (I)(rows * inner);
+  p.rows = (I)rows, p.chunks = (I)chunks, p.n = (I)n, p.inner = (I)inner;
+  p.excl = excl, p.rev = rev;
+  int by;
+  const dim3 block = scan_block(lp, rows, slots, &by);
+  hipLaunchKernelGGL((k_scan<T, I, V, SUMS>),
+                     dim3((unsigned)lp.tiles, (unsigned)row_grid(rows, by), (unsigned)slots),
+                     block, 0, S(stream), (const T*)x, (const T*)off, (T*)out, p);
+  MX_LAUNCH_CHECK();
+  return 0;
+}
+
+// One level of the scan: an axis of one chunk in one launch; a longer one through its chunk
+// sums, which are scanned (exclusive, same direction) by this function again.  ws: this
+// level's sums and offsets, slots * outer * chunks * inner elements each, then the levels below.
+static int scan_level(int elem_bytes, const void* x, int64_t x_slot, void* out, char* ws,
+                      int64_t slots, int64_t outer, int64_t n, int64_t inner, int excl, int rev,
+                      void* stream) {
+  const int64_t chunks = (n + mxr::kScanChunk - 1) / mxr::kScanChunk;
+  const int64_t n_x = outer * n * inner, n_sum = outer * chunks * inner;
+  char* sums = ws;
+  char* offs = ws + slots * n_sum * elem_bytes;
+  const bool small = fits32(1 << 17, {(slots - 1) * x_slot + n_x, slots * n_x});
+  const bool two = inner % 2 == 0 && aligned16(x) && aligned16(out) && aligned16(ws) &&
+                   x_slot % 2 == 0;
+  auto phase = [&](bool sums_only, const void* off, void* dst) {
+    return leaf_dispatch(elem_bytes, small, two, [&](auto f) {
+      using F = decltype(f);
+      using T = typename F::T;
+      using I = typename F::I;
+      return sums_only ? scan_launch<T, I, F::V, true>(x, nullptr, dst, slots, x_slot, outer, n,
+                                                       inner, excl, rev, stream)
+                       : scan_launch<T, I, F::V, false>(x, off, dst, slots, x_slot, outer, n,
+                                                        inner, excl, rev, stream);
+    });
+  };
+  if (chunks <= 1) return phase(false, nullptr, out);
+  int rc = phase(true, nullptr, sums);
+  if (rc) return rc;
+  rc = scan_level(elem_bytes, sums, n_sum, offs, offs + slots * n_sum * elem_bytes, slots, outer,
+                  chunks, inner, 1, rev, stream);
+  if (rc) return rc;
+  return phase(false, offs, out);
+}
+
+// k_segscan_cross: a row is (o, pos - j) of the products; the flag of the row -- column
+// inner - 1 at pos -- is one load, the same for all lanes of the row.
+template <class I>
+struct SegscanP {
+  I a_slot, b_slot, o_slot;  // slot strides: state (cross: both components), products, output
+  I rows, n, nj, j, inner;   // nj = n - j
+};
+
+template <class T, class I, int V>
+__global__ void __launch_bounds__(256) k_segscan_cross(const T* __restrict__ a,
+                                                       const T* __restrict__ b,
+                                                       T* __restrict__ out, SegscanP<I> p) {
+  using U = typename std::make_unsigned<I>::type;
+  using Vec = LaneVec<T, V>;
+  const unsigned by = blockDim.y;
+  const I c0 = ((I)blockIdx.x * (I)blockDim.x + (I)threadIdx.x) * V;
+  if (c0 >= p.inner) return;
+  const I z = (I)blockIdx.z;
+  const T* __restrict__ sa = a + z * p.a_slot;
+  const T* __restrict__ sb = b ? b + z * p.a_slot : nullptr;
+  T* __restrict__ dst = out + z * p.o_slot;
+  for (I row = (I)(blockIdx.y * by + threadIdx.y); row < p.rows; row += (I)(gridDim.y * by)) {
+    const I o = (I)((U)row / (U)p.nj), t = row - o * p.nj;
+    const I ti = (o * p.n + t) * p.inner + c0;
+    const I fi = (o * p.n + t + p.j) * p.inner + p.inner - 1;
+    const T ga = sa[fi];
+    const Vec ta = *reinterpret_cast<const Vec*>(sa + ti);
+    Vec v;
+    if (sb) {
+      const T gb = sb[fi];
+      const Vec tb = *reinterpret_cast<const Vec*>(sb + ti);
+#pragma unroll
+      for (int e = 0; e < V; ++e) v.v[e] = ga * (ta.v[e] + tb.v[e]) + gb * ta.v[e];
+    } else {
+#pragma unroll
+      for (int e = 0; e < V; ++e) v.v[e] = ga * ta.v[e];
+    }
+    *reinterpret_cast<Vec*>(dst + row * p.inner + c0) = v;
+  }
+}
+
+// k_segscan_apply: a row is (o, pos) of the state; below j it is copied, from j on the values
+// take the product of pos - j and the flag column is replaced by it.
+template <class T, class I, int V>
+__global__ void __launch_bounds__(256) k_segscan_apply(const T* __restrict__ x,
+                                                       const T* __restrict__ pr,
+                                                       T* __restrict__ out, SegscanP<I> p) {
+  using U = typename std::make_unsigned<I>::type;
+  using Vec = LaneVec<T, V>;
+  const unsigned by = blockDim.y;
+  const I c0 = ((I)blockIdx.x * (I)blockDim.x + (I)threadIdx.x) * V;
+  if (c0 >= p.inner) return;
+  const I z = (I)blockIdx.z;
+  const T* __restrict__ src = x + z * p.a_slot;
+  const T* __restrict__ q = pr + z * p.b_slot;
+  T* __restrict__ dst = out + z * p.o_slot;
+  for (I row = (I)(blockIdx.y * by + threadIdx.y); row < p.rows; row += (I)(gridDim.y * by)) {
+    const I o = (I)((U)row / (U)p.n), pos = row - o * p.n;
+    const I si = row * p.inner + c0;
+    Vec v = *reinterpret_cast<const Vec*>(src + si);
+    if (pos >= p.j) {
+      const Vec w = *reinterpret_cast<const Vec*>(q + (o * p.nj + pos - p.j) * p.inner + c0);
+#pragma unroll
+      for (int e = 0; e < V; ++e) v.v[e] = c0 + e == p.inner - 1 ? w.v[e] : v.v[e] + w.v[e];
+    }
+    *reinterpret_cast<Vec*>(dst + si) = v;
+  }
+}
+
+template <class I>
+static SegscanP<I> segscan_params(const mxr::SegscanGeom& g, int64_t a_slot, int64_t b_slot,
+                                  int64_t o_slot, int64_t rows) {
+  SegscanP<I> p;
+  p.a_slot = (I)a_slot, p.b_slot = (I)b_slot, p.o_slot = (I)o_slot, p.rows = (I)rows;
+  p.n = (I)g.n, p.nj = (I)(g.n - g.j), p.j = (I)g.j, p.inner = (I)g.inner;
+  return p;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mxh_scan(int elem_bytes, const void* x, void* out, void* ws, int64_t slots,
+             int64_t x_slot_stride, const mxr::ScanGeom& g, void* stream) {
+  if (slots > 65535) return -3;
+  return scan_level(elem_bytes, x, x_slot_stride, out, (char*)ws, slots, g.outer, g.n, g.inner,
+                    g.exclusive, g.reverse, stream);
+}
+
+int mxh_segscan_cross(int elem_bytes, const void* a, const void* b, void* out, int64_t slots,
+                      int64_t slot_stride, const mxr::SegscanGeom& g, void* stream) {
+  if (slots > 65535) return -3;
+  const bool small = fits32(1 << 17, {(slots - 1) * slot_stride + g.n_x, slots * g.n_p});
+  const bool two = g.inner % 2 == 0 && aligned16(a) && aligned16(b) && aligned16(out) &&
+                   slot_stride % 2 == 0;
+  const int64_t rows = g.outer * (g.n - g.j);
+  return leaf_dispatch(elem_bytes, small, two, [&](auto f) {
+    using F = decltype(f);
+    using T = typename F::T;
+    const LanePlan lp = lane_plan(g.inner, F::V);
+    const auto p = segscan_params<typename F::I>(g, slot_stride, 0, g.n_p, rows);
+    hipLaunchKernelGGL((k_segscan_cross<T, typename F::I, F::V>),
+                       dim3((unsigned)lp.tiles, (unsigned)row_grid(rows, lp.by), (unsigned)slots),
+                       dim3(lp.bx, lp.by), 0, S(stream), (const T*)a, (const T*)b, (T*)out, p);
+    MX_LAUNCH_CHECK();
+    return 0;
+  });
+}
+
+int mxh_segscan_apply(int elem_bytes, const void* x, const void* pr, void* out, int64_t slots,
+                      int64_t x_slot_stride, int64_t p_slot_stride, const mxr::SegscanGeom& g,
+                      void* stream) {
+  if (slots > 65535) return -3;
+  const bool small = fits32(1 << 17, {(slots - 1) * x_slot_stride + g.n_x,
+                                      (slots - 1) * p_slot_stride + g.n_p, slots * g.n_x});
+  const bool two = g.inner % 2 == 0 && aligned16(x) && aligned16(pr) && aligned16(out) &&
+                   x_slot_stride % 2 == 0 && p_slot_stride % 2 == 0;
+  const int64_t rows = g.outer * g.n;
+  return leaf_dispatch(elem_bytes, small, two, [&](auto f) {
+    using F = decltype(f);
+    using T = typename F::T;
+    const LanePlan lp = lane_plan(g.inner, F::V);
+    const auto p = segscan_params<typename F::I>(g, x_slot_stride, p_slot_stride, g.n_x, rows);
+    hipLaunchKernelGGL((k_segscan_apply<T, typename F::I, F::V>),
+                       dim3((unsigned)lp.tiles, (unsigned)row_grid(rows, lp.by), (unsigned)slots),
+                       dim3(lp.bx, lp.by), 0, S(stream), (const T*)x, (const T*)pr, (T*)out, p);
+    MX_LAUNCH_CHECK();
+    return 0;
+  });
+}
 
 int mxh_perm_gather(int elem_bytes, const void* a, const void* b, const void* p, const void* m,
                     const int64_t* perm, void* out, int64_t slots, int64_t a_slot_stride,

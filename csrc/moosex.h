@@ -192,6 +192,39 @@ int mx_perm_gather(int dev, int elem_bytes, const void* a, const void* b, const 
                    const void* m, const int64_t* perm, void* out, int64_t slots,
                    int64_t a_slot_stride, int64_t b_slot_stride, int64_t p_slot_stride,
                    int64_t m_slot_stride, int64_t outer, int64_t n, int64_t inner, void* stream);
+// Prefix sum in Z_2^64 / Z_2^128 (elem_bytes 8 / 16), wrapping, along the middle axis of an
+// [outer, n, inner] array per slot (segscan_geom.h):
+//   out[o, pos, c] = sum of x[o, t, c] over t <= pos (exclusive: t < pos, the first element 0);
+//   reverse: over t >= pos (t > pos), from the far end
+// A lane walks up to mx_scan_chunk() positions with the running sum in registers; a longer
+// axis takes three phases -- the sums of every chunk, this entry again on the sums, an add
+// pass -- in `ws`, a buffer of the caller's with at least mx_scan_ws_elems(slots, outer, n,
+// inner) elements (0 for an axis of one chunk; -3 where it is smaller).  No workgroup waits
+// for another.  Input slots are x_slot_stride elements apart (views of a larger buffer are
+// read in place), output slots are dense; out must not overlap x.
+int64_t mx_scan_chunk(void);
+int64_t mx_scan_ws_elems(int64_t slots, int64_t outer, int64_t n, int64_t inner);
+int mx_scan(int dev, int elem_bytes, const void* x, void* out, void* ws, int64_t ws_elems,
+            int64_t slots, int64_t x_slot_stride, int64_t outer, int64_t n, int64_t inner,
+            int exclusive, int reverse, void* stream);
+// One stage j (1 <= j < n, any n) of a segmented Hillis-Steele prefix sum over a state
+// [outer, n, inner] per slot whose last column is the continuation flag g and whose other
+// columns are values.
+//   mx_segscan_cross: one party's local products with its own component a and the next one b,
+//                     out[o, pos - j, c] = ga*(Ta + Tb) + gb*Ta for pos in [j, n) and every c,
+//                     ga = a[o, pos, inner-1], gb = b[o, pos, inner-1], Ta = a[o, pos-j, c],
+//                     Tb = b[o, pos-j, c]: [outer, n - j, inner].  b == null: plain, ga*Ta.
+//                     a and b share slot_stride
+//   mx_segscan_apply: out[o, pos, c] = x[o, pos, c] + p[o, pos-j, c] for c < inner-1,
+//                     out[o, pos, inner-1] = p[o, pos-j, inner-1] for pos >= j; out = x below j
+// Ring-linear: the flag is any ring value.  Input slots are *_slot_stride elements apart,
+// output slots are dense.
+int mx_segscan_cross(int dev, int elem_bytes, const void* a, const void* b, void* out,
+                     int64_t slots, int64_t slot_stride, int64_t outer, int64_t n,
+                     int64_t inner, int64_t j, void* stream);
+int mx_segscan_apply(int dev, int elem_bytes, const void* x, const void* p, void* out,
+                     int64_t slots, int64_t x_slot_stride, int64_t p_slot_stride, int64_t outer,
+                     int64_t n, int64_t inner, int64_t j, void* stream);
 // mx_ew_binary_slot on a0 (slot which0) and a1 (slot which1) with one public b
 int mx_ew_binary_slot2(int dev, int op, int words, const void* a0, const void* a1,
                        const void* b, int64_t nb, void* out0, void* out1, int64_t m,

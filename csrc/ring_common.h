@@ -6,6 +6,7 @@
 #include "aes_core.h"
 #include "cswap_geom.h"
 #include "img_geom.h"
+#include "segscan_geom.h"
 #include "moosex.h"
 
 namespace mxr {
@@ -310,6 +311,15 @@ int mxh_perm_gather(int elem_bytes, const void* a, const void* b, const void* p,
                     const int64_t* perm, void* out, int64_t slots, int64_t a_slot_stride,
                     int64_t b_slot_stride, int64_t p_slot_stride, int64_t m_slot_stride,
                     int64_t outer, int64_t n, int64_t inner, void* stream);
+// the prefix-sum leaves: g is validated and filled by scan_geom_check / segscan_geom_check
+// (segscan_geom.h); ws holds slots * g.ws elements (mx_scan checked it)
+int mxh_scan(int elem_bytes, const void* x, void* out, void* ws, int64_t slots,
+             int64_t x_slot_stride, const mxr::ScanGeom& g, void* stream);
+int mxh_segscan_cross(int elem_bytes, const void* a, const void* b, void* out, int64_t slots,
+                      int64_t slot_stride, const mxr::SegscanGeom& g, void* stream);
+int mxh_segscan_apply(int elem_bytes, const void* x, const void* p, void* out, int64_t slots,
+                      int64_t x_slot_stride, int64_t p_slot_stride, const mxr::SegscanGeom& g,
+                      void* stream);
 int mxh_ks_cross1(int words, const void* g0, const void* g1, const void* p0, const void* p1,
                   void* z, int64_t n, int d, int both, const uint8_t* keys16, uint64_t nonce,
                   void* stream);

@@ -109,6 +109,9 @@ from moose_amd.edsl.base import swish  # noqa: F401
 from moose_amd.edsl.base import relu6  # noqa: F401
 from moose_amd.edsl.base import tanh  # noqa: F401
 from moose_amd.edsl.base import thresholded_relu  # noqa: F401
+from moose_amd.edsl.base import cumsum  # noqa: F401
+from moose_amd.edsl.base import group_by_count  # noqa: F401
+from moose_amd.edsl.base import group_by_sum  # noqa: F401
 from moose_amd.edsl.base import median  # noqa: F401
 from moose_amd.edsl.base import quantile  # noqa: F401
 from moose_amd.edsl.base import sample_rows  # noqa: F401

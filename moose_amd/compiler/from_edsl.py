@@ -103,6 +103,17 @@ _OPS = {
         lambda o: {"axis": int(o.axis), "descending": bool(o.descending), "by": int(o.by)},
     ),
     "ShuffleOperation": ("Shuffle", ["x"], lambda o: {"axis": int(o.axis)}),
+    "CumSumOperation": (
+        "CumSum",
+        ["x"],
+        lambda o: {"axis": int(o.axis), "exclusive": bool(o.exclusive),
+                   "reverse": bool(o.reverse)},
+    ),
+    "GroupBySumOperation": (
+        "GroupBySum",
+        ["x"],
+        lambda o: {"by": int(o.by), "count": bool(o.count), "shuffle": bool(o.shuffle)},
+    ),
     "PiecewiseLinearOperation": (
         "PiecewiseLinear",
         ["x"],

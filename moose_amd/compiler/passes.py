@@ -73,7 +73,7 @@ def typing_pass(comp: Computation, **_) -> Computation:
 
 _SAME_SHAPE_OPS = {"Cast", "Identity", "Relu", "Sigmoid", "Abs", "Neg", "Exp", "Sqrt", "Log",
                    "Log2", "Softmax", "Share", "Reveal", "PiecewiseLinear", "Sort",
-                   "PiecewisePolynomial", "Shuffle", "PermGather", "PermFromKeys"}
+                   "PiecewisePolynomial", "Shuffle", "PermGather", "PermFromKeys", "CumSum"}
 
 
 def _static_shape(op, shapes):
@@ -101,6 +101,10 @@ def _static_shape(op, shapes):
             return
         elif kind in _SAME_SHAPE_OPS:
             shp = ins[0]
+        elif kind == "GroupBySum":
+            if len(ins[0]) != 2:
+                raise ValueError(f"expects a rank-2 table, found shape {ins[0]}")
+            shp = (ins[0][0], ins[0][1] + int(bool(a.get("count", False))) + 1)
         elif kind == "Transpose":
             shp = ins[0][::-1]
         elif kind == "Permute":

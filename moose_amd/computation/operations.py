@@ -94,6 +94,8 @@ OPERATION_TABLE = [
     ("PiecewisePolynomialOperation", ["breakpoints", "coefficients", "degree"]),
     ("SortOperation", ["axis", "descending", "by"]),
     ("ShuffleOperation", ["axis"]),
+    ("CumSumOperation", ["axis", "exclusive", "reverse"]),
+    ("GroupBySumOperation", ["by", "count", "shuffle"]),
 ]
 
 OPERATION_CLASSES = {}

@@ -1029,6 +1029,78 @@ def sort_rows(x, by=0, descending=False, placement=None):
     return e
 
 
+def _not_bits(fn, x):
+    d = x.vtype.dtype if isinstance(x, Expression) and isinstance(x.vtype, ty.TensorType) \
+        else None
+    if d is None or d.is_boolean:
+        raise ValueError(f"`{fn}` expects a float or fixed-point tensor (bit tensors are not "
+                         f"supported), found {getattr(x, 'vtype', type(x))}")
+
+
+def cumsum(x, axis=0, exclusive=False, reverse=False, placement=None):
+    """Prefix sums of ``x`` along ``axis``: element i holds the sum of the elements up to and
+    including i (``exclusive``: before i, so the first is 0; ``reverse``: counted from the far
+    end).  On a host placement floats go through torch and fixed-point tensors through the
+    ring scan; on a replicated placement a secret fixed-point ``x`` is summed locally on its
+    shares -- no communication, exact."""
+    _not_bits("cumsum", x)
+    axis = _sort_axis("cumsum", axis, x.static_shape)
+    e = _expr("cumsum", [x], x.vtype, placement, axis=axis, exclusive=bool(exclusive),
+              reverse=bool(reverse))
+    e.static_shape = x.static_shape
+    return e
+
+
+def group_by_sum(x, by=0, count=False, shuffle=True, placement=None, input_shape=None):
+    """Group the rows of the rank-2 table ``x`` [n, c] by column ``by`` and sum every other
+    column per key.  The result is [n, c + count + 1] in key order: the last row of each group
+    holds the key, the column sums over the group (in the columns' order, then the group's size
+    where ``count``) and ``valid = 1.0``; every other row is all zeros.
+
+    On a replicated placement the key and the values stay secret: a sort by the key, one sign
+    extraction for the group boundaries, a segmented prefix sum of ceil(log2 n)
+    multiplications and one more multiplication, exact.  ``shuffle=True`` then reorders the
+    rows obliviously (every evaluation draws a fresh order; such a program is not replayed).
+    On a host placement the same table is computed in the clear, never shuffled.
+
+    Limits: opening the table reveals the number of groups; without the shuffle the positions
+    of the valid rows reveal the group sizes too.  ``sort_rows``' condition on the keys
+    applies (strictly inside the fixed-point type's range), and the sums grow past the nominal
+    integral width as those of ``mul`` and ``dot`` do.  Needs the static shape of ``x``: a
+    ``shape=`` on the pm.Argument, or ``input_shape=``."""
+    fn = "group_by_sum"
+    _not_bits(fn, x)
+    if isinstance(by, bool) or not isinstance(by, (int, np.integer)) or by < 0:
+        raise ValueError(f"`{fn}`: `by` must be a column index, found {by!r}")
+    shape = _sort_shape(fn, x, input_shape, need=True)
+    if len(shape) != 2 or shape[1] is None or not by < shape[1]:
+        raise ValueError(f"`{fn}` expects a rank-2 tensor with more than {by} columns, found "
+                         f"shape {shape}")
+    e = _expr("group_by_sum", [x], x.vtype, placement, by=int(by), count=bool(count),
+              shuffle=bool(shuffle))
+    e.static_shape = (shape[0], shape[1] + int(bool(count)) + 1)
+    return e
+
+
+def group_by_count(x, by=0, shuffle=True, placement=None, input_shape=None):
+    """The size of every group of rows of the rank-2 ``x`` with equal values in column ``by``:
+    [n, 3] in key order, the last row of each group holding (key, count, valid = 1.0), every
+    other row zero -- :func:`group_by_sum` of the key column alone with ``count=True``."""
+    fn = "group_by_count"
+    try:
+        _not_bits(fn, x)
+        shape = _sort_shape(fn, x, input_shape, need=True)
+        if isinstance(by, bool) or not isinstance(by, (int, np.integer)) or by < 0 \
+                or len(shape) != 2 or shape[1] is None or not by < shape[1]:
+            raise ValueError(f"`{fn}` expects a rank-2 tensor and a column index `by` inside "
+                             f"it, found shape {shape} and by = {by!r}")
+        key = strided_slice(x, [slice(None), slice(int(by), int(by) + 1)], placement)
+        key.static_shape = (shape[0], 1)
+        return group_by_sum(key, 0, True, shuffle, placement)
+    except ValueError as e:
+        raise ValueError(str(e).replace("`group_by_sum`", f"`{fn}`")) from None
+
+
 def top_k(x, k, axis=-1, largest=True, placement=None, input_shape=None):
     """The ``k`` largest (``largest=False``: smallest) values along ``axis``, sorted from the
     extreme inwards: a sort and a slice.  A negative ``axis`` needs the rank of ``x`` (a

@@ -71,6 +71,8 @@ _OPS = {
                              ["breakpoints", "coefficients", "degree"]),
     "sort": ("SortOperation", ["x"], "sort", ["axis", "descending", "by"]),
     "shuffle": ("ShuffleOperation", ["x"], "shuffle", ["axis"]),
+    "cumsum": ("CumSumOperation", ["x"], "cumsum", ["axis", "exclusive", "reverse"]),
+    "group_by_sum": ("GroupBySumOperation", ["x"], "group_by_sum", ["by", "count", "shuffle"]),
     "shape": ("ShapeOperation", ["x"], "shape", []),
     "mux": ("MuxOperation", ["selector", "x", "y"], "mux", []),
     "load": ("LoadOperation", ["key", "query"], "load", []),

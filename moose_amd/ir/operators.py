@@ -184,6 +184,15 @@ EXTENSION_OPERATORS = {
     # fused with the step's sums -- inputs (a, perm, then the optional operands `form` names:
     # b gathered and added, p added in place, m subtracted in place)
     "PermFromKeys": [],
+    # prefix sums along `axis` (exclusive: of the elements before each one; reverse: from the
+    # far end).  Linear: on a secret fixed-point x a local kernel on every share component
+    "CumSum": [("axis", "int"), ("exclusive", "bool"), ("reverse", "bool")],
+    # group the rows of a rank-2 table [n, c] by column `by` and sum the other columns per
+    # key: [n, c + count + 1] in key order, the last row of each group holding (key, sums...,
+    # the group's size if `count`, valid = 1), every other row zero; `shuffle` reorders the
+    # rows obliviously at the end.  On a secret x: a sort, one sign extraction, a segmented
+    # scan of ceil(log2 n) multiplications and one more multiplication, exact
+    "GroupBySum": [("by", "int"), ("count", "bool"), ("shuffle", "bool")],
     "PermGather": [("axis", "int"), ("form", "str")],
 }
 

@@ -63,6 +63,19 @@ _SIGS = {
                        + [c_vp]),
     # (dev, elem_bytes, a b p m perm out, slots, a b p m slot strides, outer n inner, stream)
     "mx_perm_gather": (c_int, [c_int, c_int] + [c_vp] * 6 + [c_i64] * 5 + [c_i64] * 3 + [c_vp]),
+    "mx_scan_chunk": (c_i64, []),
+    # (slots, outer, n, inner)
+    "mx_scan_ws_elems": (c_i64, [c_i64] * 4),
+    # (dev, elem_bytes, x out ws, ws_elems, slots, x_slot_stride, outer n inner, exclusive,
+    #  reverse, stream)
+    "mx_scan": (c_int, [c_int, c_int] + [c_vp] * 3 + [c_i64] * 3 + [c_i64] * 3 + [c_int] * 2
+                + [c_vp]),
+    # (dev, elem_bytes, a b out, slots, slot_stride, outer n inner j, stream)
+    "mx_segscan_cross": (c_int, [c_int, c_int] + [c_vp] * 3 + [c_i64] * 2 + [c_i64] * 4
+                         + [c_vp]),
+    # (dev, elem_bytes, x p out, slots, x_slot_stride, p_slot_stride, outer n inner j, stream)
+    "mx_segscan_apply": (c_int, [c_int, c_int] + [c_vp] * 3 + [c_i64] * 3 + [c_i64] * 4
+                         + [c_vp]),
     # (dev, elem_bytes, x0 x1 w0 w1 out, slots, x_slot_stride, w_slot_stride, N C H W mult,
     #  KH KW, sh sw, pt pl, dh dw, OH OW, nhwc, stream)
     "mx_dwconv": (c_int, [c_int, c_int] + [c_vp] * 5 + [c_i64] * 3 + [c_i64] * 15

@@ -1868,6 +1868,245 @@ def perm_gather(a: RT, perm, b=None, plus=None, minus=None, axis=0, nb=0) -> RT:
     return out
 
 
+# ---------------------------------------------------------------------------
+# prefix sums: the plain scan and the stages of a segmented scan
+# ---------------------------------------------------------------------------
+# the device path of scan, and of segscan_cross / segscan_apply: the native kernels (True) or
+# the torch compositions *_torch (False); a CPU tensor always takes the native loops
+SCAN_KERNEL = True
+SEGSCAN_KERNEL = True
+# positions of the axis one lane walks with the running sum in registers (csrc/segscan_geom.h
+# kScanChunk, mx_scan_chunk()); a longer axis takes three phases and a workspace
+SCAN_CHUNK = 256
+
+
+class ScanGeom(NamedTuple):
+    """A prefix sum along the middle axis of an [outer, n, inner] array
+    (csrc/segscan_geom.h): element (o, pos, c) lives at (o*n + pos)*inner + c."""
+
+    outer: int
+    n: int
+    inner: int
+    exclusive: bool = False
+    reverse: bool = False
+
+
+class SegscanGeom(NamedTuple):
+    """Stage ``j`` (1 <= j < n, any n) of a segmented Hillis-Steele scan over a state
+    [outer, n, inner] whose last column is the continuation flag (csrc/segscan_geom.h)."""
+
+    outer: int
+    n: int
+    inner: int
+    j: int = 1
+
+
+def segscan_stages(n: int):
+    """The offsets j = 1, 2, 4, ... < n of a segmented scan over n positions: ceil(log2 n)."""
+    out, j = [], 1
+    while j < n:
+        out.append(j)
+        j *= 2
+    return out
+
+
+def scan_ws_elems(slots: int, outer: int, n: int, inner: int) -> int:
+    """Elements of the workspace :func:`scan` hands the native entry (mx_scan_ws_elems): the
+    sums and the offsets of every level of chunks, 0 for an axis of one chunk."""
+    ws = 0
+    while n > SCAN_CHUNK:
+        n = -(-n // SCAN_CHUNK)
+        ws += 2 * outer * inner * n
+    return slots * ws
+
+
+def _scan_check(what, g, nb, x: RT, others=()):
+    bits = x.bits
+    if bits not in (64, 128) or any(t.bits != bits for t, _ in others if t is not None):
+        raise ValueError(f"{what} is arithmetic only: operands over one of Z_2^64 / Z_2^128")
+    if nb not in (0, 1):
+        raise ValueError(f"{what} takes at most one batch dim")
+    lead = tuple(x.shape[:nb])
+    if math.prod(x.shape[nb:]) != g.outer * g.n * g.inner:
+        raise ValueError(f"{what}: operand of shape {tuple(x.shape)} does not hold "
+                         f"{g.outer} x {g.n} x {g.inner} elements after {nb} batch dims")
+    for t, want in others:
+        if t is not None and (tuple(t.shape[:nb]) != lead or math.prod(t.shape[nb:]) != want):
+            raise ValueError(f"{what}: operand of shape {tuple(t.shape)}, expected {want} "
+                             f"elements after the batch dims {lead}")
+    return bits, lead
+
+
+def _scan_geom(g) -> ScanGeom:
+    g = ScanGeom(*g)
+    g = ScanGeom(int(g.outer), int(g.n), int(g.inner), bool(g.exclusive), bool(g.reverse))
+    if g.outer < 0 or g.n < 0 or g.inner < 0:
+        raise ValueError(f"scan: malformed geometry {g}")
+    return g
+
+
+def _segscan_geom(what, g) -> SegscanGeom:
+    g = SegscanGeom(*(int(v) for v in SegscanGeom(*g)))
+    if g.outer < 0 or g.inner < 0 or g.j < 1 or not g.j < g.n:
+        raise ValueError(f"{what}: malformed stage {g}")
+    return g
+
+
+def scan_torch(x: RT, g: ScanGeom, nb=0) -> RT:
+    """:func:`scan` as a torch composition: ``torch.cumsum`` on the int64 view for Z_2^64 (it
+    wraps as the ring does); for Z_2^128, whose two words cumsum cannot carry between,
+    Hillis-Steele steps of ``binary("add")`` on slices.  The benchmark's opponent."""
+    g = _scan_geom(g)
+    bits, lead = _scan_check("scan", g, nb, x)
+    if x.data.numel() == 0:
+        return RT(x.data.clone(), bits)
+    v = reshape(x, (g.outer, g.n, g.inner), nb)
+    ax = nb + 1
+    if bits == 64:
+        d = v.data.flip(ax) if g.reverse else v.data
+        c = torch.cumsum(d, dim=ax)
+        if g.exclusive:
+            c = c - d
+        out = RT((c.flip(ax) if g.reverse else c).contiguous(), 64)
+    else:
+        acc, d, n = v, 1, g.n
+        while d < n:
+            lo, hi = slice_axis(acc, 1, 0, n - d, nb=nb), slice_axis(acc, 1, d, n, nb=nb)
+            s = binary("add", lo, hi)
+            if g.reverse:
+                acc = concat([s, slice_axis(acc, 1, n - d, n, nb=nb)], 1, nb)
+            else:
+                acc = concat([slice_axis(acc, 1, 0, d, nb=nb), s], 1, nb)
+            d *= 2
+        out = binary("sub", acc, v.contiguous()) if g.exclusive else acc
+    return reshape(out, x.shape[nb:], nb)
+
+
+def scan(x: RT, g: ScanGeom, nb=0) -> RT:
+    """The prefix sums of ``x`` seen as [.., outer, n, inner] along the middle axis, wrapping
+    in the ring, in ``x``'s shape: ``out[o, pos, c]`` is the sum of ``x[o, t, c]`` over ``t <=
+    pos`` (``exclusive``: ``t < pos``, the first element 0; ``reverse``: from the far end).
+    One native entry over all batch slots (``mx_scan``); a [slots, ...] view with dense slots
+    is read in place.  An axis of up to ``SCAN_CHUNK`` positions is one launch; a longer one
+    takes the sums of its chunks, their scan and an add pass, in a workspace allocated here."""
+    g = _scan_geom(g)
+    bits, lead = _scan_check("scan", g, nb, x)
+    shape = tuple(x.shape)
+    if x.device.type == "meta":  # shape inference of the symbolic session
+        return empty(shape, bits, x.device)
+    if x.device.type == "cuda" and not SCAN_KERNEL:
+        return scan_torch(x, g, nb)
+    out = empty(shape, bits, x.device)
+    if out.data.numel() == 0:
+        return out
+    slots = math.prod(lead)
+    xd, xst = _leaf_operand(x, nb, g.outer * g.n * g.inner)
+    nws = scan_ws_elems(slots, g.outer, g.n, g.inner)
+    ws = empty((nws,), bits, x.device) if nws else None
+    nat.check(
+        nat.lib().mx_scan(nat.dev_of(out.data), _elem_bytes(bits), nat.ptr(xd),
+                          nat.ptr(out.data), nat.ptr(ws.data) if nws else None, nws, slots, xst,
+                          g.outer, g.n, g.inner, int(g.exclusive), int(g.reverse),
+                          nat.stream_of(out.data)),
+        "scan",
+    )
+    return out
+
+
+def _segscan_flag(t: RT, g: SegscanGeom, nb):
+    """The flag column of positions [j, n), [.., outer, n - j, 1], and the state of positions
+    [0, n - j), [.., outer, n - j, inner]."""
+    v = reshape(t, (g.outer, g.n, g.inner), nb)
+    flag = slice_axis(slice_axis(v, 1, g.j, g.n, nb=nb), 2, g.inner - 1, g.inner, nb=nb)
+    return flag, slice_axis(v, 1, 0, g.n - g.j, nb=nb)
+
+
+def segscan_cross_torch(a: RT, b, g: SegscanGeom, nb=0) -> RT:
+    """:func:`segscan_cross` as a composition of the existing kernels."""
+    g = _segscan_geom("segscan_cross", g)
+    _scan_check("segscan_cross", g, nb, a, ((b, g.outer * g.n * g.inner),))
+    ga, ta = _segscan_flag(a, g, nb)
+    if b is None:
+        return binary("mul", ga, ta)
+    gb, tb = _segscan_flag(b, g, nb)
+    return binary("add", binary("mul", ga, binary("add", ta, tb)), binary("mul", gb, ta))
+
+
+def segscan_apply_torch(x: RT, p: RT, g: SegscanGeom, nb=0) -> RT:
+    """:func:`segscan_apply` as a composition of the existing kernels."""
+    g = _segscan_geom("segscan_apply", g)
+    _scan_check("segscan_apply", g, nb, x, ((p, g.outer * (g.n - g.j) * g.inner),))
+    v = reshape(x, (g.outer, g.n, g.inner), nb)
+    pp = reshape(p, (g.outer, g.n - g.j, g.inner), nb)
+    tail = slice_axis(pp, 2, g.inner - 1, g.inner, nb=nb)
+    if g.inner > 1:
+        hi = slice_axis(slice_axis(v, 1, g.j, g.n, nb=nb), 2, 0, g.inner - 1, nb=nb)
+        vals = binary("add", hi, slice_axis(pp, 2, 0, g.inner - 1, nb=nb))
+        tail = concat([vals, tail], 2, nb)
+    out = concat([slice_axis(v, 1, 0, g.j, nb=nb), tail], 1, nb)
+    return reshape(out, x.shape[nb:], nb)
+
+
+def segscan_cross(a: RT, b, g: SegscanGeom, nb=0) -> RT:
+    """One party's local products of stage ``g`` of a segmented scan, with its own component
+    ``a`` of the state and the next party's ``b``: for ``pos`` in [j, n) and every column,
+    ``ga * (Ta + Tb) + gb * Ta`` with ``g*`` the flag column at ``pos`` and ``T*`` the state
+    at ``pos - j`` (own times the sum plus next times own, as :func:`cswap_cross`), as
+    [.., outer, n - j, inner].  ``b = None``: the plain form ``ga * Ta``.  One native launch
+    over all batch slots (``mx_segscan_cross``); the stage travels in its arguments."""
+    g = _segscan_geom("segscan_cross", g)
+    bits, lead = _scan_check("segscan_cross", g, nb, a, ((b, g.outer * g.n * g.inner),))
+    shape = lead + (g.outer, g.n - g.j, g.inner)
+    if a.device.type == "meta":
+        return empty(shape, bits, a.device)
+    if a.device.type == "cuda" and not SEGSCAN_KERNEL:
+        return segscan_cross_torch(a, b, g, nb)
+    out = empty(shape, bits, a.device)
+    if out.data.numel() == 0:
+        return out
+    nx = g.outer * g.n * g.inner
+    ad, st = _leaf_operand(a, nb, nx)
+    bd = None
+    if b is not None:
+        bd, bst = _leaf_operand(b, nb, nx)
+        ad, bd, st = _leaf_pair(ad, st, bd, bst, nx)
+    nat.check(
+        nat.lib().mx_segscan_cross(nat.dev_of(out.data), _elem_bytes(bits), nat.ptr(ad),
+                                   nat.ptr(bd) if bd is not None else None, nat.ptr(out.data),
+                                   math.prod(lead), st, g.outer, g.n, g.inner, g.j,
+                                   nat.stream_of(out.data)),
+        "segscan_cross",
+    )
+    return out
+
+
+def segscan_apply(x: RT, p: RT, g: SegscanGeom, nb=0) -> RT:
+    """The update of stage ``g``: from position j on, the value columns of the state ``x`` take
+    the products ``p`` [.., outer, n - j, inner] of position ``pos - j`` and the flag column is
+    replaced by its product; positions below j are copied.  In ``x``'s shape.  One native
+    launch over all batch slots (``mx_segscan_apply``)."""
+    g = _segscan_geom("segscan_apply", g)
+    bits, lead = _scan_check("segscan_apply", g, nb, x,
+                             ((p, g.outer * (g.n - g.j) * g.inner),))
+    shape = tuple(x.shape)
+    if x.device.type == "meta":
+        return empty(shape, bits, x.device)
+    if x.device.type == "cuda" and not SEGSCAN_KERNEL:
+        return segscan_apply_torch(x, p, g, nb)
+    out = empty(shape, bits, x.device)
+    if out.data.numel() == 0:
+        return out
+    xd, xst = _leaf_operand(x, nb, g.outer * g.n * g.inner)
+    pd, pst = _leaf_operand(p, nb, g.outer * (g.n - g.j) * g.inner)
+    nat.check(
+        nat.lib().mx_segscan_apply(nat.dev_of(out.data), _elem_bytes(bits), nat.ptr(xd),
+                                   nat.ptr(pd), nat.ptr(out.data), math.prod(lead), xst, pst,
+                                   g.outer, g.n, g.inner, g.j, nat.stream_of(out.data)),
+        "segscan_apply",
+    )
+    return out
+
+
 def select_mask(a: RT, axis: int, mask: torch.Tensor, nb=0) -> RT:
     ax = _ax(a, axis, nb)
     keep = torch.nonzero(mask.reshape(-1).to(torch.bool)).reshape(-1).to(a.device)

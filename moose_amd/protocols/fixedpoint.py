@@ -741,6 +741,81 @@ def shuffle(sess, x: RepFixed, axis: int = 0) -> RepFixed:
     return _with(x, rep.shuffle(sess, x.t, axis))
 
 
+def cumsum(sess, x: RepFixed, axis: int = 0, exclusive: bool = False,
+           reverse: bool = False) -> RepFixed:
+    """Prefix sums of ``x`` along ``axis`` (rep.cumsum: local, exact); the precision is
+    unchanged, and the sums may grow past the nominal integral width as any sum does."""
+    return _with(x, rep.cumsum(sess, x.t, axis, exclusive, reverse))
+
+
+def group_by_sum(sess, x: RepFixed, by: int = 0, count: bool = False,
+                 shuffle: bool = True) -> RepFixed:
+    """Group the rows of the table ``x`` [n, c] by the secret key column ``by`` and sum the
+    other columns per key.  The result is a table [n, c + count + 1] in key order: the LAST row
+    of every group holds the key, the sums of the non-key columns over the group (in their
+    order), the group's size where ``count``, and ``valid = 1.0``; every other row is all
+    zeros.  ``shuffle`` reorders the rows obliviously at the end (rep.shuffle).
+
+    Steps: sort by the key (fixedpoint.sort); the keys are then non-decreasing, so ``key[i] ==
+    key[i-1]`` iff ``key[i] - key[i-1] - 1 < 0`` -- one sign extraction gives the continuation
+    flags g, with ``g[0] = 0`` public; rep.segmented_scan of the values under g; ``last[i] = 1
+    - g[i+1]`` (a local shift, ``last[n-1] = 1``); one replicated multiplication of ``last``
+    with [key, sums].  The flags are the integers 0 / 1, so nothing truncates and the opened
+    table is exact.
+
+    Limits: opening the table reveals the number of groups; without the shuffle the positions
+    of the valid rows reveal the group sizes as well.  sort's condition applies: a key equal
+    to the largest encodable value may change places with the network's padding.  The sums
+    grow past the nominal integral width, as those of ``mul`` and ``dot`` do: the caller keeps
+    them inside the ring."""
+    shape = tuple(shape_of(sess, x))
+    if len(shape) != 2 or isinstance(by, bool) or not isinstance(by, int) \
+            or not 0 <= by < shape[1]:
+        raise ValueError(f"group_by_sum: by={by!r} takes a rank-2 table with more than {by} "
+                         f"columns, found shape {shape}")
+    n, c = shape
+    w = check_sort_width(x.integ, x.frac, x.bits, "group_by_sum")
+    width = w if 2 < w < x.bits else None
+    plc, bits, dev = x.plc, x.bits, sess.device
+    one = 1 << x.frac
+
+    def pub(shp, v):
+        return rep.from_public(sess, plc, R.fill(shp, v, bits, dev), bits)
+
+    def cut(t, rows=slice(0, None), cols=slice(0, None)):
+        return rep.local(sess, t, "StridedSlice", slices=[rows, cols])
+
+    if n == 0:
+        return _with(x, pub((0, c + int(bool(count)) + 1), 0))
+    s = sort(sess, x, by=by).t
+    key = cut(s, cols=slice(by, by + 1))
+    parts = [cut(s, cols=slice(lo, hi)) for lo, hi in ((0, by), (by + 1, c)) if hi > lo]
+    if count:
+        parts.append(pub((n, 1), one))
+    if n > 1:
+        d = rep.sub_public(sess, rep.sub(sess, cut(key, slice(1, n)), cut(key, slice(0, n - 1))),
+                           R.fill((), 1, bits, dev))
+        g1 = rep.less_than_zero_arith(sess, d, width=width)
+        g = concat(sess, [pub((1, 1), 0), g1], 0)
+        last = concat(sess, [rep.public_sub(sess, R.fill((), 1, bits, dev), g1), pub((1, 1), 1)],
+                      0)
+    else:
+        g, last = pub((1, 1), 0), pub((1, 1), 1)
+    table = key
+    if parts:
+        vals = concat(sess, parts, 1) if len(parts) > 1 else parts[0]
+        nv = c - 1 + int(bool(count))
+        sums = rep.segmented_scan(sess, rep.local(sess, vals, "Reshape", shape=(1, n, nv)),
+                                  rep.local(sess, g, "Reshape", shape=(1, n, 1)))
+        table = concat(sess, [key, rep.local(sess, sums, "Reshape", shape=(n, nv))], 1)
+    wide = rep.local(sess, last, "Broadcast", shape=(n, c + int(bool(count))))
+    out = concat(sess, [rep.mul(sess, wide, table),
+                        rep.mul_public(sess, last, R.fill((), one, bits, dev))], 1)
+    if shuffle:
+        out = rep.shuffle(sess, out, 0)
+    return _with(x, out)
+
+
 # ---------------------------------------------------------------------------
 # normalisation: leading-bit one-hot
 # ---------------------------------------------------------------------------

@@ -1368,6 +1368,127 @@ def shuffle(sess, x: RepTensor, axis: int = 0) -> RepTensor:
     return x
 
 
+def _rows(sess, x: RepTensor, lo, hi, cols=None) -> RepTensor:
+    """Positions [lo, hi) of the middle axis of a rank-3 value (and the columns ``cols``)."""
+    slices = [slice(0, None), slice(lo, hi)] + ([slice(*cols)] if cols is not None else [])
+    return local(sess, x, "StridedSlice", slices=slices)
+
+
+def _cat(sess, xs, axis) -> RepTensor:
+    x = xs[0]
+    return RepTensor(x.plc, x.bits, x.kind,
+                     sess.p("Concat", x.plc, *[t.s0 for t in xs], axis=axis),
+                     sess.p("Concat", x.plc, *[t.s1 for t in xs], axis=axis))
+
+
+def _cumsum_composed(sess, x: RepTensor, n, exclusive, reverse) -> RepTensor:
+    """R.scan on a rank-3 value from Slice, Add, Sub and Concat -- Hillis-Steele steps, the
+    operators a lowered graph's executor already has."""
+    acc, d = x, 1
+    while d < n:
+        s = add(sess, _rows(sess, acc, 0, n - d), _rows(sess, acc, d, n))
+        acc = _cat(sess, [s, _rows(sess, acc, n - d, n)] if reverse
+                   else [_rows(sess, acc, 0, d), s], 1)
+        d *= 2
+    return sub(sess, acc, x) if exclusive else acc
+
+
+def cumsum(sess, x: RepTensor, axis: int = 0, exclusive: bool = False,
+           reverse: bool = False) -> RepTensor:
+    """Prefix sums along ``axis``, wrapping in the ring: a prefix sum is linear, so it is
+    R.scan on each share component and costs no communication.  ``exclusive``: the sum of the
+    elements before each one (the first is 0); ``reverse``: from the far end.  Arithmetic
+    sharings over Z_2^64 / Z_2^128 of rank >= 1.  A symbolic session composes it from Reshape,
+    Slice, Add, Sub and Concat."""
+    if x.kind != "arith" or x.bits not in (64, 128):
+        raise ValueError("cumsum takes an arithmetic sharing over Z_2^64 or Z_2^128; a bit "
+                         "sharing is not supported (inject the bits into a ring first)")
+    shape = tuple(sess.p_shape(x.s0))
+    nd = len(shape)
+    if nd < 1:
+        raise ValueError("cumsum takes a tensor of rank >= 1, found a scalar")
+    if isinstance(axis, bool) or not isinstance(axis, int) or not -nd <= axis < nd:
+        raise ValueError(f"cumsum: axis {axis!r} out of range for a tensor of rank {nd}")
+    axis %= nd
+    n = shape[axis]
+    if math.prod(shape) == 0 or (n == 1 and not exclusive):
+        return x
+    geom = R.ScanGeom(math.prod(shape[:axis]), n, math.prod(shape[axis + 1:]),
+                      bool(exclusive), bool(reverse))
+    with span("rep.cumsum"):
+        if getattr(sess, "symbolic", False):
+            v = local(sess, x, "Reshape", shape=(geom.outer, n, geom.inner))
+            return local(sess, _cumsum_composed(sess, v, n, exclusive, reverse), "Reshape",
+                         shape=shape)
+        s0, s1 = _sharewise(sess, "Scan", x.plc, (x.s0, x.s1), geom=tuple(geom))
+    return RepTensor(x.plc, x.bits, "arith", s0, s1)
+
+
+def _segscan_apply_composed(sess, x: RepTensor, p: RepTensor, g) -> RepTensor:
+    """R.segscan_apply from Slice, Add and Concat on rank-3 values."""
+    tail = _rows(sess, p, 0, g.n - g.j, (g.inner - 1, g.inner))
+    if g.inner > 1:
+        vals = add(sess, _rows(sess, x, g.j, g.n, (0, g.inner - 1)),
+                   _rows(sess, p, 0, g.n - g.j, (0, g.inner - 1)))
+        tail = _cat(sess, [vals, tail], 2)
+    return _cat(sess, [_rows(sess, x, 0, g.j), tail], 1)
+
+
+def segmented_scan(sess, v: RepTensor, g: RepTensor, on_stage=None) -> RepTensor:
+    """Inclusive segmented prefix sums of ``v`` [outer, n, cols] along the middle axis, under
+    the secret arithmetic 0/1 flags ``g`` [outer, n, 1]: ``g[pos] = 1`` says that ``pos``
+    belongs to the segment of ``pos - 1``.  ``g[0]`` is forced to 0 (a public fact: nothing
+    precedes the first position), whatever it held.
+
+    A Hillis-Steele scan on the state S = [v | g]: stage j = 1, 2, 4, ... < n sets, from
+    position j on, ``v[pos] += g[pos] * v[pos - j]`` and ``g[pos] *= g[pos - j]`` -- one
+    replicated multiplication by the flag column, run as the parties' local products (session
+    ``p_segscan_cross``), a zero share and a reshare, and R.segscan_apply share-wise.
+    ceil(log2 n) rounds; nothing truncates, so the revealed result is exact.
+
+    Invariant: because ``g[0] = 0``, before the stage of offset j the flag column is 0 at
+    every position below j (it says "the j positions ending here are one segment", which
+    cannot hold where fewer than j precede), and after it at every position below 2j.  That is
+    why a stage may leave the positions below j alone.  ``on_stage(j, S)`` sees the state after
+    each stage (tests).  A symbolic session composes the local steps from Slice, Mul, Add and
+    Concat, so a lowered graph needs no operator of its own."""
+    if v.kind != "arith" or g.kind != "arith" or v.bits not in (64, 128) or g.bits != v.bits:
+        raise ValueError("segmented_scan takes arithmetic sharings over one of Z_2^64 / Z_2^128 "
+                         "(inject flag bits into the ring first)")
+    plc, bits = v.plc, v.bits
+    vs, gs = tuple(sess.p_shape(v.s0)), tuple(sess.p_shape(g.s0))
+    if len(vs) != 3 or gs != vs[:2] + (1,):
+        raise ValueError(f"segmented_scan: values of shape {vs} take flags of shape "
+                         f"{vs[:2] + (1,) if len(vs) == 3 else '[outer, n, 1]'}, found {gs}")
+    outer, n, cols = vs
+    if n <= 1 or math.prod(vs) == 0:
+        return v
+    composed = getattr(sess, "symbolic", False)
+    with span("rep.segmented_scan"):
+        zero = from_public(sess, plc, R.fill((outer, 1, 1), 0, bits,
+                                             getattr(sess, "device", "cpu")), bits)
+        x = _cat(sess, [v, _cat(sess, [zero, _rows(sess, g, 1, n)], 1)], 2)
+        for j in R.segscan_stages(n):
+            geom = R.SegscanGeom(outer, n, cols + 1, j)
+            with span("rep.segscan_stage"):
+                z = sess.p_segscan_cross(plc, x.s0, x.s1, geom)
+                fused = getattr(sess, "p_zero_share_reshare", None)
+                if fused is not None and getattr(sess, "fused", False):
+                    p0, p1 = fused(plc, z, "arith")
+                    p = RepTensor(plc, bits, "arith", p0, p1)
+                else:
+                    p = _reshare(sess, plc, sess.p_add_zero_share(plc, z, "arith"), bits, "arith")
+                if composed:
+                    x = _segscan_apply_composed(sess, x, p, geom)
+                else:
+                    o0, o1 = _sharewise(sess, "SegscanApply", plc, (x.s0, x.s1), (p.s0, p.s1),
+                                        geom=tuple(geom))
+                    x = RepTensor(plc, bits, "arith", o0, o1)
+            if on_stage is not None:
+                on_stage(j, x)
+        return _rows(sess, x, 0, n, (0, cols))
+
+
 def dwconv_public(sess, x: RepTensor, c, geom: dict, public_image=False) -> RepTensor:
     """Depthwise convolution of a secret image with the public weight ``c`` (or, with
     ``public_image``, of the public image ``c`` with a secret weight): the plain kernel

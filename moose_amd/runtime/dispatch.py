@@ -183,6 +183,10 @@ kernel("Sort", "rep", "rep_ring")(_sort_ring)
 # are primitives of runtime/prims.py, run by name like every host operator)
 kernel("Shuffle", "rep", "rep_ring")(
     lambda c, x: rep.shuffle(c.sess, x, int(c.attr("axis", default=0))))
+kernel("CumSum", "rep", "rep_ring")(
+    lambda c, x: rep.cumsum(c.sess, x, int(c.attr("axis", default=0)),
+                            bool(c.attr("exclusive", default=False)),
+                            bool(c.attr("reverse", default=False))))
 kernel("Neg", "rep", "rep_ring")(lambda c, x: rep.neg(c.sess, x))
 kernel("Sum", "rep", "rep_ring")(lambda c, x: rep.sum(c.sess, x, c.attr("axis")))
 kernel("AddN", "rep", "rep_ring", variadic=True)(lambda c, *xs: _add_n(c, xs))

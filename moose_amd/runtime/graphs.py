@@ -27,6 +27,7 @@ back to eager evaluation.
 """
 from __future__ import annotations
 
+import gc
 import os
 import warnings
 from typing import Dict
@@ -110,10 +111,17 @@ def capturable(comp) -> bool:
     share checkpoints and computed keys keep the computation eager, and so does a Shuffle: its
     permutation is a device argsort of fresh PRF output, which is not captured -- run eagerly,
     every evaluation draws fresh keys and with them a fresh permutation."""
+    from moose_amd.ir.computation import ReplicatedPlacement
     from moose_amd.runtime import storage_tap
 
-    if any(op.kind == "Shuffle" for op in comp.operations):
-        return False
+    for op in comp.operations:
+        if op.kind == "Shuffle":
+            return False
+        # a GroupBySum that ends in a shuffle likewise; one on a host or mirrored placement
+        # sorts in the clear with a device argsort, which is not captured either
+        if op.kind == "GroupBySum" and (op.attrs.get("shuffle", True) or
+                                        not isinstance(op.placement, ReplicatedPlacement)):
+            return False
     return storage_tap.capturable(comp)
 
 
@@ -206,6 +214,13 @@ class GraphPlan:
 
         self.interp.on_op = rotate
         self.interp.storage_tap = self.tap
+        # No cyclic collection while the stream captures: a dropped plan (it sits in a
+        # reference cycle with its own closures) would have its graphs destroyed by whatever
+        # collection starts next, hipGraphDestroy is not permitted during a capture, and an
+        # error in that destructor aborts the process.  Collect now instead.
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
         with _upload_hook(stager), torch.cuda.stream(stream):
             try:
                 self.outs = self.interp.run(comp, self.static)
@@ -218,8 +233,12 @@ class GraphPlan:
                     sys.stderr.flush()
                 raise
             finally:
-                if state["g"] is not None:
-                    end()
+                try:
+                    if state["g"] is not None:
+                        end()
+                finally:
+                    if gc_was_on:
+                        gc.enable()
         self.interp.on_op = None
         self.interp.storage_tap = None
         torch.cuda.synchronize(self.device)

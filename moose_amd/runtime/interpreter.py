@@ -1592,6 +1592,64 @@ class Interpreter:
         except ValueError as e:
             raise MooseRuntimeError(f"{op.name}: {e}") from None
 
+    def op_CumSum(self, op, ins):
+        """Prefix sums along an axis: a host's (or a public) tensor through the plaintext
+        primitive -- floats via torch, the ring values of a fixed-point tensor via the ring
+        scan -- and a replicated fixed-point tensor through fixedpoint.cumsum (local, exact)."""
+        a = op.attrs
+        attrs = dict(axis=int(a.get("axis", 0)), exclusive=bool(a.get("exclusive", False)),
+                     reverse=bool(a.get("reverse", False)))
+        x = self.at(op, ins[0])
+        if x.kind != "tensor":
+            raise MooseRuntimeError(f"{op.name}: CumSum expects a tensor, got a {x.kind}")
+        if x.dtype is not None and x.dtype.kind == "Bool":
+            raise MooseRuntimeError(
+                f"{op.name}: CumSum expects a float or fixed-point tensor, got {x.dtype}; bit "
+                "tensors are not supported")
+        try:
+            if x.is_host:
+                return LV(x.plc, "tensor", x.dtype, self.sess.h("CumSum", x.host, x.v, **attrs))
+            if x.is_mir or (x.is_rep and isinstance(x.v, MV)):
+                return self._public_prim(x, "CumSum", **attrs)
+            if x.dtype is None or not x.dtype.is_fixed:
+                raise MooseRuntimeError(
+                    f"{op.name}: CumSum on a replicated placement expects a fixed-point tensor, "
+                    f"got {x.dtype}; cast a float tensor to fixed point first")
+            return LV(x.plc, "tensor", x.dtype, fxp.cumsum(self.sess, x.v, **attrs))
+        except ValueError as e:
+            raise MooseRuntimeError(f"{op.name}: {e}") from None
+
+    def op_GroupBySum(self, op, ins):
+        """Group a table's rows by a key column and sum the others per key (ir/operators.py
+        GroupBySum).  A host's table in the clear through the plaintext primitive -- the
+        specification; a replicated fixed-point table through fixedpoint.group_by_sum.  A
+        host's result is not shuffled: the host knows every row anyway."""
+        a = op.attrs
+        by, count = int(a.get("by", 0)), bool(a.get("count", False))
+        x = self.at(op, ins[0])
+        if x.kind != "tensor":
+            raise MooseRuntimeError(f"{op.name}: GroupBySum expects a tensor, got a {x.kind}")
+        if x.dtype is not None and x.dtype.kind == "Bool":
+            raise MooseRuntimeError(
+                f"{op.name}: GroupBySum expects a float or fixed-point table, got {x.dtype}; "
+                "bit tensors are not supported")
+        fixed = x.dtype is not None and x.dtype.is_fixed
+        one = (1 << x.dtype.fractional_precision) if fixed else 1.0
+        try:
+            if x.is_host:
+                return LV(x.plc, "tensor", x.dtype,
+                          self.sess.h("GroupBySum", x.host, x.v, by=by, count=count, one=one))
+            if x.is_mir or (x.is_rep and isinstance(x.v, MV)):
+                return self._public_prim(x, "GroupBySum", by=by, count=count, one=one)
+            if not fixed:
+                raise MooseRuntimeError(
+                    f"{op.name}: GroupBySum on a replicated placement expects a fixed-point "
+                    f"tensor, got {x.dtype}; cast a float tensor to fixed point first")
+            return LV(x.plc, "tensor", x.dtype,
+                      fxp.group_by_sum(self.sess, x.v, by, count, bool(a.get("shuffle", True))))
+        except ValueError as e:
+            raise MooseRuntimeError(f"{op.name}: {e}") from None
+
     def op_PiecewiseLinear(self, op, ins):
         """Piecewise-linear activation of a fixed-point tensor: replicated values through
         fixedpoint.piecewise_linear (one sign extraction, one local kernel, one truncation);

@@ -417,6 +417,100 @@ def _cswap_apply(nb, x, p, geom):
     return R.cswap_apply(x, p, R.CswapGeom(*geom), nb)
 
 
+@prim("Scan")
+def _scan(nb, x, geom):
+    """The prefix sums of a ring tensor seen as [outer, n, inner] (R.scan)."""
+    return R.scan(x, R.ScanGeom(*geom), nb)
+
+
+@prim("SegscanApply")
+def _segscan_apply(nb, x, p, geom):
+    """The update of one stage of a segmented scan (R.segscan_apply)."""
+    return R.segscan_apply(x, p, R.SegscanGeom(*geom), nb)
+
+
+def _axis_geom(shape, axis, what):
+    nd = len(shape)
+    if isinstance(axis, bool) or not isinstance(axis, int) or nd < 1 or not -nd <= axis < nd:
+        raise ValueError(f"{what}: axis {axis!r} out of range for a tensor of rank {nd}")
+    axis %= nd
+    return axis, (math.prod(shape[:axis]), shape[axis], math.prod(shape[axis + 1:]))
+
+
+@prim("CumSum")
+def _cumsum(nb, x, axis=0, exclusive=False, reverse=False):
+    """Plaintext prefix sums of a host's tensor along ``axis``: floats through torch.cumsum,
+    fixed-point ring values through R.scan (exact, wrapping in the ring)."""
+    axis, geom = _axis_geom(tuple(x.shape[nb:]), axis, "cumsum")
+    if _is_rt(x):
+        return R.scan(x, R.ScanGeom(*geom, bool(exclusive), bool(reverse)), nb)
+    ax = axis + nb
+    d = x.flip(ax) if reverse else x
+    c = torch.cumsum(d, dim=ax)
+    if exclusive:  # shifted, not subtracted: floats do not cancel exactly
+        c = torch.cat([torch.zeros_like(c.narrow(ax, 0, 1)), c.narrow(ax, 0, c.shape[ax] - 1)],
+                      dim=ax) if c.shape[ax] else c
+    return c.flip(ax) if reverse else c
+
+
+@prim("GroupBySum")
+def _group_by_sum(nb, x, by=0, count=False, one=1):
+    """Plaintext group-by of a host's table [n, c] -- the specification of the secure path:
+    the rows sorted by column ``by``; the LAST row of every run of equal keys holds the key,
+    the sums of the other columns over the run, the run's length times ``one`` where ``count``,
+    and ``one`` (valid); every other row is zero.  [n, c + count + 1].  ``one`` is the
+    encoding of 1: 1.0 for floats, 2^frac for the ring values of a fixed-point tensor."""
+    rt = _is_rt(x)
+    if nb or len(x.shape) != 2 or not 0 <= by < x.shape[1]:
+        raise ValueError(f"group_by_sum takes a rank-2 table with more than {by} columns, found "
+                         f"shape {tuple(x.shape)}")
+    n, c = x.shape
+    s = _sort(0, x, axis=0, by=by)
+    d = s.data if rt else s
+    w128 = rt and x.bits == 128
+    ncol = c + int(bool(count)) + 1
+    tail = (2,) if w128 else ()
+    if n == 0:
+        out = torch.zeros((n, ncol) + tail, dtype=d.dtype, device=d.device)
+        return R.RT(out, x.bits) if rt else out
+    # Every step keeps the shape [n, ...] whatever the data: nothing waits for the device.
+    key = d[:, by]
+    same = key[1:] == key[:-1]
+    if w128:
+        same = same.all(dim=-1)
+    first = torch.ones(n, dtype=torch.bool, device=d.device)
+    last = torch.ones(n, dtype=torch.bool, device=d.device)
+    first[1:] = ~same
+    last[:-1] = ~same
+    vals = torch.cat([d[:, :by], d[:, by + 1:]], dim=1)  # (no index list: no upload)
+    if rt:
+        ones = R.fill((n, 1), int(one), x.bits, d.device).data
+    else:
+        ones = torch.full((n, 1), one, dtype=d.dtype, device=d.device)
+    if count:
+        vals = torch.cat([vals, ones], dim=1)
+    nv = vals.shape[1]
+    cols = [key.unsqueeze(1)]
+    if nv and rt:
+        # the prefix sums less those at the end of the run before: exact in the ring
+        idx = torch.arange(n, device=d.device)
+        start = torch.cummax(torch.where(first, idx, torch.zeros_like(idx)), 0).values
+        cs = R.scan(R.RT(vals.contiguous(), x.bits), R.ScanGeom(1, n, nv))
+        prev = cs.data[(start - 1).clamp(min=0)]
+        none = (start == 0).reshape((n,) + (1,) * (prev.dim() - 1))
+        prev = torch.where(none, torch.zeros_like(prev), prev)
+        cols.append(R.binary("sub", cs, R.RT(prev.contiguous(), x.bits)).data)
+    elif nv:  # every run summed on its own
+        gid = torch.cumsum(first.to(torch.int64), 0) - 1
+        runs = torch.zeros((n, nv), dtype=d.dtype, device=d.device).index_add_(0, gid, vals)
+        cols.append(runs[gid])
+    cols.append(ones)
+    row = torch.cat(cols, dim=1)
+    keep = last.reshape((n,) + (1,) * (row.dim() - 1))
+    out = torch.where(keep, row, torch.zeros_like(row))
+    return R.RT(out, x.bits) if rt else out
+
+
 @prim("PermFromKeys", ty=lambda tys, **a: T.Ty("HostUint64Tensor"))
 def _perm_from_keys(nb, keys):
     """The permutation that stably sorts a Z_2^64 vector of PRF output as unsigned integers

@@ -299,7 +299,7 @@ class StackedSession(Session):
 
     # per-party primitives that run over a pair-stacked base (every slot independent)
     _PAIR_SLOTWISE = ("WeightedSum", "BitExtract", "BitSplit", "Slice", "Im2Col", "Col2Im",
-                      "Resize", "Permute", "CswapDiff")
+                      "Resize", "Permute", "CswapDiff", "Scan")
     # slot-wise with one public operand, the same for both share vectors
     _PAIR_SLOTWISE_PUB = ("MulLeading", "DepthwiseConv")
 
@@ -345,7 +345,8 @@ class StackedSession(Session):
             out = PRIMS[prim].impl(1, base, *extra, **self._attrs(prim, attrs))
             return (PV(plc, R.RT(out.data[0:3], out.bits)),
                     PV(plc, R.RT(out.data[o:o + 3], out.bits)))
-        if prim == "CswapApply":  # slot-wise in both operands: two pair buffers of one layout
+        # slot-wise in both operands: two pair buffers of one layout
+        if prim in ("CswapApply", "SegscanApply"):
             pa, pb = self._pair_base(a[0].v, a[1].v), self._pair_base(b[0].v, b[1].v)
             if pa is None or pb is None or pa[1:] != pb[1:]:
                 return None
@@ -959,6 +960,12 @@ class StackedSession(Session):
         compare-exchange stage (R.cswap_cross) in one launch: the share vectors -- the views of
         a share-pair buffer included -- are read in place."""
         return PV(plc, R.cswap_cross(s0.v, s1.v, x0.v, x1.v, geom, nb=1))
+
+    def p_segscan_cross(self, plc, x0, x1, geom):
+        """The three parties' local products of one stage of a segmented scan
+        (R.segscan_cross) in one launch: the share vectors -- the views of a share-pair buffer
+        included -- are read in place."""
+        return PV(plc, R.segscan_cross(x0.v, x1.v, geom, nb=1))
 
     def end_evaluation(self, ok=True):
         """Drop per-evaluation caches (prepared GEMM operands hold device memory and must
