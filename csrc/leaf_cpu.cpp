@@ -1,7 +1,8 @@
 // Host (CPU) twins of the leaf kernels of leaf_hip.hip -- the image leaves, the piecewise-
-// linear local step, the compare-exchange leaves, the permuted row gather and the prefix-sum
-// leaves -- and their mx_* entry points, which check the geometry (img_geom.h, cswap_geom.h,
-// segscan_geom.h) and the sizes for both sides.  Plain loops: the oracle.
+// linear local step, the compare-exchange leaves, the permuted row gather, the prefix-sum
+// leaves and the outer-product leaf -- and their mx_* entry points, which check the geometry
+// (img_geom.h, cswap_geom.h, segscan_geom.h, outer_geom.h) and the sizes for both sides.  Plain
+// loops: the oracle.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -375,9 +376,53 @@ void segscan_apply_cpu(const T* x, const T* p, T* out, int64_t slots, int64_t x_
   });
 }
 
+using mxr::OuterGeom;
+
+// The outer-product leaf (moosex.h mx_outer_cross): one (slot, group, row) at a time, the run
+// of A columns of every b.
+template <class T>
+void outer_cross_cpu(const T* la, const T* lb, const T* ha, const T* hb, T* out, int64_t slots,
+                     int64_t l_slot, int64_t l_group, int64_t h_slot, int64_t h_group,
+                     const OuterGeom& g) {
+  const int64_t lines = g.groups * g.rows;
+  parallel_for(slots * lines, std::max<int64_t>(1, 4096 / g.n_out), [&](int64_t q0, int64_t q1) {
+    for (int64_t q = q0; q < q1; ++q) {
+      const int64_t s = q / lines, line = q - s * lines, gi = line / g.rows, r = line - gi * g.rows;
+      const int64_t li = s * l_slot + gi * l_group + r * g.A;
+      const int64_t hi = s * h_slot + gi * h_group + r * g.B;
+      T* dst = out + q * g.n_out;
+      for (int64_t c = 0; c < g.n_out; ++c) {
+        const int64_t b = c / g.A, a = c - b * g.A;
+        dst[c] = lb ? la[li + a] * (ha[hi + b] + hb[hi + b]) + lb[li + a] * ha[hi + b]
+                    : la[li + a] * ha[hi + b];
+      }
+    }
+  });
+}
+
 }  // namespace
 
 extern "C" {
+
+int mx_outer_cross(int dev, int elem_bytes, const void* la, const void* lb, const void* ha,
+                   const void* hb, void* out, int64_t slots, int64_t l_slot_stride,
+                   int64_t l_group_stride, int64_t h_slot_stride, int64_t h_group_stride,
+                   int64_t groups, int64_t rows, int64_t A, int64_t B, int64_t n_out,
+                   void* stream) {
+  OuterGeom g{groups, rows, A, B, n_out};
+  const int rc = mxr::outer_geom_check(g, elem_bytes, slots, l_slot_stride, l_group_stride,
+                                       h_slot_stride, h_group_stride);
+  if (rc <= 0) return rc;
+  if (!la || !ha || !out || (lb == nullptr) != (hb == nullptr)) return -3;
+  if (dev)
+    return mxh_outer_cross(elem_bytes, la, lb, ha, hb, out, slots, l_slot_stride, l_group_stride,
+                           h_slot_stride, h_group_stride, g, stream);
+  DISPATCH_ELEM(elem_bytes, T, {
+    outer_cross_cpu((const T*)la, (const T*)lb, (const T*)ha, (const T*)hb, (T*)out, slots,
+                    l_slot_stride, l_group_stride, h_slot_stride, h_group_stride, g);
+    return 0;
+  });
+}
 
 int64_t mx_scan_chunk(void) { return mxr::kScanChunk; }
 

@@ -1,9 +1,10 @@
 // gfx950 leaf kernels of the moosex ring dialect: the image leaves (im2col, dwconv, col2im,
 // resize2d), the piecewise-linear and piecewise-polynomial local steps (pwl_cross, pwp_cross),
 // the compare-exchange leaves (cswap_diff / _cross / _apply), the permuted row gather of a
-// shuffle step (perm_gather) and the prefix-sum leaves (scan, segscan_cross / _apply).  Each is
-// a share-wise kernel over slots whose geometry and sizes are checked on the host (img_geom.h,
-// cswap_geom.h, segscan_geom.h, mx_perm_gather) before it gets here.
+// shuffle step (perm_gather), the prefix-sum leaves (scan, segscan_cross / _apply) and the
+// outer-product leaf of a demultiplexer level (outer_cross).  Each is a share-wise kernel over
+// slots whose geometry and sizes are checked on the host (img_geom.h, cswap_geom.h,
+// segscan_geom.h, outer_geom.h, mx_perm_gather) before it gets here.
 
 #include <hip/hip_runtime.h>
 
@@ -1210,9 +1211,90 @@ static SegscanP<I> segscan_params(const mxr::SegscanGeom& g, int64_t a_slot, int
   return p;
 }
 
+// k_outer_cross (moosex.h mx_outer_cross), on the segscan leaves' plan: a (groups * rows) x
+// n_out index space, a lane owns V adjacent output columns and strides over the lines.  The
+// lane's columns are fixed, so its b = c / A and a = c % A are formed once, outside the loop,
+// for any A (a block's columns span several b where A is small).  V = 2 only where A is even:
+// then both columns lie in one run of A and take one H element.  Per line a lane loads one
+// vector of L and one element of H (per component); the lanes of a run read the same H
+// address.  L and H are read at their own slot and group strides, the output is dense.
+template <class I>
+struct OuterP {
+  I l_slot, l_group, h_slot, h_group, o_slot;
+  I lines, rows, A, B, n_out;  // lines = groups * rows
+};
+
+template <class T, class I, int V>
+__global__ void __launch_bounds__(256) k_outer_cross(const T* __restrict__ la,
+                                                     const T* __restrict__ lb,
+                                                     const T* __restrict__ ha,
+                                                     const T* __restrict__ hb,
+                                                     T* __restrict__ out, OuterP<I> p) {
+  using U = typename std::make_unsigned<I>::type;
+  using Vec = LaneVec<T, V>;
+  const unsigned by = blockDim.y;
+  const I c0 = ((I)blockIdx.x * (I)blockDim.x + (I)threadIdx.x) * V;
+  if (c0 >= p.n_out) return;
+  const I b = (I)((U)c0 / (U)p.A), a0 = c0 - b * p.A;
+  const I z = (I)blockIdx.z;
+  const T* __restrict__ sla = la + z * p.l_slot + a0;
+  const T* __restrict__ sha = ha + z * p.h_slot + b;
+  const T* __restrict__ slb = lb ? lb + z * p.l_slot + a0 : nullptr;
+  const T* __restrict__ shb = lb ? hb + z * p.h_slot + b : nullptr;
+  T* __restrict__ dst = out + z * p.o_slot + c0;
+  for (I q = (I)(blockIdx.y * by + threadIdx.y); q < p.lines; q += (I)(gridDim.y * by)) {
+    const I gi = (I)((U)q / (U)p.rows), r = q - gi * p.rows;
+    const I li = gi * p.l_group + r * p.A, hi = gi * p.h_group + r * p.B;
+    const Vec xa = *reinterpret_cast<const Vec*>(sla + li);
+    const T ya = sha[hi];
+    Vec v;
+    if (slb) {
+      const Vec xb = *reinterpret_cast<const Vec*>(slb + li);
+      const T ys = ya + shb[hi];
+#pragma unroll
+      for (int e = 0; e < V; ++e) v.v[e] = xa.v[e] * ys + xb.v[e] * ya;
+    } else {
+#pragma unroll
+      for (int e = 0; e < V; ++e) v.v[e] = xa.v[e] * ya;
+    }
+    *reinterpret_cast<Vec*>(dst + q * p.n_out) = v;
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+int mxh_outer_cross(int elem_bytes, const void* la, const void* lb, const void* ha,
+                    const void* hb, void* out, int64_t slots, int64_t l_slot_stride,
+                    int64_t l_group_stride, int64_t h_slot_stride, int64_t h_group_stride,
+                    const mxr::OuterGeom& g, void* stream) {
+  if (slots > 65535) return -3;
+  // outer_geom_check kept every term within slot_cap, so neither sum wraps
+  const int64_t l_reach = (slots - 1) * l_slot_stride + (g.groups - 1) * l_group_stride + g.n_l;
+  const int64_t h_reach = (slots - 1) * h_slot_stride + (g.groups - 1) * h_group_stride + g.n_h;
+  const bool small = fits32(1 << 17, {l_reach, h_reach, slots * g.n_o});
+  // the vector accesses are L's and the output's; H is read one element at a time
+  const bool two = g.A % 2 == 0 && g.n_out % 2 == 0 && aligned16(la) && aligned16(lb) &&
+                   aligned16(out) && l_slot_stride % 2 == 0 && l_group_stride % 2 == 0;
+  const int64_t lines = g.groups * g.rows;
+  return leaf_dispatch(elem_bytes, small, two, [&](auto f) {
+    using F = decltype(f);
+    using T = typename F::T;
+    using I = typename F::I;
+    const LanePlan lp = lane_plan(g.n_out, F::V);
+    OuterP<I> p;
+    p.l_slot = (I)l_slot_stride, p.l_group = (I)l_group_stride, p.h_slot = (I)h_slot_stride;
+    p.h_group = (I)h_group_stride, p.o_slot = (I)g.n_o, p.lines = (I)lines, p.rows = (I)g.rows;
+    p.A = (I)g.A, p.B = (I)g.B, p.n_out = (I)g.n_out;
+    hipLaunchKernelGGL((k_outer_cross<T, I, F::V>),
+                       dim3((unsigned)lp.tiles, (unsigned)row_grid(lines, lp.by), (unsigned)slots),
+                       dim3(lp.bx, lp.by), 0, S(stream), (const T*)la, (const T*)lb,
+                       (const T*)ha, (const T*)hb, (T*)out, p);
+    MX_LAUNCH_CHECK();
+    return 0;
+  });
+}
 
 int mxh_scan(int elem_bytes, const void* x, void* out, void* ws, int64_t slots,
              int64_t x_slot_stride, const mxr::ScanGeom& g, void* stream) {

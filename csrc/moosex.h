@@ -225,6 +225,21 @@ int mx_segscan_cross(int dev, int elem_bytes, const void* a, const void* b, void
 int mx_segscan_apply(int dev, int elem_bytes, const void* x, const void* p, void* out,
                      int64_t slots, int64_t x_slot_stride, int64_t p_slot_stride, int64_t outer,
                      int64_t n, int64_t inner, int64_t j, void* stream);
+// Row-wise outer products in Z_2^64 / Z_2^128 (elem_bytes 8 / 16), wrapping (outer_geom.h):
+// L is [groups, rows, A], H is [groups, rows, B] per slot and
+//   out[g, r, c] = L[g, r, c % A] * H[g, r, c / A] for c < n_out, 1 <= n_out <= A * B,
+// [groups, rows, n_out] per slot, dense.  With lb and hb (both or neither) it is one party's
+// local products of a replicated multiplication with its own components la, ha and the next
+// party's lb, hb: La*(Ha + Hb) + Lb*Ha, mx_segscan_cross's convention.  Ring-bilinear: the
+// operands are any ring values.  L and H have their own base pointers, slot strides and group
+// strides in elements (la and lb share L's, ha and hb share H's): the groups (2g, 2g + 1) of
+// one [2 * groups, rows, A] array are read in place as H = L + rows * A at a group stride of
+// 2 * rows * A.  A row of an operand is dense.  out must not overlap an operand.
+int mx_outer_cross(int dev, int elem_bytes, const void* la, const void* lb, const void* ha,
+                   const void* hb, void* out, int64_t slots, int64_t l_slot_stride,
+                   int64_t l_group_stride, int64_t h_slot_stride, int64_t h_group_stride,
+                   int64_t groups, int64_t rows, int64_t A, int64_t B, int64_t n_out,
+                   void* stream);
 // mx_ew_binary_slot on a0 (slot which0) and a1 (slot which1) with one public b
 int mx_ew_binary_slot2(int dev, int op, int words, const void* a0, const void* a1,
                        const void* b, int64_t nb, void* out0, void* out1, int64_t m,

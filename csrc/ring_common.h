@@ -6,6 +6,7 @@
 #include "aes_core.h"
 #include "cswap_geom.h"
 #include "img_geom.h"
+#include "outer_geom.h"
 #include "segscan_geom.h"
 #include "moosex.h"
 
@@ -320,6 +321,12 @@ int mxh_segscan_cross(int elem_bytes, const void* a, const void* b, void* out, i
 int mxh_segscan_apply(int elem_bytes, const void* x, const void* p, void* out, int64_t slots,
                       int64_t x_slot_stride, int64_t p_slot_stride, const mxr::SegscanGeom& g,
                       void* stream);
+// the outer-product leaf: g is validated and filled by outer_geom_check (outer_geom.h); lb and
+// hb are both null (plain) or both set (cross)
+int mxh_outer_cross(int elem_bytes, const void* la, const void* lb, const void* ha,
+                    const void* hb, void* out, int64_t slots, int64_t l_slot_stride,
+                    int64_t l_group_stride, int64_t h_slot_stride, int64_t h_group_stride,
+                    const mxr::OuterGeom& g, void* stream);
 int mxh_ks_cross1(int words, const void* g0, const void* g1, const void* p0, const void* p1,
                   void* z, int64_t n, int d, int both, const uint8_t* keys16, uint64_t nonce,
                   void* stream);

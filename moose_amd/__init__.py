@@ -109,6 +109,9 @@ from moose_amd.edsl.base import swish  # noqa: F401
 from moose_amd.edsl.base import relu6  # noqa: F401
 from moose_amd.edsl.base import tanh  # noqa: F401
 from moose_amd.edsl.base import thresholded_relu  # noqa: F401
+from moose_amd.edsl.base import bincount  # noqa: F401
+from moose_amd.edsl.base import lookup  # noqa: F401
+from moose_amd.edsl.base import one_hot  # noqa: F401
 from moose_amd.edsl.base import cumsum  # noqa: F401
 from moose_amd.edsl.base import group_by_count  # noqa: F401
 from moose_amd.edsl.base import group_by_sum  # noqa: F401

@@ -114,6 +114,9 @@ _OPS = {
         ["x"],
         lambda o: {"by": int(o.by), "count": bool(o.count), "shuffle": bool(o.shuffle)},
     ),
+    "OneHotOperation": ("OneHot", ["idx"], lambda o: {"depth": int(o.depth)}),
+    "LookupOperation": ("Lookup", ["table", "idx"], None),
+    "BinCountOperation": ("BinCount", "array", lambda o: {"length": int(o.length)}),
     "PiecewiseLinearOperation": (
         "PiecewiseLinear",
         ["x"],

@@ -105,6 +105,12 @@ def _static_shape(op, shapes):
             if len(ins[0]) != 2:
                 raise ValueError(f"expects a rank-2 table, found shape {ins[0]}")
             shp = (ins[0][0], ins[0][1] + int(bool(a.get("count", False))) + 1)
+        elif kind == "OneHot":
+            shp = tuple(ins[0]) + (int(a["depth"]),)
+        elif kind == "Lookup":
+            shp = tuple(ins[1]) + tuple(ins[0][1:])
+        elif kind == "BinCount":
+            shp = (int(a["length"]),) + (tuple(ins[1][1:]) if len(ins) > 1 else ())
         elif kind == "Transpose":
             shp = ins[0][::-1]
         elif kind == "Permute":

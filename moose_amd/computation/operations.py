@@ -96,6 +96,9 @@ OPERATION_TABLE = [
     ("ShuffleOperation", ["axis"]),
     ("CumSumOperation", ["axis", "exclusive", "reverse"]),
     ("GroupBySumOperation", ["by", "count", "shuffle"]),
+    ("OneHotOperation", ["depth"]),
+    ("LookupOperation", []),
+    ("BinCountOperation", ["length"]),
 ]
 
 OPERATION_CLASSES = {}

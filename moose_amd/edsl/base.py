@@ -1101,6 +1101,84 @@ def group_by_count(x, by=0, shuffle=True, placement=None, input_shape=None):
         raise ValueError(str(e).replace("`group_by_sum`", f"`{fn}`")) from None
 
 
+def _index_arg(fn, idx):
+    d = idx.vtype.dtype if isinstance(idx, Expression) and isinstance(idx.vtype, ty.TensorType) \
+        else None
+    if d is None or d.is_boolean:
+        raise ValueError(f"`{fn}` expects a uint64 or fixed-point index tensor (bit tensors are "
+                         f"not supported), found {getattr(idx, 'vtype', type(idx))}")
+
+
+def _count_arg(fn, name, n):
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError(f"`{fn}`: `{name}` must be a positive integer, found {n!r}")
+    return int(n)
+
+
+def one_hot(idx, depth, dtype=None, placement=None):
+    """The one-hot rows ``[..., depth]`` of the index tensor ``idx``: 1.0 at column ``idx`` and
+    0 elsewhere, in ``dtype`` (default: the index's own type).  ``idx`` is the result of
+    ``argmax`` (a uint64 tensor) or a fixed-point tensor holding integers (fractional bits are
+    ignored).  On a replicated placement the index stays secret: its bits are expanded by a
+    demultiplexer of ceil(log2 ceil(log2 depth)) multiplications, exact.
+
+    Precondition: ``0 <= idx < 2^w`` with ``w = max(1, ceil(log2 depth))``; higher bits are
+    ignored, and an ``idx`` in ``[depth, 2^w)`` selects nothing: its row is all zeros."""
+    _index_arg("one_hot", idx)
+    depth = _count_arg("one_hot", "depth", depth)
+    vtype = ty.TensorType(dtype) if dtype is not None else idx.vtype
+    e = _expr("one_hot", [idx], vtype, placement, depth=depth)
+    if idx.static_shape is not None:
+        e.static_shape = tuple(idx.static_shape) + (depth,)
+    return e
+
+
+def lookup(table, idx, placement=None, input_shape=None):
+    """``table[idx]``: the rows of ``table`` (``[n, d]`` or ``[n]``) that the index tensor
+    ``idx`` names, ``[rows, d]`` or ``[rows]`` in the table's type.  On a replicated placement
+    the index stays secret and the table may be secret, mirrored or a constant: the one-hot
+    matrix of the indices times the table, one untruncated ring product, so the result holds
+    the table's values exactly.  Needs the table's leading size: a ``shape=`` on the
+    pm.Argument, a constant, or ``input_shape=`` (the table's shape).
+
+    Precondition: ``0 <= idx < 2^w`` with ``w = max(1, ceil(log2 n))``; higher bits are ignored,
+    and an ``idx`` in ``[n, 2^w)`` selects nothing: the lookup returns 0."""
+    _index_arg("lookup", idx)
+    _not_bits("lookup", table)
+    shape = _sort_shape("lookup", table, input_shape, need=False)
+    if shape is None or len(shape) not in (1, 2) or shape[0] is None:
+        raise ValueError(f"`lookup` needs a table [n, d] or [n] whose leading size is known "
+                         f"(pass `input_shape=`, or give the pm.Argument a `shape=`), found "
+                         f"shape {shape}")
+    e = _expr("lookup", [table, idx], table.vtype, placement)
+    if idx.static_shape is not None and None not in shape:
+        e.static_shape = tuple(idx.static_shape) + tuple(shape[1:])
+    return e
+
+
+def bincount(idx, length, weights=None, placement=None):
+    """The histogram of the index tensor ``idx`` over ``length`` bins: ``[length]`` counts (as
+    1.0 per entry, in the index's fixed-point type), or with ``weights`` ``[rows, d]`` /
+    ``[rows]`` the sums of the weights per bin, ``[length, d]`` / ``[length]`` -- a
+    ``scatter_add``, the group-by of a key with a small known domain without a sort.  On a
+    replicated placement: the one-hot matrix of the indices, its column sums or one
+    untruncated ring product with the weights, exact.
+
+    Precondition: ``0 <= idx < 2^w`` with ``w = max(1, ceil(log2 length))``; higher bits are
+    ignored, and an ``idx`` in ``[length, 2^w)`` is counted nowhere."""
+    _index_arg("bincount", idx)
+    length = _count_arg("bincount", "length", length)
+    if weights is not None:
+        _not_bits("bincount", weights)
+    e = _expr("bincount", [idx] + ([weights] if weights is not None else []),
+              weights.vtype if weights is not None else idx.vtype, placement, length=length)
+    if weights is None:
+        e.static_shape = (length,)
+    elif weights.static_shape is not None:
+        e.static_shape = (length,) + tuple(weights.static_shape[1:])
+    return e
+
+
 def top_k(x, k, axis=-1, largest=True, placement=None, input_shape=None):
     """The ``k`` largest (``largest=False``: smallest) values along ``axis``, sorted from the
     extreme inwards: a sort and a slice.  A negative ``axis`` needs the rank of ``x`` (a

@@ -73,6 +73,9 @@ _OPS = {
     "shuffle": ("ShuffleOperation", ["x"], "shuffle", ["axis"]),
     "cumsum": ("CumSumOperation", ["x"], "cumsum", ["axis", "exclusive", "reverse"]),
     "group_by_sum": ("GroupBySumOperation", ["x"], "group_by_sum", ["by", "count", "shuffle"]),
+    "one_hot": ("OneHotOperation", ["idx"], "one_hot", ["depth"]),
+    "lookup": ("LookupOperation", ["table", "idx"], "lookup", []),
+    "bincount": ("BinCountOperation", "array", "bincount", ["length"]),
     "shape": ("ShapeOperation", ["x"], "shape", []),
     "mux": ("MuxOperation", ["selector", "x", "y"], "mux", []),
     "load": ("LoadOperation", ["key", "query"], "load", []),

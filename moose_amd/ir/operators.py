@@ -193,6 +193,16 @@ EXTENSION_OPERATORS = {
     # rows obliviously at the end.  On a secret x: a sort, one sign extraction, a segmented
     # scan of ceil(log2 n) multiplications and one more multiplication, exact
     "GroupBySum": [("by", "int"), ("count", "bool"), ("shuffle", "bool")],
+    # addressing by a secret index (a replicated uint64 tensor, as Argmax returns, or a
+    # fixed-point tensor holding an integer; 0 <= idx < 2^ceil(log2 n), an idx past the last
+    # entry selects nothing).  OneHot: [..., depth] rows of 0 / 1.0 in the result type.  Lookup:
+    # inputs (table [n, d] or [n], idx), the rows table[idx].  BinCount: inputs (idx[, weights]),
+    # the counts per bin [length] or the sums of the weights per bin [length, d].  On a secret
+    # index: a demultiplexer of ceil(log2 ceil(log2 n)) multiplications, then one untruncated
+    # ring GEMM; exact
+    "OneHot": [("depth", "int")],
+    "Lookup": [],
+    "BinCount": [("length", "int")],
     "PermGather": [("axis", "int"), ("form", "str")],
 }
 

@@ -76,6 +76,9 @@ _SIGS = {
     # (dev, elem_bytes, x p out, slots, x_slot_stride, p_slot_stride, outer n inner j, stream)
     "mx_segscan_apply": (c_int, [c_int, c_int] + [c_vp] * 3 + [c_i64] * 3 + [c_i64] * 4
                          + [c_vp]),
+    # (dev, elem_bytes, la lb ha hb out, slots, l_slot l_group h_slot h_group strides,
+    #  groups rows A B n_out, stream)
+    "mx_outer_cross": (c_int, [c_int, c_int] + [c_vp] * 5 + [c_i64] * 5 + [c_i64] * 5 + [c_vp]),
     # (dev, elem_bytes, x0 x1 w0 w1 out, slots, x_slot_stride, w_slot_stride, N C H W mult,
     #  KH KW, sh sw, pt pl, dh dw, OH OW, nhwc, stream)
     "mx_dwconv": (c_int, [c_int, c_int] + [c_vp] * 5 + [c_i64] * 3 + [c_i64] * 15

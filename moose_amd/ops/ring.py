@@ -2107,6 +2107,144 @@ def segscan_apply(x: RT, p: RT, g: SegscanGeom, nb=0) -> RT:
     return out
 
 
+# ---------------------------------------------------------------------------
+# row-wise outer products: a level of a demultiplexer
+# ---------------------------------------------------------------------------
+# the device path of outer_cross: the native kernel (True) or the torch composition
+# outer_cross_torch (False); a CPU tensor always takes the native loops
+OUTER_KERNEL = True
+
+
+class OuterGeom(NamedTuple):
+    """Row-wise outer products (csrc/outer_geom.h): ``L`` is [groups, rows, A], ``H`` is
+    [groups, rows, B] and the output [groups, rows, n_out] holds ``L[.., c % A] * H[.., c // A]``
+    at column c; A, B >= 1 and 1 <= n_out <= A * B."""
+
+    groups: int
+    rows: int
+    A: int
+    B: int
+    n_out: int
+
+
+def _outer_geom(g) -> OuterGeom:
+    g = OuterGeom(*(int(v) for v in OuterGeom(*g)))
+    if g.groups < 0 or g.rows < 0 or g.A < 1 or g.B < 1 or not 1 <= g.n_out <= g.A * g.B:
+        raise ValueError(f"outer_cross: malformed geometry {g}")
+    return g
+
+
+def _outer_check(g, nb, la: RT, lb, ha: RT, hb):
+    bits = la.bits
+    if bits not in (64, 128) or any(t is not None and t.bits != bits for t in (lb, ha, hb)):
+        raise ValueError("outer_cross is arithmetic only: operands over one of Z_2^64 / Z_2^128")
+    if nb not in (0, 1):
+        raise ValueError("outer_cross takes at most one batch dim")
+    if (lb is None) != (hb is None):
+        raise ValueError("outer_cross takes the next components of both operands or of neither")
+    lead = tuple(la.shape[:nb])
+    for t, x in ((la, g.A), (lb, g.A), (ha, g.B), (hb, g.B)):
+        if t is not None and (tuple(t.shape[:nb]) != lead
+                              or tuple(t.shape[nb:]) != (g.groups, g.rows, x)):
+            raise ValueError(f"outer_cross: operand of shape {tuple(t.shape)}, expected "
+                             f"{lead + (g.groups, g.rows, x)}")
+    return bits, lead
+
+
+def _outer_operand(t: RT, nb, groups, rows, x):
+    """(data, slot stride, group stride in elements) of an operand [slots?, groups, rows, x]: a
+    view whose rows are dense within a group is read in place at its own strides (the even or
+    odd groups of a wider array, the slot views of a share-pair buffer), anything else as a
+    contiguous copy."""
+    d, w = t.data, 2 if t.bits == 128 else 1
+    dense = (groups * rows * x, rows * x)
+    if d.numel() and d[(0,) * (nb + 1)].is_contiguous():
+        st = (d.stride(0) if nb and d.shape[0] > 1 else dense[0] * w,
+              d.stride(nb) if groups > 1 else dense[1] * w)
+        if all(s >= 0 and s % w == 0 for s in st):
+            return d, st[0] // w, st[1] // w
+    return d.contiguous(), dense[0], dense[1]
+
+
+def _outer_component_pair(a, b, nb, groups, rows, x):
+    """Both components of one operand at one pair of strides: as they are when their strides
+    agree, else both dense."""
+    ad, ast, agr = _outer_operand(a, nb, groups, rows, x)
+    if b is None:
+        return ad, None, ast, agr
+    bd, bst, bgr = _outer_operand(b, nb, groups, rows, x)
+    if (ast, agr) != (bst, bgr):
+        ad, bd, ast, agr = ad.contiguous(), bd.contiguous(), groups * rows * x, rows * x
+    return ad, bd, ast, agr
+
+
+def outer_pairs(x: RT, nb=0):
+    """The groups (2g, 2g + 1) of ``x`` [.., G, rows, A] as two uncopied views ``(L, H)`` of
+    [.., G // 2, rows, A]: ``H = L + rows * A`` at a group stride of ``2 * rows * A``.  An odd
+    last group belongs to neither."""
+    G = x.shape[nb]
+    idx = (slice(None),) * nb
+    return (RT(x.data[idx + (slice(0, G - G % 2, 2),)], x.bits),
+            RT(x.data[idx + (slice(1, G, 2),)], x.bits))
+
+
+def outer_cross_torch(la: RT, lb, ha: RT, hb, g: OuterGeom, nb=0) -> RT:
+    """:func:`outer_cross` as a composition of the existing kernels: broadcast products over a
+    [.., groups, rows, B, A] buffer, trimmed to ``n_out`` columns.  The benchmark's opponent."""
+    g = _outer_geom(g)
+    _outer_check(g, nb, la, lb, ha, hb)
+
+    wide = (g.groups, g.rows, g.B, g.A)
+
+    def col(t):
+        return broadcast_to(reshape(t.contiguous(), (g.groups, g.rows, 1, g.A), nb), wide, nb)
+
+    def row(t):
+        return broadcast_to(reshape(t.contiguous(), (g.groups, g.rows, g.B, 1), nb), wide, nb)
+
+    if lb is None:
+        v = binary("mul", col(la), row(ha))
+    else:
+        v = binary("add", binary("mul", col(la), row(binary("add", ha.contiguous(),
+                                                            hb.contiguous()))),
+                   binary("mul", col(lb), row(ha)))
+    v = reshape(v, (g.groups, g.rows, g.A * g.B), nb)
+    return v if g.n_out == g.A * g.B else slice_axis(v, 2, 0, g.n_out, nb=nb)
+
+
+def outer_cross(la: RT, lb, ha: RT, hb, g: OuterGeom, nb=0) -> RT:
+    """Row-wise outer products of ``L`` [.., groups, rows, A] and ``H`` [.., groups, rows, B]:
+    ``out[.., c] = L[.., c % A] * H[.., c // A]`` for ``c < n_out``, as [.., groups, rows,
+    n_out] -- one level of a demultiplexer tree, whose one-hot groups of A and B entries become
+    one of A * B (the last level trims to ``n_out``).  With the next party's components ``lb``
+    and ``hb`` it is one party's local products of a replicated multiplication, ``La * (Ha +
+    Hb) + Lb * Ha`` (as :func:`segscan_cross`); ``lb = hb = None`` is the plain product.  One
+    native launch over all batch slots (``mx_outer_cross``); ``L`` and ``H`` go to the entry at
+    their own slot and group strides, so the views of :func:`outer_pairs` and the slot views
+    of a share-pair buffer are read in place."""
+    g = _outer_geom(g)
+    bits, lead = _outer_check(g, nb, la, lb, ha, hb)
+    shape = lead + (g.groups, g.rows, g.n_out)
+    if la.device.type == "meta":
+        return empty(shape, bits, la.device)
+    if la.device.type == "cuda" and not OUTER_KERNEL:
+        return outer_cross_torch(la, lb, ha, hb, g, nb)
+    out = empty(shape, bits, la.device)
+    if out.data.numel() == 0:
+        return out
+    lad, lbd, lst, lgr = _outer_component_pair(la, lb, nb, g.groups, g.rows, g.A)
+    had, hbd, hst, hgr = _outer_component_pair(ha, hb, nb, g.groups, g.rows, g.B)
+    nat.check(
+        nat.lib().mx_outer_cross(nat.dev_of(out.data), _elem_bytes(bits), nat.ptr(lad),
+                                 nat.ptr(lbd) if lbd is not None else None, nat.ptr(had),
+                                 nat.ptr(hbd) if hbd is not None else None, nat.ptr(out.data),
+                                 math.prod(lead), lst, lgr, hst, hgr, g.groups, g.rows, g.A, g.B,
+                                 g.n_out, nat.stream_of(out.data)),
+        "outer_cross",
+    )
+    return out
+
+
 def select_mask(a: RT, axis: int, mask: torch.Tensor, nb=0) -> RT:
     ax = _ax(a, axis, nb)
     keep = torch.nonzero(mask.reshape(-1).to(torch.bool)).reshape(-1).to(a.device)

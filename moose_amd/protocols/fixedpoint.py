@@ -817,6 +817,94 @@ def group_by_sum(sess, x: RepFixed, by: int = 0, count: bool = False,
 
 
 # ---------------------------------------------------------------------------
+# addressing by a secret index: one-hot, table lookup, bincount
+# ---------------------------------------------------------------------------
+def _index_one_hot(sess, what, idx, n, ring_bits):
+    """(the integer one-hot matrix [rows, n] over Z_2^ring_bits of the secret indices ``idx``,
+    idx's shape).  ``idx`` is a replicated uint64 ring tensor, as ``argmax`` returns (bit t of
+    the value is index bit t), or a fixed-point tensor holding an integer (bit frac + t;
+    fractional bits are ignored).  Precondition: 0 <= idx < 2^w with w = rep.demux_width(n);
+    higher bits are ignored, and an idx in [n, 2^w) selects nothing (its row is zero).  The
+    index bits come from rep.bit_decompose and rep.b2a_planes, which injects them into the
+    result's ring -- a Z_2^64 index can address a Z_2^128 table -- and rep.demux expands them."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError(f"{what}: the number of entries must be a positive integer, found {n!r}")
+    t, start = (idx.t, idx.frac) if isinstance(idx, RepFixed) else (idx, 0)
+    if not isinstance(t, RepTensor) or t.kind != "arith" or t.bits not in (64, 128):
+        raise ValueError(f"{what}: the index must be a replicated uint64 or fixed-point tensor, "
+                         f"found {'a bit tensor' if getattr(t, 'bits', 0) == 1 else type(t).__name__}")
+    n = int(n)
+    shape = tuple(shape_of(sess, t))
+    rows = math.prod(shape)
+    if n == 1:
+        ones = R.fill((rows, 1), 1, ring_bits, sess.device)
+        return rep.from_public(sess, t.plc, ones, ring_bits), shape
+    w = rep.demux_width(n)
+    flat = rep.local(sess, t, "Reshape", shape=(rows,))
+    top = start + w
+    bd = rep.bit_decompose(sess, flat, width=top if 2 < top < t.bits else None)
+    planes = rep.b2a_planes(sess, bd, start, w, ring_bits)
+    return rep.demux(sess, planes, n), shape
+
+
+def one_hot(sess, idx, depth: int, frac: int, integ: int, ring_bits: int) -> RepFixed:
+    """The one-hot rows [..., depth] of the secret indices ``idx`` as fixed(integ, frac) over
+    Z_2^ring_bits: entries 0 and 1.0 -- the demultiplexer's output times 2^frac, a local
+    step.  Index forms and the precondition 0 <= idx < 2^w: :func:`_index_one_hot`."""
+    d, shape = _index_one_hot(sess, "one_hot", idx, depth, ring_bits)
+    if frac:
+        d = rep.shl(sess, d, frac)
+    return RepFixed(rep.local(sess, d, "Reshape", shape=shape + (int(depth),)), frac, integ)
+
+
+def lookup(sess, table, idx, ptable=None):
+    """``table[idx]`` for secret indices: ``demux(idx) . table``, [rows..., d] for a table [n, d]
+    and [rows...] for a table [n].  A secret ``table`` (RepFixed) goes through rep.dot, a public
+    one (``ptable``, a ring tensor) through rep.dot_public; the one-hot matrix holds the
+    integers 0 / 1, so nothing truncates and the opened rows equal the table's encoded rows
+    exactly.  Precondition 0 <= idx < 2^w; an idx in [n, 2^w) returns 0
+    (:func:`_index_one_hot`).  Returns the ring sharing; the caller keeps the table's type."""
+    src = ptable if ptable is not None else table.t
+    tshape = tuple(ptable.shape) if ptable is not None else tuple(shape_of(sess, table))
+    if len(tshape) not in (1, 2) or tshape[0] is None:
+        raise ValueError(f"lookup: the table must be [n, d] or [n] with a known n, found shape "
+                         f"{tshape}")
+    n, d = tshape[0], (tshape[1] if len(tshape) == 2 else 1)
+    iplc = (idx.t if isinstance(idx, RepFixed) else idx).plc
+    if ptable is None and table.plc != iplc:
+        raise ValueError(f"lookup: the table is on {table.plc} and the index on {iplc}; both "
+                         "must be on one replicated placement")
+    oh, shape = _index_one_hot(sess, "lookup", idx, n, src.bits)
+    if ptable is not None:
+        out = rep.dot_public(sess, oh, R.reshape(ptable, (n, d)))
+    else:
+        out = rep.dot(sess, oh, rep.local(sess, src, "Reshape", shape=(n, d)))
+    return rep.local(sess, out, "Reshape", shape=shape + ((d,) if len(tshape) == 2 else ()))
+
+
+def bincount(sess, idx, n: int, weights=None, frac: int = 0, ring_bits: int = 64):
+    """Histogram of the secret indices ``idx`` over ``n`` bins.  Without ``weights`` the column
+    sums of the one-hot matrix times 2^frac, [n]; with secret ``weights`` (RepFixed, [rows, d]
+    or [rows]) ``demux(idx)^T . weights`` untruncated, [n, d] or [n] in the weights' type.
+    Exact.  Precondition 0 <= idx < 2^w; an idx in [n, 2^w) is counted nowhere
+    (:func:`_index_one_hot`).  Returns the ring sharing."""
+    if weights is None:
+        oh, _ = _index_one_hot(sess, "bincount", idx, n, ring_bits)
+        out = rep.sum(sess, oh, 0)
+        return rep.shl(sess, out, frac) if frac else out
+    wshape = tuple(shape_of(sess, weights))
+    oh, shape = _index_one_hot(sess, "bincount", idx, n, weights.bits)
+    rows = math.prod(shape)
+    if len(wshape) not in (1, 2) or wshape[0] != rows:
+        raise ValueError(f"bincount: {rows} indices take weights [{rows}, d] or [{rows}], found "
+                         f"shape {wshape}")
+    d = wshape[1] if len(wshape) == 2 else 1
+    out = rep.dot(sess, rep.local(sess, oh, "Transpose"),
+                  rep.local(sess, weights.t, "Reshape", shape=(rows, d)))
+    return out if len(wshape) == 2 else rep.local(sess, out, "Reshape", shape=(int(n),))
+
+
+# ---------------------------------------------------------------------------
 # normalisation: leading-bit one-hot
 # ---------------------------------------------------------------------------
 def _or(sess, a: RepTensor, b: RepTensor) -> RepTensor:

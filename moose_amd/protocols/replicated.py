@@ -1489,6 +1489,97 @@ def segmented_scan(sess, v: RepTensor, g: RepTensor, on_stage=None) -> RepTensor
         return _rows(sess, x, 0, n, (0, cols))
 
 
+def demux_width(n: int) -> int:
+    """Index bits a demultiplexer of ``n`` outputs reads: max(1, ceil(log2 n))."""
+    return max(1, (int(n) - 1).bit_length())
+
+
+def demux(sess, planes: RepTensor, n: int, on_level=None) -> RepTensor:
+    """The one-hot rows of secret indices: ``planes`` [w, rows] holds arithmetic 0/1 sharings of
+    the index bits, the low bit first, ``w = demux_width(n)``; the result [rows, n] has a 1 at
+    column ``idx = sum_t planes[t] * 2^t`` and 0 elsewhere.  A row whose ``idx >= n`` (possible
+    where n is no power of two) is all zeros.
+
+    A tree of outer products.  Level 0 is local: bit t becomes the group ``[1 - b_t, b_t]``, w
+    groups of 2 entries.  Every later level pairs the adjacent groups (2g, 2g + 1), the lower
+    one as L: the one-hot of the pair's bits is the outer product ``L[c % A] * H[c // A]``,
+    one replicated multiplication -- the parties' local products (session ``p_outer_cross``),
+    a zero share and a reshare.  An odd last group is carried over.  After a level all groups
+    have the same size except possibly the last, so a level is one launch over the equal pairs
+    and at most one more for the last pair.  The last level writes only the first ``n``
+    columns.  ceil(log2 w) rounds; nothing truncates, so the opened matrix is the integer
+    one-hot exactly.
+
+    ``on_level(k, groups)`` sees the state after level k (tests): the list of the equal groups
+    [G, rows, size] and, where there is one, the smaller last group [1, rows, size'].  A
+    symbolic session composes the local products from Reshape, IndexAxis, Broadcast, Mul and
+    Add, so a lowered graph needs no operator of its own."""
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"demux: the number of outputs must be a positive integer, found {n!r}")
+    if planes.kind != "arith" or planes.bits not in (64, 128):
+        raise ValueError("demux takes arithmetic 0/1 sharings over Z_2^64 or Z_2^128 (inject "
+                         "the index bits into the ring first: b2a_planes)")
+    plc, bits = planes.plc, planes.bits
+    shape = tuple(sess.p_shape(planes.s0))
+    w = demux_width(n)
+    if len(shape) != 2 or shape[0] != w:
+        raise ValueError(f"demux: {n} outputs take the index bits as [{w}, rows], found shape "
+                         f"{shape}")
+    rows = shape[1]
+    dev = getattr(sess, "device", "cpu")
+    if n == 1:
+        return from_public(sess, plc, R.fill((rows, 1), 1, bits, dev), bits)
+    with span("rep.demux"):
+        hi = local(sess, planes, "Reshape", shape=(w, rows, 1))
+        full = _cat(sess, [public_sub(sess, R.fill((), 1, bits, dev), hi), hi], 2)
+        tail, size, tsize, k = None, 2, 0, 0
+        if on_level is not None:
+            on_level(0, [full])
+        fused = getattr(sess, "p_zero_share_reshare", None)
+        if not getattr(sess, "fused", False):
+            fused = None
+
+        def product(geom, x, y=None):
+            with span("rep.demux_level"):
+                z = sess.p_outer_cross(plc, x.s0, x.s1, geom) if y is None else \
+                    sess.p_outer_cross(plc, x.s0, x.s1, geom, y.s0, y.s1)
+                if fused is not None:
+                    return RepTensor(plc, bits, "arith", *fused(plc, z, "arith"))
+                return _reshare(sess, plc, sess.p_add_zero_share(plc, z, "arith"), bits, "arith")
+
+        # State between levels, in bit order: `full` holds G groups of `size` entries each
+        # ([G, rows, size]) and `tail`, where there is one, a last group of `tsize` entries
+        # ([1, rows, tsize]) that covers the highest bits.  A level
+        #   - multiplies the pairs (2g, 2g + 1) of `full` in one launch: G // 2 groups of size^2;
+        #   - if G is odd, its last group `odd` has no partner in `full`: it is multiplied with
+        #     `tail` (odd as L, the lower bits) in a second launch, or becomes the tail;
+        #   - if G is even, `tail` is carried as it is.
+        # With G = 1 the lone group goes into the tail's product, which is then all there is.
+        G = w
+        while G + (tail is not None) > 1:
+            k += 1
+            last = G // 2 + (G % 2 or tail is not None) == 1  # one group is left after this level
+            odd = local(sess, full, "StridedSlice", slices=[slice(G - 1, G)]) if G % 2 else None
+            nxt = None
+            if G >= 2:
+                n_out = n if last else size * size
+                nxt = product(R.OuterGeom(G // 2, rows, size, size, n_out), full)
+            if odd is not None and tail is not None:
+                n_out = n if last else size * tsize
+                tail = product(R.OuterGeom(1, rows, size, tsize, n_out), odd, tail)
+                tsize = size * tsize
+            elif odd is not None:
+                tail, tsize = odd, size
+            if nxt is None:  # the lone equal group went into the last pair
+                full, size, tail = tail, tsize, None
+            else:
+                full, size = nxt, size * size
+            G = max(G // 2, 1)
+            if on_level is not None:
+                on_level(k, [full] + ([tail] if tail is not None else []))
+        return local(sess, full, "Reshape", shape=(rows, n))
+
+
 def dwconv_public(sess, x: RepTensor, c, geom: dict, public_image=False) -> RepTensor:
     """Depthwise convolution of a secret image with the public weight ``c`` (or, with
     ``public_image``, of the public image ``c`` with a secret weight): the plain kernel

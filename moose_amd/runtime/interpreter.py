@@ -1650,6 +1650,125 @@ class Interpreter:
         except ValueError as e:
             raise MooseRuntimeError(f"{op.name}: {e}") from None
 
+    # -- addressing by a secret index: OneHot, Lookup, BinCount (ir/operators.py) -------------
+    def _index_operand(self, op, x, what):
+        """The index of OneHot / Lookup / BinCount at the op's placement, and the position of
+        its bit 0: a uint64 tensor (0) or a fixed-point tensor holding an integer (frac)."""
+        x = self.at(op, x)
+        d = x.dtype
+        if x.kind != "tensor" or d is None or d.kind == "Bool" or not (d.is_fixed
+                                                                      or d.kind == "Uint64"):
+            raise ValueError(f"{what} expects a uint64 or fixed-point index (bit tensors are not "
+                             f"supported), found {d if x.kind == 'tensor' else x.kind}")
+        return x, (d.fractional_precision if d.is_fixed else 0)
+
+    @staticmethod
+    def _encoding(d):
+        """(the encoding of 1, ring bits or 0 for a float) of a result dtype."""
+        if d is not None and d.is_fixed:
+            return 1 << d.fractional_precision, d.ring_bits
+        return 1.0, 0
+
+    def _clear(self, op, prim, vals, dtype, **attrs):
+        """A plaintext primitive on a host's or a mirrored placement's values."""
+        x = vals[0]
+        if x.is_host:
+            return LV(x.plc, "tensor", dtype,
+                      self.sess.h(prim, x.host, *[v.v for v in vals], **attrs))
+        o = x.plc.owners[0]
+        r = self.sess.h(prim, o, *[HV(o, v.v.v) for v in vals], **attrs)
+        return LV(x.plc, "tensor", dtype, MV(x.plc, r.v))
+
+    @staticmethod
+    def _is_clear(v):
+        return v.is_host or v.is_mir or (v.is_rep and isinstance(v.v, MV))
+
+    def op_OneHot(self, op, ins):
+        """One-hot rows of an index: in the clear through the plaintext primitive on a host
+        or mirrored placement -- the specification; fixedpoint.one_hot on a replicated one."""
+        depth = op.attrs.get("depth")
+        d = self._ret_dtype(op)
+        try:
+            if isinstance(depth, bool) or not isinstance(depth, int) or depth < 1:
+                raise ValueError(f"OneHot: depth must be a positive integer, found {depth!r}")
+            x, f = self._index_operand(op, ins[0], "OneHot")
+            if d is None or not (d.is_fixed or d.kind in ("Float64", "Float32")):
+                d = x.dtype
+            one, bits = self._encoding(d)
+            if self._is_clear(x):
+                return self._clear(op, "OneHot", [x], d, depth=depth, idx_frac=f, one=one,
+                                   bits=bits)
+            if not d.is_fixed:
+                raise ValueError(f"OneHot on a replicated placement produces a fixed-point "
+                                 f"tensor: pass dtype=, found {d}")
+            return LV(x.plc, "tensor", d,
+                      fxp.one_hot(self.sess, x.v, depth, d.fractional_precision,
+                                  d.integral_precision, d.ring_bits))
+        except ValueError as e:
+            raise MooseRuntimeError(f"{op.name}: {e}") from None
+
+    def op_Lookup(self, op, ins):
+        """table[idx]: in the clear where table and index are (the specification); on a
+        replicated placement fixedpoint.lookup, a secret table through rep.dot and a public
+        (mirrored, constant) one through rep.dot_public, untruncated."""
+        try:
+            t = self.at(op, ins[0])
+            x, f = self._index_operand(op, ins[1], "Lookup")
+            if t.kind != "tensor" or t.dtype is None or t.dtype.kind == "Bool":
+                raise ValueError(f"Lookup expects a float or fixed-point table, found "
+                                 f"{t.dtype if t.kind == 'tensor' else t.kind}")
+            if self._is_clear(t) and self._is_clear(x):
+                return self._clear(op, "Lookup", [t, x], t.dtype, idx_frac=f)
+            if self._is_clear(x):
+                raise ValueError("Lookup: a secret table with a public index is an index_axis; "
+                                 "the index must be secret")
+            if not t.dtype.is_fixed:
+                raise ValueError(f"Lookup on a replicated placement expects a fixed-point table, "
+                                 f"found {t.dtype}")
+            pub = self._public(t)
+            r = fxp.lookup(self.sess, None if pub is not None else t.v, x.v, ptable=pub)
+            return LV(x.plc, "tensor", t.dtype, RepFixed(r, t.dtype.fractional_precision,
+                                                         t.dtype.integral_precision))
+        except ValueError as e:
+            raise MooseRuntimeError(f"{op.name}: {e}") from None
+
+    def op_BinCount(self, op, ins):
+        """Histogram of an index over `length` bins, with optional weights: in the clear on a
+        host or mirrored placement (the specification); fixedpoint.bincount on a replicated
+        one.  Without weights the result has the index's fixed-point type (counts times 1.0)."""
+        n = op.attrs.get("length")
+        try:
+            if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+                raise ValueError(f"BinCount: length must be a positive integer, found {n!r}")
+            x, f = self._index_operand(op, ins[0], "BinCount")
+            w = self.at(op, ins[1]) if len(ins) > 1 else None
+            if w is not None and (w.kind != "tensor" or w.dtype is None or w.dtype.kind == "Bool"):
+                raise ValueError(f"BinCount expects float or fixed-point weights, found "
+                                 f"{w.dtype if w.kind == 'tensor' else w.kind}")
+            d = w.dtype if w is not None else self._ret_dtype(op)
+            if d is None or not (d.is_fixed or d.kind in ("Float64", "Float32")):
+                d = x.dtype
+            one, bits = self._encoding(d)
+            if self._is_clear(x) and (w is None or self._is_clear(w)):
+                vals = [x] + ([w] if w is not None else [])
+                attrs = dict(length=n, idx_frac=f)
+                if w is None:
+                    attrs.update(one=one, bits=bits)
+                return self._clear(op, "BinCount", vals, d, **attrs)
+            if self._is_clear(x):
+                raise ValueError("BinCount: the index must be secret on a replicated placement")
+            if not d.is_fixed:
+                raise ValueError(f"BinCount on a replicated placement produces a fixed-point "
+                                 f"tensor, found {d}")
+            if w is not None and isinstance(w.v, MV):
+                w = self._share_public(w)
+            r = fxp.bincount(self.sess, x.v, n, None if w is None else w.v,
+                             d.fractional_precision, d.ring_bits)
+            return LV(x.plc, "tensor", d, RepFixed(r, d.fractional_precision,
+                                                   d.integral_precision))
+        except ValueError as e:
+            raise MooseRuntimeError(f"{op.name}: {e}") from None
+
     def op_PiecewiseLinear(self, op, ins):
         """Piecewise-linear activation of a fixed-point tensor: replicated values through
         fixedpoint.piecewise_linear (one sign extraction, one local kernel, one truncation);

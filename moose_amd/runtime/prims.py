@@ -511,6 +511,77 @@ def _group_by_sum(nb, x, by=0, count=False, one=1):
     return R.RT(out, x.bits) if rt else out
 
 
+def _plain_index(idx, n, frac):
+    """The indices a host's tensor holds, as int64 in [0, 2^w), w = max(1, ceil(log2 n)): bit t
+    of a uint64 tensor, bit frac + t of a fixed-point tensor's ring values (fractional bits
+    and higher bits are ignored, as on the replicated placement)."""
+    w = max(1, (int(n) - 1).bit_length())
+    if _is_rt(idx):
+        if idx.bits == 1 or frac + w > 63:
+            raise ValueError(f"an index of {w} bits above {frac} fractional bits in a "
+                             f"{idx.bits}-bit tensor is not supported")
+        v = (idx.data[..., 0] if idx.bits == 128 else idx.data) >> frac
+    else:
+        v = idx.to(torch.int64)
+    return v & ((1 << w) - 1)
+
+
+def _plain_ring(x, one, bits):
+    """An integer tensor times ``one`` as a ring tensor of ``bits`` (0: as float64)."""
+    if not bits:
+        return x.to(torch.float64) * float(one)
+    lo = x.to(torch.int64) * int(one)
+    return R.RT(lo if bits == 64 else torch.stack([lo, torch.zeros_like(lo)], dim=-1), bits)
+
+
+@prim("OneHot")
+def _one_hot(nb, idx, depth=1, idx_frac=0, one=1, bits=0):
+    """Plaintext one-hot rows [..., depth] of a host's indices -- the specification of the
+    secure path: ``one`` at column idx, 0 elsewhere, all zeros where idx >= depth."""
+    v = _plain_index(idx, depth, idx_frac)
+    cols = torch.arange(int(depth), device=v.device)
+    return _plain_ring(v.unsqueeze(-1) == cols, one, bits)
+
+
+@prim("Lookup")
+def _lookup(nb, table, idx, idx_frac=0):
+    """Plaintext ``table[idx]`` of a host's table [n, d] or [n]: the rows the indices name, 0
+    where idx >= n."""
+    rt = _is_rt(table)
+    if len(table.shape) not in (1, 2):
+        raise ValueError(f"lookup takes a table [n, d] or [n], found shape {tuple(table.shape)}")
+    n = table.shape[0]
+    v = _plain_index(idx, n, idx_frac)
+    d = table.data if rt else table
+    got = d[v.clamp(max=n - 1)]
+    keep = (v < n).reshape(tuple(v.shape) + (1,) * (got.dim() - v.dim()))
+    out = torch.where(keep, got, torch.zeros_like(got))
+    return R.RT(out.contiguous(), table.bits) if rt else out
+
+
+@prim("BinCount")
+def _bincount(nb, idx, weights=None, length=1, idx_frac=0, one=1, bits=0):
+    """Plaintext histogram of a host's indices over ``length`` bins: the counts times ``one``
+    [length], or with weights [rows, d] / [rows] the sums of the weights per bin, exact in the
+    ring; an idx >= length is counted nowhere."""
+    n = int(length)
+    v = _plain_index(idx, n, idx_frac).reshape(-1)
+    oh = v.unsqueeze(-1) == torch.arange(n, device=v.device)  # [rows, n]
+    if weights is None:
+        return _plain_ring(oh.sum(0), one, bits)
+    wshape = tuple(weights.shape)
+    if len(wshape) not in (1, 2) or wshape[0] != v.shape[0]:
+        raise ValueError(f"bincount: {v.shape[0]} indices take weights [{v.shape[0]}, d] or "
+                         f"[{v.shape[0]}], found shape {wshape}")
+    if not _is_rt(weights):
+        return oh.to(weights.dtype).t() @ weights
+    rows, d = wshape[0], (wshape[1] if len(wshape) == 2 else 1)
+    sel = R.broadcast_to(_plain_ring(oh.unsqueeze(-1), 1, weights.bits), (rows, n, d))
+    w = R.broadcast_to(R.reshape(weights, (rows, 1, d)), (rows, n, d))
+    out = R.sum(R.binary("mul", sel, w), 0)
+    return out if len(wshape) == 2 else R.reshape(out, (n,))
+
+
 @prim("PermFromKeys", ty=lambda tys, **a: T.Ty("HostUint64Tensor"))
 def _perm_from_keys(nb, keys):
     """The permutation that stably sorts a Z_2^64 vector of PRF output as unsigned integers

@@ -967,6 +967,17 @@ class StackedSession(Session):
         included -- are read in place."""
         return PV(plc, R.segscan_cross(x0.v, x1.v, geom, nb=1))
 
+    def p_outer_cross(self, plc, x0, x1, geom, y0=None, y1=None):
+        """The three parties' local products of one demultiplexer level (R.outer_cross) in one
+        launch.  Without ``y`` the operands are the groups (2g, 2g + 1) of ``x``, read in
+        place as the views of R.outer_pairs; with it L = x and H = y.  The share vectors --
+        the views of a share-pair buffer included -- are not copied either."""
+        if y0 is None:
+            (l0, h0), (l1, h1) = R.outer_pairs(x0.v, nb=1), R.outer_pairs(x1.v, nb=1)
+        else:
+            l0, l1, h0, h1 = x0.v, x1.v, y0.v, y1.v
+        return PV(plc, R.outer_cross(l0, l1, h0, h1, geom, nb=1))
+
     def end_evaluation(self, ok=True):
         """Drop per-evaluation caches (prepared GEMM operands hold device memory and must
         not outlive the evaluation whose values they were prepared from)."""
